@@ -6,6 +6,7 @@ achieved HBM GB/s, Sponza 1080p 8-bounce).
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...          (no WORLD_SIZE in the environment: starts the N ranks itself, see self_launch)
     python bench.py --gltf Sponza.gltf --eye X Y Z --center X Y Z [--fov F]   (a supplied scene file instead of the atrium)
+    python bench.py ... --dump-outputs DIR   (also writes the image of the last timed step, DIR/image.npy, for output-for-output comparisons)
 
 A "step" is one progressive frame of the workload: the seeded procedural Sponza-class atrium
 (tools/atrium.py; the real Sponza.gltf is not available offline), 16 spp per frame
@@ -174,6 +175,35 @@ def fresh_profile(path, key):
     return d
 
 
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: write each [rows, ...] array (a torch tensor) as directory/<name>.npy in float32.  When they would take
+    more than DUMP_BUDGET_BYTES together, each keeps the same share of its rows, drawn once with a fixed seed (sorted), and
+    <name>_rows.npy (float64) holds the indices of the rows kept.  Returns {file name: shape} for the result line."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    header = 128  # bytes of one .npy header
+    scale = 1.0
+    if total + header * len(host) > DUMP_BUDGET_BYTES:
+        scale = (DUMP_BUDGET_BYTES - 2 * header * len(host)) / (total + 8 * sum(a.shape[0] for a in host.values()))
+    written = {}
+    for name, a in host.items():
+        if scale < 1.0:
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.shape[0], size=max(1, int(a.shape[0] * scale)), replace=False))
+            a = a[rows]
+            np.save(os.path.join(directory, f"{name}_rows.npy"), rows.astype(np.float64))
+            written[f"{name}_rows.npy"] = [int(rows.shape[0])]
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+        written[f"{name}.npy"] = [int(x) for x in a.shape]
+    return written
+
+
 def issue_mix_block(mix, valu_per_ray, node_wave_steps_per_ray, frac_of_peak):
     """roofline.issue_mix: what the kernel's opcode mix allows.  A half-rate opcode (v_cvt_f32_ubyte*, v_min/max(3)_f32, v_cmp, SDWA and
     VOP3 integer work; profiles/r02_issue_microbench.json) takes the issue slots of two full-rate ones, so a wave whose instructions
@@ -223,8 +253,13 @@ def main():
     ap.add_argument("--center", type=float, nargs=3, default=None, help="look-at point (default: the origin)")
     ap.add_argument("--up", type=float, nargs=3, default=None)
     ap.add_argument("--fov", type=float, default=None, help="vertical field of view in degrees (default 60)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the image the last timed step produced as DIR/<name>.npy (float32, at most "
+                         f"{DUMP_BUDGET_BYTES >> 20} MB: a fixed, seeded sample of rows when the image is larger)")
     ap.add_argument("--launch-selftest", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
     if args.launch_selftest:
@@ -334,11 +369,11 @@ def main():
         (rr or r).reset_counters(stream)
         sync()
         t0 = time.perf_counter()
-        k = 0
+        k, last = 0, None
         while k < n:  # exactly n steps (frames), per_call of them per library call
             m = min(per_call, n - k)
             if rr is None:
-                step(first_frame + k, n=m)
+                last = step(first_frame + k, n=m)
             else:
                 render(first_frame + k, m, rr=rr)
             k += m
@@ -347,13 +382,15 @@ def main():
         sync()
         dt = time.perf_counter() - t0
         c = (rr or r).counters()
-        return dt, t_local, c
+        return dt, t_local, c, last
 
     if per_call > 1:  # touch the frames-in-flight path once before anything is timed (a throw-away image; lanes, events and staging planes exist after vkrt_reserve)
         render(0, 2, img=torch.zeros_like(image))
     for f in range(args.warmup):
         step(f)
-    elapsed, local_s, cnt = timed_frames(args.warmup, args.steps)
+    elapsed, local_s, cnt, last_image = timed_frames(args.warmup, args.steps)
+    dumped = dump_outputs(args.dump_outputs, {"image": last_image}) if args.dump_outputs and rank == 0 else None
+    del last_image  # the untimed passes below render into the same buffers
     rays_local = cnt["rays_closest"] + cnt["rays_shadow"]
     assert cnt["traversal_faults"] == 0, "traversal faults: a stack push was dropped or a walk hit the step bound"
 
@@ -442,6 +479,8 @@ def main():
                 "mode": mode, "source_hash": vkrt_amd.source_hash(), "workload_key": key,
             },
         }
+        if dumped is not None:
+            out["config"]["dumped_outputs"] = dumped
         if same_frame:
             out["config"]["same_frame_single_gpu_Mrays_s"] = same_frame["Mrays_s"]
             out["config"]["same_frame_single_gpu_ms_per_frame"] = same_frame["ms_per_frame"]
@@ -571,7 +610,7 @@ def main():
                 r.build(other)
                 for f in range(1):
                     step(f)
-                dt, _, c2 = timed_frames(1, 2)
+                dt, _, c2, _ = timed_frames(1, 2)
                 builds[other]["Mrays_s"] = (c2["rays_closest"] + c2["rays_shadow"]) / dt / 1e6
             builds[args.build]["Mrays_s"] = mrays
             r.build(args.build)

@@ -242,3 +242,36 @@ def test_round5_bench_line_carries_the_shade_and_frame_rooflines():
     # the counter summaries the line quotes belong to the same sources
     for name in ("pmc_issue.json", "pmc_traffic.json", "isa_mix.json"):
         assert json.load(open(os.path.join(ROOT, "profiles", name)))["source_hash"] == d["config"]["source_hash"], name
+
+
+def test_dump_outputs_keeps_the_budget_and_a_fixed_sample(tmp_path):
+    """--dump-outputs: an image that fits is written whole in float32; a larger one (the 4K frame of N > 1) keeps the same
+    seeded rows on every run, their indices beside it, and all files together stay within the 64 MB budget."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    small = torch.arange(6 * 5 * 4, dtype=torch.float32).reshape(6, 5, 4)
+    assert bench.dump_outputs(str(tmp_path / "s"), {"image": small}) == {"image.npy": [6, 5, 4]}
+    got = np.load(tmp_path / "s" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy())
+
+    big = torch.rand((2160, 3840, 4), generator=torch.Generator().manual_seed(3))
+    runs = []
+    for d in ("a", "b"):
+        w = bench.dump_outputs(str(tmp_path / d), {"image": big})
+        assert set(w) == {"image.npy", "image_rows.npy"} and w["image.npy"][1:] == [3840, 4]
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= bench.DUMP_BUDGET_BYTES
+        img, rows = np.load(tmp_path / d / "image.npy"), np.load(tmp_path / d / "image_rows.npy")
+        assert img.dtype == np.float32 and rows.dtype == np.float64 and len(rows) == img.shape[0] > 1000
+        assert np.all(np.diff(rows) > 0) and np.array_equal(img, big.numpy()[rows.astype(np.int64)])
+        runs.append(rows)
+    assert np.array_equal(runs[0], runs[1])
+
+
+def test_bench_refuses_zero_steps():
+    import subprocess
+
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 2 and "--steps" in p.stderr

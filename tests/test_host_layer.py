@@ -15,8 +15,6 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import vkrt_amd  # noqa: E402,F401
 from vkrt_amd import host_py  # noqa: E402
 
-REF_CORNELL = "/root/reference/media/scenes/cornell.gltf"
-
 
 def _same_geometry(a, b, exact_tangents=False):
     assert a.positions.shape == b.positions.shape and np.array_equal(a.positions, b.positions)
@@ -37,12 +35,29 @@ def _same_geometry(a, b, exact_tangents=False):
         assert np.allclose(a.lights[k], b.lights[k], atol=1e-6), k
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CORNELL), reason="reference tree not mounted")
-def test_cpp_loader_matches_numpy_restatement_on_cornell(cornell_flat):
+@pytest.fixture(scope="module")
+def cornell_gltf(tmp_path_factory, cornell_flat):
+    """The cornell scene as a .gltf + .bin written from the committed fixture (tests/golden/cornell_flat.npz): one node per
+    primMesh, its KHR_lights_punctual light, and no TANGENT accessor, as in the shipped asset, so both loaders generate tangents."""
+    import gltf_export
+
+    path = str(tmp_path_factory.mktemp("cornell") / "cornell.gltf")
+    gltf_export.export_gltf(cornell_flat, path, write_lights=True)
+    with open(path) as f:
+        g = json.load(f)
+    for mesh in g["meshes"]:
+        for prim in mesh["primitives"]:
+            del prim["attributes"]["TANGENT"]
+    with open(path, "w") as f:
+        json.dump(g, f)
+    return path
+
+
+def test_cpp_loader_matches_numpy_restatement_on_cornell(cornell_flat, cornell_gltf):
     import gltf_flatten
 
-    a = host_py.load_gltf(REF_CORNELL)
-    b = gltf_flatten.load_gltf(REF_CORNELL)
+    a = host_py.load_gltf(cornell_gltf)
+    b = gltf_flatten.load_gltf(cornell_gltf)
     _same_geometry(a, b)
     _same_geometry(a, cornell_flat)  # and the committed fixture
     assert a.positions.shape[0] == 16808 and a.indices.shape[0] == 50160 and len(a.prim_meshes) == 9 and len(a.nodes) == 10
