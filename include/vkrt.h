@@ -371,6 +371,33 @@ int vkrt_hybrid_trace_nrd(vkrt_scene* scene, const PushConstantRay* pc, const Gl
 int vkrt_post(int device, const PushConstantPost* pc, uint32_t n_pixels, const float* main_rgba32f, const float* rt_rgba32f,
               float* out_rgba32f, void* hip_stream);
 
+/* ---- diffuse denoiser (stands where the reference's commented-out NRD.Denoise sits, main.cpp:565-602) ---------------------
+ * A spatio-temporal variance-guided filter (SVGF, Schied et al. 2017) of the hybrid GI term: it reads the planes that
+ * vkrt_gbuffer_raycast_nrd and vkrt_hybrid_trace_nrd write (nrd->viewZ, nrd->diffRadianceHitDist) and the G-buffer, and writes
+ * the filtered GI radiance.  Three stages on the caller's stream -- temporal reprojection + moments, variance, `atrous_iterations`
+ * edge-avoiding a-trous passes -- with no host synchronisation and no allocation inside the call; the history lives in the handle.
+ * Whole-frame planes only (no vkrt_shard): a host that renders strips denoises the gathered frame.  Same inputs and history give
+ * bitwise the same output (no atomics).  These entry points came after ABI version 4 without changing it: detect them by symbol.
+ * The handle is bound to one device and one width x height; every plane passed to it has exactly that many pixels. */
+typedef struct vkrt_denoiser vkrt_denoiser;
+typedef struct vkrt_denoise_settings {
+  uint32_t struct_size;       /* sizeof(vkrt_denoise_settings) */
+  int32_t  atrous_iterations; /* 0..5, default 5 (0 = temporal stage only) */
+  int32_t  max_history;       /* 1..255, default 32 (1 = no temporal reuse) */
+} vkrt_denoise_settings;
+/* Allocates everything the filter keeps (128 B per pixel); VKRT_ERR_NO_DEVICE without a HIP device. */
+int  vkrt_denoiser_create(int device, uint32_t width, uint32_t height, vkrt_denoiser** out);
+void vkrt_denoiser_destroy(vkrt_denoiser* dn);
+/* Drops the history: the next call behaves like the first (a camera cut; the reference's resetFrame). */
+int  vkrt_denoiser_reset(vkrt_denoiser* dn);
+/* cam = the camera the G-buffer was cast with (its viewProj is kept for the next call's reprojection); settings NULL = defaults.
+ * out_rgba32f: W*H rgba32f; .xyz is written at pixels with geometry (G-buffer position or normal non-zero), everything else --
+ * .w and the background -- is left untouched, so a host can denoise into a copy of the accumulation plane and hand it to vkrt_post
+ * unchanged.  Refused with VKRT_ERR_INVALID_ARGUMENT: struct_size too small, settings out of range, a NULL handle, camera,
+ * G-buffer plane, nrd->viewZ, nrd->diffRadianceHitDist or output. */
+int  vkrt_denoise_diffuse(vkrt_denoiser* dn, const vkrt_denoise_settings* settings, const GlobalUniforms* cam, const vkrt_gbuffer* gbuffer,
+                          const vkrt_nrd_planes* nrd, float* out_rgba32f, void* hip_stream);
+
 /* ---- counters / timing ------------------------------------------------------------ */
 int vkrt_counters_reset(vkrt_scene* scene, void* hip_stream);
 int vkrt_counters_read(vkrt_scene* scene, vkrt_counters* out); /* synchronises the device */

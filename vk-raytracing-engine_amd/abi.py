@@ -163,6 +163,10 @@ class PushConstantPost(C.Structure):
     _fields_ = [("aspectRatio", c_f), ("rtMode", c_i), ("viewAccumulated", c_i), ("useGI", c_i)]
 
 
+class DenoiseSettings(C.Structure):
+    _fields_ = [("struct_size", c_u), ("atrous_iterations", c_i), ("max_history", c_i)]
+
+
 class TraceTiming(C.Structure):
     _fields_ = [("total_ms", c_f), ("traverse_ms", c_f), ("traverse_launches", c_u), ("mode", c_u), ("shade_ms", c_f), ("shade_launches", c_u)]
 
@@ -215,6 +219,10 @@ VKRT_SYMBOLS = [
     "vkrt_gbuffer_raycast_nrd",
     "vkrt_hybrid_trace_nrd",
     "vkrt_post",
+    "vkrt_denoiser_create",
+    "vkrt_denoiser_destroy",
+    "vkrt_denoiser_reset",
+    "vkrt_denoise_diffuse",
     "vkrt_counters_reset",
     "vkrt_counters_read",
     "vkrt_last_trace_ms",
@@ -270,6 +278,14 @@ def declare_vkrt(lib):
     lib.vkrt_hybrid_trace_nrd.restype = C.c_int
     lib.vkrt_post.argtypes = [C.c_int, P(PushConstantPost), c_u, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.vkrt_post.restype = C.c_int
+    lib.vkrt_denoiser_create.argtypes = [C.c_int, c_u, c_u, P(C.c_void_p)]
+    lib.vkrt_denoiser_create.restype = C.c_int
+    lib.vkrt_denoiser_destroy.argtypes = [C.c_void_p]
+    lib.vkrt_denoiser_destroy.restype = None
+    lib.vkrt_denoiser_reset.argtypes = [C.c_void_p]
+    lib.vkrt_denoiser_reset.restype = C.c_int
+    lib.vkrt_denoise_diffuse.argtypes = [C.c_void_p, P(DenoiseSettings), P(GlobalUniforms), P(Gbuffer), P(NrdPlanes), C.c_void_p, C.c_void_p]
+    lib.vkrt_denoise_diffuse.restype = C.c_int
     lib.vkrt_counters_reset.argtypes = [C.c_void_p, C.c_void_p]
     lib.vkrt_counters_reset.restype = C.c_int
     lib.vkrt_counters_read.argtypes = [C.c_void_p, P(Counters)]

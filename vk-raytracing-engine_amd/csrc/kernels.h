@@ -83,3 +83,43 @@ hipError_t vkrt_launch_hybrid_gi(const TraceParams& P, const WfBuffers& B, const
 uint2* vkrt_wf_hybrid_tmp(const WfBuffers& B);
 hipError_t vkrt_launch_post(int rtMode, int viewAccumulated, int useGI, unsigned n, const float* mainImg, const float* rtImg, float* out,
                             hipStream_t stream);
+
+// denoise.hip: the SVGF stages of vkrt_denoise_diffuse.  Whole-frame W x H planes, rows tightly packed.
+struct DenoiseParams
+{
+  uint32_t W, H;
+  const float4* color;     // G-buffer planes (albedo in the three .w channels)
+  const float4* position;
+  const float4* normal;
+  const float2* rough;     // roughness, metalness
+  const float* viewZ;      // nrd->viewZ
+  const float4* radHitD;   // nrd->diffRadianceHitDist (YCoCg)
+  const float4* histColor; // colour history (rgb demodulated), read at the reprojected taps
+  const float4* geomPrev;  // previous call's (position.xyz, oct normal); normal word 0x80008000 = no geometry
+  float4* geomCur;
+  const float4* momPrev;   // (m1, m2, history length, 0)
+  float4* momCur;
+  float4* rec;             // guide record (viewZ, dz/dx, dz/dy, oct normal)
+  float4* colorOut;        // temporal result (rgb, 0)
+  float4* colorVar;        // k_dn_variance output (rgb, variance)
+  float* out;              // non-NULL: temporal stage only, remodulated rgb written here
+  float curViewProj[16];
+  float prevViewProj[16];
+  int useHistory;
+  int maxHistory;
+};
+struct DenoiseAtrous
+{
+  uint32_t W, H;
+  int step;
+  const float4* rec;
+  const float4* in;        // (rgb, variance)
+  float4* outBuf;
+  float* out;              // non-NULL on the last iteration
+  const float4* color;     // albedo for the remodulation of the last iteration
+  const float4* position;
+  const float4* normal;
+  const float2* rough;
+};
+hipError_t vkrt_launch_denoise_temporal(const DenoiseParams& D, bool variance, hipStream_t stream);
+hipError_t vkrt_launch_denoise_atrous(const DenoiseAtrous& A, hipStream_t stream);

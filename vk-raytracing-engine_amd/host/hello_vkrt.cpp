@@ -86,21 +86,34 @@ void HelloVkrt::setShard(uint32_t rank, uint32_t world)
 
 void HelloVkrt::createOffscreenRender()
 {
-  float** planes[6] = {&m_offscreenColor, &m_positionTexture, &m_normalTexture, &m_roughnessTexture, &m_accumulatedTexture, &m_displayImage};
+  float** planes[10] = {&m_offscreenColor, &m_positionTexture, &m_normalTexture, &m_roughnessTexture, &m_accumulatedTexture, &m_displayImage,
+                        &m_nrdNormRough, &m_nrdViewZ, &m_nrdRadHitD, &m_denoisedTexture};
   m_shard.full_width = (uint32_t)m_size.width;
   m_shard.full_height = (uint32_t)m_size.height;
+  if(m_denoise && m_shard.shard_count > 1)
+    throw std::runtime_error("createOffscreenRender: the denoiser works on whole frames (no strips)");
   const size_t px = (size_t)m_size.width * (m_shard.shard_count > 1 ? vkrt_shard_rows(&m_shard) : (uint32_t)m_size.height);
-  const size_t bytes[6] = {px * 16, px * 16, px * 16, px * 8, px * 16, px * 16};
+  const size_t bytes[10] = {px * 16, px * 16, px * 16, px * 8, px * 16, px * 16, px * 16, px * 4, px * 16, px * 16};
   if(hipSetDevice(m_device) != hipSuccess)
     throw std::runtime_error("createOffscreenRender: hipSetDevice failed");
-  for(int k = 0; k < 6; k++)
+  if(m_denoiser) vkrt_denoiser_destroy(m_denoiser);
+  m_denoiser = nullptr;
+  for(int k = 0; k < 10; k++)
   {
+    if(k >= 6 && !m_denoise)
+    {
+      if(*planes[k]) (void)hipFree(*planes[k]);
+      *planes[k] = nullptr;
+      continue;
+    }
     if(*planes[k]) (void)hipFree(*planes[k]);
     *planes[k] = nullptr;
     if(hipMalloc((void**)planes[k], bytes[k]) != hipSuccess)
       throw std::runtime_error("createOffscreenRender: hipMalloc failed");
     (void)hipMemset(*planes[k], 0, bytes[k]);
   }
+  if(m_denoise)
+    check(vkrt_denoiser_create(m_device, (uint32_t)m_size.width, (uint32_t)m_size.height, &m_denoiser), "vkrt_denoiser_create");
 }
 
 void HelloVkrt::updateUniformBuffer() { m_hostUBO = makeGlobalUniforms(CameraManip, m_size.width, m_size.height); }
@@ -170,6 +183,13 @@ void HelloVkrt::rasterizeGltf(const float clearColor[4])
   // sharded like the path tracer: every plane holds this rank's strips stacked from row 0 (the ABI's shard semantics)
   const vkrt_shard shard = launchShard();
   const vkrt_gbuffer g{m_offscreenColor, m_positionTexture, m_normalTexture, m_roughnessTexture};
+  if(m_denoise)
+  {  // the NRD variant of the raster pass (frag_shader.frag:133-136): pcRaster.viewMatrix = CameraManip.getMatrix() (hello_vulkan.cpp:600)
+    const vkrt_nrd_planes nrd{m_nrdNormRough, m_nrdViewZ, m_nrdRadHitD};
+    const vkrt_mat4 view = CameraManip.getMatrix();
+    check(vkrt_gbuffer_raycast_nrd(m_scene, clearColor, m_pcRay.lightsCount, &m_hostUBO, view.m, &shard, &g, &nrd, nullptr), "vkrt_gbuffer_raycast_nrd");
+    return;
+  }
   check(vkrt_gbuffer_raycast(m_scene, clearColor, m_pcRay.lightsCount /* m_pcRaster.lightsCount, :323 */, &m_hostUBO, &shard, &g, nullptr),
         "vkrt_gbuffer_raycast");
 }
@@ -181,7 +201,26 @@ void HelloVkrt::raytraceRasterizedScene()
   const vkrt_trace_opts opts{m_seed, m_traceFlags};
   const vkrt_shard shard = launchShard();
   const vkrt_gbuffer g{m_offscreenColor, m_positionTexture, m_normalTexture, m_roughnessTexture};
+  if(m_denoise)
+  {
+    const vkrt_nrd_planes nrd{m_nrdNormRough, m_nrdViewZ, m_nrdRadHitD};
+    check(vkrt_hybrid_trace_nrd(m_scene, &m_pcRay, &m_hostUBO, &opts, &shard, &g, &nrd, m_accumulatedTexture, nullptr), "vkrt_hybrid_trace_nrd");
+    return;
+  }
   check(vkrt_hybrid_trace(m_scene, &m_pcRay, &m_hostUBO, &opts, &shard, &g, m_accumulatedTexture, nullptr), "vkrt_hybrid_trace");
+}
+
+void HelloVkrt::denoise()
+{
+  if(!m_denoise || !m_denoiser)
+    throw std::runtime_error("denoise without m_denoise / createOffscreenRender");
+  // the accumulation plane's copy: .w (visibility * (1 - ao)) and the background pass through, .xyz becomes the denoised GI term
+  const size_t bytes = (size_t)m_size.width * m_size.height * 16;
+  if(hipMemcpyAsync(m_denoisedTexture, m_accumulatedTexture, bytes, hipMemcpyDeviceToDevice, nullptr) != hipSuccess)
+    throw std::runtime_error("denoise: hipMemcpyAsync failed");
+  const vkrt_gbuffer g{m_offscreenColor, m_positionTexture, m_normalTexture, m_roughnessTexture};
+  const vkrt_nrd_planes nrd{m_nrdNormRough, m_nrdViewZ, m_nrdRadHitD};
+  check(vkrt_denoise_diffuse(m_denoiser, &m_denoiseSettings, &m_hostUBO, &g, &nrd, m_denoisedTexture, nullptr), "vkrt_denoise_diffuse");
 }
 
 const float* HelloVkrt::drawPostDevice()
@@ -190,7 +229,8 @@ const float* HelloVkrt::drawPostDevice()
   m_pcPost.useGI = m_pcRay.useGI;
   const vkrt_shard shard = launchShard();
   const uint32_t n = (uint32_t)((size_t)m_size.width * vkrt_shard_rows(&shard));  // per pixel: the strips of this rank, or the whole image
-  check(vkrt_post(m_device, &m_pcPost, n, m_offscreenColor, m_accumulatedTexture, m_displayImage, nullptr), "vkrt_post");
+  const float* rt = m_denoise ? m_denoisedTexture : m_accumulatedTexture;
+  check(vkrt_post(m_device, &m_pcPost, n, m_offscreenColor, rt, m_displayImage, nullptr), "vkrt_post");
   return m_displayImage;
 }
 
@@ -216,8 +256,11 @@ void HelloVkrt::destroyResources()
 {
   if(m_scene) vkrt_scene_destroy(m_scene);
   m_scene = nullptr;
-  float** planes[6] = {&m_offscreenColor, &m_positionTexture, &m_normalTexture, &m_roughnessTexture, &m_accumulatedTexture, &m_displayImage};
-  for(int k = 0; k < 6; k++)
+  if(m_denoiser) vkrt_denoiser_destroy(m_denoiser);
+  m_denoiser = nullptr;
+  float** planes[10] = {&m_offscreenColor, &m_positionTexture, &m_normalTexture, &m_roughnessTexture, &m_accumulatedTexture, &m_displayImage,
+                        &m_nrdNormRough, &m_nrdViewZ, &m_nrdRadHitD, &m_denoisedTexture};
+  for(int k = 0; k < 10; k++)
   {
     if(*planes[k]) (void)hipFree(*planes[k]);
     *planes[k] = nullptr;
@@ -280,6 +323,9 @@ AppConfig parseConfig(const std::string& text)
   c.useShadows = j["useShadows"].boolean(c.useShadows);
   c.useAO = j["useAO"].boolean(c.useAO);
   c.useGI = j["useGI"].boolean(c.useGI);
+  c.denoise = j["denoise"].boolean(c.denoise);
+  if(c.denoise && (c.mode != "hybrid" || !c.useGI))
+    throw std::runtime_error("config.json: \"denoise\" needs \"mode\": \"hybrid\" with \"useGI\": true");
   if(j.has("watertight")) c.watertight = j["watertight"].boolean(false) ? 1 : 0;
   if(j.has("anyHitDissolve")) c.anyHitDissolve = j["anyHitDissolve"].boolean(false) ? 1 : 0;
   if(j.has("skipDeadShadowRays")) c.skipDeadShadowRays = j["skipDeadShadowRays"].boolean(false) ? 1 : 0;

@@ -54,6 +54,10 @@ public:
   // hybrid mode (rtMode == 0): main.cpp:510-561 = rasterizeGltf -> raytraceRasterizedScene -> drawPost
   void rasterizeGltf(const float clearColor[4]);          // :583-615 (ray-cast G-buffer: no raster path from HIP)
   void raytraceRasterizedScene();                         // :1450-1473
+  // m_denoise: the G-buffer and hybrid passes also write the NRD front-end planes, and denoise() -- the step that stands where the
+  // reference's commented-out NRD.Denoise sits (main.cpp:565-602) -- filters the GI term of the accumulation plane into a copy that
+  // drawPost composites instead (the accumulation itself stays intact).  Whole image only (no setShard).
+  void denoise();                                         // vkrt_denoise_diffuse
   void drawPost(std::vector<float>& displayRgba);         // :882-897 + post.frag (composite + gamma), downloaded
   const float* drawPostDevice();                          // the same, left on the device (rows of this rank's shard): what a gather sends
   void onResize(int w, int h);                            // :620-626
@@ -89,6 +93,8 @@ public:
   int m_skipDeadShadowRays = -1;  // VKRT_OPT_SKIP_DEAD_SHADOW_RAYS: same pixels, fewer shadow rays
   uint32_t m_traceFlags = 0;
   PushConstantPost m_pcPost{1.0f, 0, 0, 0};  // rtMode 0 = hybrid (hello_vulkan.cpp:917), 1 = path tracer
+  bool m_denoise = false;         // hybrid mode: denoise the GI term (set before createOffscreenRender)
+  vkrt_denoise_settings m_denoiseSettings{sizeof(vkrt_denoise_settings), 5, 32};
 
 private:
   void check(int rc, const char* what) const;
@@ -102,6 +108,12 @@ private:
   float* m_roughnessTexture = nullptr;
   float* m_accumulatedTexture = nullptr;
   float* m_displayImage = nullptr;
+  // denoiser inputs / output (m_denoise): NRD normal-roughness, viewZ, GI radiance planes, the denoised copy of the accumulation
+  float* m_nrdNormRough = nullptr;
+  float* m_nrdViewZ = nullptr;
+  float* m_nrdRadHitD = nullptr;
+  float* m_denoisedTexture = nullptr;
+  vkrt_denoiser* m_denoiser = nullptr;
   bool m_blasRequested = false;
   vkrt_shard m_shard{0, 0, 0, 1, 0};  // whole image unless setShard was called
   // updateFrame()'s function-local statics in the reference (:1508-1509)
@@ -128,6 +140,7 @@ struct AppConfig
   std::string build = "ploc";  // "ploc" (device, default) | "lbvh" (device, fastest build) | "sah" (host)
   std::string mode = "pathtrace";
   bool useShadows = true, useAO = true, useGI = false;  // hello_vulkan.cpp:913-915
+  bool denoise = false;   // hybrid mode with GI: filter the GI term (vkrt_denoise_diffuse) before drawPost
   int watertight = -1, anyHitDissolve = -1, skipDeadShadowRays = -1;  // library options (include/vkrt.h): -1 = key absent (environment / library default)
   int framesPerCall = 1;  // > 1: the frame loop hands that many progressive frames to the library at once (HelloVkrt::pathtraceFrames)
   std::string output;

@@ -179,6 +179,7 @@ int main(int argc, char** argv)
     const auto t0 = std::chrono::steady_clock::now();
     helloVk.loadGltfScene(scenePath);                           // main.cpp:226
     if(!helloVk.m_gltfScene.warnings.empty()) fprintf(stderr, "warning: %s\n", helloVk.m_gltfScene.warnings.c_str());
+    helloVk.m_denoise = cfg.denoise;
     helloVk.createOffscreenRender();                            // main.cpp:228
     helloVk.initRayTracing();                                   // main.cpp:235
     helloVk.m_buildFlags = cfg.build == "lbvh" ? VKRT_BUILD_LBVH_GPU : cfg.build == "sah" ? VKRT_BUILD_SAH_HOST : VKRT_BUILD_PLOC_GPU;
@@ -217,6 +218,8 @@ int main(int argc, char** argv)
       {
         helloVk.rasterizeGltf(cfg.clearColor);                  // main.cpp:513
         helloVk.raytraceRasterizedScene();                      // main.cpp:547
+        if(cfg.denoise)
+          helloVk.denoise();                                    // main.cpp:565-602 (NRD.Denoise, commented out there)
         if(gather && f + 1 == cfg.frames)  // the ranks composite their own strips (post.frag is per pixel); the display strips travel
           gather->gather(helloVk.drawPostDevice(), nullptr);
       }

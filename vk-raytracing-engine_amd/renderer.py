@@ -234,6 +234,58 @@ class Renderer:
         return t, u, v, gid
 
 
+class Denoiser:
+    """vkrt_denoise_diffuse: SVGF of the hybrid GI term (include/vkrt.h).  One handle per device and width x height; it keeps the
+    history between calls, so hand it consecutive frames of one camera path (reset() at a cut)."""
+
+    def __init__(self, device, width, height):
+        self.lib = load_library()
+        self.device, self.width, self.height = int(device), int(width), int(height)
+        h = C.c_void_p()
+        _check(self.lib.vkrt_denoiser_create(self.device, self.width, self.height, C.byref(h)), "vkrt_denoiser_create")
+        self._h = h
+
+    def denoise(self, cam, gbuffer, out=None, iterations=5, max_history=32, stream=None):
+        """gbuffer: the dict Renderer.gbuffer_raycast(view_matrix=...) returns, after hybrid_trace filled its radiance plane.
+        out: torch float32 [H, W, 4] on this device (.xyz written where there is geometry, the rest untouched); a zeroed one
+        when None.  Returns out."""
+        import torch
+
+        W, H = self.width, self.height
+        for k, ch in (("color", 4), ("position", 4), ("normal", 4), ("roughMetal", 2), ("nrdRadianceHitDist", 4)):
+            t = gbuffer[k]
+            if tuple(t.shape) != (H, W, ch) or t.dtype != torch.float32 or not t.is_contiguous():
+                raise VkrtError(f"denoise: plane {k} is {tuple(t.shape)}, the denoiser was made for {(H, W, ch)}")
+        if tuple(gbuffer["nrdViewZ"].shape) != (H, W):
+            raise VkrtError(f"denoise: plane nrdViewZ is {tuple(gbuffer['nrdViewZ'].shape)}, the denoiser was made for {(H, W)}")
+        if out is None:
+            out = torch.zeros((H, W, 4), dtype=torch.float32, device=f"cuda:{self.device}")
+        if tuple(out.shape) != (H, W, 4) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise VkrtError(f"denoise: out is {tuple(out.shape)}, the denoiser was made for {(H, W, 4)}")
+        stream = stream or torch.cuda.current_stream(out.device)
+        gb = abi.Gbuffer(*(gbuffer[k].data_ptr() for k in ("color", "position", "normal", "roughMetal")))
+        nrd = abi.NrdPlanes(gbuffer["nrdNormalRoughness"].data_ptr() if "nrdNormalRoughness" in gbuffer else None,
+                            gbuffer["nrdViewZ"].data_ptr(), gbuffer["nrdRadianceHitDist"].data_ptr())
+        st = abi.DenoiseSettings(C.sizeof(abi.DenoiseSettings), int(iterations), int(max_history))
+        _check(self.lib.vkrt_denoise_diffuse(self._h, C.byref(st), C.byref(cam), C.byref(gb), C.byref(nrd), C.c_void_p(out.data_ptr()),
+                                             C.c_void_p(stream.cuda_stream)), "vkrt_denoise_diffuse")
+        return out
+
+    def reset(self):
+        _check(self.lib.vkrt_denoiser_reset(self._h), "vkrt_denoiser_reset")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.vkrt_denoiser_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def eval_math(op, a, b=None, device=0):
     lib = load_library()
     a = np.ascontiguousarray(a, np.float32)
