@@ -270,7 +270,28 @@ int vkrt_scene_get_option(const vkrt_scene* scene, int option, int* value);
 /* ---- acceleration structure (replaces createBottomLevelASGltf :1001-1011 and
  *      createTopLevelAsGltf :1031-1047) ------------------------------------------- */
 int vkrt_accel_build(vkrt_scene* scene, uint32_t build_flags, void* hip_stream);
+/* After a vkrt_accel_refit: sah_cost is the refitted tree's (same formula as the builders'; reading it synchronises the device), the
+ * number a caller weighs to decide when a full rebuild pays; build_ms stays that of the build. */
 int vkrt_accel_get_info(const vkrt_scene* scene, vkrt_accel_info* out);
+
+/* ---- moving instances (replaces the update path of the TLAS build: VK_BUILD_ACCELERATION_STRUCTURE_ALLOW_UPDATE_BIT_KHR at
+ *      createTopLevelAsGltf :1031-1047, then vkCmdBuildAccelerationStructuresKHR with VK_BUILD_ACCELERATION_STRUCTURE_MODE_UPDATE_KHR).
+ *      Rigid motion of whole instances only: no vertex deformation, no topology change.  These entry points came after ABI version 4
+ *      without changing it or any struct: detect them by symbol. ---------------------------------------------------------------- */
+/* Replace the transforms of nodes [first, first+count) (vkrt_node as at vkrt_scene_create; primMesh must equal the node's
+ * existing primMesh).  Enqueued on hip_stream; the array is copied before return.  After this call the scene's tree is stale:
+ * trace / G-buffer / hybrid entry points (and the vkrt_debug_* tree hooks) return VKRT_ERR_NOT_BUILT until vkrt_accel_refit or
+ * vkrt_accel_build.  Same rules as vkrt_scene_create: a non-finite matrix, a range outside the scene's nodes, a changed primMesh or a
+ * NULL scene give VKRT_ERR_INVALID_ARGUMENT and change nothing; what vkrt_scene_create accepts (a zero scale that hides an
+ * instance, a mirroring matrix) is accepted.  A later vkrt_accel_build builds the moved scene. */
+int vkrt_scene_update_nodes(vkrt_scene* scene, uint32_t first, uint32_t count, const vkrt_node* nodes, void* hip_stream);
+/* Refit the built tree to the scene's current node transforms: same topology, same slots, new boxes and triangle records.
+ * Enqueued on hip_stream.  No host synchronisation and no allocation, except on the first refit of a build.  Everything the build
+ * decided stays (layout, record format, split references, any-hit order, traversal stack); options changed since the build take effect
+ * at the next vkrt_accel_build.  The image stays a property of the triangle set: a refitted tree traces exactly the pixels and ray
+ * counts of a fresh build of the moved scene; only its speed depends on how far the instances moved (vkrt_accel_info.sah_cost).
+ * VKRT_ERR_NOT_BUILT before any vkrt_accel_build. */
+int vkrt_accel_refit(vkrt_scene* scene, void* hip_stream);
 
 /* ---- path trace (replaces HelloVulkan::pathtrace :1423-1448 = one
  *      vkCmdTraceRaysKHR over raytrace.rgen/.rchit/.rmiss/raytraceShadow.rmiss) ---- */

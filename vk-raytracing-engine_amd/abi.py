@@ -211,6 +211,8 @@ VKRT_SYMBOLS = [
     "vkrt_reserve_frames",
     "vkrt_accel_build",
     "vkrt_accel_get_info",
+    "vkrt_scene_update_nodes",
+    "vkrt_accel_refit",
     "vkrt_shard_rows",
     "vkrt_pathtrace",
     "vkrt_pathtrace_frames",
@@ -255,6 +257,10 @@ def declare_vkrt(lib):
     lib.vkrt_accel_build.restype = C.c_int
     lib.vkrt_accel_get_info.argtypes = [C.c_void_p, P(AccelInfo)]
     lib.vkrt_accel_get_info.restype = C.c_int
+    lib.vkrt_scene_update_nodes.argtypes = [C.c_void_p, c_u, c_u, P(Node), C.c_void_p]
+    lib.vkrt_scene_update_nodes.restype = C.c_int
+    lib.vkrt_accel_refit.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vkrt_accel_refit.restype = C.c_int
     lib.vkrt_debug_check_accel.argtypes = [C.c_void_p, P(AccelCheck)]
     lib.vkrt_debug_check_accel.restype = C.c_int
     lib.vkrt_shard_rows.argtypes = [P(Shard)]

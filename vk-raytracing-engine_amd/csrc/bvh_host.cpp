@@ -210,12 +210,6 @@ void invert3x3_rows(const float o2w[12], float w2o[9])
   w2o[8] = (float)((a * e - b * d) * inv);
 }
 
-static inline void xformPoint(const float m[12], const float* p, float* r)
-{
-  r[0] = ((m[0] * p[0] + m[1] * p[1]) + m[2] * p[2]) + m[3];
-  r[1] = ((m[4] * p[0] + m[5] * p[1]) + m[6] * p[2]) + m[7];
-  r[2] = ((m[8] * p[0] + m[9] * p[1]) + m[10] * p[2]) + m[11];
-}
 
 void flatten_instances(const float* positions, const uint32_t* indices, const vkrt_prim_mesh* pm, const vkrt_node* nodes,
                        uint32_t nodeCount, std::vector<FlatTri>& out)
@@ -235,9 +229,9 @@ void flatten_instances(const float* positions, const uint32_t* indices, const vk
       const uint32_t i1 = indices[p.firstIndex + 3 * t + 1] + p.vertexOffset;
       const uint32_t i2 = indices[p.firstIndex + 3 * t + 2] + p.vertexOffset;
       float a[3], b[3], c[3];
-      xformPoint(m, positions + 3 * (size_t)i0, a);
-      xformPoint(m, positions + 3 * (size_t)i1, b);
-      xformPoint(m, positions + 3 * (size_t)i2, c);
+      vkrt_xform_point(m, positions + 3 * (size_t)i0, a);
+      vkrt_xform_point(m, positions + 3 * (size_t)i1, b);
+      vkrt_xform_point(m, positions + 3 * (size_t)i2, c);
       FlatTri ft;
       for(int k = 0; k < 3; k++) { ft.v0[k] = a[k]; ft.e1[k] = b[k] - a[k]; ft.e2[k] = c[k] - a[k]; ft.p1[k] = b[k]; ft.p2[k] = c[k]; }
       ft.gid = gid++; ft.inst = n; ft.prim = t;

@@ -79,25 +79,22 @@ __global__ void k_flatten(FlatArgs A, int watertight, float4* triU, float* triBo
     const DevInstance in = A.instances[inst];
     const uint32_t base = A.instFirstIndex[inst] + 3u * prim, vo = A.instVertexOffset[inst];
     const uint32_t i0 = A.indices[base] + vo, i1 = A.indices[base + 1] + vo, i2 = A.indices[base + 2] + vo;
-    f3 p[3];
     const uint32_t ii[3] = {i0, i1, i2};
+    float p[3][3];
 #pragma unroll
     for(int k = 0; k < 3; k++)
     {
-      const f3 q = mk3(A.positions[3 * ii[k]], A.positions[3 * ii[k] + 1], A.positions[3 * ii[k] + 2]);
-      p[k].x = ((in.o2w[0] * q.x + in.o2w[1] * q.y) + in.o2w[2] * q.z) + in.o2w[3];
-      p[k].y = ((in.o2w[4] * q.x + in.o2w[5] * q.y) + in.o2w[6] * q.z) + in.o2w[7];
-      p[k].z = ((in.o2w[8] * q.x + in.o2w[9] * q.y) + in.o2w[10] * q.z) + in.o2w[11];
+      const float q[3] = {A.positions[3 * ii[k]], A.positions[3 * ii[k] + 1], A.positions[3 * ii[k] + 2]};
+      vkrt_xform_point(in.o2w, q, p[k]);
     }
-    const f3 v0 = p[0], e1 = p[1] - p[0], e2 = p[2] - p[0];
-    const f3 r1 = watertight ? p[1] : e1, r2 = watertight ? p[2] : e2;
-    triU[3 * (size_t)gid + 0] = make_float4(v0.x, v0.y, v0.z, r1.x);
-    triU[3 * (size_t)gid + 1] = make_float4(r1.y, r1.z, r2.x, r2.y);
-    triU[3 * (size_t)gid + 2] = make_float4(r2.z, __int_as_float((int)gid), __int_as_float((int)inst), __int_as_float((int)prim));
+    // (the refit, refit.hip, rewrites records with the same two helpers)
+    float g[9], e1[3], e2[3];
+    vkrt_tri_record(p[0], p[1], p[2], watertight, g, e1, e2);
+    triU[3 * (size_t)gid + 0] = make_float4(g[0], g[1], g[2], g[3]);
+    triU[3 * (size_t)gid + 1] = make_float4(g[4], g[5], g[6], g[7]);
+    triU[3 * (size_t)gid + 2] = make_float4(g[8], __int_as_float((int)gid), __int_as_float((int)inst), __int_as_float((int)prim));
     // the box every builder starts from (tri_prep.h): both forms of the vertices, widened by the reach of the triangle test
-    const float q0[3] = {p[0].x, p[0].y, p[0].z}, q1[3] = {p[1].x, p[1].y, p[1].z}, q2[3] = {p[2].x, p[2].y, p[2].z};
-    const float a1[3] = {e1.x, e1.y, e1.z}, a2[3] = {e2.x, e2.y, e2.z};
-    vkrt_tri_bounds(q0, q1, q2, a1, a2, watertight, lo, hi);
+    vkrt_tri_bounds(p[0], p[1], p[2], e1, e2, watertight, lo, hi);
 #pragma unroll
     for(int k = 0; k < 3; k++)
     {

@@ -25,6 +25,30 @@
 #endif
 
 // (plain float arithmetic in source order; the translation units that include this are built with -ffp-contract=off)
+
+// One object-space vertex to world space with the instance's object->world rows (3x4 row-major): the one sequence of operations that
+// every flatten (k_flatten in lbvh.hip, flatten_instances in bvh_host.cpp) and the refit (refit.hip) use, so that their records agree bit
+// for bit.
+VKRT_HD void vkrt_xform_point(const float m[12], const float p[3], float r[3])
+{
+  r[0] = ((m[0] * p[0] + m[1] * p[1]) + m[2] * p[2]) + m[3];
+  r[1] = ((m[4] * p[0] + m[5] * p[1]) + m[6] * p[2]) + m[7];
+  r[2] = ((m[8] * p[0] + m[9] * p[1]) + m[10] * p[2]) + m[11];
+}
+
+// The 9 geometry floats of a 48-byte triangle record (device_scene.h) from the world-space vertices: (v0, e1, e2) for Moeller-Trumbore
+// or, watertight, the exact vertices (p0, p1, p2).  e1 / e2 = p1 - p0 / p2 - p0 either way (what vkrt_tri_bounds takes).
+VKRT_HD void vkrt_tri_record(const float p0[3], const float p1[3], const float p2[3], int watertight, float g[9], float e1[3], float e2[3])
+{
+  for(int k = 0; k < 3; k++)
+  {
+    e1[k] = p1[k] - p0[k];
+    e2[k] = p2[k] - p0[k];
+    g[k] = p0[k];
+    g[3 + k] = watertight ? p1[k] : e1[k];
+    g[6 + k] = watertight ? p2[k] : e2[k];
+  }
+}
 VKRT_HD float vkrt_tri_slop(const float e1[3], const float e2[3])
 {
   const float l1 = (e1[0] * e1[0] + e1[1] * e1[1]) + e1[2] * e1[2];

@@ -6,6 +6,7 @@
 // without a HIP device the compute entry points fail with VKRT_ERR_NO_DEVICE.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -27,6 +28,7 @@
 #define VKRT_WF_FRAMES_IN_FLIGHT_DEFAULT 3
 #define VKRT_SPLIT_BUDGET_DEFAULT -1  // automatic (round 5): vkrt_accel_build decides per scene
 #include "lbvh.h"
+#include "refit.h"
 
 namespace {
 
@@ -92,6 +94,10 @@ struct vkrt_scene
                                 VKRT_WF_FRAMES_IN_FLIGHT_DEFAULT, VKRT_SPLIT_BUDGET_DEFAULT};
   bool hasLargeTriangles = false;  // some instanced triangle covers more than 1 % of the largest face of the scene's box (any-hit order heuristic)
   bool wavefront = true;  // execution mode the acceleration structure was built for (opt[VKRT_OPT_MODE] at vkrt_accel_build)
+  // moving instances (vkrt_scene_update_nodes / vkrt_accel_refit)
+  bool stale = false;      // node transforms changed since the tree was built or refitted: no trace until the next refit or build
+  bool refitted = false;   // the tree has been refitted since its build: vkrt_accel_get_info reads the refit's SAH cost from the device
+  vkrt::RefitScratch refit;  // level lists + exact node boxes of the current build (allocated at its first refit)
 };
 
 namespace {
@@ -241,6 +247,21 @@ void freeAccel(vkrt_scene* s)
   if(s->accelShade) (void)hipFree(s->accelShade);
   s->accelNodes = s->accelTris = s->accelShade = nullptr;
   s->built = false;
+  vkrt::refit_free(s->refit);
+  s->refitted = false;
+  s->stale = false;
+}
+
+// gl_ObjectToWorldEXT / gl_WorldToObjectEXT of one node (rchit:72-76): the same code at vkrt_scene_create and vkrt_scene_update_nodes,
+// so that a moved scene's records are bit for bit those of a scene created with the moved nodes
+void makeInstance(const vkrt_node& node, DevInstance& in)
+{
+  memset(&in, 0, sizeof in);
+  for(int r = 0; r < 3; r++)
+    for(int c = 0; c < 4; c++)
+      in.o2w[r * 4 + c] = node.worldMatrix[c * 4 + r];
+  vkrt::invert3x3_rows(in.o2w, in.w2o);
+  in.primMesh = node.primMesh;
 }
 
 int setDevice(const vkrt_scene* s)
@@ -374,15 +395,7 @@ int vkrt_scene_create(const vkrt_scene_desc* d, int device, vkrt_scene** out)
   // instances: object->world rows + inverse (gl_ObjectToWorldEXT / gl_WorldToObjectEXT, rchit:72-76)
   std::vector<DevInstance> inst(d->node_count);
   for(uint32_t n = 0; n < d->node_count; n++)
-  {
-    DevInstance& in = inst[n];
-    memset(&in, 0, sizeof in);
-    for(int r = 0; r < 3; r++)
-      for(int c = 0; c < 4; c++)
-        in.o2w[r * 4 + c] = d->nodes[n].worldMatrix[c * 4 + r];
-    vkrt::invert3x3_rows(in.o2w, in.w2o);
-    in.primMesh = d->nodes[n].primMesh;
-  }
+    makeInstance(d->nodes[n], inst[n]);
   if((rc = upload(s, inst.data(), inst.size(), &D.instances)) != VKRT_OK) return bail(rc);
   // textures: RGBA8 pool + table + sRGB decode table
   float lut[512];
@@ -990,6 +1003,79 @@ int vkrt_accel_get_info(const vkrt_scene* s, vkrt_accel_info* out)
   if(!s->built)
     return fail(VKRT_ERR_NOT_BUILT, "vkrt_accel_build has not been called");
   *out = s->info;
+  if(s->refitted && s->refit.levelStart.size() > 1)
+  {  // the refitted tree's SAH cost (k_rf_finish), same formula as the builders'; reading it waits for the refit
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(&out->sah_cost, &s->refit.words[2], 4, hipMemcpyDeviceToHost));
+  }
+  return VKRT_OK;
+}
+
+int vkrt_scene_update_nodes(vkrt_scene* s, uint32_t first, uint32_t count, const vkrt_node* nodes, void* hip_stream)
+{
+  if(!s)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "scene is NULL");
+  if(count && !nodes)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "nodes is NULL");
+  if((uint64_t)first + count > s->nodes.size())
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "nodes [%u, %llu) outside the scene's %zu nodes", first, (unsigned long long)first + count, s->nodes.size());
+  // the rules of vkrt_scene_create, checked for the whole range before anything changes (a refused call leaves the scene as it was)
+  for(uint32_t i = 0; i < count; i++)
+  {
+    if(nodes[i].primMesh != s->nodes[(size_t)first + i].primMesh)
+      return fail(VKRT_ERR_INVALID_ARGUMENT, "node %u: primMesh %d != %d (an update moves instances, it does not change their geometry)", first + i,
+                  nodes[i].primMesh, s->nodes[(size_t)first + i].primMesh);
+    for(int k = 0; k < 16; k++)
+      if(!std::isfinite(nodes[i].worldMatrix[k]))
+        return fail(VKRT_ERR_INVALID_ARGUMENT, "node %u: worldMatrix[%d] is not finite", first + i, k);
+  }
+  if(count == 0)
+    return VKRT_OK;
+  int rc = setDevice(s);
+  if(rc != VKRT_OK)
+    return rc;
+  std::vector<DevInstance> inst(count);
+  for(uint32_t i = 0; i < count; i++)
+    makeInstance(nodes[i], inst[i]);
+  // Stream-ordered: the records travel as kernel arguments of launches on hip_stream, after whatever the caller enqueued there before
+  // (a trace that still reads the old transforms) and before whatever comes after (the refit, the next trace).  The trace entry points'
+  // internal lane streams fork from and join to the caller's stream, so ordering on it is all that is needed.
+  HIP_TRY(vkrt::upload_instances(const_cast<DevInstance*>(s->dev.instances), first, count, inst.data(), (hipStream_t)hip_stream));
+  std::copy(nodes, nodes + count, s->nodes.begin() + first);
+  // (the any-hit stage's per-instance dissolve flags -- bit 31 of the records' id words -- follow from primMesh, which an update keeps)
+  if(s->built)
+    s->stale = true;
+  return VKRT_OK;
+}
+
+int vkrt_accel_refit(vkrt_scene* s, void* hip_stream)
+{
+  if(!s)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "scene is NULL");
+  if(!s->built)
+    return fail(VKRT_ERR_NOT_BUILT, "vkrt_accel_refit before vkrt_accel_build");
+  int rc = setDevice(s);
+  if(rc != VKRT_OK)
+    return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  std::string err;
+  if(!s->refit.mem)
+  {  // first refit of this build: scratch + level lists (the one place a refit allocates and synchronises)
+    const uint32_t nodeCap = (uint32_t)(s->info.node_bytes / (s->dev.layout == 1u ? VKRT_WNODE_BYTES : 64u));
+    if((rc = vkrt::refit_prepare(s->dev, nodeCap, stream, s->refit, err)) != VKRT_OK)
+    {
+      vkrt::refit_free(s->refit);
+      return fail(rc, "vkrt_accel_refit: %s", err.c_str());
+    }
+  }
+  // Everything the build decided stays: layout, record format, split references, dissolve flags, any-hit order, stackCap, step bound.
+  // sceneLo / sceneHi (read only by the any-hit order heuristic, which cannot change a pixel) also stay as built: updating them would
+  // need the new bounds on the host, i.e. a synchronisation.
+  if((rc = vkrt::refit_enqueue(s->dev, (uint32_t)s->nodes.size(), s->refit, stream, err)) != VKRT_OK)
+    return fail(rc, "vkrt_accel_refit: %s", err.c_str());
+  s->refitted = true;
+  s->stale = false;
   return VKRT_OK;
 }
 
@@ -1028,6 +1114,8 @@ int vkrt_pathtrace_frames(vkrt_scene* s, const PushConstantRay* pc, const Global
     return fail(VKRT_ERR_INVALID_ARGUMENT, "NULL image");
   if(!s->built)
     return fail(VKRT_ERR_NOT_BUILT, "vkrt_pathtrace before vkrt_accel_build");
+  if(s->stale)
+    return fail(VKRT_ERR_NOT_BUILT, "vkrt_pathtrace after vkrt_scene_update_nodes: vkrt_accel_refit or vkrt_accel_build first");
   if(shard->full_width == 0 || shard->full_height == 0)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "empty launch size");
   if(shard->shard_count > 1 && (shard->strip_rows == 0 || shard->shard_index >= shard->shard_count))
@@ -1144,6 +1232,8 @@ int fillParams(vkrt_scene* s, const PushConstantRay* pc, const GlobalUniforms* c
 {
   if(!s->built)
     return fail(VKRT_ERR_NOT_BUILT, "acceleration structure not built");
+  if(s->stale)
+    return fail(VKRT_ERR_NOT_BUILT, "node transforms changed since the acceleration structure was built: vkrt_accel_refit or vkrt_accel_build first");
   if(shard->full_width == 0 || shard->full_height == 0)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "empty launch size");
   if(shard->shard_count > 1 && (shard->strip_rows == 0 || shard->shard_index >= shard->shard_count))
@@ -1391,6 +1481,8 @@ int vkrt_debug_trace_rays(vkrt_scene* s, uint32_t n, const float* origins, const
     return fail(VKRT_ERR_INVALID_ARGUMENT, "NULL argument");
   if(!s->built)
     return fail(VKRT_ERR_NOT_BUILT, "vkrt_debug_trace_rays before vkrt_accel_build");
+  if(s->stale)
+    return fail(VKRT_ERR_NOT_BUILT, "vkrt_debug_trace_rays after vkrt_scene_update_nodes: vkrt_accel_refit or vkrt_accel_build first");
   if(n == 0)
     return VKRT_OK;
   int rc = setDevice(s);
@@ -1423,6 +1515,8 @@ int vkrt_debug_check_accel(vkrt_scene* s, vkrt_accel_check* out)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "NULL argument");
   if(!s->built)
     return fail(VKRT_ERR_NOT_BUILT, "vkrt_accel_build has not run");
+  if(s->stale)
+    return fail(VKRT_ERR_NOT_BUILT, "vkrt_debug_check_accel after vkrt_scene_update_nodes: vkrt_accel_refit or vkrt_accel_build first");
   int rc = setDevice(s);
   if(rc != VKRT_OK)
     return rc;

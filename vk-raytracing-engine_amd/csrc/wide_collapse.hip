@@ -345,35 +345,19 @@ __global__ void k_w8_write(Emit E, uint32_t lvl)
     slotOf[bc] = bs;
     childAt[bs] = bc;
   }
-  // grid: origin = lo, per-axis power-of-two cell so that the extent fits QMAX cells
-  const int QMAX = VKRT_WNODE_QMAX;
-  uint32_t eb[3];
-  for(int q = 0; q < 3; q++)
+  // grid: origin = lo, per-axis power-of-two cell so that the extent fits QMAX cells (wide_node.h, shared with the refit)
+  float slo[8][3], shi[8][3];
+  uint32_t slotMask = 0;
+  for(int s = 0; s < 8; s++)
   {
-    const double ext = (double)hi[q] - (double)lo[q];
-    int e = -126;
-    if(ext > 0)
-    {
-      int ex;
-      const double m = frexp(ext / (double)QMAX, &ex);  // ext / QMAX = m 2^ex, m in [0.5, 1): ceil(log2) = ex, or ex - 1 for an exact power of two
-      e = m == 0.5 ? ex - 1 : ex;
-    }
-    e = e < -126 ? -126 : (e > 126 ? 126 : e);
-    for(;;)
-    {  // make sure every child's hi really fits (ceil may need one more cell)
-      const double sc = ldexp(1.0, e);
-      bool ok = true;
-      for(int k = 0; k < n; k++)
-        if(ceil(((double)kids[k].hi[q] - (double)lo[q]) / sc) > (double)QMAX) ok = false;
-      if(ok || e >= 126) break;
-      e++;
-    }
-    eb[q] = (uint32_t)(e + 127);
+    const int c = childAt[s];
+    for(int q = 0; q < 3; q++) { slo[s][q] = c < 0 ? 0.0f : kids[c].lo[q]; shi[s][q] = c < 0 ? 0.0f : kids[c].hi[q]; }
+    if(c >= 0) slotMask |= 1u << s;
   }
-  uint32_t imask = 0, meta[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t eb[3];
   uint16_t qlo[3][8], qhi[3][8];
-  for(int q = 0; q < 3; q++)
-    for(int s = 0; s < 8; s++) { qlo[q][s] = 0; qhi[q][s] = 0; }
+  vkrt_wnode_quantise(lo, hi, slotMask, slo, shi, eb, qlo, qhi);
+  uint32_t imask = 0, meta[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const uint32_t triBase = E.baseT[me], childBase = E.baseI[me];
   uint32_t triOff = 0, nInternal = 0;
   double sah = (double)areaOf(lo, hi) * kNodeCost;
@@ -383,18 +367,6 @@ __global__ void k_w8_write(Emit E, uint32_t lvl)
     if(c < 0)
       continue;
     const Kid& ch = kids[c];
-    for(int q = 0; q < 3; q++)
-    {
-      const double sc = ldexp(1.0, (int)eb[q] - 127), o = (double)lo[q];
-      int ql = (int)floor(((double)ch.lo[q] - o) / sc);
-      ql = ql < 0 ? 0 : (ql > QMAX ? QMAX : ql);
-      while(ql > 0 && o + ql * sc > (double)ch.lo[q]) ql--;
-      int qh = (int)ceil(((double)ch.hi[q] - o) / sc);
-      qh = qh < 0 ? 0 : (qh > QMAX ? QMAX : qh);
-      while(qh < QMAX && o + qh * sc < (double)ch.hi[q]) qh++;
-      qlo[q][s] = (uint16_t)ql;
-      qhi[q][s] = (uint16_t)qh;
-    }
     if(!((leafMask >> c) & 1u))
     {
       imask |= 1u << s;

@@ -118,6 +118,47 @@ int vkrt_host_render_gltf(const char* path, int device, int width, int height, i
   catch(const std::exception& e) { g_err = e.what(); return 1; }
 }
 
+// vkrt_host_render_gltf with moving instances: build, then `steps` times HelloVkrt::updateNodeTransforms(first, matrices[step]) +
+// refitAccel (matrices: steps x count x 16 floats, column-major), then the frames; rgbaOut as vkrt_host_render_gltf
+int vkrt_host_render_gltf_moved(const char* path, int device, int width, int height, int samples, int depth, int frames, uint32_t seed0,
+                                const float* eye, const float* center, const float* up, float fov, uint32_t buildFlags, uint32_t first,
+                                uint32_t count, uint32_t steps, const float* matrices, float* rgbaOut)
+{
+  try
+  {
+    HelloVkrt vk(device);
+    vk.setup(width, height);
+    vk.CameraManip.setLookat(Vec3{eye[0], eye[1], eye[2]}, Vec3{center[0], center[1], center[2]}, Vec3{up[0], up[1], up[2]});
+    vk.CameraManip.setFov(fov);
+    vk.loadGltfScene(path);
+    vk.createOffscreenRender();
+    vk.initRayTracing();
+    vk.m_buildFlags = buildFlags;
+    vk.createBottomLevelASGltf();
+    vk.createTopLevelAsGltf();
+    for(uint32_t k = 0; k < steps; k++)
+    {
+      vk.updateNodeTransforms(first, std::vector<float>(matrices + (size_t)k * count * 16, matrices + (size_t)(k + 1) * count * 16));
+      vk.refitAccel();
+    }
+    vk.m_pcRay.samples = samples;
+    vk.m_pcRay.depth = depth;
+    const float clear[4] = {1, 1, 1, 1};
+    for(int f = 0; f < frames; f++)
+    {
+      vk.updateUniformBuffer();
+      vk.updateFrame();
+      vk.m_seed = seed0 + (uint32_t)f;
+      vk.pathtrace(clear);
+    }
+    std::vector<float> img;
+    vk.downloadImage(img);
+    memcpy(rgbaOut, img.data(), img.size() * sizeof(float));
+    return 0;
+  }
+  catch(const std::exception& e) { g_err = e.what(); return 1; }
+}
+
 // The hybrid sequence of the reference's frame loop (main.cpp:510-561: rasterizeGltf -> raytraceRasterizedScene -> drawPost)
 // through HelloVkrt for ONE rank of a `world`-rank job (setShard): displayOut receives the rank's display strips (rows of its
 // shard x width x rgba32f, after post.frag).  world = 1: the whole image.  GI on, shadows and AO on.

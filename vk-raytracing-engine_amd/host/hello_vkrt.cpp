@@ -77,6 +77,29 @@ void HelloVkrt::createTopLevelAsGltf()
   check(vkrt_accel_build(m_scene, m_buildFlags, nullptr), "vkrt_accel_build");
 }
 
+void HelloVkrt::updateNodeTransforms(uint32_t first, const std::vector<float>& matrices)
+{
+  if(!m_scene)
+    throw std::runtime_error("updateNodeTransforms before loadGltfScene");
+  if(matrices.size() % 16 != 0)
+    throw std::runtime_error("updateNodeTransforms: matrices must hold 16 floats per node");
+  const uint32_t count = (uint32_t)(matrices.size() / 16);
+  if((uint64_t)first + count > m_gltfScene.m_nodes.size())
+    throw std::runtime_error("updateNodeTransforms: node range outside the scene");
+  std::vector<vkrt_node> nodes(m_gltfScene.m_nodes.begin() + first, m_gltfScene.m_nodes.begin() + first + count);
+  for(uint32_t i = 0; i < count; i++)
+    memcpy(nodes[i].worldMatrix, &matrices[(size_t)i * 16], 16 * sizeof(float));
+  check(vkrt_scene_update_nodes(m_scene, first, count, nodes.data(), nullptr), "vkrt_scene_update_nodes");
+  std::copy(nodes.begin(), nodes.end(), m_gltfScene.m_nodes.begin() + first);  // the host copy follows, like m_gltfScene's node matrices
+}
+
+void HelloVkrt::refitAccel()
+{
+  if(!m_scene)
+    throw std::runtime_error("refitAccel before loadGltfScene");
+  check(vkrt_accel_refit(m_scene, nullptr), "vkrt_accel_refit");
+}
+
 void HelloVkrt::setShard(uint32_t rank, uint32_t world)
 {
   if(world == 0 || rank >= world)

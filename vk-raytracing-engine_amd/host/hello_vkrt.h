@@ -41,6 +41,10 @@ public:
   void initRayTracing();                                  // :901-919
   void createBottomLevelASGltf();                         // :1001-1011
   void createTopLevelAsGltf();                            // :1031-1047
+  // the reference's TLAS update path (buildTlas(..., update = true) with ALLOW_UPDATE, raytrace_vkpp's animation loop): new transforms
+  // for nodes [first, first + matrices.size() / 16) (column-major 4x4 each, primMesh kept), then a refit of the built tree
+  void updateNodeTransforms(uint32_t first, const std::vector<float>& matrices);  // vkrt_scene_update_nodes
+  void refitAccel();                                                             // vkrt_accel_refit
   void createOffscreenRender();                           // :637-665 (colour image only)
   void updateUniformBuffer();                             // :61-102
   void resetFrame();                                      // :1501-1504

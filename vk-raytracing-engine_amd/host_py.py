@@ -32,6 +32,10 @@ def lib():
         L.vkrt_host_render_gltf.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p]
         L.vkrt_host_render_gltf.restype = C.c_int
+        L.vkrt_host_render_gltf_moved.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                  C.c_void_p, C.c_void_p]
+        L.vkrt_host_render_gltf_moved.restype = C.c_int
         L.vkrt_host_render_gltf_hybrid.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_float, C.c_uint32, C.c_uint32, C.c_void_p]
         L.vkrt_host_render_gltf_hybrid.restype = C.c_int
@@ -128,6 +132,22 @@ def render_gltf(path, width, height, samples=1, depth=3, frames=1, seed0=0, eye=
                                      c.ctypes.data, p.ctypes.data, fov, build, img.ctypes.data)
     if rc != 0:
         raise RuntimeError("vkrt_host_render_gltf: " + lib().vkrt_host_last_error().decode())
+    return img
+
+
+def render_gltf_moved(path, width, height, first, matrices, samples=1, depth=3, frames=1, seed0=0, eye=(0, 0, 15), center=(0, 0, 0), up=(0, 1, 0),
+                      fov=60.0, build=abi.VKRT_BUILD_PLOC_GPU, device=0):
+    """render_gltf after moving nodes through the C++ HelloVkrt: matrices (steps, count, 16) column-major; each step is
+    updateNodeTransforms(first, matrices[step]) + refitAccel()."""
+    m = np.ascontiguousarray(matrices, np.float32)
+    if m.ndim == 2:
+        m = m[None]
+    img = np.zeros((height, width, 4), np.float32)
+    e, c, p = (np.asarray(v, np.float32) for v in (eye, center, up))
+    rc = lib().vkrt_host_render_gltf_moved(os.fsencode(path), device, width, height, samples, depth, frames, seed0, e.ctypes.data, c.ctypes.data,
+                                           p.ctypes.data, fov, build, first, m.shape[1], m.shape[0], m.ctypes.data, img.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("vkrt_host_render_gltf_moved: " + lib().vkrt_host_last_error().decode())
     return img
 
 

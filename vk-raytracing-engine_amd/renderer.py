@@ -57,6 +57,7 @@ class Renderer:
         self._h = h
         del keep
         self.lights_count = int(flat.lights.shape[0])
+        self._prim_mesh = np.array(flat.nodes["primMesh"], np.int32)  # update_nodes keeps every node's primMesh
         for k, v in (options or {}).items():
             self.set_option(k, v)
         if build:
@@ -83,6 +84,26 @@ class Renderer:
         flags = {"sah": abi.VKRT_BUILD_SAH_HOST, "lbvh": abi.VKRT_BUILD_LBVH_GPU, "ploc": abi.VKRT_BUILD_PLOC_GPU}[kind]
         _check(self.lib.vkrt_accel_build(self._h, flags, None), "vkrt_accel_build")
         self.build_kind = kind
+
+    def update_nodes(self, first, world_matrices, stream=None):
+        """vkrt_scene_update_nodes: new transforms for nodes [first, first + n).  world_matrices: (n, 16) float32, column-major like
+        vkrt_node.worldMatrix and FlatScene.nodes["worldMatrix"]; every node keeps its primMesh.  Enqueued on `stream` (a torch stream;
+        None = the default stream); the tree is stale until refit() or build()."""
+        m = np.ascontiguousarray(world_matrices, np.float32).reshape(-1, 16)
+        first, n = int(first), m.shape[0]
+        if first < 0 or first + n > self._prim_mesh.shape[0]:
+            raise VkrtError(f"update_nodes: nodes [{first}, {first + n}) outside the scene's {self._prim_mesh.shape[0]} nodes")
+        arr = (abi.Node * max(n, 1))()
+        for i in range(n):
+            arr[i].worldMatrix[:] = [float(v) for v in m[i]]
+            arr[i].primMesh = int(self._prim_mesh[first + i])
+        st = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        _check(self.lib.vkrt_scene_update_nodes(self._h, first, n, arr, st), "vkrt_scene_update_nodes")
+
+    def refit(self, stream=None):
+        """vkrt_accel_refit: the built tree follows the current node transforms (same topology, new boxes), enqueued on `stream`."""
+        st = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        _check(self.lib.vkrt_accel_refit(self._h, st), "vkrt_accel_refit")
 
     def close(self):
         if getattr(self, "_h", None):
