@@ -306,6 +306,22 @@ void pack_triangles(const std::vector<FlatTri>& tris, const std::vector<uint32_t
   }
 }
 
+FlatTri unpack_triangle(const float rec[12], bool watertight)
+{
+  FlatTri ft;
+  for(int c = 0; c < 3; c++)
+  {
+    ft.v0[c] = rec[c];
+    ft.e1[c] = watertight ? rec[3 + c] - rec[c] : rec[3 + c];
+    ft.e2[c] = watertight ? rec[6 + c] - rec[c] : rec[6 + c];
+    ft.p1[c] = watertight ? rec[3 + c] : rec[c] + rec[3 + c];
+    ft.p2[c] = watertight ? rec[6 + c] : rec[c] + rec[6 + c];
+  }
+  memcpy(&ft.gid, &rec[9], 4); memcpy(&ft.inst, &rec[10], 4); memcpy(&ft.prim, &rec[11], 4);
+  ft.gid &= 0x7fffffffu;
+  return ft;
+}
+
 }  // namespace vkrt
 
 // =========================================================================================================

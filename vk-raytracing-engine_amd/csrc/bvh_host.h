@@ -41,6 +41,9 @@ void pack_tri_shade(const std::vector<FlatTri>& tris, const std::vector<uint32_t
 // 48-byte device triangle records in slot order: (v0, e1, e2, ids) for Moeller-Trumbore, (p0, p1, p2, ids) when watertight
 void pack_triangles(const std::vector<FlatTri>& tris, const std::vector<uint32_t>& order, std::vector<float>& out, bool watertight = false,
                     const std::vector<uint8_t>* instDissolves = nullptr);  // instDissolves[inst] != 0: the instance's material is not opaque
+// One 48-byte record back as a FlatTri: vertices, edges and ids, gid without bit 31 (the any-hit flag pack_triangles sets).  The form
+// the record does not hold is re-derived: p1 = v0 + e1 from a (v0, e1, e2) record, e1 = p1 - p0 from a watertight (p0, p1, p2) one.
+FlatTri unpack_triangle(const float rec[12], bool watertight);
 
 }  // namespace vkrt
 

@@ -115,6 +115,15 @@ int upload(vkrt_scene* s, const T* src, size_t count, const T** dst)
   return VKRT_OK;
 }
 
+// node transforms: vkrt_scene_create and vkrt_scene_update_nodes refuse the same ones
+int checkTransform(const vkrt_node& n, uint32_t i)
+{
+  for(int k = 0; k < 16; k++)
+    if(!std::isfinite(n.worldMatrix[k]))
+      return fail(VKRT_ERR_INVALID_ARGUMENT, "node %u: worldMatrix[%d] is not finite", i, k);
+  return VKRT_OK;
+}
+
 int validate(const vkrt_scene_desc* d)
 {
   if(!d)
@@ -149,9 +158,8 @@ int validate(const vkrt_scene_desc* d)
   {
     if(d->nodes[i].primMesh < 0 || (uint32_t)d->nodes[i].primMesh >= d->prim_mesh_count)
       return fail(VKRT_ERR_INVALID_ARGUMENT, "node %u: primMesh %d out of range", i, d->nodes[i].primMesh);
-    for(int k = 0; k < 16; k++)
-      if(!std::isfinite(d->nodes[i].worldMatrix[k]))
-        return fail(VKRT_ERR_INVALID_ARGUMENT, "node %u: worldMatrix[%d] is not finite", i, k);
+    if(checkTransform(d->nodes[i], i) != VKRT_OK)
+      return VKRT_ERR_INVALID_ARGUMENT;
   }
   // the builders compare and quantise boxes: NaN / inf coordinates have no place in an acceleration structure (a Vulkan driver is
   // free to drop such triangles; here they are refused up front)
@@ -322,6 +330,58 @@ int ensureEventPool(vkrt_scene* s, int frames)
 // frames a call keeps in flight: the option, but never more than the call has
 int framesInFlight(const vkrt_scene* s, int frames) { return std::max(1, std::min(s->opt[VKRT_OPT_WF_FRAMES_IN_FLIGHT], frames)); }
 #define VKRT_FRAMES_PER_BATCH 32  // a longer call is rendered as batches of this many frames (bounds the event pool)
+
+// traversal workgroup size (the non-default triangle modes exist for the default 64-thread workgroup only)
+int travBlock(const vkrt_scene* s) { return (s->dev.watertight || s->dev.dissolve) ? 64 : s->opt[VKRT_OPT_WF_TRAV_BLOCK]; }
+
+// the tree can be traced: built, and not moved since (`who` names the caller in the refusal)
+int checkBuilt(const vkrt_scene* s, const char* who)
+{
+  if(!s->built)
+    return fail(VKRT_ERR_NOT_BUILT, "%s before vkrt_accel_build", who);
+  if(s->stale)
+    return fail(VKRT_ERR_NOT_BUILT, "%s after vkrt_scene_update_nodes: vkrt_accel_refit or vkrt_accel_build first", who);
+  return VKRT_OK;
+}
+
+int checkShard(const vkrt_shard* shard)
+{
+  if(shard->full_width == 0 || shard->full_height == 0)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "empty launch size");
+  if(shard->shard_count > 1 && (shard->strip_rows == 0 || shard->shard_index >= shard->shard_count))
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "bad shard (strip_rows %u, %u of %u)", shard->strip_rows, shard->shard_index,
+                shard->shard_count);
+  return VKRT_OK;
+}
+
+// The TraceParams every trace entry point shares: tree, camera, seed, public flags, the shard's rows and its 8x8 tiles, counters.
+// Callers check the tree (checkBuilt) and the shard (checkShard) first and add what is their own.
+int launchParams(const vkrt_scene* s, const PushConstantRay* pc, const GlobalUniforms* cam, const vkrt_trace_opts* opts, const vkrt_shard* shard,
+                 TraceParams& P)
+{
+  memset(&P, 0, sizeof P);
+  P.sc = s->dev;
+  if(pc) P.pc = *pc;
+  memcpy(P.viewInverse, cam->viewInverse.m, sizeof P.viewInverse);
+  memcpy(P.projInverse, cam->projInverse.m, sizeof P.projInverse);
+  P.seed = opts ? opts->seed : 0u;
+  P.flags = (opts ? opts->flags : 0u) & VKRT_TRACE_PUBLIC_FLAGS;  // (the hybrid passes never skip shadow rays: hitDists needs their result)
+  P.fullW = shard->full_width;
+  P.fullH = shard->full_height;
+  const bool sharded = shard->shard_count > 1;
+  P.stripRows = sharded ? shard->strip_rows : 0u;
+  P.shardCount = sharded ? shard->shard_count : 1u;
+  P.shardIndex = sharded ? shard->shard_index : 0u;
+  P.localRows = vkrt_shard_rows(shard);
+  P.counters = s->counters;
+  P.tilesX = (P.fullW + 7) / 8;
+  const uint64_t tiles = (uint64_t)P.tilesX * ((P.localRows + 7) / 8);
+  if(tiles * 64 >= 0xFFFFFFFFull)
+    return fail(VKRT_ERR_UNSUPPORTED, "launch too large");
+  P.tileCount = (uint32_t)tiles;
+  P.tileFirst = 0;
+  return VKRT_OK;
+}
 
 }  // namespace
 
@@ -618,11 +678,9 @@ int vkrt_reserve_frames(vkrt_scene* s, const vkrt_shard* shard, uint32_t frames_
     return fail(VKRT_ERR_INVALID_ARGUMENT, "NULL argument");
   if(frames_per_call == 0)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "frames_per_call is 0");
-  if(shard->full_width == 0 || shard->full_height == 0)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "empty launch size");
-  if(shard->shard_count > 1 && (shard->strip_rows == 0 || shard->shard_index >= shard->shard_count))
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "bad shard");
-  int rc = setDevice(s);
+  int rc = checkShard(shard);
+  if(rc == VKRT_OK)
+    rc = setDevice(s);
   if(rc != VKRT_OK)
     return rc;
   const uint64_t tiles = (uint64_t)((shard->full_width + 7) / 8) * ((vkrt_shard_rows(shard) + 7) / 8);
@@ -640,326 +698,137 @@ int vkrt_reserve_frames(vkrt_scene* s, const vkrt_shard* shard, uint32_t frames_
   return rc2;
 }
 
-static int accelBuildOnce(vkrt_scene* s, uint32_t flags, void* hip_stream);
+namespace {
 
-// VKRT_OPT_SPLIT_BUDGET = -1: the library decides.  Triangle pre-splitting pays where large triangles are not aligned with the axes
-// (+14 % ... +97 % on a rotated building) and costs 1-8 % elsewhere (profiles/r05_split_rotated.jsonl), and the SAH cost of the finished
-// tree tells the two apart: a 30 % budget lowers it by 18-30 % in the first case and by at most 5 % -- or raises it -- in the second.
-// So: build with a 30 % budget, build without, keep the split tree only when its cost is below 0.9 of the unsplit one (one more build
-// in that case; device builds are ~13 ms each for 262 k triangles).  Pixels do not depend on the outcome.
-int vkrt_accel_build(vkrt_scene* s, uint32_t flags, void* hip_stream)
+// What a builder produced: the tree's three device buffers and what vkrt_accel_info reports about it.  installTree moves it into the scene.
+struct BuiltTree
 {
-  if(!s)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "scene is NULL");
-  const bool deviceBuild = flags == 0 || (flags & (VKRT_BUILD_LBVH_GPU | VKRT_BUILD_PLOC_GPU)) != 0;
-  if(s->opt[VKRT_OPT_SPLIT_BUDGET] >= 0 || !deviceBuild)
-  {
-    const int keep = s->opt[VKRT_OPT_SPLIT_BUDGET];
-    if(keep < 0) s->opt[VKRT_OPT_SPLIT_BUDGET] = 0;  // (the host builder does not split)
-    const int rc = accelBuildOnce(s, flags, hip_stream);
-    s->splitResolved = s->opt[VKRT_OPT_SPLIT_BUDGET];
-    s->opt[VKRT_OPT_SPLIT_BUDGET] = keep;
-    return rc;
-  }
-  const auto t0 = std::chrono::steady_clock::now();
-  auto once = [&](int budget, float* sah) {
-    s->opt[VKRT_OPT_SPLIT_BUDGET] = budget;
-    const int rc = accelBuildOnce(s, flags, hip_stream);
-    if(rc == VKRT_OK && sah) *sah = s->info.sah_cost;
-    return rc;
-  };
-  float sahSplit = 0.0f, sahPlain = 0.0f;
-  int rc = once(30, &sahSplit);
-  if(rc == VKRT_OK) rc = once(0, &sahPlain);
-  int resolved = 0;
-  if(rc == VKRT_OK && sahSplit < 0.9f * sahPlain)
-  {
-    rc = once(30, nullptr);
-    resolved = 30;
-  }
-  s->opt[VKRT_OPT_SPLIT_BUDGET] = -1;
-  s->splitResolved = resolved;
-  if(rc == VKRT_OK)
-    s->info.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();  // all the builds it took
-  return rc;
+  uint32_t layout = 0;  // 0 = BVH2, 1 = wide8
+  int32_t rootRef = VKRT_TRAV_DONE;
+  uint32_t maxDepth = 0, nodeCount = 0;
+  float sahCost = 0;
+  uint64_t nodeBytes = 0, triangleBytes = 0;
+  void* nodes = nullptr;
+  void* tris = nullptr;
+  void* triShade = nullptr;
+};
+
+void installTree(vkrt_scene* s, const BuiltTree& t)
+{
+  s->accelNodes = t.nodes;
+  s->accelTris = t.tris;
+  s->accelShade = t.triShade;
+  s->dev.nodes = (const float4*)t.nodes;
+  s->dev.tris = (const float4*)t.tris;
+  s->dev.triShade = (const uint4*)t.triShade;
+  s->dev.layout = t.layout;
+  s->dev.rootRef = t.rootRef;
+  // wide8: at most one pending group per level (uint2 entries = 2 words)
+  s->dev.stackCap = t.layout == 1 ? 2 * (t.maxDepth + 1) : t.maxDepth + 2;
+  s->info.node_count = t.nodeCount;
+  s->info.max_depth = t.maxDepth;
+  s->info.sah_cost = t.sahCost;
+  s->info.node_bytes = t.nodeBytes;
+  s->info.triangle_bytes = t.triangleBytes;
 }
 
-static int accelBuildOnce(vkrt_scene* s, uint32_t flags, void* hip_stream)
+// A tree built on the host -- a BVH2 (bvh) or a wide8 tree (w8), exactly one of them -- over `tris`: packs the triangle and shading
+// records in its slot order and uploads them with the nodes.  The host SAH builder and the host collapse of a device-built binary tree
+// both end here.
+int uploadHostTree(vkrt_scene* s, const std::vector<vkrt::FlatTri>& tris, const vkrt::BuiltBvh* bvh, const vkrt::BuiltWide8* w8,
+                   const std::vector<uint8_t>* instDissolves, hipStream_t stream, BuiltTree& t)
 {
-  if(!s)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "scene is NULL");
-  if(flags == 0)
-    flags = VKRT_BUILD_DEFAULT;
-  const bool wantPloc = (flags & VKRT_BUILD_PLOC_GPU) != 0;
-  const bool wantLbvh = (flags & VKRT_BUILD_LBVH_GPU) != 0 || wantPloc, wantSah = (flags & VKRT_BUILD_SAH_HOST) != 0;
-  if(wantLbvh == wantSah || (wantPloc && (flags & VKRT_BUILD_LBVH_GPU) != 0) || (flags & ~7u) != 0)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "build_flags must select exactly one of VKRT_BUILD_LBVH_GPU / VKRT_BUILD_PLOC_GPU / VKRT_BUILD_SAH_HOST");
-  int rc = setDevice(s);
-  if(rc != VKRT_OK)
-    return rc;
-  hipStream_t stream = (hipStream_t)hip_stream;
-  HIP_TRY(hipStreamSynchronize(stream));  // no trace may be reading the old tree
-  freeAccel(s);
-  const auto t0 = std::chrono::steady_clock::now();
-  s->info = vkrt_accel_info{};
-  s->info.build_flags = wantPloc ? VKRT_BUILD_PLOC_GPU : wantLbvh ? VKRT_BUILD_LBVH_GPU : VKRT_BUILD_SAH_HOST;
-  s->wavefront = useWavefront(s);
-  const bool watertight = s->opt[VKRT_OPT_WATERTIGHT] != 0;
-  if((watertight || s->opt[VKRT_OPT_ANYHIT_DISSOLVE] != 0) && useWavefront(s) && s->opt[VKRT_OPT_WF_TRAV_BLOCK] != 64)
-    return fail(VKRT_ERR_UNSUPPORTED, "VKRT_OPT_WATERTIGHT / VKRT_OPT_ANYHIT_DISSOLVE are built for the default 64-thread traversal workgroups "
-                "(VKRT_OPT_WF_TRAV_BLOCK = %d)", s->opt[VKRT_OPT_WF_TRAV_BLOCK]);
-  // per instance: is its material non-opaque (dissolve = pbrBaseColorFactor.a < 1)?  The stage is compiled into the traversal only when
-  // the scene has such an instance: without one no record carries the flag, the stage could never ignore a hit, and the flag test
-  // and seed load per ray would cost 3.8 % for nothing (profiles/r03_options/ANYHIT_DISSOLVE.json)
-  std::vector<uint8_t> instDissolves;
-  bool dissolve = false;
-  if(s->opt[VKRT_OPT_ANYHIT_DISSOLVE] != 0)
-    for(const vkrt_node& n : s->nodes)
-    {
-      const int32_t m = std::max(0, s->primMeshes[(size_t)n.primMesh].materialIndex);
-      const bool nonOpaque = s->materialAlpha[(size_t)m] < 1.0f && s->primMeshes[(size_t)n.primMesh].indexCount >= 3u;
-      instDissolves.push_back(nonOpaque ? 1 : 0);
-      dissolve = dissolve || nonOpaque;
-    }
-  s->dev.watertight = watertight ? 1u : 0u;
-  s->dev.dissolve = dissolve ? 1u : 0u;
-  const std::vector<uint8_t>* dissolvePtr = dissolve ? &instDissolves : nullptr;
+  const std::vector<uint32_t>& order = w8 ? w8->triOrder : bvh->triOrder;
+  std::vector<float> packed;
+  std::vector<uint32_t> shadeRec;
+  vkrt::pack_triangles(tris, order, packed, s->dev.watertight != 0, instDissolves);
+  vkrt::pack_tri_shade(tris, order, s->indices.data(), s->primMeshes.data(), s->nodes.data(), shadeRec);
+  const void* nodeData = w8 ? (const void*)w8->nodes.data() : (const void*)bvh->nodes.data();
+  t = w8 ? BuiltTree{1, tris.empty() ? VKRT_TRAV_DONE : 0, w8->maxDepth, w8->nodeCount, w8->sahCost, w8->nodes.size() * 4, packed.size() * 4}
+         : BuiltTree{0, bvh->rootRef, bvh->maxDepth, (uint32_t)(bvh->nodes.size() / 16), bvh->sahCost, bvh->nodes.size() * 4, packed.size() * 4};
+  hipError_t e = hipSuccess;
+  auto tryHip = [&](hipError_t x) { if(e == hipSuccess) e = x; };
+  tryHip(hipMalloc(&t.nodes, std::max<size_t>(t.nodeBytes, VKRT_WNODE_MIN_ALLOC)));
+  tryHip(hipMalloc(&t.tris, std::max<size_t>(t.triangleBytes, 48)));
+  tryHip(hipMalloc(&t.triShade, std::max<size_t>(shadeRec.size() * 4, 16)));
+  if(e == hipSuccess && t.nodeBytes) tryHip(hipMemcpyAsync(t.nodes, nodeData, t.nodeBytes, hipMemcpyHostToDevice, stream));
+  if(e == hipSuccess && !packed.empty()) tryHip(hipMemcpyAsync(t.tris, packed.data(), t.triangleBytes, hipMemcpyHostToDevice, stream));
+  if(e == hipSuccess && !shadeRec.empty()) tryHip(hipMemcpyAsync(t.triShade, shadeRec.data(), shadeRec.size() * 4, hipMemcpyHostToDevice, stream));
+  if(e == hipSuccess) tryHip(hipStreamSynchronize(stream));  // (the host arrays end with this call)
+  if(e != hipSuccess)
+  {
+    (void)hipFree(t.nodes); (void)hipFree(t.tris); (void)hipFree(t.triShade);
+    return fail(e == hipErrorOutOfMemory ? VKRT_ERR_OUT_OF_MEMORY : VKRT_ERR_HIP, "uploading the acceleration structure: %s", hipGetErrorString(e));
+  }
+  return VKRT_OK;
+}
 
-  if(wantSah)
+// World-space bounds of the instanced geometry, conservatively from the corners of every node's local box, and whether the scene has
+// large triangles (the any-hit order heuristic asks whether a ray ends outside the bounds; nothing else reads them)
+void sceneBounds(vkrt_scene* s)
+{
+  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  std::vector<float> meshBox(s->primMeshes.size() * 6);
+  for(size_t m = 0; m < s->primMeshes.size(); m++)
   {
-    std::vector<vkrt::FlatTri> tris;
-    vkrt::flatten_instances(s->positions.data(), s->indices.data(), s->primMeshes.data(), s->nodes.data(),
-                            (uint32_t)s->nodes.size(), tris);
-    // wide8 (compressed 8-wide) is the trace-optimised layout; the megakernel and VKRT_OPT_BVH_LAYOUT = 0 keep BVH2
-    const bool wide = useWavefront(s) && s->opt[VKRT_OPT_BVH_LAYOUT] == 1;
-    std::vector<float> packed;
-    const void* nodeData = nullptr;
-    size_t nodeBytesUsed = 0;
-    vkrt::BuiltBvh bvh;
-    vkrt::BuiltWide8 w8;
-    if(wide)
-    {
-      vkrt::build_wide8_host(tris, w8, watertight);
-      vkrt::pack_triangles(tris, w8.triOrder, packed, watertight, dissolvePtr);
-      nodeData = w8.nodes.data();
-      nodeBytesUsed = w8.nodes.size() * sizeof(uint32_t);
-    }
-    else
-    {
-      vkrt::build_sah_host(tris, 4, bvh, watertight);
-      vkrt::pack_triangles(tris, bvh.triOrder, packed, watertight, dissolvePtr);
-      nodeData = bvh.nodes.data();
-      nodeBytesUsed = bvh.nodes.size() * sizeof(float);
-    }
-    std::vector<uint32_t> shadeRec;
-    vkrt::pack_tri_shade(tris, wide ? w8.triOrder : bvh.triOrder, s->indices.data(), s->primMeshes.data(), s->nodes.data(), shadeRec);
-    HIP_TRY(hipMalloc(&s->accelShade, std::max<size_t>(shadeRec.size() * 4, 16)));
-    if(!shadeRec.empty())
-      HIP_TRY(hipMemcpyAsync(s->accelShade, shadeRec.data(), shadeRec.size() * 4, hipMemcpyHostToDevice, stream));
-    s->dev.triShade = (const uint4*)s->accelShade;
-    const size_t nodeBytes = std::max<size_t>(nodeBytesUsed, VKRT_WNODE_MIN_ALLOC);
-    const size_t triBytes = std::max<size_t>(packed.size() * sizeof(float), 48);
-    HIP_TRY(hipMalloc(&s->accelNodes, nodeBytes));
-    HIP_TRY(hipMalloc(&s->accelTris, triBytes));
-    if(nodeBytesUsed)
-      HIP_TRY(hipMemcpyAsync(s->accelNodes, nodeData, nodeBytesUsed, hipMemcpyHostToDevice, stream));
-    if(!packed.empty())
-      HIP_TRY(hipMemcpyAsync(s->accelTris, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    s->dev.nodes = (const float4*)s->accelNodes;
-    s->dev.tris = (const float4*)s->accelTris;
-    s->dev.triCount = (uint32_t)tris.size();
-    s->info.triangle_count = (uint32_t)tris.size();
-    s->info.node_bytes = nodeBytesUsed;
-    s->info.triangle_bytes = packed.size() * sizeof(float);
-    if(wide)
-    {
-      s->dev.layout = 1;
-      s->dev.rootRef = tris.empty() ? VKRT_TRAV_DONE : 0;
-      s->dev.stackCap = 2 * (w8.maxDepth + 1);  // at most one pending group per level (uint2 entries = 2 words)
-      s->info.node_count = w8.nodeCount;
-      s->info.max_depth = w8.maxDepth;
-      s->info.sah_cost = w8.sahCost;
-    }
-    else
-    {
-      s->dev.layout = 0;
-      s->dev.rootRef = bvh.rootRef;
-      s->dev.stackCap = bvh.maxDepth + 2;
-      s->info.node_count = (uint32_t)(bvh.nodes.size() / 16);
-      s->info.max_depth = bvh.maxDepth;
-      s->info.sah_cost = bvh.sahCost;
-    }
-  }
-  else
-  {
-    const bool wide = useWavefront(s) && s->opt[VKRT_OPT_BVH_LAYOUT] == 1;
-    vkrt::LbvhResult r;
-    // GPU radix-tree build (Morton codes, sort, Karras hierarchy, bottom-up fit).  For the trace-optimised layout the
-    // binary tree keeps one triangle per leaf and is collapsed into wide8 nodes by the same SAH-optimal DP as the SAH
-    // path -- on the device too (wide_collapse.hip); nothing but four statistics words comes back to the host.
-    // VKRT_BUILD_PLOC_GPU: same pipeline with the radix tree replaced by locally-ordered clustering (ploc.hip)
-    rc = vkrt::build_lbvh_device(s->dev, (uint32_t)s->nodes.size(), s->primMeshes, s->nodes, stream, r, wide ? 1u : 4u, wide, wantPloc, watertight, dissolve,
-                                 (unsigned)s->opt[VKRT_OPT_SPLIT_BUDGET]);
-    if(rc != VKRT_OK)
-      return fail(rc, "%s build failed: %s", wantPloc ? "PLOC" : "LBVH", r.error.c_str());
-    s->info.triangle_count = r.uniqueTris;
-    s->dev.triCount = r.triCount;  // slots: a pre-split triangle occupies one per reference
-    if(wide && r.hasWide)
-    {
-      (void)hipFree(r.nodes); (void)hipFree(r.tris); (void)hipFree(r.triShade);
-      s->accelNodes = r.wide.nodes;
-      s->accelTris = r.wide.tris;
-      s->accelShade = r.wide.triShade;
-      s->dev.nodes = (const float4*)s->accelNodes;
-      s->dev.tris = (const float4*)s->accelTris;
-      s->dev.triShade = (const uint4*)s->accelShade;
-      s->dev.layout = 1;
-      s->dev.rootRef = 0;
-      s->dev.stackCap = 2 * (r.wide.maxDepth + 1);  // at most one pending group per level (uint2 entries = 2 words)
-      s->info.node_count = r.wide.nodeCount;
-      s->info.max_depth = r.wide.maxDepth;
-      s->info.sah_cost = r.wide.sahCost;
-      s->info.node_bytes = (uint64_t)r.wide.nodeCount * VKRT_WNODE_BYTES;
-      s->info.triangle_bytes = (uint64_t)r.triCount * 48;
-    }
-    else if(wide && r.triCount > 0)
-    {
-      // fallback (a single triangle, or a radix tree too deep for the device collapse's level budget): download the binary
-      // tree (device layout == host layout of BuiltBvh) and the sorted triangle records, collapse on the host
-      vkrt::BuiltBvh b2;
-      b2.nodes.resize((size_t)r.nodeCount * 16);
-      std::vector<float> trisHost((size_t)r.triCount * 12);
-      hipError_t e = hipSuccess;
-      if(r.nodeCount) e = hipMemcpy(b2.nodes.data(), r.nodes, b2.nodes.size() * 4, hipMemcpyDeviceToHost);
-      if(e == hipSuccess) e = hipMemcpy(trisHost.data(), r.tris, trisHost.size() * 4, hipMemcpyDeviceToHost);
-      (void)hipFree(r.nodes); (void)hipFree(r.tris); (void)hipFree(r.triShade);
-      if(e != hipSuccess)
-        return fail(VKRT_ERR_HIP, "LBVH download: %s", hipGetErrorString(e));
-      b2.rootRef = r.rootRef;
-      b2.maxDepth = r.maxDepth;
-      b2.triOrder.resize(r.triCount);
-      std::vector<vkrt::FlatTri> tris(r.triCount);
-      for(uint32_t k = 0; k < r.triCount; k++)
+    const vkrt_prim_mesh& pm = s->primMeshes[m];
+    float* b = &meshBox[m * 6];
+    for(int k = 0; k < 3; k++) { b[k] = INFINITY; b[3 + k] = -INFINITY; }
+    for(uint32_t v = 0; v < pm.vertexCount; v++)
+      for(int k = 0; k < 3; k++)
       {
-        b2.triOrder[k] = k;
-        const float* t = &trisHost[(size_t)k * 12];
-        vkrt::FlatTri& ft = tris[k];
-        for(int c = 0; c < 3; c++)
-        {
-          ft.v0[c] = t[c];
-          // records hold (v0, e1, e2) or, watertight, (p0, p1, p2): the other form is re-derived (p1 = v0 + e1 is not the exact vertex,
-          // but the boxes below only grow by it)
-          ft.e1[c] = watertight ? t[3 + c] - t[c] : t[3 + c];
-          ft.e2[c] = watertight ? t[6 + c] - t[c] : t[6 + c];
-          ft.p1[c] = watertight ? t[3 + c] : t[c] + t[3 + c];
-          ft.p2[c] = watertight ? t[6 + c] : t[c] + t[6 + c];
-        }
-        memcpy(&ft.gid, &t[9], 4); memcpy(&ft.inst, &t[10], 4); memcpy(&ft.prim, &t[11], 4);
-        ft.gid &= 0x7fffffffu;  // (bit 31 = the any-hit stage's flag; pack_triangles sets it again)
+        const float x = s->positions[3 * (size_t)(pm.vertexOffset + v) + k];
+        b[k] = std::min(b[k], x); b[3 + k] = std::max(b[3 + k], x);
       }
-      vkrt::BuiltWide8 w8;
-      vkrt::collapse_wide8(b2, tris, w8, watertight);
-      std::vector<float> packed;
-      std::vector<uint32_t> shadeRec;
-      vkrt::pack_triangles(tris, w8.triOrder, packed, watertight, dissolvePtr);
-      vkrt::pack_tri_shade(tris, w8.triOrder, s->indices.data(), s->primMeshes.data(), s->nodes.data(), shadeRec);
-      HIP_TRY(hipMalloc(&s->accelNodes, std::max<size_t>(w8.nodes.size() * 4, VKRT_WNODE_MIN_ALLOC)));
-      HIP_TRY(hipMalloc(&s->accelTris, std::max<size_t>(packed.size() * 4, 48)));
-      HIP_TRY(hipMalloc(&s->accelShade, std::max<size_t>(shadeRec.size() * 4, 16)));
-      HIP_TRY(hipMemcpy(s->accelNodes, w8.nodes.data(), w8.nodes.size() * 4, hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(s->accelTris, packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(s->accelShade, shadeRec.data(), shadeRec.size() * 4, hipMemcpyHostToDevice));
-      s->dev.nodes = (const float4*)s->accelNodes;
-      s->dev.tris = (const float4*)s->accelTris;
-      s->dev.triShade = (const uint4*)s->accelShade;
-      s->dev.layout = 1;
-      s->dev.rootRef = 0;
-      s->dev.stackCap = 2 * (w8.maxDepth + 1);  // at most one pending group per level (uint2 entries = 2 words)
-      s->info.node_count = w8.nodeCount;
-      s->info.max_depth = w8.maxDepth;
-      s->info.sah_cost = w8.sahCost;
-      s->info.node_bytes = w8.nodes.size() * 4;
-      s->info.triangle_bytes = packed.size() * 4;
-    }
-    else
-    {
-      s->accelNodes = r.nodes;
-      s->accelTris = r.tris;
-      s->accelShade = r.triShade;
-      s->dev.triShade = (const uint4*)r.triShade;
-      s->dev.nodes = (const float4*)r.nodes;
-      s->dev.tris = (const float4*)r.tris;
-      s->dev.rootRef = r.rootRef;
-      s->dev.layout = 0;
-      s->dev.stackCap = r.maxDepth + 2;
-      s->info.node_count = r.nodeCount;
-      s->info.max_depth = r.maxDepth;
-      s->info.sah_cost = r.sahCost;
-      s->info.node_bytes = (uint64_t)r.nodeCount * 64;
-      s->info.triangle_bytes = (uint64_t)r.triCount * 48;
-    }
   }
-  // world-space bounds of the instanced geometry, conservatively from the corners of every node's local box (the any-hit order
-  // heuristic asks whether a ray ends outside them; nothing else reads them)
+  for(const vkrt_node& n : s->nodes)
   {
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    std::vector<float> meshBox(s->primMeshes.size() * 6);
-    for(size_t m = 0; m < s->primMeshes.size(); m++)
+    const float* b = &meshBox[(size_t)n.primMesh * 6];
+    if(!(b[0] <= b[3]))
+      continue;
+    for(int c = 0; c < 8; c++)
     {
-      const vkrt_prim_mesh& pm = s->primMeshes[m];
-      float* b = &meshBox[m * 6];
-      for(int k = 0; k < 3; k++) { b[k] = INFINITY; b[3 + k] = -INFINITY; }
-      for(uint32_t v = 0; v < pm.vertexCount; v++)
-        for(int k = 0; k < 3; k++)
-        {
-          const float x = s->positions[3 * (size_t)(pm.vertexOffset + v) + k];
-          b[k] = std::min(b[k], x); b[3 + k] = std::max(b[3 + k], x);
-        }
-    }
-    for(const vkrt_node& n : s->nodes)
-    {
-      const float* b = &meshBox[(size_t)n.primMesh * 6];
-      if(!(b[0] <= b[3]))
-        continue;
-      for(int c = 0; c < 8; c++)
+      const float p[3] = {(c & 1) ? b[3] : b[0], (c & 2) ? b[4] : b[1], (c & 4) ? b[5] : b[2]};
+      for(int k = 0; k < 3; k++)
       {
-        const float p[3] = {(c & 1) ? b[3] : b[0], (c & 2) ? b[4] : b[1], (c & 4) ? b[5] : b[2]};
-        for(int k = 0; k < 3; k++)
-        {
-          const float w = n.worldMatrix[k] * p[0] + n.worldMatrix[4 + k] * p[1] + n.worldMatrix[8 + k] * p[2] + n.worldMatrix[12 + k];
-          lo[k] = std::min(lo[k], w); hi[k] = std::max(hi[k], w);
-        }
+        const float w = n.worldMatrix[k] * p[0] + n.worldMatrix[4 + k] * p[1] + n.worldMatrix[8 + k] * p[2] + n.worldMatrix[12 + k];
+        lo[k] = std::min(lo[k], w); hi[k] = std::max(hi[k], w);
       }
     }
-    for(int k = 0; k < 3; k++)
-    {
-      const float pad = 1e-3f * std::max(1e-6f, hi[k] - lo[k]);
-      s->dev.sceneLo[k] = lo[k] - pad; s->dev.sceneHi[k] = hi[k] + pad;
-    }
-    // "large" = a triangle of more than 1 % of the largest face of the scene's box (world space, every instance)
-    const double ex = (double)hi[0] - lo[0], ey = (double)hi[1] - lo[1], ez = (double)hi[2] - lo[2];
-    const double face = std::max(ex * ey, std::max(ey * ez, ez * ex));
-    double maxArea = 0.0;
-    for(const vkrt_node& n : s->nodes)
-    {
-      const vkrt_prim_mesh& pm = s->primMeshes[(size_t)n.primMesh];
-      const float* M = n.worldMatrix;
-      for(uint32_t t = 0; t + 3 <= pm.indexCount; t += 3)
-      {
-        double w[3][3];
-        for(int v = 0; v < 3; v++)
-        {
-          const float* p = &s->positions[3 * (size_t)(s->indices[pm.firstIndex + t + v] + pm.vertexOffset)];
-          for(int k = 0; k < 3; k++) w[v][k] = (double)M[k] * p[0] + (double)M[4 + k] * p[1] + (double)M[8 + k] * p[2] + (double)M[12 + k];
-        }
-        const double a[3] = {w[1][0] - w[0][0], w[1][1] - w[0][1], w[1][2] - w[0][2]}, b[3] = {w[2][0] - w[0][0], w[2][1] - w[0][1], w[2][2] - w[0][2]};
-        const double cx = a[1] * b[2] - a[2] * b[1], cy = a[2] * b[0] - a[0] * b[2], cz = a[0] * b[1] - a[1] * b[0];
-        maxArea = std::max(maxArea, 0.5 * std::sqrt(cx * cx + cy * cy + cz * cz));
-      }
-    }
-    s->hasLargeTriangles = face > 0.0 && maxArea > 0.01 * face;
   }
+  for(int k = 0; k < 3; k++)
+  {
+    const float pad = 1e-3f * std::max(1e-6f, hi[k] - lo[k]);
+    s->dev.sceneLo[k] = lo[k] - pad; s->dev.sceneHi[k] = hi[k] + pad;
+  }
+  // "large" = a triangle of more than 1 % of the largest face of the scene's box (world space, every instance)
+  const double ex = (double)hi[0] - lo[0], ey = (double)hi[1] - lo[1], ez = (double)hi[2] - lo[2];
+  const double face = std::max(ex * ey, std::max(ey * ez, ez * ex));
+  double maxArea = 0.0;
+  for(const vkrt_node& n : s->nodes)
+  {
+    const vkrt_prim_mesh& pm = s->primMeshes[(size_t)n.primMesh];
+    const float* M = n.worldMatrix;
+    for(uint32_t t = 0; t + 3 <= pm.indexCount; t += 3)
+    {
+      double w[3][3];
+      for(int v = 0; v < 3; v++)
+      {
+        const float* p = &s->positions[3 * (size_t)(s->indices[pm.firstIndex + t + v] + pm.vertexOffset)];
+        for(int k = 0; k < 3; k++) w[v][k] = (double)M[k] * p[0] + (double)M[4 + k] * p[1] + (double)M[8 + k] * p[2] + (double)M[12 + k];
+      }
+      const double a[3] = {w[1][0] - w[0][0], w[1][1] - w[0][1], w[1][2] - w[0][2]}, b[3] = {w[2][0] - w[0][0], w[2][1] - w[0][1], w[2][2] - w[0][2]};
+      const double cx = a[1] * b[2] - a[2] * b[1], cy = a[2] * b[0] - a[0] * b[2], cz = a[0] * b[1] - a[1] * b[0];
+      maxArea = std::max(maxArea, 0.5 * std::sqrt(cx * cx + cy * cy + cz * cz));
+    }
+  }
+  s->hasLargeTriangles = face > 0.0 && maxArea > 0.01 * face;
+}
+
+// The traversal settings of the installed tree: step bound, any-hit order, triangle postponing and work sharing (from the options),
+// and the LDS stack they need.
+int traversalSettings(vkrt_scene* s)
+{
   s->info.reference_count = s->dev.triCount;
   s->dev.stepLimit = 4u * (s->info.node_count + s->dev.triCount) + 64u;
   s->dev.triThreshold = 0;
@@ -991,9 +860,164 @@ static int accelBuildOnce(vkrt_scene* s, uint32_t flags, void* hip_stream)
   if((size_t)s->dev.stackCap * 256 * 4 > 64 * 1024)
     return fail(VKRT_ERR_UNSUPPORTED, "BVH depth %u needs a %zu-byte LDS stack per workgroup (limit 64 KiB)", s->info.max_depth,
                 (size_t)s->dev.stackCap * 256 * 4);
+  return VKRT_OK;
+}
+
+// One build with a given pre-split budget (read by the device builders only): validate flags -> free the old tree -> build (host or
+// device) -> install -> scene bounds -> traversal settings.
+int accelBuildOnce(vkrt_scene* s, uint32_t flags, int splitBudget, hipStream_t stream)
+{
+  if(flags == 0)
+    flags = VKRT_BUILD_DEFAULT;
+  const bool wantPloc = (flags & VKRT_BUILD_PLOC_GPU) != 0;
+  const bool wantLbvh = (flags & VKRT_BUILD_LBVH_GPU) != 0 || wantPloc, wantSah = (flags & VKRT_BUILD_SAH_HOST) != 0;
+  if(wantLbvh == wantSah || (wantPloc && (flags & VKRT_BUILD_LBVH_GPU) != 0) || (flags & ~7u) != 0)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "build_flags must select exactly one of VKRT_BUILD_LBVH_GPU / VKRT_BUILD_PLOC_GPU / VKRT_BUILD_SAH_HOST");
+  int rc = setDevice(s);
+  if(rc != VKRT_OK)
+    return rc;
+  HIP_TRY(hipStreamSynchronize(stream));  // no trace may be reading the old tree
+  freeAccel(s);
+  const auto t0 = std::chrono::steady_clock::now();
+  s->info = vkrt_accel_info{};
+  s->info.build_flags = wantPloc ? VKRT_BUILD_PLOC_GPU : wantLbvh ? VKRT_BUILD_LBVH_GPU : VKRT_BUILD_SAH_HOST;
+  s->wavefront = useWavefront(s);
+  const bool watertight = s->opt[VKRT_OPT_WATERTIGHT] != 0;
+  if((watertight || s->opt[VKRT_OPT_ANYHIT_DISSOLVE] != 0) && useWavefront(s) && s->opt[VKRT_OPT_WF_TRAV_BLOCK] != 64)
+    return fail(VKRT_ERR_UNSUPPORTED, "VKRT_OPT_WATERTIGHT / VKRT_OPT_ANYHIT_DISSOLVE are built for the default 64-thread traversal workgroups "
+                "(VKRT_OPT_WF_TRAV_BLOCK = %d)", s->opt[VKRT_OPT_WF_TRAV_BLOCK]);
+  // per instance: is its material non-opaque (dissolve = pbrBaseColorFactor.a < 1)?  The stage is compiled into the traversal only when
+  // the scene has such an instance: without one no record carries the flag, the stage could never ignore a hit, and the flag test
+  // and seed load per ray would cost 3.8 % for nothing (profiles/r03_options/ANYHIT_DISSOLVE.json)
+  std::vector<uint8_t> instDissolves;
+  bool dissolve = false;
+  if(s->opt[VKRT_OPT_ANYHIT_DISSOLVE] != 0)
+    for(const vkrt_node& n : s->nodes)
+    {
+      const int32_t m = std::max(0, s->primMeshes[(size_t)n.primMesh].materialIndex);
+      const bool nonOpaque = s->materialAlpha[(size_t)m] < 1.0f && s->primMeshes[(size_t)n.primMesh].indexCount >= 3u;
+      instDissolves.push_back(nonOpaque ? 1 : 0);
+      dissolve = dissolve || nonOpaque;
+    }
+  s->dev.watertight = watertight ? 1u : 0u;
+  s->dev.dissolve = dissolve ? 1u : 0u;
+  const std::vector<uint8_t>* dissolvePtr = dissolve ? &instDissolves : nullptr;
+  // wide8 (compressed 8-wide) is the trace-optimised layout; the megakernel and VKRT_OPT_BVH_LAYOUT = 0 keep BVH2
+  const bool wide = useWavefront(s) && s->opt[VKRT_OPT_BVH_LAYOUT] == 1;
+
+  BuiltTree tree;
+  if(wantSah)
+  {
+    std::vector<vkrt::FlatTri> tris;
+    vkrt::flatten_instances(s->positions.data(), s->indices.data(), s->primMeshes.data(), s->nodes.data(),
+                            (uint32_t)s->nodes.size(), tris);
+    vkrt::BuiltBvh bvh;
+    vkrt::BuiltWide8 w8;
+    if(wide)
+      vkrt::build_wide8_host(tris, w8, watertight);
+    else
+      vkrt::build_sah_host(tris, 4, bvh, watertight);
+    if((rc = uploadHostTree(s, tris, wide ? nullptr : &bvh, wide ? &w8 : nullptr, dissolvePtr, stream, tree)) != VKRT_OK)
+      return rc;
+    s->dev.triCount = (uint32_t)tris.size();
+    s->info.triangle_count = (uint32_t)tris.size();
+  }
+  else
+  {
+    vkrt::LbvhResult r;
+    // GPU radix-tree build (Morton codes, sort, Karras hierarchy, bottom-up fit).  For the trace-optimised layout the
+    // binary tree keeps one triangle per leaf and is collapsed into wide8 nodes by the same SAH-optimal DP as the SAH
+    // path -- on the device too (wide_collapse.hip); nothing but four statistics words comes back to the host.
+    // VKRT_BUILD_PLOC_GPU: same pipeline with the radix tree replaced by locally-ordered clustering (ploc.hip)
+    rc = vkrt::build_lbvh_device(s->dev, (uint32_t)s->nodes.size(), s->primMeshes, s->nodes, stream, r, wide ? 1u : 4u, wide, wantPloc, watertight, dissolve,
+                                 (unsigned)splitBudget);
+    if(rc != VKRT_OK)
+      return fail(rc, "%s build failed: %s", wantPloc ? "PLOC" : "LBVH", r.error.c_str());
+    s->info.triangle_count = r.uniqueTris;
+    s->dev.triCount = r.triCount;  // slots: a pre-split triangle occupies one per reference
+    if(wide && r.hasWide)
+    {
+      (void)hipFree(r.nodes); (void)hipFree(r.tris); (void)hipFree(r.triShade);
+      tree = BuiltTree{1, 0, r.wide.maxDepth, r.wide.nodeCount, r.wide.sahCost, (uint64_t)r.wide.nodeCount * VKRT_WNODE_BYTES,
+                       (uint64_t)r.triCount * 48, r.wide.nodes, r.wide.tris, r.wide.triShade};
+    }
+    else if(wide && r.triCount > 0)
+    {
+      // fallback (a single triangle, or a radix tree too deep for the device collapse's level budget): download the binary
+      // tree (device layout == host layout of BuiltBvh) and the sorted triangle records, collapse on the host
+      vkrt::BuiltBvh b2;
+      b2.nodes.resize((size_t)r.nodeCount * 16);
+      std::vector<float> records((size_t)r.triCount * 12);
+      hipError_t e = hipSuccess;
+      if(r.nodeCount) e = hipMemcpy(b2.nodes.data(), r.nodes, b2.nodes.size() * 4, hipMemcpyDeviceToHost);
+      if(e == hipSuccess) e = hipMemcpy(records.data(), r.tris, records.size() * 4, hipMemcpyDeviceToHost);
+      (void)hipFree(r.nodes); (void)hipFree(r.tris); (void)hipFree(r.triShade);
+      if(e != hipSuccess)
+        return fail(VKRT_ERR_HIP, "LBVH download: %s", hipGetErrorString(e));
+      b2.rootRef = r.rootRef;
+      b2.maxDepth = r.maxDepth;
+      b2.triOrder.resize(r.triCount);
+      // (decoded p1 = v0 + e1 is not the exact vertex, but the boxes of the collapse only grow by it; pack_triangles sets the any-hit
+      // flag that decoding clears again)
+      std::vector<vkrt::FlatTri> tris(r.triCount);
+      for(uint32_t k = 0; k < r.triCount; k++)
+      {
+        b2.triOrder[k] = k;
+        tris[k] = vkrt::unpack_triangle(&records[(size_t)k * 12], watertight);
+      }
+      vkrt::BuiltWide8 w8;
+      vkrt::collapse_wide8(b2, tris, w8, watertight);
+      if((rc = uploadHostTree(s, tris, nullptr, &w8, dissolvePtr, stream, tree)) != VKRT_OK)
+        return rc;
+    }
+    else
+      tree = BuiltTree{0, r.rootRef, r.maxDepth, r.nodeCount, r.sahCost, (uint64_t)r.nodeCount * 64, (uint64_t)r.triCount * 48,
+                       r.nodes, r.tris, r.triShade};
+  }
+  installTree(s, tree);
+  sceneBounds(s);
+  if((rc = traversalSettings(s)) != VKRT_OK)
+    return rc;
   s->info.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   s->built = true;
   return VKRT_OK;
+}
+
+}  // namespace
+
+// VKRT_OPT_SPLIT_BUDGET = -1: the library decides.  Triangle pre-splitting pays where large triangles are not aligned with the axes
+// (+14 % ... +97 % on a rotated building) and costs 1-8 % elsewhere (profiles/r05_split_rotated.jsonl), and the SAH cost of the finished
+// tree tells the two apart: a 30 % budget lowers it by 18-30 % in the first case and by at most 5 % -- or raises it -- in the second.
+// So: build with a 30 % budget, build without, keep the split tree only when its cost is below 0.9 of the unsplit one (one more build
+// in that case; device builds are ~13 ms each for 262 k triangles).  Pixels do not depend on the outcome.
+int vkrt_accel_build(vkrt_scene* s, uint32_t flags, void* hip_stream)
+{
+  if(!s)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "scene is NULL");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const bool deviceBuild = flags == 0 || (flags & (VKRT_BUILD_LBVH_GPU | VKRT_BUILD_PLOC_GPU)) != 0;
+  if(s->opt[VKRT_OPT_SPLIT_BUDGET] >= 0 || !deviceBuild)
+  {
+    s->splitResolved = std::max(0, s->opt[VKRT_OPT_SPLIT_BUDGET]);  // (the host builder does not split)
+    return accelBuildOnce(s, flags, s->splitResolved, stream);
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  float sahSplit = 0.0f;
+  int rc = accelBuildOnce(s, flags, 30, stream);
+  if(rc == VKRT_OK)
+  {
+    sahSplit = s->info.sah_cost;
+    rc = accelBuildOnce(s, flags, 0, stream);
+  }
+  s->splitResolved = 0;
+  if(rc == VKRT_OK && sahSplit < 0.9f * s->info.sah_cost)
+  {
+    rc = accelBuildOnce(s, flags, 30, stream);
+    s->splitResolved = 30;
+  }
+  if(rc == VKRT_OK)
+    s->info.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();  // all the builds it took
+  return rc;
 }
 
 int vkrt_accel_get_info(const vkrt_scene* s, vkrt_accel_info* out)
@@ -1026,9 +1050,8 @@ int vkrt_scene_update_nodes(vkrt_scene* s, uint32_t first, uint32_t count, const
     if(nodes[i].primMesh != s->nodes[(size_t)first + i].primMesh)
       return fail(VKRT_ERR_INVALID_ARGUMENT, "node %u: primMesh %d != %d (an update moves instances, it does not change their geometry)", first + i,
                   nodes[i].primMesh, s->nodes[(size_t)first + i].primMesh);
-    for(int k = 0; k < 16; k++)
-      if(!std::isfinite(nodes[i].worldMatrix[k]))
-        return fail(VKRT_ERR_INVALID_ARGUMENT, "node %u: worldMatrix[%d] is not finite", first + i, k);
+    if(checkTransform(nodes[i], first + i) != VKRT_OK)
+      return VKRT_ERR_INVALID_ARGUMENT;
   }
   if(count == 0)
     return VKRT_OK;
@@ -1112,51 +1135,27 @@ int vkrt_pathtrace_frames(vkrt_scene* s, const PushConstantRay* pc, const Global
     return fail(VKRT_ERR_INVALID_ARGUMENT, "n_frames %u out of range", n_frames);
   if(!image && vkrt_shard_rows(shard) != 0u)  // (a shard without rows -- more ranks than strips -- has no image to pass)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "NULL image");
-  if(!s->built)
-    return fail(VKRT_ERR_NOT_BUILT, "vkrt_pathtrace before vkrt_accel_build");
-  if(s->stale)
-    return fail(VKRT_ERR_NOT_BUILT, "vkrt_pathtrace after vkrt_scene_update_nodes: vkrt_accel_refit or vkrt_accel_build first");
-  if(shard->full_width == 0 || shard->full_height == 0)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "empty launch size");
-  if(shard->shard_count > 1 && (shard->strip_rows == 0 || shard->shard_index >= shard->shard_count))
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "bad shard (strip_rows %u, %u of %u)", shard->strip_rows, shard->shard_index,
-                shard->shard_count);
+  int rc = checkBuilt(s, "vkrt_pathtrace");
+  if(rc == VKRT_OK)
+    rc = checkShard(shard);
+  if(rc != VKRT_OK)
+    return rc;
   if(pc->lightsCount < 0 || (uint32_t)pc->lightsCount > s->lightCount)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "PushConstantRay.lightsCount %d outside [0,%u]", pc->lightsCount, s->lightCount);
   if(pc->samples < 0 || pc->depth < 0 || pc->depth > 99)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "samples/depth out of range");
-  int rc = setDevice(s);
-  if(rc != VKRT_OK)
+  if((rc = setDevice(s)) != VKRT_OK)
     return rc;
   hipStream_t stream = (hipStream_t)hip_stream;
   TraceParams P;
-  memset(&P, 0, sizeof P);
-  P.sc = s->dev;
-  P.pc = *pc;
-  memcpy(P.viewInverse, cam->viewInverse.m, sizeof P.viewInverse);
-  memcpy(P.projInverse, cam->projInverse.m, sizeof P.projInverse);
-  P.seed = opts ? opts->seed : 0u;
-  P.flags = (opts ? opts->flags : 0u) & VKRT_TRACE_PUBLIC_FLAGS;
-  if(s->opt[VKRT_OPT_SKIP_DEAD_SHADOW_RAYS])
-    P.flags |= VKRT_FLAG_SKIP_DEAD_SHADOW;  // internal bit (device_scene.h)
-  P.fullW = shard->full_width;
-  P.fullH = shard->full_height;
-  const bool sharded = shard->shard_count > 1;
-  P.stripRows = sharded ? shard->strip_rows : 0u;
-  P.shardCount = sharded ? shard->shard_count : 1u;
-  P.shardIndex = sharded ? shard->shard_index : 0u;
-  P.localRows = vkrt_shard_rows(shard);
-  P.image = image;
-  P.workCounter = s->workCounter;
-  P.counters = s->counters;
+  if((rc = launchParams(s, pc, cam, opts, shard, P)) != VKRT_OK)
+    return rc;
   if(P.localRows == 0)
     return VKRT_OK;
-  P.tilesX = (P.fullW + 7) / 8;
-  const uint64_t tiles = (uint64_t)P.tilesX * ((P.localRows + 7) / 8);
-  if(tiles * 64 >= 0xFFFFFFFFull)
-    return fail(VKRT_ERR_UNSUPPORTED, "launch too large");
-  P.tileCount = (uint32_t)tiles;
-  P.tileFirst = 0;
+  if(s->opt[VKRT_OPT_SKIP_DEAD_SHADOW_RAYS])
+    P.flags |= VKRT_FLAG_SKIP_DEAD_SHADOW;  // internal bit (device_scene.h)
+  P.image = image;
+  P.workCounter = s->workCounter;
 
   const bool count = (P.flags & VKRT_TRACE_COUNT_TRAVERSAL) != 0;
   if(s->wavefront)
@@ -1187,7 +1186,7 @@ int vkrt_pathtrace_frames(vkrt_scene* s, const PushConstantRay* pc, const Global
     HIP_TRY(hipEventRecord(s->evStart, stream));
     WfOptions wo;
     wo.subframes = s->opt[VKRT_OPT_WF_SUBFRAMES];
-    wo.travBlock = (s->dev.watertight || s->dev.dissolve) ? 64 : s->opt[VKRT_OPT_WF_TRAV_BLOCK];  // (the non-default triangle modes exist for the default workgroup only)
+    wo.travBlock = travBlock(s);
     wo.inFlight = framesInFlight(s, (int)n_frames);
     if(timing)
       timing->used = 0;  // one timing record per call: the batches of a long call append to it
@@ -1207,7 +1206,7 @@ int vkrt_pathtrace_frames(vkrt_scene* s, const PushConstantRay* pc, const Global
   HIP_TRY(vkrt_pathtrace_occupancy(lds, &perCU));
   if(perCU < 1)
     return fail(VKRT_ERR_UNSUPPORTED, "path-trace kernel does not fit a CU with %zu B of LDS", lds);
-  const uint64_t wantBlocks = (tiles * 64 + 255) / 256;
+  const uint64_t wantBlocks = ((uint64_t)P.tileCount * 64 + 255) / 256;
   const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(wantBlocks, (uint64_t)s->cuCount * perCU));
 
   HIP_TRY(hipEventRecord(s->evStart, stream));
@@ -1224,44 +1223,6 @@ int vkrt_pathtrace_frames(vkrt_scene* s, const PushConstantRay* pc, const Global
   s->wfTimed = false;
   return VKRT_OK;
 }
-
-namespace {
-// launch geometry shared by the hybrid entry points (same shard semantics as vkrt_pathtrace)
-int fillParams(vkrt_scene* s, const PushConstantRay* pc, const GlobalUniforms* cam, const vkrt_trace_opts* opts, const vkrt_shard* shard,
-               TraceParams& P)
-{
-  if(!s->built)
-    return fail(VKRT_ERR_NOT_BUILT, "acceleration structure not built");
-  if(s->stale)
-    return fail(VKRT_ERR_NOT_BUILT, "node transforms changed since the acceleration structure was built: vkrt_accel_refit or vkrt_accel_build first");
-  if(shard->full_width == 0 || shard->full_height == 0)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "empty launch size");
-  if(shard->shard_count > 1 && (shard->strip_rows == 0 || shard->shard_index >= shard->shard_count))
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "bad shard");
-  memset(&P, 0, sizeof P);
-  P.sc = s->dev;
-  if(pc) P.pc = *pc;
-  memcpy(P.viewInverse, cam->viewInverse.m, sizeof P.viewInverse);
-  memcpy(P.projInverse, cam->projInverse.m, sizeof P.projInverse);
-  P.seed = opts ? opts->seed : 0u;
-  P.flags = (opts ? opts->flags : 0u) & VKRT_TRACE_PUBLIC_FLAGS;  // (the hybrid passes never skip shadow rays: hitDists needs their result)
-  P.fullW = shard->full_width;
-  P.fullH = shard->full_height;
-  const bool sharded = shard->shard_count > 1;
-  P.stripRows = sharded ? shard->strip_rows : 0u;
-  P.shardCount = sharded ? shard->shard_count : 1u;
-  P.shardIndex = sharded ? shard->shard_index : 0u;
-  P.localRows = vkrt_shard_rows(shard);
-  P.counters = s->counters;
-  P.tilesX = (P.fullW + 7) / 8;
-  const uint64_t tiles = (uint64_t)P.tilesX * ((P.localRows + 7) / 8);
-  if(tiles * 64 >= 0xFFFFFFFFull)
-    return fail(VKRT_ERR_UNSUPPORTED, "launch too large");
-  P.tileCount = (uint32_t)tiles;
-  P.tileFirst = 0;
-  return VKRT_OK;
-}
-}  // namespace
 
 namespace {
 int gbufferImpl(vkrt_scene* s, const float clearColor[4], int lightsCount, const GlobalUniforms* cam, const float* viewMatrix, const vkrt_shard* shard,
@@ -1316,7 +1277,8 @@ int gbufferImpl(vkrt_scene* s, const float clearColor[4], int lightsCount, const
   if(rc != VKRT_OK)
     return rc;
   TraceParams P;
-  if((rc = fillParams(s, nullptr, cam, nullptr, shard, P)) != VKRT_OK)
+  if((rc = checkBuilt(s, "vkrt_gbuffer_raycast")) != VKRT_OK || (rc = checkShard(shard)) != VKRT_OK ||
+     (rc = launchParams(s, nullptr, cam, nullptr, shard, P)) != VKRT_OK)
     return rc;
   if(P.localRows == 0)
     return VKRT_OK;
@@ -1347,7 +1309,8 @@ int hybridImpl(vkrt_scene* s, const PushConstantRay* pc, const GlobalUniforms* c
   if(rc != VKRT_OK)
     return rc;
   TraceParams P;
-  if((rc = fillParams(s, pc, cam, opts, shard, P)) != VKRT_OK)
+  if((rc = checkBuilt(s, "vkrt_hybrid_trace")) != VKRT_OK || (rc = checkShard(shard)) != VKRT_OK ||
+     (rc = launchParams(s, pc, cam, opts, shard, P)) != VKRT_OK)
     return rc;
   if(P.localRows == 0)
     return VKRT_OK;
@@ -1370,7 +1333,7 @@ int hybridImpl(vkrt_scene* s, const PushConstantRay* pc, const GlobalUniforms* c
     HIP_TRY(vkrt_launch_hybrid(P, g->color, g->position, g->normal, g->roughMetal, accum, nrd ? &np : nullptr, vkrt_wf_hybrid_tmp(s->wf), stream));
     HybridGi G{(const float4*)g->color, (const float4*)g->position, (const float4*)g->normal, (const float2*)g->roughMetal, (float4*)accum,
                nrd ? (float4*)nrd->diffRadianceHitDist : nullptr, nrd ? nrd->viewZ : nullptr};
-    HIP_TRY(vkrt_launch_hybrid_gi(P, s->wf, G, (s->dev.watertight || s->dev.dissolve) ? 64u : (unsigned)s->opt[VKRT_OPT_WF_TRAV_BLOCK], stream));
+    HIP_TRY(vkrt_launch_hybrid_gi(P, s->wf, G, (unsigned)travBlock(s), stream));
   }
   else
     HIP_TRY(vkrt_launch_hybrid(P, g->color, g->position, g->normal, g->roughMetal, accum, nrd ? &np : nullptr, nullptr, stream));
@@ -1479,14 +1442,10 @@ int vkrt_debug_trace_rays(vkrt_scene* s, uint32_t n, const float* origins, const
 {
   if(!s || (n && (!origins || !directions || !t || !u || !v || !gid)))
     return fail(VKRT_ERR_INVALID_ARGUMENT, "NULL argument");
-  if(!s->built)
-    return fail(VKRT_ERR_NOT_BUILT, "vkrt_debug_trace_rays before vkrt_accel_build");
-  if(s->stale)
-    return fail(VKRT_ERR_NOT_BUILT, "vkrt_debug_trace_rays after vkrt_scene_update_nodes: vkrt_accel_refit or vkrt_accel_build first");
-  if(n == 0)
-    return VKRT_OK;
-  int rc = setDevice(s);
-  if(rc != VKRT_OK)
+  int rc = checkBuilt(s, "vkrt_debug_trace_rays");
+  if(rc != VKRT_OK || n == 0)
+    return rc;
+  if((rc = setDevice(s)) != VKRT_OK)
     return rc;
   float *dO = nullptr, *dD = nullptr, *dT = nullptr, *dU = nullptr, *dV = nullptr;
   int* dG = nullptr;
@@ -1513,11 +1472,9 @@ int vkrt_debug_check_accel(vkrt_scene* s, vkrt_accel_check* out)
 {
   if(!s || !out)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "NULL argument");
-  if(!s->built)
-    return fail(VKRT_ERR_NOT_BUILT, "vkrt_accel_build has not run");
-  if(s->stale)
-    return fail(VKRT_ERR_NOT_BUILT, "vkrt_debug_check_accel after vkrt_scene_update_nodes: vkrt_accel_refit or vkrt_accel_build first");
-  int rc = setDevice(s);
+  int rc = checkBuilt(s, "vkrt_debug_check_accel");
+  if(rc == VKRT_OK)
+    rc = setDevice(s);
   if(rc != VKRT_OK)
     return rc;
   HIP_TRY(hipDeviceSynchronize());
@@ -1534,11 +1491,7 @@ int vkrt_debug_check_accel(vkrt_scene* s, vkrt_accel_check* out)
   // slots per triangle id: a triangle with one slot must lie inside every box above that slot (its vertices do: convexity); the slots
   // of a pre-split triangle (VKRT_OPT_SPLIT_BUDGET) are checked together at the end: `reach[slot]` = intersection of the chain
   auto gidOf = [&](uint32_t slot) { uint32_t g; memcpy(&g, &tris[(size_t)slot * 12 + 9], 4); return g & 0x7fffffffu; };
-  auto vertexOf = [&](uint32_t slot, int v, float p[3]) {
-    const float* t = &tris[(size_t)slot * 12];  // (v0, e1, e2) or, watertight, (p0, p1, p2)
-    for(int k = 0; k < 3; k++)
-      p[k] = v == 0 ? t[k] : (s->dev.watertight ? t[3 * v + k] : (v == 1 ? t[k] + t[3 + k] : t[k] + t[6 + k]));
-  };
+  auto decode = [&](uint32_t slot) { return vkrt::unpack_triangle(&tris[(size_t)slot * 12], s->dev.watertight != 0); };
   const uint32_t gidCount = s->info.triangle_count;
   std::vector<uint32_t> slotsOfGid(gidCount, 0u);
   for(uint32_t k = 0; k < T; k++)
@@ -1563,14 +1516,11 @@ int vkrt_debug_check_accel(vkrt_scene* s, vkrt_accel_check* out)
       }
     if(!single)
       return;
-    for(int v = 0; v < 3; v++)
-    {
-      float p[3];
-      vertexOf(slot, v, p);
+    const vkrt::FlatTri ft = decode(slot);
+    for(const float* p : {ft.v0, ft.p1, ft.p2})
       for(const Bound& b : chain)
         for(int k = 0; k < 3; k++)
           if(!(p[k] >= b.lo[k] && p[k] <= b.hi[k])) { out->box_violations++; break; }
-    }
   };
   if(s->dev.layout == 1u)
   {
@@ -1685,9 +1635,8 @@ int vkrt_debug_check_accel(vkrt_scene* s, vkrt_accel_check* out)
       if(slotsOfGid[g] == 0u) { out->triangles_uncovered++; continue; }  // an instanced triangle the tree does not hold at all
       if(slotsOfGid[g] == 1u) continue;
       out->triangles_split++;
-      const uint32_t s0 = bySlot[first[g]];
-      float v[3][3];
-      for(int c = 0; c < 3; c++) vertexOf(s0, c, v[c]);
+      const vkrt::FlatTri ft = decode(bySlot[first[g]]);
+      const float* v[3] = {ft.v0, ft.p1, ft.p2};
       bool covered = true;
       const int n = 8;  // lattice: barycentric (i, j, n - i - j) / n
       for(int i = 0; i <= n && covered; i++)
