@@ -1,0 +1,83 @@
+// dev_buffer.h -- host-side owners of device memory, the built-tree record every builder fills, and the one mapping of HIP errors to
+// vkrt return codes.  No device code.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstdint>
+#include <memory>
+#include <string>
+#include <vector>
+#include "../../include/vkrt.h"
+#include "device_scene.h"
+
+namespace vkrt {
+
+// hipError_t -> vkrt return code; a failure also leaves "<what>: <HIP's message>" in err
+inline int hip_status(hipError_t e, const char* what, std::string& err)
+{
+  if(e == hipSuccess)
+    return VKRT_OK;
+  err = std::string(what) + ": " + hipGetErrorString(e);
+  return e == hipErrorOutOfMemory ? VKRT_ERR_OUT_OF_MEMORY : VKRT_ERR_HIP;
+}
+
+// return the code of a failed HIP call from the enclosing function, its message in err
+#define VKRT_TRY(err, expr)                                                         \
+  do                                                                                \
+  {                                                                                 \
+    if(const int rc_ = vkrt::hip_status((expr), #expr, err); rc_ != VKRT_OK)        \
+      return rc_;                                                                   \
+  } while(0)
+
+// One hipMalloc, freed by the destructor or when another DevBuf is moved over it.
+class DevBuf
+{
+public:
+  hipError_t alloc(size_t bytes)
+  {
+    p_.reset();
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, bytes);
+    p_.reset(e == hipSuccess ? q : nullptr);
+    return e;
+  }
+  template <typename T = void>
+  T* get() const { return (T*)p_.get(); }
+
+private:
+  struct Free { void operator()(void* p) const { (void)hipFree(p); } };
+  std::unique_ptr<void, Free> p_;
+};
+
+// Scratch of one build: typed allocations of at least 16 bytes, all freed when the arena goes.
+struct DevArena
+{
+  std::vector<DevBuf> bufs;
+  template <typename T>
+  hipError_t alloc(T** p, size_t count)
+  {
+    bufs.emplace_back();
+    const hipError_t e = bufs.back().alloc(std::max<size_t>(count * sizeof(T), 16));
+    *p = bufs.back().get<T>();
+    return e;
+  }
+};
+
+// The tree's device buffers: nodes, then 48-B triangle and 16-B shading records (vertex indices + material) in the tree's slot order.
+struct TreeBuffers
+{
+  DevBuf nodes, tris, triShade;
+};
+
+// What a builder produced: the buffers and what vkrt_accel_info reports about them.  An empty record (no node buffer) is no tree.
+struct BuiltTree
+{
+  uint32_t layout = 0;  // 0 = BVH2, 1 = wide8
+  int32_t rootRef = VKRT_TRAV_DONE;
+  uint32_t maxDepth = 0, nodeCount = 0;
+  float sahCost = 0;
+  uint64_t nodeBytes = 0, triangleBytes = 0;
+  TreeBuffers buf;
+};
+
+}  // namespace vkrt

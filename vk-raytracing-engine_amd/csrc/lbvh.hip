@@ -17,7 +17,6 @@
 #include <cstring>
 #include <string>
 #include <algorithm>
-#include <cstdlib>
 #include <vector>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -949,294 +948,309 @@ struct TopBuilder
   }
 };
 
-struct Temp
+// What the stages of one build share.  The one scratch arena is freed when the build returns: the parent arrays outlive the collapse.
+struct Ctx
 {
-  std::vector<void*> ptrs;
-  ~Temp()
-  {
-    for(void* p : ptrs) (void)hipFree(p);
-  }
-  template <typename T>
-  hipError_t alloc(T** p, size_t count)
-  {
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, std::max<size_t>(count * sizeof(T), 16));
-    if(e == hipSuccess) ptrs.push_back(q);
-    *p = (T*)q;
-    return e;
-  }
+  hipStream_t stream;
+  std::string& err;
+  DevArena tmp;
 };
 
-}  // namespace
-
-#define LB_TRY(expr)                                         \
-  do                                                         \
-  {                                                          \
-    hipError_t e_ = (expr);                                  \
-    if(e_ != hipSuccess)                                     \
-    {                                                        \
-      out.error = std::string(#expr) + ": " + hipGetErrorString(e_); \
-      if(out.nodes) (void)hipFree(out.nodes);                \
-      if(out.tris) (void)hipFree(out.tris);                  \
-      if(out.triShade) (void)hipFree(out.triShade);          \
-      out.nodes = out.tris = out.triShade = nullptr;         \
-      return e_ == hipErrorOutOfMemory ? VKRT_ERR_OUT_OF_MEMORY : VKRT_ERR_HIP; \
-    }                                                        \
-  } while(0)
-
-int build_lbvh_device(const DevScene& sc, uint32_t instCount, const std::vector<vkrt_prim_mesh>& pm, const std::vector<vkrt_node>& nodes,
-                      hipStream_t stream, LbvhResult& out, unsigned leafSize, bool wantWide, bool ploc, bool watertight, bool dissolve, unsigned splitPercent)
+// The flattened instances.  The host tables stay until the build returns: their uploads are asynchronous.
+struct Flat
 {
-  bool topSah = ploc;  // the FAST_TRACE device build re-builds its upper levels with SAH; the radix tree stays the pure fast build
-  if(const char* e = getenv("VKRT_TOP_SAH"))  // test hook: force on / off for either builder
-    topSah = atoi(e) != 0;
-  // (clustered subtrees are not runs of the Morton order, so the PLOC tree keeps one triangle per leaf)
-  const unsigned kLeaf = ploc ? 1u : (leafSize < 1u ? 1u : (leafSize > 8u ? 8u : leafSize));
-  out = LbvhResult{};
-  std::vector<uint32_t> firstGid(instCount + 1, 0), firstIndex(instCount, 0), vertexOffset(instCount, 0);
-  std::vector<int32_t> material(instCount, 0);
-  for(uint32_t n = 0; n < instCount; n++)
-  {
-    const vkrt_prim_mesh& p = pm[nodes[n].primMesh];
-    firstGid[n + 1] = firstGid[n] + p.indexCount / 3;
-    firstIndex[n] = p.firstIndex;
-    vertexOffset[n] = p.vertexOffset;
-    material[n] = p.materialIndex;
-  }
-  const uint32_t triangles = firstGid[instCount];
-  out.triCount = triangles;
-  out.uniqueTris = triangles;
-  out.rootRef = VKRT_TRAV_DONE;
-  if(triangles == 0)
-  {
-    LB_TRY(hipMalloc(&out.nodes, 64));
-    LB_TRY(hipMalloc(&out.tris, 48));
-    LB_TRY(hipMalloc(&out.triShade, 16));
-    return VKRT_OK;
-  }
+  std::vector<uint32_t> firstGid, firstIndex, vertexOffset;
+  std::vector<int32_t> material;
+  unsigned initBounds[8] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u, 0u};
+  FlatArgs A{};                // A.triCount = instanced triangles
+  int32_t* dMaterial = nullptr;
+  float4* triU = nullptr;      // world-space (v0,e1,e2) records
+  float* triBox = nullptr;     // 6 per triangle
+  unsigned* bounds = nullptr;  // scene bounds, lo3 hi3 ordered
+};
 
-  Temp tmp;
-  uint32_t *dFirstGid, *dFirstIndex, *dVertexOffset;
-  int32_t* dMaterial;
-  LB_TRY(tmp.alloc(&dMaterial, instCount));
-  LB_TRY(hipMemcpyAsync(dMaterial, material.data(), instCount * 4, hipMemcpyHostToDevice, stream));
-  LB_TRY(tmp.alloc(&dFirstGid, instCount + 1));
-  LB_TRY(tmp.alloc(&dFirstIndex, instCount));
-  LB_TRY(tmp.alloc(&dVertexOffset, instCount));
-  LB_TRY(hipMemcpyAsync(dFirstGid, firstGid.data(), (instCount + 1) * 4, hipMemcpyHostToDevice, stream));
-  LB_TRY(hipMemcpyAsync(dFirstIndex, firstIndex.data(), instCount * 4, hipMemcpyHostToDevice, stream));
-  LB_TRY(hipMemcpyAsync(dVertexOffset, vertexOffset.data(), instCount * 4, hipMemcpyHostToDevice, stream));
+// The leaves: T references (>= triangles), the triangle of each (null: the identity), their boxes, then their sorted codes and order.
+struct Leaves
+{
+  uint32_t T = 0;
+  const unsigned* tri = nullptr;
+  float* box = nullptr;
+  unsigned long long* keys = nullptr;
+  unsigned* order = nullptr;
+};
 
-  float4* triU;
-  float* triBox;
-  unsigned* bounds;
-  LB_TRY(tmp.alloc(&triU, (size_t)triangles * 3));
-  LB_TRY(tmp.alloc(&triBox, (size_t)triangles * 6));
-  LB_TRY(tmp.alloc(&bounds, 8));
-  const unsigned initB[8] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u, 0u};
-  LB_TRY(hipMemcpyAsync(bounds, initB, sizeof initB, hipMemcpyHostToDevice, stream));
-
-  const unsigned B = 256;
-  FlatArgs A{sc.positions, sc.indices, sc.instances, dFirstGid, dFirstIndex, dVertexOffset, instCount, triangles};
-  hipLaunchKernelGGL(k_flatten, dim3((triangles + B - 1) / B), dim3(B), 0, stream, A, watertight ? 1 : 0, triU, triBox, bounds);
-  LB_TRY(hipGetLastError());
-
-  // ---- triangle pre-splitting: T = references (>= triangles), refTri / refBox replace the identity / triBox ------------------
-  uint32_t T = triangles;
-  const unsigned* refTri = nullptr;
-  const float* refBox = triBox;
-  const unsigned budget = (unsigned)std::min<uint64_t>((uint64_t)triangles * splitPercent / 100u, 0x3fffffffu);
-  if(budget > 0u && triangles > 1u)
-  {
-    const unsigned G3 = (triangles + B - 1) / B;
-    float *prio, *dD;
-    unsigned *counts, *offsets;
-    LB_TRY(tmp.alloc(&prio, triangles));
-    LB_TRY(tmp.alloc(&dD, 4));
-    LB_TRY(tmp.alloc(&counts, (size_t)triangles + 1));
-    LB_TRY(tmp.alloc(&offsets, (size_t)triangles + 1));
-    hipLaunchKernelGGL(k_split_priority, dim3(G3), dim3(B), 0, stream, triangles, (const float4*)triU, (const float*)triBox, (const unsigned*)bounds, watertight ? 1 : 0, prio);
-    float dmax = INFINITY;
-    if(const char* e = getenv("VKRT_SPLIT_DMAX"))  // test hook: cap of the priority scale D (splits per unit of priority)
-      dmax = (float)atof(e);
-    hipLaunchKernelGGL(k_split_budget, dim3(1), dim3(1024), 0, stream, triangles, (const float*)prio, budget, dmax, dD);
-    LB_TRY(hipMemsetAsync(counts + triangles, 0, 4, stream));
-    hipLaunchKernelGGL((k_split_refs<false>), dim3(G3), dim3(B), 0, stream, triangles, (const float4*)triU, (const float*)triBox, (const unsigned*)bounds,
-                       watertight ? 1 : 0, (const float*)prio, (const float*)dD, counts, (unsigned*)nullptr, (float*)nullptr);
-    LB_TRY(hipGetLastError());
-    size_t scanBytes = 0;
-    LB_TRY(rocprim::exclusive_scan(nullptr, scanBytes, counts, offsets, 0u, (size_t)triangles + 1, rocprim::plus<unsigned>(), stream));
-    void* scanTmp;
-    LB_TRY(tmp.alloc((char**)&scanTmp, scanBytes));
-    LB_TRY(rocprim::exclusive_scan(scanTmp, scanBytes, counts, offsets, 0u, (size_t)triangles + 1, rocprim::plus<unsigned>(), stream));
-    unsigned total = 0;
-    LB_TRY(hipMemcpyAsync(&total, offsets + triangles, 4, hipMemcpyDeviceToHost, stream));
-    LB_TRY(hipStreamSynchronize(stream));
-    if(total < triangles || total > triangles + budget)
-    {
-      out.error = "triangle pre-splitting: reference count out of range (internal error)";
-      return VKRT_ERR_HIP;
-    }
-    if(total > triangles)
-    {
-      unsigned* rt;
-      float* rb;
-      LB_TRY(tmp.alloc(&rt, total));
-      LB_TRY(tmp.alloc(&rb, (size_t)total * 6));
-      hipLaunchKernelGGL((k_split_refs<true>), dim3(G3), dim3(B), 0, stream, triangles, (const float4*)triU, (const float*)triBox, (const unsigned*)bounds,
-                         watertight ? 1 : 0, (const float*)prio, (const float*)dD, offsets, rt, rb);
-      LB_TRY(hipGetLastError());
-      T = total;
-      refTri = rt;
-      refBox = rb;
-    }
-  }
-  out.triCount = T;
-  LB_TRY(hipMalloc(&out.nodes, std::max<size_t>((size_t)(T > 1 ? T - 1 : 1) * 64, 64)));
-  LB_TRY(hipMalloc(&out.tris, std::max<size_t>((size_t)T * 48, 48)));
-  LB_TRY(hipMalloc(&out.triShade, std::max<size_t>((size_t)T * 16, 16)));
-  out.nodeCount = T > 1 ? T - 1 : 0;
-
-  unsigned long long *keysA, *keysB;
-  unsigned *valsA, *valsB;
-  LB_TRY(tmp.alloc(&keysA, T));
-  LB_TRY(tmp.alloc(&keysB, T));
-  LB_TRY(tmp.alloc(&valsA, T));
-  LB_TRY(tmp.alloc(&valsB, T));
-  const unsigned G = (T + B - 1) / B;
-  triBox = const_cast<float*>(refBox);  // from here on "triangle" means reference -- one leaf of the tree -- and triBox its box
-  hipLaunchKernelGGL(k_morton, dim3(G), dim3(B), 0, stream, T, (const float*)triBox, (const unsigned*)bounds, keysA, valsA);
-  LB_TRY(hipGetLastError());
-
-  size_t sortBytes = 0;
-  LB_TRY(rocprim::radix_sort_pairs(nullptr, sortBytes, keysA, keysB, valsA, valsB, (size_t)T, 0, 63, stream));
-  void* sortTmp;
-  LB_TRY(tmp.alloc((char**)&sortTmp, sortBytes));
-  LB_TRY(rocprim::radix_sort_pairs(sortTmp, sortBytes, keysA, keysB, valsA, valsB, (size_t)T, 0, 63, stream));
-  const unsigned* order = valsB;
-
-  hipLaunchKernelGGL(k_pack, dim3(G), dim3(B), 0, stream, T, order, (const float4*)triU, (float4*)out.tris, A, (const int*)dMaterial, (uint4*)out.triShade,
-                     dissolve ? sc.materials : (const DevMaterial*)nullptr, refTri);
-  LB_TRY(hipGetLastError());
-
-  if(T <= kLeaf)
-  {
-    out.rootRef = (int32_t) ~((0u << 3) | (T - 1u));
-    out.maxDepth = 0;
-    out.nodeCount = 0;
-    LB_TRY(hipStreamSynchronize(stream));
-    return VKRT_OK;
-  }
-
+// The binary hierarchy over the sorted leaves (node 0 is the root).
+struct Hierarchy
+{
   int2 *children, *range;
   int *parentInternal, *parentLeaf;
   float* nodeBox;
+  unsigned* scalars;  // [0] maxDepth, [1] sah accum (float), [2] frontier entries, [3] nodes above the frontier
+};
+
+// Instance tables (first triangle, index and vertex offset, material), uploaded, then k_flatten.  An empty scene allocates nothing here.
+int flattenInstances(Ctx& c, const DevScene& sc, uint32_t instCount, const std::vector<vkrt_prim_mesh>& pm, const std::vector<vkrt_node>& nodes,
+                     Flat& f)
+{
+  f.firstGid.assign(1, 0);
+  for(uint32_t n = 0; n < instCount; n++)
+  {
+    const vkrt_prim_mesh& p = pm[nodes[n].primMesh];
+    f.firstGid.push_back(f.firstGid[n] + p.indexCount / 3);
+    f.firstIndex.push_back(p.firstIndex);
+    f.vertexOffset.push_back(p.vertexOffset);
+    f.material.push_back(p.materialIndex);
+  }
+  const uint32_t triangles = f.firstGid[instCount];
+  f.A.triCount = triangles;
+  if(triangles == 0)
+    return VKRT_OK;
+  uint32_t *dFirstGid, *dFirstIndex, *dVertexOffset;
+  VKRT_TRY(c.err, c.tmp.alloc(&f.dMaterial, instCount));
+  VKRT_TRY(c.err, hipMemcpyAsync(f.dMaterial, f.material.data(), instCount * 4, hipMemcpyHostToDevice, c.stream));
+  VKRT_TRY(c.err, c.tmp.alloc(&dFirstGid, instCount + 1));
+  VKRT_TRY(c.err, c.tmp.alloc(&dFirstIndex, instCount));
+  VKRT_TRY(c.err, c.tmp.alloc(&dVertexOffset, instCount));
+  VKRT_TRY(c.err, hipMemcpyAsync(dFirstGid, f.firstGid.data(), (instCount + 1) * 4, hipMemcpyHostToDevice, c.stream));
+  VKRT_TRY(c.err, hipMemcpyAsync(dFirstIndex, f.firstIndex.data(), instCount * 4, hipMemcpyHostToDevice, c.stream));
+  VKRT_TRY(c.err, hipMemcpyAsync(dVertexOffset, f.vertexOffset.data(), instCount * 4, hipMemcpyHostToDevice, c.stream));
+
+  VKRT_TRY(c.err, c.tmp.alloc(&f.triU, (size_t)triangles * 3));
+  VKRT_TRY(c.err, c.tmp.alloc(&f.triBox, (size_t)triangles * 6));
+  VKRT_TRY(c.err, c.tmp.alloc(&f.bounds, 8));
+  VKRT_TRY(c.err, hipMemcpyAsync(f.bounds, f.initBounds, sizeof f.initBounds, hipMemcpyHostToDevice, c.stream));
+
+  const unsigned B = 256;
+  f.A = FlatArgs{sc.positions, sc.indices, sc.instances, dFirstGid, dFirstIndex, dVertexOffset, instCount, triangles};
+  hipLaunchKernelGGL(k_flatten, dim3((triangles + B - 1) / B), dim3(B), 0, c.stream, f.A, sc.watertight ? 1 : 0, f.triU, f.triBox, f.bounds);
+  VKRT_TRY(c.err, hipGetLastError());
+  return VKRT_OK;
+}
+
+// Triangle pre-splitting: a budget of splitPercent % extra references, handed out by priority (see k_split_priority).
+int preSplit(Ctx& c, const DevScene& sc, const Flat& f, unsigned splitPercent, Leaves& l)
+{
+  const int watertight = sc.watertight ? 1 : 0;
+  const uint32_t triangles = f.A.triCount;
+  l.T = triangles;
+  l.box = f.triBox;
+  const unsigned budget = (unsigned)std::min<uint64_t>((uint64_t)triangles * splitPercent / 100u, 0x3fffffffu);
+  if(budget == 0u || triangles <= 1u)
+    return VKRT_OK;
+  const unsigned B = 256, G3 = (triangles + B - 1) / B;
+  float *prio, *dD;
+  unsigned *counts, *offsets;
+  VKRT_TRY(c.err, c.tmp.alloc(&prio, triangles));
+  VKRT_TRY(c.err, c.tmp.alloc(&dD, 4));
+  VKRT_TRY(c.err, c.tmp.alloc(&counts, (size_t)triangles + 1));
+  VKRT_TRY(c.err, c.tmp.alloc(&offsets, (size_t)triangles + 1));
+  hipLaunchKernelGGL(k_split_priority, dim3(G3), dim3(B), 0, c.stream, triangles, (const float4*)f.triU, (const float*)f.triBox, (const unsigned*)f.bounds,
+                     watertight, prio);
+  const float dmax = INFINITY;  // cap of the priority scale D (splits per unit of priority): none
+  hipLaunchKernelGGL(k_split_budget, dim3(1), dim3(1024), 0, c.stream, triangles, (const float*)prio, budget, dmax, dD);
+  VKRT_TRY(c.err, hipMemsetAsync(counts + triangles, 0, 4, c.stream));
+  hipLaunchKernelGGL((k_split_refs<false>), dim3(G3), dim3(B), 0, c.stream, triangles, (const float4*)f.triU, (const float*)f.triBox, (const unsigned*)f.bounds,
+                     watertight, (const float*)prio, (const float*)dD, counts, (unsigned*)nullptr, (float*)nullptr);
+  VKRT_TRY(c.err, hipGetLastError());
+  size_t scanBytes = 0;
+  VKRT_TRY(c.err, rocprim::exclusive_scan(nullptr, scanBytes, counts, offsets, 0u, (size_t)triangles + 1, rocprim::plus<unsigned>(), c.stream));
+  char* scanTmp;
+  VKRT_TRY(c.err, c.tmp.alloc(&scanTmp, scanBytes));
+  VKRT_TRY(c.err, rocprim::exclusive_scan((void*)scanTmp, scanBytes, counts, offsets, 0u, (size_t)triangles + 1, rocprim::plus<unsigned>(), c.stream));
+  unsigned total = 0;
+  VKRT_TRY(c.err, hipMemcpyAsync(&total, offsets + triangles, 4, hipMemcpyDeviceToHost, c.stream));
+  VKRT_TRY(c.err, hipStreamSynchronize(c.stream));
+  if(total < triangles || total > triangles + budget)
+  {
+    c.err = "triangle pre-splitting: reference count out of range (internal error)";
+    return VKRT_ERR_HIP;
+  }
+  if(total > triangles)
+  {
+    unsigned* rt;
+    float* rb;
+    VKRT_TRY(c.err, c.tmp.alloc(&rt, total));
+    VKRT_TRY(c.err, c.tmp.alloc(&rb, (size_t)total * 6));
+    hipLaunchKernelGGL((k_split_refs<true>), dim3(G3), dim3(B), 0, c.stream, triangles, (const float4*)f.triU, (const float*)f.triBox, (const unsigned*)f.bounds,
+                       watertight, (const float*)prio, (const float*)dD, offsets, rt, rb);
+    VKRT_TRY(c.err, hipGetLastError());
+    l.T = total;
+    l.tri = rt;
+    l.box = rb;
+  }
+  return VKRT_OK;
+}
+
+// Morton codes of the leaf boxes, radix sort, then the triangle and shading records in leaf order ("triangle" = reference from here).
+int sortAndPack(Ctx& c, const DevScene& sc, const Flat& f, Leaves& l, TreeBuffers& buf)
+{
+  const uint32_t T = l.T;
+  unsigned long long* keysA;  // (sorted into l.keys, their gids into l.order)
+  unsigned* valsA;
+  VKRT_TRY(c.err, c.tmp.alloc(&keysA, T));
+  VKRT_TRY(c.err, c.tmp.alloc(&l.keys, T));
+  VKRT_TRY(c.err, c.tmp.alloc(&valsA, T));
+  VKRT_TRY(c.err, c.tmp.alloc(&l.order, T));
+  const unsigned B = 256, G = (T + B - 1) / B;
+  hipLaunchKernelGGL(k_morton, dim3(G), dim3(B), 0, c.stream, T, (const float*)l.box, (const unsigned*)f.bounds, keysA, valsA);
+  VKRT_TRY(c.err, hipGetLastError());
+
+  size_t sortBytes = 0;
+  VKRT_TRY(c.err, rocprim::radix_sort_pairs(nullptr, sortBytes, keysA, l.keys, valsA, l.order, (size_t)T, 0, 63, c.stream));
+  char* sortTmp;
+  VKRT_TRY(c.err, c.tmp.alloc(&sortTmp, sortBytes));
+  VKRT_TRY(c.err, rocprim::radix_sort_pairs((void*)sortTmp, sortBytes, keysA, l.keys, valsA, l.order, (size_t)T, 0, 63, c.stream));
+
+  hipLaunchKernelGGL(k_pack, dim3(G), dim3(B), 0, c.stream, T, (const unsigned*)l.order, (const float4*)f.triU, buf.tris.get<float4>(), f.A,
+                     (const int*)f.dMaterial, buf.triShade.get<uint4>(), sc.dissolve ? sc.materials : (const DevMaterial*)nullptr, l.tri);
+  VKRT_TRY(c.err, hipGetLastError());
+  return VKRT_OK;
+}
+
+// Children, parents and boxes of the T - 1 internal nodes: the Karras radix tree with a bottom-up fit, or PLOC clustering.
+int buildHierarchy(Ctx& c, bool ploc, const Leaves& l, Hierarchy& h)
+{
+  const uint32_t T = l.T;
   unsigned* arrive;
-  unsigned* scalars;  // [0] maxDepth, [1] sah accum (float)
-  LB_TRY(tmp.alloc(&children, T - 1));
-  LB_TRY(tmp.alloc(&range, T - 1));
-  LB_TRY(tmp.alloc(&parentInternal, T - 1));
-  LB_TRY(tmp.alloc(&parentLeaf, T));
-  LB_TRY(tmp.alloc(&nodeBox, (size_t)(T - 1) * 6));
-  LB_TRY(tmp.alloc(&arrive, T - 1));
-  LB_TRY(tmp.alloc(&scalars, 4));  // [0] maxDepth, [1] sah accum, [2] frontier entries, [3] nodes above the frontier
-  LB_TRY(hipMemsetAsync(arrive, 0, (size_t)(T - 1) * 4, stream));
-  LB_TRY(hipMemsetAsync(scalars, 0, 16, stream));
+  VKRT_TRY(c.err, c.tmp.alloc(&h.children, T - 1));
+  VKRT_TRY(c.err, c.tmp.alloc(&h.range, T - 1));
+  VKRT_TRY(c.err, c.tmp.alloc(&h.parentInternal, T - 1));
+  VKRT_TRY(c.err, c.tmp.alloc(&h.parentLeaf, T));
+  VKRT_TRY(c.err, c.tmp.alloc(&h.nodeBox, (size_t)(T - 1) * 6));
+  VKRT_TRY(c.err, c.tmp.alloc(&arrive, T - 1));
+  VKRT_TRY(c.err, c.tmp.alloc(&h.scalars, 4));
+  VKRT_TRY(c.err, hipMemsetAsync(arrive, 0, (size_t)(T - 1) * 4, c.stream));
+  VKRT_TRY(c.err, hipMemsetAsync(h.scalars, 0, 16, c.stream));
   if(ploc)
-  {
-    const int rcp = ploc_cluster_device(T, order, (const float*)triBox, stream, children, range, parentInternal, parentLeaf, nodeBox, nullptr, out.error);
-    if(rcp != VKRT_OK)
-    {
-      (void)hipFree(out.nodes); (void)hipFree(out.tris); (void)hipFree(out.triShade);
-      out.nodes = out.tris = out.triShade = nullptr;
-      return rcp;
-    }
-  }
-  else
-  {
-    hipLaunchKernelGGL(k_hierarchy, dim3(G), dim3(B), 0, stream, (int)T, (const unsigned long long*)keysB, children, range, parentInternal,
-                       parentLeaf);
-    hipLaunchKernelGGL(k_fit, dim3(G), dim3(B), 0, stream, (int)T, order, (const float*)triBox, (const int2*)children,
-                       (const int*)parentInternal, (const int*)parentLeaf, nodeBox, arrive);
-  }
-  if(topSah && T > 4096u)
-  {
-    // re-build the levels above subtrees of <= K triangles with a full-sweep SAH over those subtrees (see k_top_select)
-    // ~2 k subtrees whatever the scene size (16 k of them: twice the build time at 2 M triangles for the same ray rate, #71)
-    unsigned K = std::max(16u, T / 2048u);
-    if(const char* e = getenv("VKRT_TOP_SAH_LEAF"))  // test hook: triangles per frontier subtree
-      K = (unsigned)std::max(8, atoi(e));
-    const unsigned cap = 32768u;
-    TopEntry* dFrontier;
-    int* dTopIds;
-    TopNode* dTop;
-    LB_TRY(tmp.alloc(&dFrontier, cap));
-    LB_TRY(tmp.alloc(&dTopIds, cap));
-    LB_TRY(tmp.alloc(&dTop, cap));
-    LB_TRY(hipMemsetAsync(&scalars[2], 0, 8, stream));
-    hipLaunchKernelGGL(k_top_select, dim3((2 * T - 1 + B - 1) / B), dim3(B), 0, stream, (int)T, K, cap, order, (const float*)triBox, (const int2*)range,
-                       (const int*)parentInternal, (const int*)parentLeaf, (const float*)nodeBox, dFrontier, dTopIds, &scalars[2]);
-    LB_TRY(hipGetLastError());
-    unsigned cnt[2];
-    LB_TRY(hipMemcpyAsync(cnt, &scalars[2], 8, hipMemcpyDeviceToHost, stream));
-    LB_TRY(hipStreamSynchronize(stream));
-    if(cnt[0] >= 2u && cnt[0] <= cap && cnt[1] + 1u == cnt[0])  // (a frontier too large for the host pass keeps the tree as built)
-    {
-      std::vector<TopEntry> fr(cnt[0]);
-      std::vector<int> ids(cnt[1]);
-      LB_TRY(hipMemcpyAsync(fr.data(), dFrontier, (size_t)cnt[0] * sizeof(TopEntry), hipMemcpyDeviceToHost, stream));
-      LB_TRY(hipMemcpyAsync(ids.data(), dTopIds, (size_t)cnt[1] * sizeof(int), hipMemcpyDeviceToHost, stream));
-      LB_TRY(hipStreamSynchronize(stream));
-      std::sort(ids.begin(), ids.end());  // the atomics hand out slots in any order: fix it (ids[0] = 0, the root)
-      std::sort(fr.begin(), fr.end(), [](const TopEntry& x, const TopEntry& y) { return x.ref < y.ref; });
-      std::vector<TopNode> top;
-      top.reserve(cnt[1]);
-      TopBuilder tb{fr, ids, top};
-      (void)tb.build(0, fr.size());
-      LB_TRY(hipMemcpyAsync(dTop, top.data(), top.size() * sizeof(TopNode), hipMemcpyHostToDevice, stream));
-      hipLaunchKernelGGL(k_top_apply, dim3(((unsigned)top.size() + B - 1) / B), dim3(B), 0, stream, (unsigned)top.size(), (const TopNode*)dTop, children, range,
-                         parentInternal, parentLeaf, nodeBox);
-      LB_TRY(hipGetLastError());
-      LB_TRY(hipStreamSynchronize(stream));  // `top` is read by the copy until here
-    }
-  }
-  hipLaunchKernelGGL(k_emit, dim3(G), dim3(B), 0, stream, kLeaf, (int)T, order, (const float*)triBox, (const int2*)children, (const int2*)range,
-                     (const float*)nodeBox, (float4*)out.nodes, (float*)&scalars[1]);
-  hipLaunchKernelGGL(k_depth, dim3(G), dim3(B), 0, stream, kLeaf, (int)T, (const int2*)range, (const int*)parentInternal, (const int*)parentLeaf,
-                     &scalars[0]);
-  LB_TRY(hipGetLastError());
-  if(wantWide && kLeaf == 1u)
-  {
-    // the whole acceleration structure on the device: collapse the radix tree into 8-wide compressed nodes while the parent
-    // arrays are still here (wide_collapse.hip); a tree that does not fit its level budget is reported, not guessed at
-    WideCollapseIn in{T, (const float4*)out.nodes, (const int*)parentInternal, (const int*)parentLeaf, (const float4*)out.tris, (const uint4*)out.triShade};
-    const int rcw = collapse_wide8_device(in, stream, out.wide, out.error);
-    if(rcw != VKRT_OK)
-    {
-      (void)hipFree(out.nodes); (void)hipFree(out.tris); (void)hipFree(out.triShade);
-      out.nodes = out.tris = out.triShade = nullptr;
-      return rcw;
-    }
-    out.hasWide = !out.wide.overflow;
-    if(out.wide.overflow)
-    {
-      (void)hipFree(out.wide.nodes); (void)hipFree(out.wide.tris); (void)hipFree(out.wide.triShade);
-      out.wide.nodes = out.wide.tris = out.wide.triShade = nullptr;
-    }
-  }
+    return ploc_cluster_device(T, l.order, (const float*)l.box, c.stream, h.children, h.range, h.parentInternal, h.parentLeaf, h.nodeBox, c.err);
+  const unsigned B = 256, G = (T + B - 1) / B;
+  hipLaunchKernelGGL(k_hierarchy, dim3(G), dim3(B), 0, c.stream, (int)T, (const unsigned long long*)l.keys, h.children, h.range, h.parentInternal,
+                     h.parentLeaf);
+  hipLaunchKernelGGL(k_fit, dim3(G), dim3(B), 0, c.stream, (int)T, (const unsigned*)l.order, (const float*)l.box, (const int2*)h.children,
+                     (const int*)h.parentInternal, (const int*)h.parentLeaf, h.nodeBox, arrive);
+  return VKRT_OK;
+}
+
+// Re-build the levels above subtrees of <= K triangles with a full-sweep SAH over those subtrees (see k_top_select).
+int topLevelsSah(Ctx& c, const Leaves& l, const Hierarchy& h)
+{
+  const uint32_t T = l.T;
+  // ~2 k subtrees whatever the scene size (16 k of them: twice the build time at 2 M triangles for the same ray rate, #71)
+  const unsigned K = std::max(16u, T / 2048u);
+  const unsigned B = 256, cap = 32768u;
+  TopEntry* dFrontier;
+  int* dTopIds;
+  TopNode* dTop;
+  VKRT_TRY(c.err, c.tmp.alloc(&dFrontier, cap));
+  VKRT_TRY(c.err, c.tmp.alloc(&dTopIds, cap));
+  VKRT_TRY(c.err, c.tmp.alloc(&dTop, cap));
+  VKRT_TRY(c.err, hipMemsetAsync(&h.scalars[2], 0, 8, c.stream));
+  hipLaunchKernelGGL(k_top_select, dim3((2 * T - 1 + B - 1) / B), dim3(B), 0, c.stream, (int)T, K, cap, (const unsigned*)l.order, (const float*)l.box,
+                     (const int2*)h.range, (const int*)h.parentInternal, (const int*)h.parentLeaf, (const float*)h.nodeBox, dFrontier, dTopIds, &h.scalars[2]);
+  VKRT_TRY(c.err, hipGetLastError());
+  unsigned cnt[2];
+  VKRT_TRY(c.err, hipMemcpyAsync(cnt, &h.scalars[2], 8, hipMemcpyDeviceToHost, c.stream));
+  VKRT_TRY(c.err, hipStreamSynchronize(c.stream));
+  if(!(cnt[0] >= 2u && cnt[0] <= cap && cnt[1] + 1u == cnt[0]))
+    return VKRT_OK;  // (a frontier too large for the host pass keeps the tree as built)
+  std::vector<TopEntry> fr(cnt[0]);
+  std::vector<int> ids(cnt[1]);
+  VKRT_TRY(c.err, hipMemcpyAsync(fr.data(), dFrontier, (size_t)cnt[0] * sizeof(TopEntry), hipMemcpyDeviceToHost, c.stream));
+  VKRT_TRY(c.err, hipMemcpyAsync(ids.data(), dTopIds, (size_t)cnt[1] * sizeof(int), hipMemcpyDeviceToHost, c.stream));
+  VKRT_TRY(c.err, hipStreamSynchronize(c.stream));
+  std::sort(ids.begin(), ids.end());  // the atomics hand out slots in any order: fix it (ids[0] = 0, the root)
+  std::sort(fr.begin(), fr.end(), [](const TopEntry& x, const TopEntry& y) { return x.ref < y.ref; });
+  std::vector<TopNode> top;
+  top.reserve(cnt[1]);
+  TopBuilder tb{fr, ids, top};
+  (void)tb.build(0, fr.size());
+  VKRT_TRY(c.err, hipMemcpyAsync(dTop, top.data(), top.size() * sizeof(TopNode), hipMemcpyHostToDevice, c.stream));
+  hipLaunchKernelGGL(k_top_apply, dim3(((unsigned)top.size() + B - 1) / B), dim3(B), 0, c.stream, (unsigned)top.size(), (const TopNode*)dTop, h.children,
+                     h.range, h.parentInternal, h.parentLeaf, h.nodeBox);
+  VKRT_TRY(c.err, hipGetLastError());
+  VKRT_TRY(c.err, hipStreamSynchronize(c.stream));  // `top` is read by the copy until here
+  return VKRT_OK;
+}
+
+// The 64-B nodes (subtrees of <= kLeaf triangles become leaves), their SAH sum and the tree depth.
+int emitAndDepth(Ctx& c, unsigned kLeaf, const Leaves& l, const Hierarchy& h, float4* nodes)
+{
+  const unsigned B = 256, G = (l.T + B - 1) / B;
+  hipLaunchKernelGGL(k_emit, dim3(G), dim3(B), 0, c.stream, kLeaf, (int)l.T, (const unsigned*)l.order, (const float*)l.box, (const int2*)h.children,
+                     (const int2*)h.range, (const float*)h.nodeBox, nodes, (float*)&h.scalars[1]);
+  hipLaunchKernelGGL(k_depth, dim3(G), dim3(B), 0, c.stream, kLeaf, (int)l.T, (const int2*)h.range, (const int*)h.parentInternal, (const int*)h.parentLeaf,
+                     &h.scalars[0]);
+  VKRT_TRY(c.err, hipGetLastError());
+  return VKRT_OK;
+}
+
+// Depth and SAH cost of the binary tree (the SAH sum over the root's area).
+int readBack(Ctx& c, const Hierarchy& h, BuiltTree& t)
+{
   unsigned hs[4];
   float rootBox[6];
-  LB_TRY(hipMemcpyAsync(hs, scalars, 16, hipMemcpyDeviceToHost, stream));
-  LB_TRY(hipMemcpyAsync(rootBox, nodeBox, 24, hipMemcpyDeviceToHost, stream));
-  LB_TRY(hipStreamSynchronize(stream));
-  out.rootRef = 0;
-  out.maxDepth = hs[0];
+  VKRT_TRY(c.err, hipMemcpyAsync(hs, h.scalars, 16, hipMemcpyDeviceToHost, c.stream));
+  VKRT_TRY(c.err, hipMemcpyAsync(rootBox, h.nodeBox, 24, hipMemcpyDeviceToHost, c.stream));
+  VKRT_TRY(c.err, hipStreamSynchronize(c.stream));
+  t.rootRef = 0;
+  t.maxDepth = hs[0];
   float sah;
   memcpy(&sah, &hs[1], 4);
   const float ra = 2.0f * ((rootBox[3] - rootBox[0]) * (rootBox[4] - rootBox[1]) + (rootBox[4] - rootBox[1]) * (rootBox[5] - rootBox[2]) +
                            (rootBox[5] - rootBox[2]) * (rootBox[3] - rootBox[0]));
-  out.sahCost = ra > 0.0f ? sah / ra : 0.0f;
+  t.sahCost = ra > 0.0f ? sah / ra : 0.0f;
   return VKRT_OK;
+}
+
+}  // namespace
+
+int build_lbvh_device(const DevScene& sc, uint32_t instCount, const std::vector<vkrt_prim_mesh>& pm, const std::vector<vkrt_node>& nodes,
+                      const LbvhParams& p, hipStream_t stream, LbvhResult& out)
+{
+  // (the device collapse wants one triangle per leaf; clustered subtrees are not runs of the Morton order, so the PLOC tree keeps one too)
+  const unsigned kLeaf = p.ploc || p.wide ? 1u : 4u;
+  out = LbvhResult{};
+  BuiltTree& t = out.tree;
+  Ctx c{stream, out.error, {}};
+  Flat f;
+  int rc = flattenInstances(c, sc, instCount, pm, nodes, f);
+  if(rc != VKRT_OK)
+    return rc;
+  out.uniqueTris = f.A.triCount;
+  Leaves l;
+  if((rc = preSplit(c, sc, f, p.splitPercent, l)) != VKRT_OK)
+    return rc;
+  const uint32_t T = l.T;
+  out.triCount = T;
+  VKRT_TRY(c.err, t.buf.nodes.alloc(std::max<size_t>((size_t)(T > 1 ? T - 1 : 1) * 64, 64)));
+  VKRT_TRY(c.err, t.buf.tris.alloc(std::max<size_t>((size_t)T * 48, 48)));
+  VKRT_TRY(c.err, t.buf.triShade.alloc(std::max<size_t>((size_t)T * 16, 16)));
+  t.triangleBytes = (uint64_t)T * 48;
+  if(T == 0)
+    return VKRT_OK;  // an empty scene: minimal buffers, no tree
+  if((rc = sortAndPack(c, sc, f, l, t.buf)) != VKRT_OK)
+    return rc;
+  if(T <= kLeaf)
+  {
+    t.rootRef = (int32_t) ~((0u << 3) | (T - 1u));
+    VKRT_TRY(c.err, hipStreamSynchronize(stream));
+    return VKRT_OK;
+  }
+  t.nodeCount = T - 1;
+  t.nodeBytes = (uint64_t)t.nodeCount * 64;
+  Hierarchy h;
+  if((rc = buildHierarchy(c, p.ploc, l, h)) != VKRT_OK)
+    return rc;
+  // the FAST_TRACE device build re-builds its upper levels with SAH; the radix tree stays the pure fast build
+  if(p.ploc && T > 4096u && (rc = topLevelsSah(c, l, h)) != VKRT_OK)
+    return rc;
+  if((rc = emitAndDepth(c, kLeaf, l, h, t.buf.nodes.get<float4>())) != VKRT_OK)
+    return rc;
+  // the whole acceleration structure on the device: collapse the radix tree into 8-wide compressed nodes while the parent
+  // arrays are still here (wide_collapse.hip); a tree that does not fit its level budget is reported, not guessed at
+  if(p.wide && (rc = collapse_wide8_device(T, t.buf, h.parentInternal, h.parentLeaf, stream, out.wide, c.err)) != VKRT_OK)
+    return rc;
+  return readBack(c, h, t);
 }
 
 }  // namespace vkrt

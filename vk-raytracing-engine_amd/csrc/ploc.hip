@@ -246,47 +246,28 @@ __global__ __launch_bounds__(PLOC_BLOCK) void k_ploc_apply(int nc, int nextId, c
   out[pos] = a;
 }
 
-struct Scratch
-{
-  void* p = nullptr;
-  ~Scratch() { if(p) (void)hipFree(p); }
-};
-
 }  // namespace
 
 int ploc_cluster_device(uint32_t T, const unsigned* order, const float* triBox, hipStream_t stream, int2* children, int2* range, int* parentInternal,
-                        int* parentLeaf, float* nodeBox, unsigned* passes, std::string& err)
+                        int* parentLeaf, float* nodeBox, std::string& err)
 {
-  int radius = 16;
-  if(const char* e = getenv("VKRT_PLOC_RADIUS"))  // test hook: search window of the clustering (1..32)
-    radius = std::max(1, std::min(PLOC_MAX_RADIUS, atoi(e)));
+  const int radius = 16;  // search window of the clustering (1..PLOC_MAX_RADIUS)
   int metric = 2;
   if(const char* e = getenv("VKRT_PLOC_METRIC"))  // test hook: merge cost (see k_ploc_nn)
     metric = atoi(e);
   const unsigned maxBlocks = (T + PLOC_BLOCK - 1) / PLOC_BLOCK;
   const size_t clusterBytes = (size_t)T * sizeof(PlocCluster);
   const size_t bytes = 2 * clusterBytes + (size_t)T * 4 + (size_t)maxBlocks * 8 + 64;
-  Scratch s;
-#define PLOC_TRY(expr)                                                  \
-  do                                                                    \
-  {                                                                     \
-    hipError_t e_ = (expr);                                             \
-    if(e_ != hipSuccess)                                                \
-    {                                                                   \
-      err = std::string(#expr) + ": " + hipGetErrorString(e_);          \
-      return e_ == hipErrorOutOfMemory ? VKRT_ERR_OUT_OF_MEMORY : VKRT_ERR_HIP; \
-    }                                                                   \
-  } while(0)
-  PLOC_TRY(hipMalloc(&s.p, bytes));
-  PlocCluster* cl[2] = {(PlocCluster*)s.p, (PlocCluster*)((char*)s.p + clusterBytes)};
-  int* nn = (int*)((char*)s.p + 2 * clusterBytes);
+  DevBuf s;
+  VKRT_TRY(err, s.alloc(bytes));
+  PlocCluster* cl[2] = {s.get<PlocCluster>(), (PlocCluster*)(s.get<char>() + clusterBytes)};
+  int* nn = (int*)(s.get<char>() + 2 * clusterBytes);
   uint2* blockCounts = (uint2*)((char*)nn + (size_t)T * 4);
   unsigned* totals = (unsigned*)((char*)blockCounts + (size_t)maxBlocks * 8);
   hipLaunchKernelGGL(k_ploc_leaves, dim3(maxBlocks), dim3(PLOC_BLOCK), 0, stream, T, order, triBox, cl[0]);
   uint32_t nc = T;
   int nextId = (int)T - 2;
   int cur = 0;
-  unsigned pass = 0;
   bool forcePairs = false;
   while(nc > 1)
   {
@@ -296,10 +277,10 @@ int ploc_cluster_device(uint32_t T, const unsigned* order, const float* triBox, 
     hipLaunchKernelGGL(k_ploc_scan, dim3(1), dim3(1024), 0, stream, blocks, blockCounts, totals);
     hipLaunchKernelGGL(k_ploc_apply, dim3(blocks), dim3(PLOC_BLOCK), 0, stream, (int)nc, nextId, (const int*)nn, (const PlocCluster*)cl[cur],
                        (const uint2*)blockCounts, cl[cur ^ 1], children, range, parentInternal, parentLeaf, nodeBox);
-    PLOC_TRY(hipGetLastError());
+    VKRT_TRY(err, hipGetLastError());
     unsigned h[2];
-    PLOC_TRY(hipMemcpyAsync(h, totals, 8, hipMemcpyDeviceToHost, stream));
-    PLOC_TRY(hipStreamSynchronize(stream));
+    VKRT_TRY(err, hipMemcpyAsync(h, totals, 8, hipMemcpyDeviceToHost, stream));
+    VKRT_TRY(err, hipStreamSynchronize(stream));
     if((h[1] == 0u && forcePairs) || h[0] != nc - h[1] || (int)h[1] > nextId + 1)
     {
       err = "PLOC pass without progress (internal error)";
@@ -309,11 +290,7 @@ int ploc_cluster_device(uint32_t T, const unsigned* order, const float* triBox, 
     nc = h[0];
     nextId -= (int)h[1];
     cur ^= 1;
-    pass++;
   }
-#undef PLOC_TRY
-  if(passes)
-    *passes = pass;
   return nextId == -1 ? VKRT_OK : VKRT_ERR_HIP;
 }
 

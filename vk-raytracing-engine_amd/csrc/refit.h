@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <string>
 #include <vector>
+#include "dev_buffer.h"
 #include "device_scene.h"
 
 namespace vkrt {
@@ -12,7 +13,7 @@ namespace vkrt {
 // the tree's nodes grouped by depth level (derived from the node words on the device), one exact float box and one SAH term per node.
 struct RefitScratch
 {
-  void* mem = nullptr;           // one allocation for everything below
+  DevBuf mem;                    // one allocation for everything below
   float* box = nullptr;          // [nodeCap][6]: lo.xyz, hi.xyz of every node reached from the root
   float* cost = nullptr;         // [nodeCap]: SAH terms of the node (0 for array entries that are not part of the tree)
   uint32_t* list = nullptr;      // [nodeCap]: node ids, level after level (root first)
@@ -31,7 +32,5 @@ int refit_prepare(const DevScene& sc, uint32_t nodeCap, hipStream_t stream, Refi
 // The refit itself, enqueued on `stream` without host synchronisation or allocation: triangle records from the current instance
 // table, then the node boxes level by level from the deepest to the root, then the SAH cost into rs.words[2].
 int refit_enqueue(const DevScene& sc, uint32_t instCount, const RefitScratch& rs, hipStream_t stream, std::string& err);
-
-void refit_free(RefitScratch& rs);
 
 }  // namespace vkrt

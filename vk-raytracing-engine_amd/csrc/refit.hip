@@ -259,39 +259,22 @@ hipError_t upload_instances(DevInstance* table, uint32_t first, uint32_t count, 
   return hipGetLastError();
 }
 
-void refit_free(RefitScratch& rs)
-{
-  if(rs.mem) (void)hipFree(rs.mem);
-  rs = RefitScratch{};
-}
-
-#define RF_TRY(expr)                                                           \
-  do                                                                           \
-  {                                                                            \
-    hipError_t e_ = (expr);                                                    \
-    if(e_ != hipSuccess)                                                       \
-    {                                                                          \
-      err = std::string(#expr) + ": " + hipGetErrorString(e_);                 \
-      return e_ == hipErrorOutOfMemory ? VKRT_ERR_OUT_OF_MEMORY : VKRT_ERR_HIP; \
-    }                                                                          \
-  } while(0)
-
 int refit_prepare(const DevScene& sc, uint32_t nodeCap, hipStream_t stream, RefitScratch& rs, std::string& err)
 {
-  refit_free(rs);
+  rs = RefitScratch{};
   rs.nodeCap = nodeCap;
   const size_t boxBytes = (size_t)nodeCap * 24, costBytes = (size_t)nodeCap * 4, listBytes = (size_t)nodeCap * 4;
-  RF_TRY(hipMalloc(&rs.mem, boxBytes + costBytes + listBytes + 16));
-  rs.box = (float*)rs.mem;
-  rs.cost = (float*)((char*)rs.mem + boxBytes);
-  rs.list = (uint32_t*)((char*)rs.mem + boxBytes + costBytes);
-  rs.words = (uint32_t*)((char*)rs.mem + boxBytes + costBytes + listBytes);
-  RF_TRY(hipMemsetAsync(rs.cost, 0, costBytes + listBytes + 16, stream));
+  VKRT_TRY(err, rs.mem.alloc(boxBytes + costBytes + listBytes + 16));
+  rs.box = rs.mem.get<float>();
+  rs.cost = rs.box + (size_t)nodeCap * 6;
+  rs.list = (uint32_t*)(rs.cost + nodeCap);
+  rs.words = rs.list + nodeCap;
+  VKRT_TRY(err, hipMemsetAsync(rs.cost, 0, costBytes + listBytes + 16, stream));
   rs.levelStart.assign(1, 0u);
   if(sc.rootRef != 0 || nodeCap == 0)
     return VKRT_OK;  // no nodes (an empty scene, or a BVH2 whose root is a leaf): the refit rewrites triangle records only
   const uint32_t one = 1;  // list[0] = node 0 (zeroed above), tail = 1
-  RF_TRY(hipMemcpyAsync(rs.words, &one, 4, hipMemcpyHostToDevice, stream));
+  VKRT_TRY(err, hipMemcpyAsync(rs.words, &one, 4, hipMemcpyHostToDevice, stream));
   rs.levelStart.push_back(1u);
   const unsigned B = 256;
   for(int lvl = 0;; lvl++)
@@ -304,10 +287,10 @@ int refit_prepare(const DevScene& sc, uint32_t nodeCap, hipStream_t stream, Refi
     const uint32_t start = rs.levelStart[(size_t)lvl], count = rs.levelStart[(size_t)lvl + 1] - start;
     hipLaunchKernelGGL(k_rf_expand, dim3((count + B - 1) / B), dim3(B), 0, stream, sc.layout, (const uint4*)sc.nodes, rs.list, start, count, nodeCap,
                        rs.words);
-    RF_TRY(hipGetLastError());
+    VKRT_TRY(err, hipGetLastError());
     uint32_t w[2];
-    RF_TRY(hipMemcpyAsync(w, rs.words, 8, hipMemcpyDeviceToHost, stream));
-    RF_TRY(hipStreamSynchronize(stream));
+    VKRT_TRY(err, hipMemcpyAsync(w, rs.words, 8, hipMemcpyDeviceToHost, stream));
+    VKRT_TRY(err, hipStreamSynchronize(stream));
     if(w[1] != 0u)
     {
       err = "node words reference " + std::to_string(w[1]) + " children outside the node array";
@@ -340,7 +323,7 @@ int refit_enqueue(const DevScene& sc, uint32_t instCount, const RefitScratch& rs
   }
   if(levels > 0)
     hipLaunchKernelGGL(k_rf_finish, dim3(1), dim3(1024), 0, stream, rs.nodeCap, (const float*)rs.cost, (const float*)rs.box, rs.words);
-  RF_TRY(hipGetLastError());
+  VKRT_TRY(err, hipGetLastError());
   return VKRT_OK;
 }
 

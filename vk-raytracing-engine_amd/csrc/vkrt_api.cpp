@@ -18,6 +18,7 @@
 
 #include "../../include/vkrt.h"
 #include "bvh_host.h"
+#include "dev_buffer.h"
 #include "device_scene.h"
 #include "kernels.h"
 #include "wide_node.h"
@@ -45,13 +46,12 @@ int fail(int code, const char* fmt, ...)
   return code;
 }
 
-#define HIP_TRY(expr)                                                                                  \
-  do                                                                                                   \
-  {                                                                                                    \
-    hipError_t e_ = (expr);                                                                            \
-    if(e_ != hipSuccess)                                                                               \
-      return fail(e_ == hipErrorOutOfMemory ? VKRT_ERR_OUT_OF_MEMORY : VKRT_ERR_HIP, "%s: %s", #expr, \
-                  hipGetErrorString(e_));                                                              \
+#define HIP_TRY(expr)                                                      \
+  do                                                                       \
+  {                                                                        \
+    std::string m_;                                                        \
+    if(const int rc_ = vkrt::hip_status((expr), #expr, m_); rc_ != VKRT_OK) \
+      return fail(rc_, "%s", m_.c_str());                                  \
   } while(0)
 
 }  // namespace
@@ -70,9 +70,7 @@ struct vkrt_scene
   // device allocations
   std::vector<void*> allocs;
   DevScene dev{};
-  void* accelNodes = nullptr;
-  void* accelTris = nullptr;
-  void* accelShade = nullptr;
+  vkrt::TreeBuffers accel;  // the built tree (dev.nodes / tris / triShade point into it)
   bool built = false;
   vkrt_accel_info info{};
   unsigned int* workCounter = nullptr;
@@ -250,12 +248,9 @@ void optionsFromEnvironment(vkrt_scene* s)
 
 void freeAccel(vkrt_scene* s)
 {
-  if(s->accelNodes) (void)hipFree(s->accelNodes);
-  if(s->accelTris) (void)hipFree(s->accelTris);
-  if(s->accelShade) (void)hipFree(s->accelShade);
-  s->accelNodes = s->accelTris = s->accelShade = nullptr;
+  s->accel = vkrt::TreeBuffers{};
   s->built = false;
-  vkrt::refit_free(s->refit);
+  s->refit = vkrt::RefitScratch{};
   s->refitted = false;
   s->stale = false;
 }
@@ -700,27 +695,13 @@ int vkrt_reserve_frames(vkrt_scene* s, const vkrt_shard* shard, uint32_t frames_
 
 namespace {
 
-// What a builder produced: the tree's three device buffers and what vkrt_accel_info reports about it.  installTree moves it into the scene.
-struct BuiltTree
+// Moves a builder's record into the scene.
+void installTree(vkrt_scene* s, vkrt::BuiltTree& t)
 {
-  uint32_t layout = 0;  // 0 = BVH2, 1 = wide8
-  int32_t rootRef = VKRT_TRAV_DONE;
-  uint32_t maxDepth = 0, nodeCount = 0;
-  float sahCost = 0;
-  uint64_t nodeBytes = 0, triangleBytes = 0;
-  void* nodes = nullptr;
-  void* tris = nullptr;
-  void* triShade = nullptr;
-};
-
-void installTree(vkrt_scene* s, const BuiltTree& t)
-{
-  s->accelNodes = t.nodes;
-  s->accelTris = t.tris;
-  s->accelShade = t.triShade;
-  s->dev.nodes = (const float4*)t.nodes;
-  s->dev.tris = (const float4*)t.tris;
-  s->dev.triShade = (const uint4*)t.triShade;
+  s->accel = std::move(t.buf);
+  s->dev.nodes = s->accel.nodes.get<const float4>();
+  s->dev.tris = s->accel.tris.get<const float4>();
+  s->dev.triShade = s->accel.triShade.get<const uint4>();
   s->dev.layout = t.layout;
   s->dev.rootRef = t.rootRef;
   // wide8: at most one pending group per level (uint2 entries = 2 words)
@@ -736,7 +717,7 @@ void installTree(vkrt_scene* s, const BuiltTree& t)
 // records in its slot order and uploads them with the nodes.  The host SAH builder and the host collapse of a device-built binary tree
 // both end here.
 int uploadHostTree(vkrt_scene* s, const std::vector<vkrt::FlatTri>& tris, const vkrt::BuiltBvh* bvh, const vkrt::BuiltWide8* w8,
-                   const std::vector<uint8_t>* instDissolves, hipStream_t stream, BuiltTree& t)
+                   const std::vector<uint8_t>* instDissolves, hipStream_t stream, vkrt::BuiltTree& t)
 {
   const std::vector<uint32_t>& order = w8 ? w8->triOrder : bvh->triOrder;
   std::vector<float> packed;
@@ -744,23 +725,20 @@ int uploadHostTree(vkrt_scene* s, const std::vector<vkrt::FlatTri>& tris, const 
   vkrt::pack_triangles(tris, order, packed, s->dev.watertight != 0, instDissolves);
   vkrt::pack_tri_shade(tris, order, s->indices.data(), s->primMeshes.data(), s->nodes.data(), shadeRec);
   const void* nodeData = w8 ? (const void*)w8->nodes.data() : (const void*)bvh->nodes.data();
-  t = w8 ? BuiltTree{1, tris.empty() ? VKRT_TRAV_DONE : 0, w8->maxDepth, w8->nodeCount, w8->sahCost, w8->nodes.size() * 4, packed.size() * 4}
-         : BuiltTree{0, bvh->rootRef, bvh->maxDepth, (uint32_t)(bvh->nodes.size() / 16), bvh->sahCost, bvh->nodes.size() * 4, packed.size() * 4};
+  t = w8 ? vkrt::BuiltTree{1, tris.empty() ? VKRT_TRAV_DONE : 0, w8->maxDepth, w8->nodeCount, w8->sahCost, w8->nodes.size() * 4, packed.size() * 4}
+         : vkrt::BuiltTree{0, bvh->rootRef, bvh->maxDepth, (uint32_t)(bvh->nodes.size() / 16), bvh->sahCost, bvh->nodes.size() * 4, packed.size() * 4};
   hipError_t e = hipSuccess;
   auto tryHip = [&](hipError_t x) { if(e == hipSuccess) e = x; };
-  tryHip(hipMalloc(&t.nodes, std::max<size_t>(t.nodeBytes, VKRT_WNODE_MIN_ALLOC)));
-  tryHip(hipMalloc(&t.tris, std::max<size_t>(t.triangleBytes, 48)));
-  tryHip(hipMalloc(&t.triShade, std::max<size_t>(shadeRec.size() * 4, 16)));
-  if(e == hipSuccess && t.nodeBytes) tryHip(hipMemcpyAsync(t.nodes, nodeData, t.nodeBytes, hipMemcpyHostToDevice, stream));
-  if(e == hipSuccess && !packed.empty()) tryHip(hipMemcpyAsync(t.tris, packed.data(), t.triangleBytes, hipMemcpyHostToDevice, stream));
-  if(e == hipSuccess && !shadeRec.empty()) tryHip(hipMemcpyAsync(t.triShade, shadeRec.data(), shadeRec.size() * 4, hipMemcpyHostToDevice, stream));
+  tryHip(t.buf.nodes.alloc(std::max<size_t>(t.nodeBytes, VKRT_WNODE_MIN_ALLOC)));
+  tryHip(t.buf.tris.alloc(std::max<size_t>(t.triangleBytes, 48)));
+  tryHip(t.buf.triShade.alloc(std::max<size_t>(shadeRec.size() * 4, 16)));
+  if(e == hipSuccess && t.nodeBytes) tryHip(hipMemcpyAsync(t.buf.nodes.get(), nodeData, t.nodeBytes, hipMemcpyHostToDevice, stream));
+  if(e == hipSuccess && !packed.empty()) tryHip(hipMemcpyAsync(t.buf.tris.get(), packed.data(), t.triangleBytes, hipMemcpyHostToDevice, stream));
+  if(e == hipSuccess && !shadeRec.empty()) tryHip(hipMemcpyAsync(t.buf.triShade.get(), shadeRec.data(), shadeRec.size() * 4, hipMemcpyHostToDevice, stream));
   if(e == hipSuccess) tryHip(hipStreamSynchronize(stream));  // (the host arrays end with this call)
-  if(e != hipSuccess)
-  {
-    (void)hipFree(t.nodes); (void)hipFree(t.tris); (void)hipFree(t.triShade);
-    return fail(e == hipErrorOutOfMemory ? VKRT_ERR_OUT_OF_MEMORY : VKRT_ERR_HIP, "uploading the acceleration structure: %s", hipGetErrorString(e));
-  }
-  return VKRT_OK;
+  std::string m;
+  const int rc = vkrt::hip_status(e, "uploading the acceleration structure", m);
+  return rc == VKRT_OK ? VKRT_OK : fail(rc, "%s", m.c_str());
 }
 
 // World-space bounds of the instanced geometry, conservatively from the corners of every node's local box, and whether the scene has
@@ -905,7 +883,7 @@ int accelBuildOnce(vkrt_scene* s, uint32_t flags, int splitBudget, hipStream_t s
   // wide8 (compressed 8-wide) is the trace-optimised layout; the megakernel and VKRT_OPT_BVH_LAYOUT = 0 keep BVH2
   const bool wide = useWavefront(s) && s->opt[VKRT_OPT_BVH_LAYOUT] == 1;
 
-  BuiltTree tree;
+  vkrt::BuiltTree tree;
   if(wantSah)
   {
     std::vector<vkrt::FlatTri> tris;
@@ -924,38 +902,37 @@ int accelBuildOnce(vkrt_scene* s, uint32_t flags, int splitBudget, hipStream_t s
   }
   else
   {
-    vkrt::LbvhResult r;
     // GPU radix-tree build (Morton codes, sort, Karras hierarchy, bottom-up fit).  For the trace-optimised layout the
     // binary tree keeps one triangle per leaf and is collapsed into wide8 nodes by the same SAH-optimal DP as the SAH
     // path -- on the device too (wide_collapse.hip); nothing but four statistics words comes back to the host.
     // VKRT_BUILD_PLOC_GPU: same pipeline with the radix tree replaced by locally-ordered clustering (ploc.hip)
-    rc = vkrt::build_lbvh_device(s->dev, (uint32_t)s->nodes.size(), s->primMeshes, s->nodes, stream, r, wide ? 1u : 4u, wide, wantPloc, watertight, dissolve,
-                                 (unsigned)splitBudget);
+    vkrt::LbvhParams p;
+    p.wide = wide;
+    p.ploc = wantPloc;
+    p.splitPercent = (unsigned)splitBudget;
+    vkrt::LbvhResult r;
+    rc = vkrt::build_lbvh_device(s->dev, (uint32_t)s->nodes.size(), s->primMeshes, s->nodes, p, stream, r);
     if(rc != VKRT_OK)
       return fail(rc, "%s build failed: %s", wantPloc ? "PLOC" : "LBVH", r.error.c_str());
     s->info.triangle_count = r.uniqueTris;
     s->dev.triCount = r.triCount;  // slots: a pre-split triangle occupies one per reference
-    if(wide && r.hasWide)
-    {
-      (void)hipFree(r.nodes); (void)hipFree(r.tris); (void)hipFree(r.triShade);
-      tree = BuiltTree{1, 0, r.wide.maxDepth, r.wide.nodeCount, r.wide.sahCost, (uint64_t)r.wide.nodeCount * VKRT_WNODE_BYTES,
-                       (uint64_t)r.triCount * 48, r.wide.nodes, r.wide.tris, r.wide.triShade};
-    }
+    if(r.wide.buf.nodes.get())
+      tree = std::move(r.wide);
     else if(wide && r.triCount > 0)
     {
       // fallback (a single triangle, or a radix tree too deep for the device collapse's level budget): download the binary
       // tree (device layout == host layout of BuiltBvh) and the sorted triangle records, collapse on the host
       vkrt::BuiltBvh b2;
-      b2.nodes.resize((size_t)r.nodeCount * 16);
+      b2.nodes.resize((size_t)r.tree.nodeCount * 16);
       std::vector<float> records((size_t)r.triCount * 12);
       hipError_t e = hipSuccess;
-      if(r.nodeCount) e = hipMemcpy(b2.nodes.data(), r.nodes, b2.nodes.size() * 4, hipMemcpyDeviceToHost);
-      if(e == hipSuccess) e = hipMemcpy(records.data(), r.tris, records.size() * 4, hipMemcpyDeviceToHost);
-      (void)hipFree(r.nodes); (void)hipFree(r.tris); (void)hipFree(r.triShade);
+      if(r.tree.nodeCount) e = hipMemcpy(b2.nodes.data(), r.tree.buf.nodes.get(), b2.nodes.size() * 4, hipMemcpyDeviceToHost);
+      if(e == hipSuccess) e = hipMemcpy(records.data(), r.tree.buf.tris.get(), records.size() * 4, hipMemcpyDeviceToHost);
+      r.tree.buf = vkrt::TreeBuffers{};  // (freed before the wide tree is uploaded)
       if(e != hipSuccess)
         return fail(VKRT_ERR_HIP, "LBVH download: %s", hipGetErrorString(e));
-      b2.rootRef = r.rootRef;
-      b2.maxDepth = r.maxDepth;
+      b2.rootRef = r.tree.rootRef;
+      b2.maxDepth = r.tree.maxDepth;
       b2.triOrder.resize(r.triCount);
       // (decoded p1 = v0 + e1 is not the exact vertex, but the boxes of the collapse only grow by it; pack_triangles sets the any-hit
       // flag that decoding clears again)
@@ -971,8 +948,7 @@ int accelBuildOnce(vkrt_scene* s, uint32_t flags, int splitBudget, hipStream_t s
         return rc;
     }
     else
-      tree = BuiltTree{0, r.rootRef, r.maxDepth, r.nodeCount, r.sahCost, (uint64_t)r.nodeCount * 64, (uint64_t)r.triCount * 48,
-                       r.nodes, r.tris, r.triShade};
+      tree = std::move(r.tree);
   }
   installTree(s, tree);
   sceneBounds(s);
@@ -1083,12 +1059,12 @@ int vkrt_accel_refit(vkrt_scene* s, void* hip_stream)
     return rc;
   hipStream_t stream = (hipStream_t)hip_stream;
   std::string err;
-  if(!s->refit.mem)
+  if(!s->refit.mem.get())
   {  // first refit of this build: scratch + level lists (the one place a refit allocates and synchronises)
     const uint32_t nodeCap = (uint32_t)(s->info.node_bytes / (s->dev.layout == 1u ? VKRT_WNODE_BYTES : 64u));
     if((rc = vkrt::refit_prepare(s->dev, nodeCap, stream, s->refit, err)) != VKRT_OK)
     {
-      vkrt::refit_free(s->refit);
+      s->refit = vkrt::RefitScratch{};
       return fail(rc, "vkrt_accel_refit: %s", err.c_str());
     }
   }
@@ -1447,22 +1423,21 @@ int vkrt_debug_trace_rays(vkrt_scene* s, uint32_t n, const float* origins, const
     return rc;
   if((rc = setDevice(s)) != VKRT_OK)
     return rc;
-  float *dO = nullptr, *dD = nullptr, *dT = nullptr, *dU = nullptr, *dV = nullptr;
-  int* dG = nullptr;
+  vkrt::DevBuf dO, dD, dT, dU, dV, dG;
   const size_t b3 = (size_t)n * 3 * sizeof(float), b1 = (size_t)n * sizeof(float);
   hipError_t e = hipSuccess;
   auto tryHip = [&](hipError_t x) { if(e == hipSuccess) e = x; };
-  tryHip(hipMalloc((void**)&dO, b3)); tryHip(hipMalloc((void**)&dD, b3)); tryHip(hipMalloc((void**)&dT, b1));
-  tryHip(hipMalloc((void**)&dU, b1)); tryHip(hipMalloc((void**)&dV, b1)); tryHip(hipMalloc((void**)&dG, b1));
-  if(e == hipSuccess) tryHip(hipMemcpy(dO, origins, b3, hipMemcpyHostToDevice));
-  if(e == hipSuccess) tryHip(hipMemcpy(dD, directions, b3, hipMemcpyHostToDevice));
-  if(e == hipSuccess) tryHip(vkrt_launch_trace_rays(s->dev, n, dO, dD, tmin, tmax, any_hit, dT, dU, dV, dG, nullptr));
+  tryHip(dO.alloc(b3)); tryHip(dD.alloc(b3)); tryHip(dT.alloc(b1));
+  tryHip(dU.alloc(b1)); tryHip(dV.alloc(b1)); tryHip(dG.alloc(b1));
+  if(e == hipSuccess) tryHip(hipMemcpy(dO.get(), origins, b3, hipMemcpyHostToDevice));
+  if(e == hipSuccess) tryHip(hipMemcpy(dD.get(), directions, b3, hipMemcpyHostToDevice));
+  if(e == hipSuccess) tryHip(vkrt_launch_trace_rays(s->dev, n, dO.get<float>(), dD.get<float>(), tmin, tmax, any_hit, dT.get<float>(), dU.get<float>(),
+                                                    dV.get<float>(), dG.get<int>(), nullptr));
   if(e == hipSuccess) tryHip(hipDeviceSynchronize());
-  if(e == hipSuccess) tryHip(hipMemcpy(t, dT, b1, hipMemcpyDeviceToHost));
-  if(e == hipSuccess) tryHip(hipMemcpy(u, dU, b1, hipMemcpyDeviceToHost));
-  if(e == hipSuccess) tryHip(hipMemcpy(v, dV, b1, hipMemcpyDeviceToHost));
-  if(e == hipSuccess) tryHip(hipMemcpy(gid, dG, b1, hipMemcpyDeviceToHost));
-  (void)hipFree(dO); (void)hipFree(dD); (void)hipFree(dT); (void)hipFree(dU); (void)hipFree(dV); (void)hipFree(dG);
+  if(e == hipSuccess) tryHip(hipMemcpy(t, dT.get(), b1, hipMemcpyDeviceToHost));
+  if(e == hipSuccess) tryHip(hipMemcpy(u, dU.get(), b1, hipMemcpyDeviceToHost));
+  if(e == hipSuccess) tryHip(hipMemcpy(v, dV.get(), b1, hipMemcpyDeviceToHost));
+  if(e == hipSuccess) tryHip(hipMemcpy(gid, dG.get(), b1, hipMemcpyDeviceToHost));
   if(e != hipSuccess)
     return fail(VKRT_ERR_HIP, "vkrt_debug_trace_rays: %s", hipGetErrorString(e));
   return VKRT_OK;
@@ -1483,7 +1458,7 @@ int vkrt_debug_check_accel(vkrt_scene* s, vkrt_accel_check* out)
   out->layout = s->dev.layout;
   std::vector<float> tris((size_t)T * 12);
   if(T)
-    HIP_TRY(hipMemcpy(tris.data(), s->accelTris, tris.size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tris.data(), s->dev.tris, tris.size() * 4, hipMemcpyDeviceToHost));
   std::vector<uint32_t> seen(T, 0u);
   std::vector<uint8_t> reached(N, 0);
   struct Bound { float lo[3], hi[3]; };
@@ -1526,7 +1501,7 @@ int vkrt_debug_check_accel(vkrt_scene* s, vkrt_accel_check* out)
   {
     std::vector<uint32_t> nodes((size_t)N * 20);
     if(N)
-      HIP_TRY(hipMemcpy(nodes.data(), s->accelNodes, nodes.size() * 4, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(nodes.data(), s->dev.nodes, nodes.size() * 4, hipMemcpyDeviceToHost));
     struct Item { uint32_t node, depth; size_t chainLen; Bound b; bool hasBound; };
     std::vector<Item> stack;
     if(s->dev.rootRef != VKRT_TRAV_DONE && N)
@@ -1587,7 +1562,7 @@ int vkrt_debug_check_accel(vkrt_scene* s, vkrt_accel_check* out)
   {
     std::vector<float> nodes((size_t)N * 16);
     if(N)
-      HIP_TRY(hipMemcpy(nodes.data(), s->accelNodes, nodes.size() * 4, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(nodes.data(), s->dev.nodes, nodes.size() * 4, hipMemcpyDeviceToHost));
     struct Item { int32_t ref; uint32_t depth; size_t chainLen; Bound b; bool hasBound; };
     std::vector<Item> stack;
     if(s->dev.rootRef != VKRT_TRAV_DONE)
@@ -1806,17 +1781,16 @@ int vkrt_debug_eval_math(int device, int op, uint32_t n, const float* a, const f
   if(n == 0)
     return VKRT_OK;
   HIP_TRY(hipSetDevice(device));
-  float *dA = nullptr, *dB = nullptr, *dC = nullptr;
+  vkrt::DevBuf dA, dB, dC;
   const size_t bytes = (size_t)n * sizeof(float);
   hipError_t e = hipSuccess;
   auto tryHip = [&](hipError_t x) { if(e == hipSuccess) e = x; };
-  tryHip(hipMalloc((void**)&dA, bytes)); tryHip(hipMalloc((void**)&dB, bytes)); tryHip(hipMalloc((void**)&dC, bytes));
-  if(e == hipSuccess) tryHip(hipMemcpy(dA, a, bytes, hipMemcpyHostToDevice));
-  if(e == hipSuccess) tryHip(hipMemcpy(dB, b, bytes, hipMemcpyHostToDevice));
-  if(e == hipSuccess) tryHip(vkrt_launch_eval_math(op, n, dA, dB, dC, nullptr));
+  tryHip(dA.alloc(bytes)); tryHip(dB.alloc(bytes)); tryHip(dC.alloc(bytes));
+  if(e == hipSuccess) tryHip(hipMemcpy(dA.get(), a, bytes, hipMemcpyHostToDevice));
+  if(e == hipSuccess) tryHip(hipMemcpy(dB.get(), b, bytes, hipMemcpyHostToDevice));
+  if(e == hipSuccess) tryHip(vkrt_launch_eval_math(op, n, dA.get<float>(), dB.get<float>(), dC.get<float>(), nullptr));
   if(e == hipSuccess) tryHip(hipDeviceSynchronize());
-  if(e == hipSuccess) tryHip(hipMemcpy(out, dC, bytes, hipMemcpyDeviceToHost));
-  (void)hipFree(dA); (void)hipFree(dB); (void)hipFree(dC);
+  if(e == hipSuccess) tryHip(hipMemcpy(out, dC.get(), bytes, hipMemcpyDeviceToHost));
   if(e != hipSuccess)
     return fail(VKRT_ERR_HIP, "vkrt_debug_eval_math: %s", hipGetErrorString(e));
   return VKRT_OK;

@@ -449,70 +449,50 @@ __global__ void k_w8_pack(uint32_t n, const uint32_t* __restrict__ triOrder, con
 
 }  // namespace
 
-#define WC_TRY(expr)                                                \
-  do                                                                \
-  {                                                                 \
-    hipError_t e_ = (expr);                                         \
-    if(e_ != hipSuccess)                                            \
-    {                                                               \
-      err = std::string(#expr) + ": " + hipGetErrorString(e_);      \
-      for(void* p_ : tmp) (void)hipFree(p_);                        \
-      if(out.nodes) (void)hipFree(out.nodes);                       \
-      if(out.tris) (void)hipFree(out.tris);                         \
-      if(out.triShade) (void)hipFree(out.triShade);                 \
-      out.nodes = out.tris = out.triShade = nullptr;                \
-      return e_ == hipErrorOutOfMemory ? VKRT_ERR_OUT_OF_MEMORY : VKRT_ERR_HIP; \
-    }                                                               \
-  } while(0)
-
-int collapse_wide8_device(const WideCollapseIn& in, hipStream_t stream, WideCollapseOut& out, std::string& err)
+int collapse_wide8_device(uint32_t T, const TreeBuffers& bin, const int* parentInternal, const int* parentLeaf, hipStream_t stream, BuiltTree& out,
+                          std::string& err)
 {
-  out = WideCollapseOut{};
-  std::vector<void*> tmp;
-  auto alloc = [&](void** p, size_t bytes) {
-    hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
-    if(e == hipSuccess) tmp.push_back(*p);
-    return e;
-  };
-  const uint32_t T = in.triCount;
+  out = BuiltTree{};
   if(T < 2)
   {
     err = "collapse_wide8_device needs a binary tree (>= 2 triangles)";
     return VKRT_ERR_INVALID_ARGUMENT;
   }
   const uint32_t cap = T - 1;  // every wide node is rooted at a distinct binary internal node
+  DevArena tmp;
   Emit E{};
   W8Dp* dp;
   unsigned* arrive;
   uint32_t* stats;
-  WC_TRY(alloc((void**)&dp, (size_t)cap * sizeof(W8Dp)));
-  WC_TRY(alloc((void**)&arrive, (size_t)cap * 4));
-  WC_TRY(alloc((void**)&E.item, (size_t)cap * 4));
-  WC_TRY(alloc((void**)&E.kids, (size_t)cap * 8 * sizeof(Kid)));
-  WC_TRY(alloc((void**)&E.kidInfo, (size_t)cap * 4));
-  WC_TRY(alloc((void**)&E.cntI, (size_t)cap * 4));
-  WC_TRY(alloc((void**)&E.cntT, (size_t)cap * 4));
-  WC_TRY(alloc((void**)&E.baseI, (size_t)cap * 4));
-  WC_TRY(alloc((void**)&E.baseT, (size_t)cap * 4));
-  WC_TRY(alloc((void**)&E.level, (8 + 2 * kMaxLevels) * 4));
-  WC_TRY(alloc((void**)&E.triOrder, (size_t)T * 4));
-  WC_TRY(alloc((void**)&E.nodeCost, (size_t)cap * 4));
-  WC_TRY(alloc((void**)&stats, 16));
-  WC_TRY(hipMalloc(&out.nodes, std::max<size_t>((size_t)cap * VKRT_WNODE_BYTES, VKRT_WNODE_MIN_ALLOC)));
-  WC_TRY(hipMalloc(&out.tris, (size_t)T * 48));
-  WC_TRY(hipMalloc(&out.triShade, (size_t)T * 16));
-  E.nodes2 = in.nodes2;
+  VKRT_TRY(err, tmp.alloc(&dp, cap));
+  VKRT_TRY(err, tmp.alloc(&arrive, cap));
+  VKRT_TRY(err, tmp.alloc(&E.item, cap));
+  VKRT_TRY(err, tmp.alloc(&E.kids, (size_t)cap * 8));
+  VKRT_TRY(err, tmp.alloc(&E.kidInfo, cap));
+  VKRT_TRY(err, tmp.alloc(&E.cntI, cap));
+  VKRT_TRY(err, tmp.alloc(&E.cntT, cap));
+  VKRT_TRY(err, tmp.alloc(&E.baseI, cap));
+  VKRT_TRY(err, tmp.alloc(&E.baseT, cap));
+  VKRT_TRY(err, tmp.alloc(&E.level, 8 + 2 * kMaxLevels));
+  VKRT_TRY(err, tmp.alloc(&E.triOrder, T));
+  VKRT_TRY(err, tmp.alloc(&E.nodeCost, cap));
+  VKRT_TRY(err, tmp.alloc(&stats, 4));
+  TreeBuffers buf;
+  VKRT_TRY(err, buf.nodes.alloc(std::max<size_t>((size_t)cap * VKRT_WNODE_BYTES, VKRT_WNODE_MIN_ALLOC)));
+  VKRT_TRY(err, buf.tris.alloc((size_t)T * 48));
+  VKRT_TRY(err, buf.triShade.alloc((size_t)T * 16));
+  E.nodes2 = bin.nodes.get<const float4>();
   E.dp = dp;
-  E.outNodes = (uint4*)out.nodes;
+  E.outNodes = buf.nodes.get<uint4>();
   E.capacity = cap;
   E.triCount = T;
-  WC_TRY(hipMemsetAsync(arrive, 0, (size_t)cap * 4, stream));
-  WC_TRY(hipMemsetAsync(E.level, 0, (8 + 2 * kMaxLevels) * 4, stream));
-  WC_TRY(hipMemsetAsync(E.item, 0, 4, stream));  // wide node 0 is rooted at binary node 0
+  VKRT_TRY(err, hipMemsetAsync(arrive, 0, (size_t)cap * 4, stream));
+  VKRT_TRY(err, hipMemsetAsync(E.level, 0, (8 + 2 * kMaxLevels) * 4, stream));
+  VKRT_TRY(err, hipMemsetAsync(E.item, 0, 4, stream));  // wide node 0 is rooted at binary node 0
   const uint32_t one = 1;
-  WC_TRY(hipMemcpyAsync(&E.level[1], &one, 4, hipMemcpyHostToDevice, stream));
+  VKRT_TRY(err, hipMemcpyAsync(&E.level[1], &one, 4, hipMemcpyHostToDevice, stream));
   const unsigned B = 256;
-  hipLaunchKernelGGL(k_w8_dp, dim3((T + B - 1) / B), dim3(B), 0, stream, (int)T, in.nodes2, in.parentInternal, in.parentLeaf, dp, arrive);
+  hipLaunchKernelGGL(k_w8_dp, dim3((T + B - 1) / B), dim3(B), 0, stream, (int)T, E.nodes2, parentInternal, parentLeaf, dp, arrive);
   uint64_t width = 1;
   for(int lvl = 0; lvl < kMaxLevels; lvl++)
   {
@@ -523,18 +503,17 @@ int collapse_wide8_device(const WideCollapseIn& in, hipStream_t stream, WideColl
     hipLaunchKernelGGL(k_w8_write, g, dim3(B), 0, stream, E, (uint32_t)lvl);
     width = std::min<uint64_t>(width * 8, cap);
   }
-  hipLaunchKernelGGL(k_w8_finish, dim3(1), dim3(1024), 0, stream, E, in.nodes2, stats);
-  hipLaunchKernelGGL(k_w8_pack, dim3((T + B - 1) / B), dim3(B), 0, stream, T, (const uint32_t*)E.triOrder, in.tris, in.triShade, (float4*)out.tris,
-                     (uint4*)out.triShade);
-  WC_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_w8_finish, dim3(1), dim3(1024), 0, stream, E, E.nodes2, stats);
+  hipLaunchKernelGGL(k_w8_pack, dim3((T + B - 1) / B), dim3(B), 0, stream, T, (const uint32_t*)E.triOrder, bin.tris.get<const float4>(),
+                     bin.triShade.get<const uint4>(), buf.tris.get<float4>(), buf.triShade.get<uint4>());
+  VKRT_TRY(err, hipGetLastError());
   uint32_t hs[4];
-  WC_TRY(hipMemcpyAsync(hs, stats, 16, hipMemcpyDeviceToHost, stream));  // four scalars, not the tree
-  WC_TRY(hipStreamSynchronize(stream));
-  for(void* p : tmp) (void)hipFree(p);
-  out.nodeCount = hs[0];
-  out.maxDepth = hs[1];
+  VKRT_TRY(err, hipMemcpyAsync(hs, stats, 16, hipMemcpyDeviceToHost, stream));  // four scalars, not the tree
+  VKRT_TRY(err, hipStreamSynchronize(stream));
+  if(hs[3] != 0u)
+    return VKRT_OK;  // overflow: the tree does not fit the level budget
+  out = BuiltTree{1, 0, hs[1], hs[0], 0.0f, (uint64_t)hs[0] * VKRT_WNODE_BYTES, (uint64_t)T * 48, std::move(buf)};
   memcpy(&out.sahCost, &hs[2], 4);
-  out.overflow = hs[3] != 0u;
   return VKRT_OK;
 }
 
