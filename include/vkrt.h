@@ -177,7 +177,11 @@ typedef struct vkrt_accel_info {
   uint32_t node_count;       /* BVH nodes in the traversal layout */
   uint32_t max_depth;
   uint32_t build_flags;      /* which builder produced it */
-  float    sah_cost;         /* SAH cost of the tree, traversal 1 / intersect 1 */
+  float    sah_cost;         /* SAH cost of the tree in its traversal layout, traversal 1 / intersect 1, every builder and the refit alike:
+                                [sum over nodes of A(node) + sum over leaf children of A(child) x triangle count] / A(root), where A is
+                                the surface area of the float (unquantised) box -- a wide8 child's or a BVH2 child's box, a node's box =
+                                the union of its children's -- and the sums run over the nodes a walk from the root reaches.  A BVH2
+                                whose root is a leaf costs its triangle count; otherwise a root box of zero area costs 0. */
   float    build_ms;         /* wall time of the last build */
   uint64_t node_bytes;
   uint64_t triangle_bytes;
@@ -459,6 +463,13 @@ typedef struct vkrt_accel_check {
   uint64_t triangles_split;      /* triangles that own more than one slot */
 } vkrt_accel_check;
 int vkrt_debug_check_accel(vkrt_scene* scene, vkrt_accel_check* out);
+/* The installed tree exactly as the kernels read it (synchronises the device; a test hook like the other vkrt_debug_* calls, added
+ * without a struct change, so VKRT_ABI_VERSION stays 4): the node array (nodes_bytes == vkrt_accel_info.node_bytes; wide8: 80-B nodes,
+ * bvh_host.h; BVH2: 64-B nodes, device_scene.h -- a device-built BVH2 array also holds radix nodes no walk from the root reaches), the
+ * 48-B triangle records in slot order (tris_bytes == triangle_bytes) and the BVH2 root reference (wide8: 0, the root node; a leaf
+ * reference for a BVH2 whose root is a leaf; VKRT_TRAV_DONE for an empty scene).  Other byte counts or a NULL pointer:
+ * VKRT_ERR_INVALID_ARGUMENT; no tree, or a stale one: VKRT_ERR_NOT_BUILT. */
+int vkrt_debug_read_accel(vkrt_scene* scene, void* nodes, uint64_t nodes_bytes, void* tris, uint64_t tris_bytes, int32_t* root_ref);
 /* Closest-hit query for n rays: o,d = vec3[n] host arrays; tmin/tmax scalars.
  * Writes t,u,v (float[n]) and the flattened triangle id gid (int32[n], -1 = miss). */
 int vkrt_debug_trace_rays(vkrt_scene* scene, uint32_t n, const float* origins,

@@ -68,6 +68,10 @@ def test_argument_validation_and_no_cpu_fallback(cornell_flat):
     hdr = open(os.path.join(ROOT, "include", "vkrt.h")).read()
     assert (abi.VKRT_OPT_WF_FRAMES_IN_FLIGHT, abi.VKRT_OPT_SPLIT_BUDGET) == (13, 14)
     assert "VKRT_OPT_LAST            = 14" in hdr and "#define VKRT_ABI_VERSION 4" in hdr and abi.VKRT_ABI_VERSION == 4
+    # the tree-reading test hook refuses a NULL scene or root pointer before it looks for a device
+    root = C.c_int32(7)
+    assert lib.vkrt_debug_read_accel(None, None, 0, None, 0, C.byref(root)) == 1 and root.value == 7
+    assert b"NULL" in lib.vkrt_last_error()
     desc, keep = cornell_flat.to_desc()
     if lib.vkrt_device_count() == 0:
         # the product never computes on the CPU: without a device creation must fail loudly

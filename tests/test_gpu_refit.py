@@ -1,7 +1,6 @@
 """Moving instances without a rebuild (vkrt_scene_update_nodes + vkrt_accel_refit).  The image is a property of the triangle set, not of
 the tree: a refitted tree must give exactly the pixels, ray counts and closest hits of a fresh build of the moved
 scene, in every layout, builder, split setting and triangle test -- no tolerance, no new oracle."""
-import copy
 import ctypes as C
 import hashlib
 import os
@@ -11,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import default_camera
+from scene_motion import _row_major, apply, moved
 
 pytestmark = pytest.mark.gpu
 
@@ -20,56 +20,6 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 def _digest(t):
     return hashlib.sha256(np.ascontiguousarray(t.cpu().numpy() if hasattr(t, "cpu") else t).tobytes()).hexdigest()[:16]
-
-
-def _row_major(m16):
-    return np.asarray(m16, np.float64).reshape(4, 4).T  # worldMatrix is column-major
-
-
-def _col_major(M):
-    return np.ascontiguousarray(M.T.reshape(16), np.float32)
-
-
-def _rigid(rng, centre, mirror=False, scale=True):
-    """A motion about the instance's own centre: rotation about a random axis, a translation, a non-uniform scale (optionally mirrored)."""
-    axis = rng.standard_normal(3)
-    axis /= np.linalg.norm(axis)
-    a = rng.uniform(-0.6, 0.6)
-    K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
-    R = np.eye(4)
-    R[:3, :3] = np.eye(3) + np.sin(a) * K + (1 - np.cos(a)) * K @ K
-    S = np.diag(list(rng.uniform(0.8, 1.25, 3) if scale else np.ones(3)) + [1.0])
-    if mirror:
-        S[0, 0] = -S[0, 0]
-    T0, T1 = np.eye(4), np.eye(4)
-    T0[:3, 3] = -centre
-    T1[:3, 3] = centre + rng.uniform(-0.4, 0.4, 3)
-    return T1 @ R @ S @ T0
-
-
-def _centre(flat, i):
-    pm = flat.prim_meshes[flat.nodes[i]["primMesh"]]
-    v = flat.positions[pm["vertexOffset"]:pm["vertexOffset"] + pm["vertexCount"]].astype(np.float64)
-    c = 0.5 * (v.min(0) + v.max(0)) if len(v) else np.zeros(3)
-    return (_row_major(flat.nodes[i]["worldMatrix"]) @ np.append(c, 1.0))[:3]
-
-
-def moved(flat, nodes, seed, mirror_first=True, scale=True):
-    """(moved FlatScene, {node: column-major matrix}) for a seeded motion of `nodes`."""
-    rng = np.random.default_rng(seed)
-    out = copy.copy(flat)
-    out.nodes = flat.nodes.copy()
-    mats = {}
-    for j, i in enumerate(nodes):
-        M = _rigid(rng, _centre(flat, i), mirror=mirror_first and j == 0, scale=scale) @ _row_major(flat.nodes[i]["worldMatrix"])
-        mats[int(i)] = _col_major(M)
-        out.nodes[i]["worldMatrix"] = mats[int(i)]
-    return out, mats
-
-
-def apply(r, mats, stream=None):
-    for i, m in sorted(mats.items()):
-        r.update_nodes(i, m[None], stream=stream)
 
 
 @pytest.fixture(scope="module")
@@ -222,10 +172,10 @@ def test_ten_successive_refits_and_frames_in_flight(atrium_small, kind):
     f.close()
 
 
-@pytest.mark.parametrize("kind", ["ploc", "lbvh"])
+@pytest.mark.parametrize("kind", ["ploc", "lbvh", "sah"])
 def test_refit_without_motion_is_a_no_op(atrium_small, cornell, kind):
     """Split budget 0: refitting an unmoved scene re-encodes every node bit for bit (shared quantisation) -- the traversal visits the
-    same nodes and tests the same triangles, the image and the SAH cost are those of the build."""
+    same nodes and tests the same triangles, the image and the SAH cost are those of the build.  Both layouts, every builder."""
     import atrium
     from vkrt_amd import abi
     from vkrt_amd.renderer import Renderer
@@ -233,8 +183,9 @@ def test_refit_without_motion_is_a_no_op(atrium_small, cornell, kind):
     # (work sharing and triangle parking make a ray's node count depend on the other rays of its wave, i.e. on the order of the
     # compacted streams: off here, so that the counts are a function of the tree alone -- the repeated render below shows it)
     opts = {abi.VKRT_OPT_SPLIT_BUDGET: 0, abi.VKRT_OPT_WF_SHARE: 0, abi.VKRT_OPT_TRI_THRESHOLD: 0}
-    for flat, kw, W, H in ((atrium_small, atrium.DEFAULT_CAMERA, 160, 90), (cornell, {}, 64, 64)):
-        r = Renderer(flat, device=0, build=kind, options=opts)
+    cases = [(layout, scene) for layout in (1, 0) for scene in ((atrium_small, atrium.DEFAULT_CAMERA, 160, 90), (cornell, {}, 64, 64))]
+    for layout, (flat, kw, W, H) in cases:
+        r = Renderer(flat, device=0, build=kind, options={**opts, abi.VKRT_OPT_BVH_LAYOUT: layout})
         built = _render(r, flat, W, H, kw, flags=abi.VKRT_TRACE_COUNT_TRAVERSAL)
         repeat = _render(r, flat, W, H, kw, flags=abi.VKRT_TRACE_COUNT_TRAVERSAL)
         assert repeat[1]["nodes_visited"] == built[1]["nodes_visited"] and repeat[1]["tris_tested"] == built[1]["tris_tested"]
@@ -245,7 +196,7 @@ def test_refit_without_motion_is_a_no_op(atrium_small, cornell, kind):
         for k in ("nodes_visited", "tris_tested", "rays_closest", "rays_shadow"):
             assert again[1][k] == built[1][k], (k, again[1][k], built[1][k])
         info = r.accel_info()
-        assert abs(info["sah_cost"] - sah) <= 1e-5 * sah, (info["sah_cost"], sah)
+        assert abs(info["sah_cost"] - sah) <= 1e-5 * sah, (layout, info["sah_cost"], sah)
         r.close()
 
 
@@ -321,9 +272,14 @@ def test_update_contract(cornell):
 
     pc = make_push_constants(samples=1, depth=2, frame=0, lights_count=len(cornell.lights))
     cam = default_camera(W, H)
-    for call in (lambda: r.pathtrace(pc, cam, W, H), lambda: r.gbuffer_raycast(cam, W, H), lambda: r.trace_rays(*_rays(cornell, 16))):
+    for call in (lambda: r.pathtrace(pc, cam, W, H), lambda: r.gbuffer_raycast(cam, W, H), lambda: r.trace_rays(*_rays(cornell, 16)),
+                 r.read_accel):
         with pytest.raises(VkrtError, match=r"\(5\)"):
             call()
+    info = r.accel_info()
+    nb, tb = int(info["node_bytes"]), int(info["triangle_bytes"])
+    nodes, tris, root = np.zeros(nb // 4 + 1, np.uint32), np.zeros(tb // 4 + 1, np.float32), C.c_int32(7)
+    assert r.lib.vkrt_debug_read_accel(r._h, nodes.ctypes.data, nb, tris.ctypes.data, tb, C.byref(root)) == 5 and root.value == 7
     # a full build after update_nodes builds the moved scene
     r.build("ploc")
     assert _render(r, mflat, W, H)[0] == want
@@ -342,6 +298,17 @@ def test_update_contract(cornell):
     ok.primMesh = int(cornell.nodes[max(mats)]["primMesh"])
     assert r.lib.vkrt_scene_update_nodes(r._h, len(cornell.nodes), 1, C.byref(ok), None) == 1  # range outside the scene
     assert _render(r, mflat, W, H)[0] == want
+    # vkrt_debug_read_accel takes exactly the tree's byte counts and non-NULL buffers
+    info = r.accel_info()
+    nb, tb = int(info["node_bytes"]), int(info["triangle_bytes"])
+    nodes, tris, root = np.zeros(nb // 4 + 1, np.uint32), np.zeros(tb // 4 + 1, np.float32), C.c_int32(7)
+    for args in ((nb + 4, tb), (nb - 4, tb), (nb, tb + 48), (nb, tb - 48)):
+        assert r.lib.vkrt_debug_read_accel(r._h, nodes.ctypes.data, args[0], tris.ctypes.data, args[1], C.byref(root)) == 1, args
+    assert r.lib.vkrt_debug_read_accel(r._h, None, nb, tris.ctypes.data, tb, C.byref(root)) == 1
+    assert r.lib.vkrt_debug_read_accel(r._h, nodes.ctypes.data, nb, None, tb, C.byref(root)) == 1
+    assert r.lib.vkrt_debug_read_accel(r._h, nodes.ctypes.data, nb, tris.ctypes.data, tb, None) == 1
+    assert root.value == 7
+    assert r.lib.vkrt_debug_read_accel(r._h, nodes.ctypes.data, nb, tris.ctypes.data, tb, C.byref(root)) == 0 and root.value == 0
     # a zero scale (a hidden instance) is accepted, as at vkrt_scene_create
     r.update_nodes(0, np.zeros((1, 16), np.float32))
     r.refit()

@@ -230,6 +230,7 @@ VKRT_SYMBOLS = [
     "vkrt_last_trace_ms",
     "vkrt_last_trace_timing",
     "vkrt_debug_check_accel",
+    "vkrt_debug_read_accel",
     "vkrt_debug_trace_rays",
     "vkrt_debug_eval_math",
 ]
@@ -263,6 +264,8 @@ def declare_vkrt(lib):
     lib.vkrt_accel_refit.restype = C.c_int
     lib.vkrt_debug_check_accel.argtypes = [C.c_void_p, P(AccelCheck)]
     lib.vkrt_debug_check_accel.restype = C.c_int
+    lib.vkrt_debug_read_accel.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, P(C.c_int32)]
+    lib.vkrt_debug_read_accel.restype = C.c_int
     lib.vkrt_shard_rows.argtypes = [P(Shard)]
     lib.vkrt_shard_rows.restype = c_u
     lib.vkrt_pathtrace.argtypes = [

@@ -266,7 +266,7 @@ void build_sah_host(const std::vector<FlatTri>& tris, uint32_t maxLeaf, BuiltBvh
   }
   double cost = 0;
   out.rootRef = cx.build(0, n, all, 0, cost);
-  out.sahCost = (float)cost;
+  out.sahCost = out.rootRef >= 0 && !(all.area() > 0.f) ? 0.0f : (float)cost;  // a root of zero area costs 0, as in the device builders
 }
 
 void pack_tri_shade(const std::vector<FlatTri>& tris, const std::vector<uint32_t>& order, const uint32_t* indices, const vkrt_prim_mesh* pm,

@@ -250,7 +250,7 @@ VKRT_DEV float boxArea(const float* b)
 }
 
 __global__ void k_emit(unsigned kLeaf, int n, const unsigned* order, const float* triBox, const int2* children, const int2* range, const float* nodeBox,
-                       float4* outNodes, float* sahAccum)
+                       float4* outNodes, float* nodeCost)
 {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if(i >= n - 1)
@@ -258,7 +258,10 @@ __global__ void k_emit(unsigned kLeaf, int n, const unsigned* order, const float
   const int2 rg = range[i];
   const unsigned cnt = (unsigned)(rg.y - rg.x + 1);
   if(cnt <= kLeaf && i != 0)
-    return;  // lives inside a collapsed leaf
+  {
+    nodeCost[i] = 0.0f;  // lives inside a collapsed leaf
+    return;
+  }
   const int2 ch = children[i];
   const int cc[2] = {ch.x, ch.y};
   float bx[2][6];
@@ -295,7 +298,25 @@ __global__ void k_emit(unsigned kLeaf, int n, const unsigned* order, const float
   outNodes[4 * (size_t)i + 1] = make_float4(bx[0][4], bx[0][5], bx[1][0], bx[1][1]);
   outNodes[4 * (size_t)i + 2] = make_float4(bx[1][2], bx[1][3], bx[1][4], bx[1][5]);
   outNodes[4 * (size_t)i + 3] = make_float4(__int_as_float(ref[0]), __int_as_float(ref[1]), 0.0f, 0.0f);
-  atomicAdd(sahAccum, cost);
+  nodeCost[i] = cost;
+}
+
+// The SAH sum of the emitted nodes: one float term per node, reduced in double in a fixed order (as k_w8_finish does), so that two builds
+// of one scene report the same bits.
+__global__ __launch_bounds__(1024) void k_sah_sum(unsigned count, const float* __restrict__ nodeCost, double* sum)
+{
+  __shared__ double part[1024];
+  double s = 0;
+  for(unsigned k = threadIdx.x; k < count; k += 1024) s += (double)nodeCost[k];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  for(unsigned off = 512; off > 0; off >>= 1)
+  {
+    if(threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
+    __syncthreads();
+  }
+  if(threadIdx.x == 0)
+    *sum = part[0];
 }
 
 // materials != NULL (VKRT_OPT_ANYHIT_DISSOLVE): bit 31 of the id word of every triangle whose material has dissolve
@@ -985,7 +1006,9 @@ struct Hierarchy
   int2 *children, *range;
   int *parentInternal, *parentLeaf;
   float* nodeBox;
-  unsigned* scalars;  // [0] maxDepth, [1] sah accum (float), [2] frontier entries, [3] nodes above the frontier
+  unsigned* scalars;  // [0] maxDepth, [1] unused, [2] frontier entries, [3] nodes above the frontier
+  float* nodeCost;    // SAH term of every internal node (0 inside a collapsed leaf)
+  double* sahSum;     // their sum
 };
 
 // Instance tables (first triangle, index and vertex offset, material), uploaded, then k_flatten.  An empty scene allocates nothing here.
@@ -1173,11 +1196,14 @@ int topLevelsSah(Ctx& c, const Leaves& l, const Hierarchy& h)
 }
 
 // The 64-B nodes (subtrees of <= kLeaf triangles become leaves), their SAH sum and the tree depth.
-int emitAndDepth(Ctx& c, unsigned kLeaf, const Leaves& l, const Hierarchy& h, float4* nodes)
+int emitAndDepth(Ctx& c, unsigned kLeaf, const Leaves& l, Hierarchy& h, float4* nodes)
 {
   const unsigned B = 256, G = (l.T + B - 1) / B;
+  VKRT_TRY(c.err, c.tmp.alloc(&h.nodeCost, l.T - 1));
+  VKRT_TRY(c.err, c.tmp.alloc(&h.sahSum, 1));
   hipLaunchKernelGGL(k_emit, dim3(G), dim3(B), 0, c.stream, kLeaf, (int)l.T, (const unsigned*)l.order, (const float*)l.box, (const int2*)h.children,
-                     (const int2*)h.range, (const float*)h.nodeBox, nodes, (float*)&h.scalars[1]);
+                     (const int2*)h.range, (const float*)h.nodeBox, nodes, h.nodeCost);
+  hipLaunchKernelGGL(k_sah_sum, dim3(1), dim3(1024), 0, c.stream, l.T - 1u, (const float*)h.nodeCost, h.sahSum);
   hipLaunchKernelGGL(k_depth, dim3(G), dim3(B), 0, c.stream, kLeaf, (int)l.T, (const int2*)h.range, (const int*)h.parentInternal, (const int*)h.parentLeaf,
                      &h.scalars[0]);
   VKRT_TRY(c.err, hipGetLastError());
@@ -1189,16 +1215,16 @@ int readBack(Ctx& c, const Hierarchy& h, BuiltTree& t)
 {
   unsigned hs[4];
   float rootBox[6];
+  double sah;
   VKRT_TRY(c.err, hipMemcpyAsync(hs, h.scalars, 16, hipMemcpyDeviceToHost, c.stream));
+  VKRT_TRY(c.err, hipMemcpyAsync(&sah, h.sahSum, 8, hipMemcpyDeviceToHost, c.stream));
   VKRT_TRY(c.err, hipMemcpyAsync(rootBox, h.nodeBox, 24, hipMemcpyDeviceToHost, c.stream));
   VKRT_TRY(c.err, hipStreamSynchronize(c.stream));
   t.rootRef = 0;
   t.maxDepth = hs[0];
-  float sah;
-  memcpy(&sah, &hs[1], 4);
   const float ra = 2.0f * ((rootBox[3] - rootBox[0]) * (rootBox[4] - rootBox[1]) + (rootBox[4] - rootBox[1]) * (rootBox[5] - rootBox[2]) +
                            (rootBox[5] - rootBox[2]) * (rootBox[3] - rootBox[0]));
-  t.sahCost = ra > 0.0f ? sah / ra : 0.0f;
+  t.sahCost = ra > 0.0f ? (float)(sah / (double)ra) : 0.0f;
   return VKRT_OK;
 }
 
@@ -1233,6 +1259,7 @@ int build_lbvh_device(const DevScene& sc, uint32_t instCount, const std::vector<
   if(T <= kLeaf)
   {
     t.rootRef = (int32_t) ~((0u << 3) | (T - 1u));
+    t.sahCost = (float)T;  // a root leaf: T intersections (include/vkrt.h sah_cost)
     VKRT_TRY(c.err, hipStreamSynchronize(stream));
     return VKRT_OK;
   }

@@ -1443,6 +1443,28 @@ int vkrt_debug_trace_rays(vkrt_scene* s, uint32_t n, const float* origins, const
   return VKRT_OK;
 }
 
+int vkrt_debug_read_accel(vkrt_scene* s, void* nodes, uint64_t nodes_bytes, void* tris, uint64_t tris_bytes, int32_t* root_ref)
+{
+  if(!s || !root_ref || (nodes_bytes && !nodes) || (tris_bytes && !tris))
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "NULL argument");
+  int rc = checkBuilt(s, "vkrt_debug_read_accel");
+  if(rc == VKRT_OK)
+    rc = setDevice(s);
+  if(rc != VKRT_OK)
+    return rc;
+  if(nodes_bytes != s->info.node_bytes || tris_bytes != s->info.triangle_bytes)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_debug_read_accel: buffers of %llu / %llu bytes for a tree of %llu / %llu",
+                (unsigned long long)nodes_bytes, (unsigned long long)tris_bytes, (unsigned long long)s->info.node_bytes,
+                (unsigned long long)s->info.triangle_bytes);
+  HIP_TRY(hipDeviceSynchronize());
+  if(nodes_bytes)
+    HIP_TRY(hipMemcpy(nodes, s->dev.nodes, nodes_bytes, hipMemcpyDeviceToHost));
+  if(tris_bytes)
+    HIP_TRY(hipMemcpy(tris, s->dev.tris, tris_bytes, hipMemcpyDeviceToHost));
+  *root_ref = s->dev.rootRef;
+  return VKRT_OK;
+}
+
 int vkrt_debug_check_accel(vkrt_scene* s, vkrt_accel_check* out)
 {
   if(!s || !out)

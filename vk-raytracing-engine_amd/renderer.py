@@ -128,6 +128,20 @@ class Renderer:
         _check(self.lib.vkrt_debug_check_accel(self._h, C.byref(c)), "vkrt_debug_check_accel")
         return {n: getattr(c, n) for n, _ in c._fields_}
 
+    def read_accel(self):
+        """The installed tree as the kernels read it (vkrt_debug_read_accel): {"layout": 1 wide8 / 0 BVH2, "root_ref": int,
+        "nodes": uint32 [N, 20] (wide8) or float32 [N, 16] (BVH2), "tris": float32 [T, 12] records in slot order}."""
+        info = self.accel_info()
+        nb, tb = int(info["node_bytes"]), int(info["triangle_bytes"])
+        nodes = np.zeros(max(nb, 4) // 4, np.uint32)
+        tris = np.zeros(max(tb, 4) // 4, np.float32)
+        root = C.c_int32()
+        _check(self.lib.vkrt_debug_read_accel(self._h, nodes.ctypes.data, nb, tris.ctypes.data, tb, C.byref(root)), "vkrt_debug_read_accel")
+        layout = int(self.check_accel()["layout"])
+        nodes, tris = nodes[: nb // 4], tris[: tb // 4]
+        nodes = nodes.reshape(-1, 20) if layout == 1 else nodes.view(np.float32).reshape(-1, 16)
+        return {"layout": layout, "root_ref": int(root.value), "nodes": nodes, "tris": tris.reshape(-1, 12)}
+
     def shard_rows(self, shard):
         return int(self.lib.vkrt_shard_rows(C.byref(shard)))
 
