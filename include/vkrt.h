@@ -297,6 +297,38 @@ int vkrt_scene_update_nodes(vkrt_scene* scene, uint32_t first, uint32_t count, c
  * VKRT_ERR_NOT_BUILT before any vkrt_accel_build. */
 int vkrt_accel_refit(vkrt_scene* scene, void* hip_stream);
 
+/* ---- ray queries (replaces traceRayEXT on rays of the caller's own, raytrace.rgen:64-97 / VK_KHR_ray_query: a closest-hit and an
+ *      occlusion query per ray of a device array).  These entry points came after ABI version 4 without changing it or any
+ *      existing struct: detect them by symbol. ---------------------------------------------------------------------------------------
+ * Memory and ordering: `rays`, `hits` and `occluded` are device memory on the scene's device; `rays` and `hits` are 16-byte aligned.
+ * The call is enqueued on hip_stream (NULL = default stream), after what was enqueued there before it; it allocates nothing, does not
+ * synchronise with the host and returns after the enqueue.  n may be any uint32_t.
+ * Closest hit: the hit the library's walks compute everywhere else -- the smallest t in the open interval (tmin, tmax), ties to the
+ * smallest flattened triangle id.  Miss: t = tmax, u = v = 0, and all five integer fields -1.
+ * Occlusion: occluded[i] = 1 when some hit exists in (tmin, tmax), else 0.
+ * Rays that miss without a walk: tmin < 0, tmin >= tmax (a NaN bound included), a zero direction, a NaN or infinite component of the
+ * origin or the direction.  tmax = +inf is accepted.  The direction need not be normalised (t is in units of its length).
+ * Scene options: the triangle options of the build apply -- VKRT_OPT_WATERTIGHT, and VKRT_OPT_ANYHIT_DISSOLVE with anyhit_seed as the
+ * payload seed of every ray (0 = what vkrt_debug_trace_rays and the oracle use).  The scheduling options (VKRT_OPT_WF_SHARE,
+ * VKRT_OPT_WF_SHARE_FLAGS, VKRT_OPT_TRI_THRESHOLD) apply too; none of them changes a result.
+ * Errors, in this order: a NULL scene, or (n > 0) a NULL or misaligned pointer: VKRT_ERR_INVALID_ARGUMENT; n == 0: VKRT_OK, nothing is
+ * enqueued; no tree, or a stale one after vkrt_scene_update_nodes: VKRT_ERR_NOT_BUILT; without a device: VKRT_ERR_NO_DEVICE.
+ * Counters: a walk cut short adds to vkrt_counters.traversal_faults, like every other walk; no other counter moves. */
+typedef struct vkrt_ray {        /* 32 B */
+  float origin[3];    float tmin;
+  float direction[3]; float tmax;
+} vkrt_ray;
+typedef struct vkrt_hit {        /* 32 B */
+  float   t, u, v;    /* u, v: barycentric weights of vertices 1 and 2, as the hit shader receives them (raytrace.rchit:68) */
+  int32_t instance;   /* node index (the reference's TLAS instance); -1 = miss */
+  int32_t primitive;  /* triangle index within its primitive-mesh (gl_PrimitiveID) */
+  int32_t prim_mesh;  /* the node's primMesh (gl_InstanceCustomIndexEXT, hello_vulkan.cpp:1039) */
+  int32_t triangle;   /* flattened triangle id: the gid of vkrt_debug_trace_rays and of the oracle */
+  int32_t material;   /* max(0, materialIndex) of the primitive-mesh: the material the hit shader reads */
+} vkrt_hit;
+int vkrt_intersect(vkrt_scene* scene, const vkrt_ray* rays, uint32_t n, uint32_t anyhit_seed, vkrt_hit* hits, void* hip_stream);
+int vkrt_occluded(vkrt_scene* scene, const vkrt_ray* rays, uint32_t n, uint32_t anyhit_seed, int32_t* occluded, void* hip_stream);
+
 /* ---- path trace (replaces HelloVulkan::pathtrace :1423-1448 = one
  *      vkCmdTraceRaysKHR over raytrace.rgen/.rchit/.rmiss/raytraceShadow.rmiss) ---- */
 uint32_t vkrt_shard_rows(const vkrt_shard* shard); /* rows of the shard's buffer */

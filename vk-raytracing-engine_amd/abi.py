@@ -171,6 +171,19 @@ class TraceTiming(C.Structure):
     _fields_ = [("total_ms", c_f), ("traverse_ms", c_f), ("traverse_launches", c_u), ("mode", c_u), ("shade_ms", c_f), ("shade_launches", c_u)]
 
 
+# ray queries (vkrt_intersect / vkrt_occluded): records of device arrays, 32 B each
+class Ray(C.Structure):
+    _fields_ = [("origin", c_f * 3), ("tmin", c_f), ("direction", c_f * 3), ("tmax", c_f)]
+
+
+class Hit(C.Structure):
+    _fields_ = [("t", c_f), ("u", c_f), ("v", c_f), ("instance", C.c_int32), ("primitive", C.c_int32), ("prim_mesh", C.c_int32),
+                ("triangle", C.c_int32), ("material", C.c_int32)]
+
+
+assert C.sizeof(Ray) == 32
+assert C.sizeof(Hit) == 32
+
 # layout contract
 assert C.sizeof(GlobalUniforms) == 192
 assert C.sizeof(PushConstantRay) == 44
@@ -213,6 +226,8 @@ VKRT_SYMBOLS = [
     "vkrt_accel_get_info",
     "vkrt_scene_update_nodes",
     "vkrt_accel_refit",
+    "vkrt_intersect",
+    "vkrt_occluded",
     "vkrt_shard_rows",
     "vkrt_pathtrace",
     "vkrt_pathtrace_frames",
@@ -262,6 +277,11 @@ def declare_vkrt(lib):
     lib.vkrt_scene_update_nodes.restype = C.c_int
     lib.vkrt_accel_refit.argtypes = [C.c_void_p, C.c_void_p]
     lib.vkrt_accel_refit.restype = C.c_int
+    # (rays, hits, occluded: device pointers)
+    lib.vkrt_intersect.argtypes = [C.c_void_p, C.c_void_p, c_u, c_u, C.c_void_p, C.c_void_p]
+    lib.vkrt_intersect.restype = C.c_int
+    lib.vkrt_occluded.argtypes = [C.c_void_p, C.c_void_p, c_u, c_u, C.c_void_p, C.c_void_p]
+    lib.vkrt_occluded.restype = C.c_int
     lib.vkrt_debug_check_accel.argtypes = [C.c_void_p, P(AccelCheck)]
     lib.vkrt_debug_check_accel.restype = C.c_int
     lib.vkrt_debug_read_accel.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, P(C.c_int32)]

@@ -10,6 +10,10 @@ hipError_t vkrt_launch_trace_rays(const DevScene& sc, unsigned n, const float* o
                                   float* t, float* u, float* v, int* gid, hipStream_t stream);
 hipError_t vkrt_launch_eval_math(int op, unsigned n, const float* a, const float* b, float* out, hipStream_t stream);
 
+// ray queries (query.hip): n caller rays (2 float4 each: origin + tmin, direction + tmax) -> closest hits (2 float4 each, vkrt_hit) when
+// hits != NULL, otherwise occluded flags (one int each) into occ.  seed = the any-hit stage's payload seed.
+hipError_t vkrt_launch_query(const DevScene& sc, const float4* rays, uint64_t n, uint32_t seed, float4* hits, int* occ, hipStream_t stream);
+
 // wavefront mode (wavefront.hip)
 struct WfTiming
 {

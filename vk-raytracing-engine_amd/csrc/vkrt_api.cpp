@@ -378,6 +378,28 @@ int launchParams(const vkrt_scene* s, const PushConstantRay* pc, const GlobalUni
   return VKRT_OK;
 }
 
+static_assert(sizeof(vkrt_ray) == 32 && sizeof(vkrt_hit) == 32, "k_query reads and writes 2 x 16 B per ray");
+// vkrt_intersect / vkrt_occluded: one k_query launch per 2^30 rays on the caller's stream (query.hip); out = hits or occluded flags
+int rayQuery(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, uint32_t seed, void* out, bool anyHit, void* hip_stream, const char* who)
+{
+  if(!s)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
+  if(n && (!rays || !out))
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: NULL array", who);
+  if(n && (((uintptr_t)rays & 15u) != 0u || (!anyHit && ((uintptr_t)out & 15u) != 0u) || (anyHit && ((uintptr_t)out & 3u) != 0u)))
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: misaligned array (rays and hits: 16 bytes, occluded: 4)", who);
+  if(n == 0)
+    return VKRT_OK;
+  int rc = checkBuilt(s, who);
+  if(rc != VKRT_OK)
+    return rc;
+  if((rc = setDevice(s)) != VKRT_OK)
+    return rc;
+  HIP_TRY(vkrt_launch_query(s->dev, (const float4*)rays, n, seed, anyHit ? nullptr : (float4*)out, anyHit ? (int*)out : nullptr,
+                            (hipStream_t)hip_stream));
+  return VKRT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1076,6 +1098,16 @@ int vkrt_accel_refit(vkrt_scene* s, void* hip_stream)
   s->refitted = true;
   s->stale = false;
   return VKRT_OK;
+}
+
+int vkrt_intersect(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, uint32_t anyhit_seed, vkrt_hit* hits, void* hip_stream)
+{
+  return rayQuery(s, rays, n, anyhit_seed, hits, false, hip_stream, "vkrt_intersect");
+}
+
+int vkrt_occluded(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, uint32_t anyhit_seed, int32_t* occluded, void* hip_stream)
+{
+  return rayQuery(s, rays, n, anyhit_seed, occluded, true, hip_stream, "vkrt_occluded");
 }
 
 uint32_t vkrt_shard_rows(const vkrt_shard* sh)

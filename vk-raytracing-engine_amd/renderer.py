@@ -42,6 +42,42 @@ def whole_image_shard(width, height):
     return abi.Shard(width, height, 0, 1, 0)
 
 
+def pack_rays(origins, directions, tmin=0.001, tmax=1e4):
+    """vkrt_ray records for Renderer.intersect / occluded: origins, directions [N, 3] torch tensors; tmin, tmax scalars or [N]
+    tensors.  Returns a contiguous float32 [N, 8] tensor on the origins' device: (origin.xyz, tmin, direction.xyz, tmax) per row."""
+    import torch
+
+    o = torch.as_tensor(origins)
+    dev = o.device
+    o = o.to(torch.float32).reshape(-1, 3)
+    d = torch.as_tensor(directions, device=dev).to(torch.float32).reshape(-1, 3)
+    if o.shape[0] != d.shape[0]:
+        raise VkrtError(f"pack_rays: {o.shape[0]} origins, {d.shape[0]} directions")
+    n = o.shape[0]
+    out = torch.empty((n, 8), dtype=torch.float32, device=dev)
+    out[:, 0:3] = o
+    out[:, 4:7] = d
+    for col, b in ((3, tmin), (7, tmax)):
+        b = torch.as_tensor(b, dtype=torch.float32, device=dev)
+        if b.dim() > 0 and b.numel() != n:
+            raise VkrtError(f"pack_rays: {b.numel()} bounds for {n} rays")
+        out[:, col] = b.reshape(-1) if b.dim() > 0 else b
+    return out
+
+
+class RayHits:
+    """Result of Renderer.intersect: views of one [N, 8] 4-byte buffer laid out like vkrt_hit.  t, u, v: float32 [N]; instance,
+    primitive, prim_mesh, triangle, material: int32 [N] (-1 = miss; t = tmax, u = v = 0 there)."""
+
+    def __init__(self, buffer):
+        import torch
+
+        self.buffer = buffer
+        f, i = buffer.view(torch.float32), buffer.view(torch.int32)
+        self.t, self.u, self.v = f[:, 0], f[:, 1], f[:, 2]
+        self.instance, self.primitive, self.prim_mesh, self.triangle, self.material = (i[:, k] for k in range(3, 8))
+
+
 class Renderer:
     def __init__(self, flat, device=0, build="ploc", options=None):
         """options: {abi.VKRT_OPT_*: value} applied before the build (per-handle execution options, include/vkrt.h)."""
@@ -257,6 +293,71 @@ class Renderer:
         _check(self.lib.vkrt_last_trace_timing(self._h, C.byref(t)), "vkrt_last_trace_timing")
         return {"total_ms": float(t.total_ms), "traverse_ms": float(t.traverse_ms), "traverse_launches": int(t.traverse_launches),
                 "mode": "wavefront" if t.mode == 1 else "megakernel", "shade_ms": float(t.shade_ms), "shade_launches": int(t.shade_launches)}
+
+    # ---- ray queries (vkrt_intersect / vkrt_occluded) --------------------------------------------------------------------------
+    def _query_args(self, rays, what):
+        """Refuse what the C ABI cannot take, before the call: rays must be a contiguous, 16-byte aligned float32 [N, 8] tensor on
+        this renderer's device."""
+        import torch
+
+        if not isinstance(rays, torch.Tensor):
+            raise VkrtError(f"{what}: rays must be a torch tensor (pack_rays), got {type(rays).__name__}")
+        if not rays.is_cuda:
+            raise VkrtError(f"{what}: rays are on {rays.device}, the scene is on cuda:{self.device}")
+        if rays.device.index != self.device:
+            raise VkrtError(f"{what}: rays are on {rays.device}, the scene is on cuda:{self.device}")
+        if rays.dtype != torch.float32:
+            raise VkrtError(f"{what}: rays are {rays.dtype}, expected torch.float32")
+        if rays.dim() != 2 or rays.shape[1] != 8:
+            raise VkrtError(f"{what}: rays have shape {tuple(rays.shape)}, expected [N, 8]")
+        if not rays.is_contiguous() or rays.data_ptr() % 16 != 0:
+            raise VkrtError(f"{what}: rays must be contiguous and 16-byte aligned")
+        if rays.shape[0] >= 1 << 32:
+            raise VkrtError(f"{what}: {rays.shape[0]} rays, at most 2^32 - 1 per call")
+        return int(rays.shape[0])
+
+    def _query_out(self, out, shape, what, align):
+        import torch
+
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.device.index != self.device:
+            raise VkrtError(f"{what}: out must be a tensor on cuda:{self.device}")
+        if out.dtype not in (torch.float32, torch.int32) or tuple(out.shape) != shape:
+            raise VkrtError(f"{what}: out is {out.dtype} {tuple(out.shape)}, expected a 4-byte dtype of shape {shape}")
+        if not out.is_contiguous() or out.data_ptr() % align != 0:
+            raise VkrtError(f"{what}: out must be contiguous and {align}-byte aligned")
+        return out
+
+    def intersect(self, rays, seed=0, out=None, stream=None):
+        """Closest hit of every ray (vkrt_intersect), enqueued on `stream` (default: the current stream of the scene's device).
+        rays: float32 [N, 8] from pack_rays; seed: the any-hit stage's payload seed (VKRT_OPT_ANYHIT_DISSOLVE); out: an optional
+        float32 / int32 [N, 8] buffer to write into.  Returns a RayHits of views of that buffer."""
+        import torch
+
+        n = self._query_args(rays, "intersect")
+        if stream is None:
+            stream = torch.cuda.current_stream(rays.device)
+        if out is None:
+            with torch.cuda.stream(stream):  # (allocated on the stream that writes it)
+                out = torch.empty((n, 8), dtype=torch.float32, device=rays.device)
+        self._query_out(out, (n, 8), "intersect", 16)
+        _check(self.lib.vkrt_intersect(self._h, C.c_void_p(rays.data_ptr()), n, int(seed) & 0xFFFFFFFF, C.c_void_p(out.data_ptr()),
+                                       C.c_void_p(stream.cuda_stream)), "vkrt_intersect")
+        return RayHits(out)
+
+    def occluded(self, rays, seed=0, out=None, stream=None):
+        """1 where some hit lies in (tmin, tmax), else 0 (vkrt_occluded): int32 [N] (or `out`), enqueued like intersect()."""
+        import torch
+
+        n = self._query_args(rays, "occluded")
+        if stream is None:
+            stream = torch.cuda.current_stream(rays.device)
+        if out is None:
+            with torch.cuda.stream(stream):
+                out = torch.empty((n,), dtype=torch.int32, device=rays.device)
+        self._query_out(out, (n,), "occluded", 4)
+        _check(self.lib.vkrt_occluded(self._h, C.c_void_p(rays.data_ptr()), n, int(seed) & 0xFFFFFFFF, C.c_void_p(out.data_ptr()),
+                                      C.c_void_p(stream.cuda_stream)), "vkrt_occluded")
+        return out.view(torch.int32)
 
     def trace_rays(self, origins, directions, tmin=0.001, tmax=10000.0, any_hit=False):
         o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
