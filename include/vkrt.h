@@ -68,7 +68,8 @@ typedef struct vkrt_prim_mesh {
 } vkrt_prim_mesh;
 
 /* One drawable node = one TLAS instance (hello_vulkan.cpp:1035-1043):
- * transform = worldMatrix, instanceCustomIndex = primMesh, mask 0xFF, cull disabled. */
+ * transform = worldMatrix, instanceCustomIndex = primMesh, mask 0xFF, cull disabled (the initial visibility of every node;
+ * vkrt_scene_set_instance_visibility changes mask and flags for the ray-query entry points). */
 typedef struct vkrt_node {
   float   worldMatrix[16]; /* column-major object->world */
   int32_t primMesh;
@@ -329,6 +330,64 @@ typedef struct vkrt_hit {        /* 32 B */
 int vkrt_intersect(vkrt_scene* scene, const vkrt_ray* rays, uint32_t n, uint32_t anyhit_seed, vkrt_hit* hits, void* hip_stream);
 int vkrt_occluded(vkrt_scene* scene, const vkrt_ray* rays, uint32_t n, uint32_t anyhit_seed, int32_t* occluded, void* hip_stream);
 
+/* ---- instance visibility and ray flags (traceRayEXT's cullMask and rayFlags, raytrace.rgen:64-66 / :86-87, acting on
+ *      VkAccelerationStructureInstanceKHR::mask and ::flags, hello_vulkan.cpp:1040-1041).  These entry points came after ABI version 4
+ *      without changing it or any existing struct: detect them by symbol. ------------------------------------------------------------
+ * They act on the ray-query entry points only: vkrt_pathtrace*, vkrt_gbuffer_raycast*, vkrt_hybrid_trace* and vkrt_debug_trace_rays
+ * trace as the reference does (cull mask 0xFF, no culling), and since a mask is never 0 their pixels and counters do not depend on
+ * any visibility setting.
+ * Candidates: a triangle of instance I is a candidate for a ray of a call with options (ray_flags, cull_mask) when
+ *   1. (I.mask & cull_mask) != 0,
+ *   2. it is not culled by facing: with VKRT_RAY_CULL_BACK_FACING (VKRT_RAY_CULL_FRONT_FACING) back-facing (front-facing) triangles are
+ *      not candidates, unless I has VKRT_INSTANCE_FACING_CULL_DISABLE,
+ *   3. the any-hit dissolve stage does not ignore it (VKRT_OPT_ANYHIT_DISSOLVE; never with VKRT_RAY_OPAQUE).
+ * Closest hit and occlusion follow the rules above over the candidates; the filter is a pure function of (ray, triangle), so a result
+ * stays a property of the triangle set, independent of builder, layout, split and schedule.
+ * Facing is decided in object space: a triangle is FRONT-facing when its object-space vertices p0, p1, p2 (index order) appear
+ * counter-clockwise seen from the ray's origin, i.e. when (p1 - p0) x (p2 - p0) points against the object-space direction (glTF's
+ * front face); VKRT_INSTANCE_FLIP_FACING swaps front and back.  (On world-space vertices: front <=> (Moeller-Trumbore's
+ * det = e1 . (d x e2) > 0) XOR (the node's 3x3 has a negative determinant) XOR FLIP_FACING.) */
+enum vkrt_instance_flags {
+  VKRT_INSTANCE_FACING_CULL_DISABLE = 0x1, /* the ray's facing-cull flags do not apply to this instance */
+  VKRT_INSTANCE_FLIP_FACING = 0x2          /* front and back are swapped */
+};
+typedef struct vkrt_instance_visibility { /* 4 B; every node starts as {0xFF, VKRT_INSTANCE_FACING_CULL_DISABLE}, the reference's TLAS */
+  uint8_t  mask;     /* 1..255 (to hide an instance from every ray give it a zero-scale transform) */
+  uint8_t  flags;    /* vkrt_instance_flags */
+  uint16_t reserved; /* 0 */
+} vkrt_instance_visibility;
+/* Set the visibility of nodes [first, first+count).  Same rules as vkrt_scene_update_nodes: the array is copied before return, the work
+ * is enqueued on hip_stream with no host synchronisation and no allocation, and ray queries enqueued on that stream after it see the new
+ * values.  It does not make the tree stale and works on a stale one.  Refused with VKRT_ERR_INVALID_ARGUMENT, changing nothing, in this
+ * order: a NULL array with count > 0; an entry with mask 0, unknown flag bits or reserved != 0; a NULL scene; a range outside the
+ * scene's nodes.  Then, without a device: VKRT_ERR_NO_DEVICE.  The visibility of a node survives vkrt_scene_update_nodes,
+ * vkrt_accel_refit and vkrt_accel_build. */
+int vkrt_scene_set_instance_visibility(vkrt_scene* scene, uint32_t first, uint32_t count, const vkrt_instance_visibility* vis, void* hip_stream);
+/* Reads the host copy (no synchronisation).  VKRT_ERR_INVALID_ARGUMENT: a NULL array with count > 0, a NULL scene, a range outside. */
+int vkrt_scene_get_instance_visibility(const vkrt_scene* scene, uint32_t first, uint32_t count, vkrt_instance_visibility* out);
+
+enum vkrt_ray_flags {                 /* the gl_RayFlags*EXT values; no other bit is accepted */
+  VKRT_RAY_OPAQUE = 0x1,              /* skip the any-hit dissolve stage, even on a scene built with VKRT_OPT_ANYHIT_DISSOLVE */
+  VKRT_RAY_CULL_BACK_FACING = 0x10,   /* back-facing triangles are not candidates (instances with FACING_CULL_DISABLE excepted) */
+  VKRT_RAY_CULL_FRONT_FACING = 0x20   /* front-facing triangles are not candidates (the same) -- not together with CULL_BACK_FACING */
+};
+typedef struct vkrt_query_opts {
+  uint32_t struct_size; /* sizeof(vkrt_query_opts) */
+  uint32_t ray_flags;   /* vkrt_ray_flags */
+  uint32_t cull_mask;   /* 0..0xFF; 0 = every ray misses (results are written, nothing is walked) */
+  uint32_t anyhit_seed; /* as in vkrt_intersect */
+} vkrt_query_opts;
+/* vkrt_intersect / vkrt_occluded with options for the whole call (a caller with two kinds of rays makes two calls); same memory,
+ * ordering, miss and error rules.  vkrt_intersect(..., seed, ...) is vkrt_intersect_ex with {sizeof, 0, 0xFF, seed}, and
+ * vkrt_occluded likewise.  Refused with VKRT_ERR_INVALID_ARGUMENT before the checks of vkrt_intersect (NULL scene, arrays; then n == 0,
+ * NOT_BUILT, NO_DEVICE): a NULL opts, struct_size < sizeof(vkrt_query_opts), a ray flag outside the three above, both cull flags,
+ * cull_mask > 0xFF.
+ * Cost: with no cull flag and a cull mask that meets every node's mask the call runs the kernel of vkrt_intersect / vkrt_occluded.
+ * Otherwise the walk filters candidates; on the 8-wide layout it also skips the children whose subtree holds no instance the mask
+ * admits (a table of one byte per child slot, kept with the tree); the BVH2 layout filters at the triangles only. */
+int vkrt_intersect_ex(vkrt_scene* scene, const vkrt_ray* rays, uint32_t n, const vkrt_query_opts* opts, vkrt_hit* hits, void* hip_stream);
+int vkrt_occluded_ex(vkrt_scene* scene, const vkrt_ray* rays, uint32_t n, const vkrt_query_opts* opts, int32_t* occluded, void* hip_stream);
+
 /* ---- path trace (replaces HelloVulkan::pathtrace :1423-1448 = one
  *      vkCmdTraceRaysKHR over raytrace.rgen/.rchit/.rmiss/raytraceShadow.rmiss) ---- */
 uint32_t vkrt_shard_rows(const vkrt_shard* shard); /* rows of the shard's buffer */
@@ -502,6 +561,11 @@ int vkrt_debug_check_accel(vkrt_scene* scene, vkrt_accel_check* out);
  * reference for a BVH2 whose root is a leaf; VKRT_TRAV_DONE for an empty scene).  Other byte counts or a NULL pointer:
  * VKRT_ERR_INVALID_ARGUMENT; no tree, or a stale one: VKRT_ERR_NOT_BUILT. */
 int vkrt_debug_read_accel(vkrt_scene* scene, void* nodes, uint64_t nodes_bytes, void* tris, uint64_t tris_bytes, int32_t* root_ref);
+/* The 8-wide tree's node-mask table as the query kernels read it (synchronises the device): 8 B per node of the node array
+ * (bytes == vkrt_accel_info.node_bytes / 80 * 8), byte s of node k = the OR of the instance masks of every triangle reference under
+ * child slot s (0 for an empty slot).  Other byte counts, a NULL pointer or a BVH2 tree: VKRT_ERR_INVALID_ARGUMENT; no tree:
+ * VKRT_ERR_NOT_BUILT (a stale tree is read as it stands: a refit leaves the table valid). */
+int vkrt_debug_read_node_masks(vkrt_scene* scene, void* out, uint64_t bytes);
 /* Closest-hit query for n rays: o,d = vec3[n] host arrays; tmin/tmax scalars.
  * Writes t,u,v (float[n]) and the flattened triangle id gid (int32[n], -1 = miss). */
 int vkrt_debug_trace_rays(vkrt_scene* scene, uint32_t n, const float* origins,

@@ -181,8 +181,19 @@ class Hit(C.Structure):
                 ("triangle", C.c_int32), ("material", C.c_int32)]
 
 
+# instance visibility and query options (vkrt_scene_set_instance_visibility, vkrt_intersect_ex / vkrt_occluded_ex)
+class InstanceVisibility(C.Structure):
+    _fields_ = [("mask", C.c_uint8), ("flags", C.c_uint8), ("reserved", C.c_uint16)]
+
+
+class QueryOpts(C.Structure):
+    _fields_ = [("struct_size", c_u), ("ray_flags", c_u), ("cull_mask", c_u), ("anyhit_seed", c_u)]
+
+
 assert C.sizeof(Ray) == 32
 assert C.sizeof(Hit) == 32
+assert C.sizeof(InstanceVisibility) == 4
+assert C.sizeof(QueryOpts) == 16
 
 # layout contract
 assert C.sizeof(GlobalUniforms) == 192
@@ -210,6 +221,9 @@ VKRT_OPT_WATERTIGHT, VKRT_OPT_SKIP_DEAD_SHADOW_RAYS, VKRT_OPT_ANYHIT_DISSOLVE = 
 VKRT_OPT_WF_FRAMES_IN_FLIGHT, VKRT_OPT_SPLIT_BUDGET = 13, 14
 VKRT_INFO_ANYHIT_ORDER = 100  # read-only: what the build resolved the any-hit child order to
 VKRT_INFO_SPLIT_BUDGET = 101  # read-only: the pre-splitting budget the build used (what -1 resolved to)
+# vkrt_instance_flags / vkrt_ray_flags (the gl_RayFlags*EXT values)
+VKRT_INSTANCE_FACING_CULL_DISABLE, VKRT_INSTANCE_FLIP_FACING = 0x1, 0x2
+VKRT_RAY_OPAQUE, VKRT_RAY_CULL_BACK_FACING, VKRT_RAY_CULL_FRONT_FACING = 0x1, 0x10, 0x20
 
 # every symbol include/vkrt.h declares (tests check the built library exports them all)
 VKRT_SYMBOLS = [
@@ -228,6 +242,10 @@ VKRT_SYMBOLS = [
     "vkrt_accel_refit",
     "vkrt_intersect",
     "vkrt_occluded",
+    "vkrt_scene_set_instance_visibility",
+    "vkrt_scene_get_instance_visibility",
+    "vkrt_intersect_ex",
+    "vkrt_occluded_ex",
     "vkrt_shard_rows",
     "vkrt_pathtrace",
     "vkrt_pathtrace_frames",
@@ -246,6 +264,7 @@ VKRT_SYMBOLS = [
     "vkrt_last_trace_timing",
     "vkrt_debug_check_accel",
     "vkrt_debug_read_accel",
+    "vkrt_debug_read_node_masks",
     "vkrt_debug_trace_rays",
     "vkrt_debug_eval_math",
 ]
@@ -282,6 +301,16 @@ def declare_vkrt(lib):
     lib.vkrt_intersect.restype = C.c_int
     lib.vkrt_occluded.argtypes = [C.c_void_p, C.c_void_p, c_u, c_u, C.c_void_p, C.c_void_p]
     lib.vkrt_occluded.restype = C.c_int
+    lib.vkrt_scene_set_instance_visibility.argtypes = [C.c_void_p, c_u, c_u, P(InstanceVisibility), C.c_void_p]
+    lib.vkrt_scene_set_instance_visibility.restype = C.c_int
+    lib.vkrt_scene_get_instance_visibility.argtypes = [C.c_void_p, c_u, c_u, P(InstanceVisibility)]
+    lib.vkrt_scene_get_instance_visibility.restype = C.c_int
+    lib.vkrt_intersect_ex.argtypes = [C.c_void_p, C.c_void_p, c_u, P(QueryOpts), C.c_void_p, C.c_void_p]
+    lib.vkrt_intersect_ex.restype = C.c_int
+    lib.vkrt_occluded_ex.argtypes = [C.c_void_p, C.c_void_p, c_u, P(QueryOpts), C.c_void_p, C.c_void_p]
+    lib.vkrt_occluded_ex.restype = C.c_int
+    lib.vkrt_debug_read_node_masks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+    lib.vkrt_debug_read_node_masks.restype = C.c_int
     lib.vkrt_debug_check_accel.argtypes = [C.c_void_p, P(AccelCheck)]
     lib.vkrt_debug_check_accel.restype = C.c_int
     lib.vkrt_debug_read_accel.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, P(C.c_int32)]

@@ -16,9 +16,13 @@ struct DevInstance
   float o2w[12];  // row-major 3x4
   float w2o[9];   // row-major 3x3 inverse of the upper-left block
   int32_t primMesh;
-  int32_t pad[2];
+  uint32_t vis;  // ray-query visibility (vkrt_scene_set_instance_visibility): bits 0-7 mask, bits 8-15 vkrt_instance_flags, VKRT_VIS_MIRRORED
+  int32_t pad;
 };
 static_assert(sizeof(DevInstance) == 96, "DevInstance");
+#define VKRT_VIS_CULL_DISABLE 0x100u  // VKRT_INSTANCE_FACING_CULL_DISABLE << 8
+#define VKRT_VIS_FLIP 0x200u          // VKRT_INSTANCE_FLIP_FACING << 8
+#define VKRT_VIS_MIRRORED 0x10000u    // the object->world 3x3 has a negative determinant (set on the host with the record)
 
 // Shading-side repack (done once at upload; the API still takes the reference's SoA arrays):
 // the per-CU L1/TA processes one 16-byte lane-load per tag lookup, so records are laid out for few,
@@ -118,6 +122,15 @@ struct DevScene
   uint32_t dissolve;          // 1: any-hit alpha / dissolve stage (VKRT_OPT_ANYHIT_DISSOLVE): bit 31 of a record's id word flags a non-opaque triangle
   unsigned long long* faults; // sticky tally of dropped stack pushes + step-limit exits (a walk that was cut short); must stay 0
 };
+// The scene of a ray query with options (k_query, query.hip): the walks receive it as their DevScene and read the fields below only in
+// the triangle modes with VKRT_TM_FILTER (traverse.h query_rejects), so every other walk compiles as it did.
+struct DevQueryScene : DevScene
+{
+  const uint2* nodeMasks;  // wide8: per node, byte s = OR of the instance masks under child slot s (vkrt_launch_node_masks)
+  uint32_t cullMask;       // 0..0xFF, launch-uniform
+  uint32_t rayFlags;       // VKRT_RAY_CULL_BACK_FACING / VKRT_RAY_CULL_FRONT_FACING or 0
+};
+
 // a traversal could not keep a pending subtree (stack full) or ran into the step bound: the result may be wrong -> make it visible
 #define VKRT_TRAV_FAULT(sc) atomicAdd((sc).faults, 1ull)
 

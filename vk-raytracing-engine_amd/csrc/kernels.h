@@ -11,8 +11,14 @@ hipError_t vkrt_launch_trace_rays(const DevScene& sc, unsigned n, const float* o
 hipError_t vkrt_launch_eval_math(int op, unsigned n, const float* a, const float* b, float* out, hipStream_t stream);
 
 // ray queries (query.hip): n caller rays (2 float4 each: origin + tmin, direction + tmax) -> closest hits (2 float4 each, vkrt_hit) when
-// hits != NULL, otherwise occluded flags (one int each) into occ.  seed = the any-hit stage's payload seed.
-hipError_t vkrt_launch_query(const DevScene& sc, const float4* rays, uint64_t n, uint32_t seed, float4* hits, int* occ, hipStream_t stream);
+// hits != NULL, otherwise occluded flags (one int each) into occ.  seed = the any-hit stage's payload seed.  filter: walk with the
+// ray-query filter (sc.cullMask / rayFlags / nodeMasks, VKRT_TM_FILTER); opaque: VKRT_RAY_OPAQUE (no any-hit dissolve stage).
+hipError_t vkrt_launch_query(const DevQueryScene& sc, const float4* rays, uint64_t n, uint32_t seed, bool filter, bool opaque, float4* hits, int* occ,
+                             hipStream_t stream);
+// The node-mask table of a wide8 tree (query.hip): `sweeps` passes over all nodes, each node ORing its leaves' instance masks and its
+// child nodes' bytes; a node of height h is exact after h passes, so sweeps >= the tree's levels gives the table without reading
+// anything back.  instCount bounds the instance ids of the records.
+hipError_t vkrt_launch_node_masks(const DevScene& sc, uint32_t nodeCount, uint32_t instCount, uint32_t sweeps, uint2* masks, hipStream_t stream);
 
 // wavefront mode (wavefront.hip)
 struct WfTiming

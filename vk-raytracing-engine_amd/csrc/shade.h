@@ -382,7 +382,7 @@ VKRT_DEV void closestHitFront(const DevScene& sc, const RayHit& hit, const uint3
     in.o2w[0] = q0.x; in.o2w[1] = q0.y; in.o2w[2] = q0.z; in.o2w[3] = q0.w; in.o2w[4] = q1.x; in.o2w[5] = q1.y; in.o2w[6] = q1.z; in.o2w[7] = q1.w;
     in.o2w[8] = q2.x; in.o2w[9] = q2.y; in.o2w[10] = q2.z; in.o2w[11] = q2.w;
     in.w2o[0] = q3.x; in.w2o[1] = q3.y; in.w2o[2] = q3.z; in.w2o[3] = q3.w; in.w2o[4] = q4.x; in.w2o[5] = q4.y; in.w2o[6] = q4.z; in.w2o[7] = q4.w;
-    in.w2o[8] = q5.x; in.primMesh = __float_as_int(q5.y); in.pad[0] = 0; in.pad[1] = 0;
+    in.w2o[8] = q5.x; in.primMesh = __float_as_int(q5.y); in.vis = 0u; in.pad = 0;
   }
   GltfPBRMaterial mat;  // (the fields this shader reads; a texture index only matters as "> -1": bit 15 of the reference's first word)
   mat.pbrBaseColorFactor[0] = m0.x; mat.pbrBaseColorFactor[1] = m0.y; mat.pbrBaseColorFactor[2] = m0.z; mat.pbrBaseColorFactor[3] = 1.0f;

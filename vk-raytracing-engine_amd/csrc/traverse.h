@@ -53,8 +53,9 @@ VKRT_DEV bool box_test(f3 o, f3 id, float lox, float loy, float loz, float hix, 
   return tn <= tf * VKRT_BOX_PAD_REL;
 }
 
-// Moeller-Trumbore on (v0,e1,e2); one IEEE division, only for rays inside the triangle.
-VKRT_DEV bool tri_test(f3 o, f3 d, f3 v0, f3 e1, f3 e2, float& t, float& u, float& v)
+// Moeller-Trumbore on (v0,e1,e2); one IEEE division, only for rays inside the triangle.  ccw: det > 0, i.e. e1 x e2 points against d --
+// the vertices appear counter-clockwise from the ray's origin (the walks without VKRT_TM_FILTER never read it: no instruction).
+VKRT_DEV bool tri_test(f3 o, f3 d, f3 v0, f3 e1, f3 e2, float& t, float& u, float& v, bool& ccw)
 {
   f3 pvec = fcross3(d, e2);
   float det = fdot3(e1, pvec);
@@ -72,6 +73,7 @@ VKRT_DEV bool tri_test(f3 o, f3 d, f3 v0, f3 e1, f3 e2, float& t, float& u, floa
     ok = false;
   if(!ok)
     return false;
+  ccw = det > 0.0f;
   float inv = 1.0f / det;
   t = T * inv;
   u = U * inv;
@@ -106,7 +108,9 @@ VKRT_DEV WtRay wt_prepare(f3 d)
 }
 // (x, y, z) of v in the permuted frame
 VKRT_DEV f3 wt_permute(int kz, f3 v) { return kz == 0 ? mk3(v.y, v.z, v.x) : (kz == 1 ? mk3(v.z, v.x, v.y) : v); }
-VKRT_DEV bool tri_test_wt(const WtRay& R, f3 o, f3 p0, f3 p1, f3 p2, float& t, float& u, float& v)
+// ccw as in tri_test: U + V + W = -((p1 - p0) x (p2 - p0)) . d / d[kz] (the sheared frame keeps the normal's z and looks along the
+// sign of d[kz]), so Moeller-Trumbore's det > 0 is det > 0 here exactly when d[kz] > 0 (tests/test_gpu_ray_query_visibility.py pins both)
+VKRT_DEV bool tri_test_wt(const WtRay& R, f3 o, f3 p0, f3 p1, f3 p2, float& t, float& u, float& v, bool& ccw)
 {
   const f3 A = wt_permute(R.kz, p0 - o), B = wt_permute(R.kz, p1 - o), C = wt_permute(R.kz, p2 - o);
   const float Ax = A.x - R.Sx * A.z, Ay = A.y - R.Sy * A.z;
@@ -135,6 +139,7 @@ VKRT_DEV bool tri_test_wt(const WtRay& R, f3 o, f3 p0, f3 p1, f3 p2, float& t, f
   const float den = (N.x * R.Sx + N.y * R.Sy) + N.z;
   if(den == 0.0f)
     return false;
+  ccw = (det > 0.0f) != (R.Sz < 0.0f);
   const float inv = 1.0f / det;
   t = (dot3(N, A) * R.Sz) / den;
   u = V * inv;   // barycentric weights: U -> p0, V -> p1, W -> p2; (u, v) weigh p1 and p2 like Moeller-Trumbore's
@@ -145,28 +150,31 @@ VKRT_DEV bool tri_test_wt(const WtRay& R, f3 o, f3 p0, f3 p1, f3 p2, float& t, f
 // Compile-time "triangle mode" TM of every traversal: bit 0 = the watertight test (VKRT_OPT_WATERTIGHT), bit 1 = the any-hit alpha /
 // dissolve stage (VKRT_OPT_ANYHIT_DISSOLVE), bit 2 = the records may carry the stage's flag in their id word although this walk
 // treats every triangle as opaque (the ray-cast G-buffer on a scene built for the stage): the id is masked, no hit is ignored.
+// Bit 3 = the ray-query filter of vkrt_intersect_ex / vkrt_occluded_ex (k_query only): instance masks against the call's cull mask and
+// facing culling (query_rejects), and on the wide8 layout the node-mask table in the node test; the walk's scene is a DevQueryScene.
 // TM = 0 is the product default and compiles to exactly the code it was before.
 #define VKRT_TM_WATERTIGHT 1
 #define VKRT_TM_DISSOLVE 2
 #define VKRT_TM_MASKID 4
+#define VKRT_TM_FILTER 8
 
 // per-ray constants + one entry point on a 48-byte record (a, b, c)
 template <bool WT> struct TriRay;
 template <> struct TriRay<false>
 {
   VKRT_DEV void set(f3) {}
-  VKRT_DEV bool hit(f3 o, f3 d, float4 a, float4 b, float4 c, float& t, float& u, float& v) const
+  VKRT_DEV bool hit(f3 o, f3 d, float4 a, float4 b, float4 c, float& t, float& u, float& v, bool& ccw) const
   {
-    return tri_test(o, d, mk3(a.x, a.y, a.z), mk3(a.w, b.x, b.y), mk3(b.z, b.w, c.x), t, u, v);
+    return tri_test(o, d, mk3(a.x, a.y, a.z), mk3(a.w, b.x, b.y), mk3(b.z, b.w, c.x), t, u, v, ccw);
   }
 };
 template <> struct TriRay<true>
 {
   WtRay R;
   VKRT_DEV void set(f3 d) { R = wt_prepare(d); }
-  VKRT_DEV bool hit(f3 o, f3, float4 a, float4 b, float4 c, float& t, float& u, float& v) const
+  VKRT_DEV bool hit(f3 o, f3, float4 a, float4 b, float4 c, float& t, float& u, float& v, bool& ccw) const
   {
-    return tri_test_wt(R, o, mk3(a.x, a.y, a.z), mk3(a.w, b.x, b.y), mk3(b.z, b.w, c.x), t, u, v);
+    return tri_test_wt(R, o, mk3(a.x, a.y, a.z), mk3(a.w, b.x, b.y), mk3(b.z, b.w, c.x), t, u, v, ccw);
   }
 };
 
@@ -194,6 +202,45 @@ VKRT_DEV bool anyhit_ignores(const DevScene& sc, unsigned slot, float idWord, ui
   return rnd(st) > alpha;
 }
 
+// ---- ray-query filter (VKRT_TM_FILTER; include/vkrt.h "instance visibility and ray flags") ----------------------------------------
+// A candidate hit is rejected when its instance's mask misses the call's cull mask, or when the call culls its facing: front <=> ccw
+// (the world-space vertices counter-clockwise from the origin) XOR the instance mirrors XOR it has FLIP_FACING.  A pure function of
+// (ray, triangle) like anyhit_ignores; c = the record's third quad (its z = the instance).  Lanes that adopt a donor's walk call it
+// with the donor's ray, as they do the triangle test.
+template <int TM>
+VKRT_DEV bool query_rejects(const DevScene& sc, float4 c, bool ccw)
+{
+  if constexpr(!(TM & VKRT_TM_FILTER))
+    return false;
+  else
+  {
+    const DevQueryScene& q = static_cast<const DevQueryScene&>(sc);
+    const uint32_t w = sc.instances[__float_as_int(c.z)].vis;
+    if((w & q.cullMask) == 0u)
+      return true;
+    if(q.rayFlags == 0u || (w & VKRT_VIS_CULL_DISABLE))
+      return false;
+    const bool front = ccw != ((w & VKRT_VIS_FLIP) != 0u) != ((w & VKRT_VIS_MIRRORED) != 0u);
+    return (q.rayFlags & (front ? 0x20u : 0x10u)) != 0u;  // VKRT_RAY_CULL_FRONT_FACING : VKRT_RAY_CULL_BACK_FACING
+  }
+}
+template <int TM>
+VKRT_DEV unsigned query_cull_mask(const DevScene& sc)
+{
+  if constexpr(!(TM & VKRT_TM_FILTER))
+    return 0xffu;
+  else
+    return static_cast<const DevQueryScene&>(sc).cullMask;
+}
+template <int TM>
+VKRT_DEV const uint2* query_node_masks(const DevScene& sc)
+{
+  if constexpr(!(TM & VKRT_TM_FILTER))
+    return nullptr;
+  else
+    return static_cast<const DevQueryScene&>(sc).nodeMasks;
+}
+
 // Child order of any-hit walks (round 3, profiles/r03_experiments.md #94).  "Is anything in the way?" has the same answer in any order,
 // so the order is a pure cost heuristic.  Front to back is right for closest-hit walks; a shadow ray, though, starts on a surface and
 // runs to a light: with the reference's eight fallback lights (hello_vulkan.cpp:247-321: one inside the building, seven far
@@ -215,7 +262,8 @@ VKRT_DEV bool anyhit_far_first(const DevScene& sc, f3 o, f3 d, float tmax)
   return !(e.x >= sc.sceneLo[0] && e.x <= sc.sceneHi[0] && e.y >= sc.sceneLo[1] && e.y <= sc.sceneHi[1] && e.z >= sc.sceneLo[2] && e.z <= sc.sceneHi[2]);
 }
 
-// stk: this lane's LDS stack column (entry k at stk[k * stride]).
+// stk: this lane's LDS stack column (entry k at stk[k * stride]).  (VKRT_TM_FILTER: BVH2 nodes carry no mask table, the filter acts on
+// the triangles only.)
 template <bool COUNT, int TM = 0>
 VKRT_DEV void traverse(const DevScene& sc, f3 o, f3 d, float tmin, float tmax, bool anyHit, int* stk, int stride, RayHit& hit,
                        TravCount& tc, uint32_t raySeed = 0u)
@@ -299,13 +347,14 @@ VKRT_DEV void traverse(const DevScene& sc, f3 o, f3 d, float tmin, float tmax, b
         const float4 c = tris[s * VKRT_TRI_QUADS + 2];
         if(COUNT) tc.tris++;
         float t, u, v;
-        if(tr.hit(o, d, a, b, c, t, u, v))
+        bool ccw;
+        if(tr.hit(o, d, a, b, c, t, u, v, ccw))
         {
           if(t > tmin)
           {
             if(anyHit)
             {
-              if(t < tmax && !anyhit_ignores<TM>(sc, s, c.y, raySeed))
+              if(t < tmax && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, raySeed))
               {
                 bestSlot = (int)s;
                 bestT = t;
@@ -316,7 +365,7 @@ VKRT_DEV void traverse(const DevScene& sc, f3 o, f3 d, float tmin, float tmax, b
             else
             {
               const int gid = tri_gid<TM>(c.y);
-              if((t < bestT || (t == bestT && gid < bestGid)) && !anyhit_ignores<TM>(sc, s, c.y, raySeed))
+              if((t < bestT || (t == bestT && gid < bestGid)) && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, raySeed))
               {
                 bestT = t; bestU = u; bestV = v; bestSlot = (int)s; bestGid = gid;
               }

@@ -210,11 +210,12 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
             if(lane == __ffsll((long long)__ballot(1)) - 1) tc.waveTriSteps++;
           }
           float t, u, v;
-          if(tr.hit(o, d, a, b, c, t, u, v) && t > tmin)
+          bool ccw;  // (an adopting lane holds the donor's ray: facing is judged with the donor's direction)
+          if(tr.hit(o, d, a, b, c, t, u, v, ccw) && t > tmin)
           {
             if(ANYHIT)
             {
-              if(t < tmax && !cd.found && !anyhit_ignores<TM>(sc, s, c.y, raySeed))
+              if(t < tmax && !cd.found && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, raySeed))
               {
                 cd.found = true; cd.t = t; cd.slot = (int)s;
               }
@@ -224,7 +225,7 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
               const int gid = tri_gid<TM>(c.y);
               const float rt = cd.found ? cd.t : bt;
               const int rg = cd.found ? cd.gid : bg;
-              if((t < rt || (t == rt && gid < rg)) && !anyhit_ignores<TM>(sc, s, c.y, raySeed))
+              if((t < rt || (t == rt && gid < rg)) && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, raySeed))
               {
                 cd.found = true; cd.t = t; cd.u = u; cd.v = v; cd.slot = (int)s; cd.gid = gid;
               }
@@ -289,7 +290,8 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
               VKRT_TRAV_FAULT(sc);
           }
           uint2 Tn;
-          w8_test_children<COUNT>(nodes, child, o, id, oct4, px, py, pz, tmin, bt, G, Tn, tc);
+          w8_test_children<COUNT, (TM & VKRT_TM_FILTER) != 0>(nodes, child, o, id, oct4, px, py, pz, tmin, bt, G, Tn, tc, query_node_masks<TM>(sc),
+                                                              query_cull_mask<TM>(sc));
           if(Tn.y != 0u)
           {
             if(T.y != 0u)

@@ -75,12 +75,18 @@ VKRT_DEV unsigned w8_piece(unsigned idx4, unsigned bits4, int k)
 // Test the 8 children of wide node `child` against the ray (oct4 = the ray's octinv in each of the four bytes, a per-ray constant the
 // callers keep: one v_mul_lo_u32 per node test otherwise): G = (child base, hit internal children | imask),
 // T = (triangle base, 24-bit mask of the leaf triangles whose boxes the ray touched).
-template <bool COUNT>
+// CULL (the ray-query filter, VKRT_TM_FILTER): slots whose byte in the node-mask table has no bit of the launch-uniform cull mask are
+// not hit -- one 8-byte load per node test; nothing of it is compiled without CULL.
+template <bool COUNT, bool CULL = false>
 VKRT_DEV void w8_test_children(const float4* __restrict__ nodes, unsigned child, f3 o, f3 id, unsigned oct4, bool px, bool py, bool pz, float tmin,
-                               float bestT_in, uint2& G, uint2& T, TravCount& tc)
+                               float bestT_in, uint2& G, uint2& T, TravCount& tc, const uint2* __restrict__ nodeMasks = nullptr,
+                               unsigned cullMask = 0xffu)
 {
   const float4* __restrict__ np = nodes + (size_t)child * VKRT_WNODE_QUADS;  // one 64-bit address, immediate offsets
   const float4 q0 = np[0], q1 = np[1], q2 = np[2], q3 = np[3], q4 = np[4];
+  uint2 slotMasks = make_uint2(0xffffffffu, 0xffffffffu);
+  if(CULL)
+    slotMasks = nodeMasks[child];
   if(COUNT)
   {
     tc.nodes++;
@@ -136,7 +142,10 @@ VKRT_DEV void w8_test_children(const float4* __restrict__ nodes, unsigned child,
       const float tn = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, tmin));
       const float tf = fminf(fminf(tfx, tfy), fminf(tfz, bestT * VKRT_BOX_PAD_REL2));
       const unsigned piece = w8_piece(bitIndex4, bits4, k);
-      hitmask |= (tn <= tf) ? piece : 0u;
+      if(CULL)
+        hitmask |= (tn <= tf && (((w == 0 ? slotMasks.x : slotMasks.y) >> (8 * k)) & cullMask) != 0u) ? piece : 0u;
+      else
+        hitmask |= (tn <= tf) ? piece : 0u;
     }
   }
 #undef VKRT_WN_PLANE
@@ -178,7 +187,8 @@ VKRT_DEV bool w8_iterate(const DevScene& sc, W8State<TM>& S, float tmin, uint2* 
       VKRT_TRAV_FAULT(sc);
       return false;
     }
-    w8_test_children<COUNT>(nodes, child, o, id, octinv * 0x01010101u, px, py, pz, tmin, S.bestT, G, T, tc);
+    w8_test_children<COUNT, (TM & VKRT_TM_FILTER) != 0>(nodes, child, o, id, octinv * 0x01010101u, px, py, pz, tmin, S.bestT, G, T, tc,
+                                                        query_node_masks<TM>(sc), query_cull_mask<TM>(sc));
   }
   // triangles of this node that the ray's boxes touched
   while(T.y != 0u)
@@ -201,13 +211,14 @@ VKRT_DEV bool w8_iterate(const DevScene& sc, W8State<TM>& S, float tmin, uint2* 
       if((int)lane_id() == __ffsll((long long)__ballot(1)) - 1) tc.waveTriSteps++;
     }
     float t, u, v;
-    if(S.tr.hit(o, d, a, b, c, t, u, v))
+    bool ccw;
+    if(S.tr.hit(o, d, a, b, c, t, u, v, ccw))
     {
       if(t > tmin)
       {
         if(ANYHIT)
         {
-          if(t < S.tmax && !anyhit_ignores<TM>(sc, s, c.y, S.raySeed))
+          if(t < S.tmax && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, S.raySeed))
           {
             S.bestSlot = (int)s;
             S.bestT = t;
@@ -217,7 +228,7 @@ VKRT_DEV bool w8_iterate(const DevScene& sc, W8State<TM>& S, float tmin, uint2* 
         else
         {
           const int gid = tri_gid<TM>(c.y);
-          if((t < S.bestT || (t == S.bestT && gid < S.bestGid)) && !anyhit_ignores<TM>(sc, s, c.y, S.raySeed))
+          if((t < S.bestT || (t == S.bestT && gid < S.bestGid)) && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, S.raySeed))
           {
             S.bestT = t; S.bestU = u; S.bestV = v; S.bestSlot = (int)s; S.bestGid = gid;
           }
@@ -281,11 +292,12 @@ VKRT_DEV void traverse_wide8_postpone(const DevScene& sc, f3 o, f3 d, float tmin
       if((int)lane_id() == __ffsll((long long)__ballot(1)) - 1) tc.waveTriSteps++;
     }
     float t, u, v;
-    if(tr.hit(o, d, a, b, c, t, u, v) && t > tmin)
+    bool ccw;
+    if(tr.hit(o, d, a, b, c, t, u, v, ccw) && t > tmin)
     {
       if(ANYHIT)
       {
-        if(t < tmax && !anyhit_ignores<TM>(sc, s, c.y, raySeed))
+        if(t < tmax && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, raySeed))
         {
           bestSlot = (int)s; bestT = t;
           return true;
@@ -294,7 +306,7 @@ VKRT_DEV void traverse_wide8_postpone(const DevScene& sc, f3 o, f3 d, float tmin
       else
       {
         const int gid = tri_gid<TM>(c.y);
-        if((t < bestT || (t == bestT && gid < bestGid)) && !anyhit_ignores<TM>(sc, s, c.y, raySeed))
+        if((t < bestT || (t == bestT && gid < bestGid)) && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, raySeed))
         {
           bestT = t; bestU = u; bestV = v; bestSlot = (int)s; bestGid = gid;
         }
@@ -341,7 +353,8 @@ VKRT_DEV void traverse_wide8_postpone(const DevScene& sc, f3 o, f3 d, float tmin
           VKRT_TRAV_FAULT(sc);
       }
       uint2 Tn;
-      w8_test_children<COUNT>(nodes, child, o, id, octinv * 0x01010101u, px, py, pz, tmin, bestT, G, Tn, tc);
+      w8_test_children<COUNT, (TM & VKRT_TM_FILTER) != 0>(nodes, child, o, id, octinv * 0x01010101u, px, py, pz, tmin, bestT, G, Tn, tc,
+                                                          query_node_masks<TM>(sc), query_cull_mask<TM>(sc));
       if(Tn.y != 0u)
       {
         if(T.y != 0u)

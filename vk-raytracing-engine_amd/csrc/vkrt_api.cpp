@@ -96,6 +96,10 @@ struct vkrt_scene
   bool stale = false;      // node transforms changed since the tree was built or refitted: no trace until the next refit or build
   bool refitted = false;   // the tree has been refitted since its build: vkrt_accel_get_info reads the refit's SAH cost from the device
   vkrt::RefitScratch refit;  // level lists + exact node boxes of the current build (allocated at its first refit)
+  // ray-query visibility (vkrt_scene_set_instance_visibility): host copy per node, and which masks occur (bit m of masksPresent[m >> 6])
+  std::vector<vkrt_instance_visibility> vis;
+  uint64_t masksPresent[4] = {0, 0, 0, 0};
+  vkrt::DevBuf nodeMasks;  // wide8: the node-mask table of the current tree (8 B per node), allocated and computed with it
 };
 
 namespace {
@@ -249,15 +253,19 @@ void optionsFromEnvironment(vkrt_scene* s)
 void freeAccel(vkrt_scene* s)
 {
   s->accel = vkrt::TreeBuffers{};
+  s->nodeMasks = vkrt::DevBuf{};
   s->built = false;
   s->refit = vkrt::RefitScratch{};
   s->refitted = false;
   s->stale = false;
 }
 
-// gl_ObjectToWorldEXT / gl_WorldToObjectEXT of one node (rchit:72-76): the same code at vkrt_scene_create and vkrt_scene_update_nodes,
-// so that a moved scene's records are bit for bit those of a scene created with the moved nodes
-void makeInstance(const vkrt_node& node, DevInstance& in)
+constexpr vkrt_instance_visibility kDefaultVisibility = {0xFF, VKRT_INSTANCE_FACING_CULL_DISABLE, 0};  // the reference's TLAS (hello_vulkan.cpp:1040-1041)
+
+// gl_ObjectToWorldEXT / gl_WorldToObjectEXT of one node (rchit:72-76) and its ray-query visibility: the same code at vkrt_scene_create,
+// vkrt_scene_update_nodes and vkrt_scene_set_instance_visibility, so that a moved scene's records are bit for bit those of a scene
+// created with the moved nodes
+void makeInstance(const vkrt_node& node, const vkrt_instance_visibility& vis, DevInstance& in)
 {
   memset(&in, 0, sizeof in);
   for(int r = 0; r < 3; r++)
@@ -265,6 +273,37 @@ void makeInstance(const vkrt_node& node, DevInstance& in)
       in.o2w[r * 4 + c] = node.worldMatrix[c * 4 + r];
   vkrt::invert3x3_rows(in.o2w, in.w2o);
   in.primMesh = node.primMesh;
+  // facing: a mirroring transform turns the world-space winding around (traverse.h query_rejects); decided in double on the matrix
+  const float* m = in.o2w;
+  const double det = (double)m[0] * ((double)m[5] * m[10] - (double)m[6] * m[9]) - (double)m[1] * ((double)m[4] * m[10] - (double)m[6] * m[8]) +
+                     (double)m[2] * ((double)m[4] * m[9] - (double)m[5] * m[8]);
+  in.vis = (uint32_t)vis.mask | ((uint32_t)vis.flags << 8) | (det < 0.0 ? VKRT_VIS_MIRRORED : 0u);
+}
+
+void noteMasks(vkrt_scene* s)
+{
+  memset(s->masksPresent, 0, sizeof s->masksPresent);
+  for(const vkrt_instance_visibility& v : s->vis)
+    s->masksPresent[v.mask >> 6] |= 1ull << (v.mask & 63u);
+}
+
+// does every node's mask meet cullMask?  (then a query with that mask and no facing flag walks exactly what vkrt_intersect walks)
+bool everyMaskMeets(const vkrt_scene* s, uint32_t cullMask)
+{
+  for(uint32_t m = 0; m < 256; m++)
+    if(((s->masksPresent[m >> 6] >> (m & 63u)) & 1ull) && (m & cullMask) == 0u)
+      return false;
+  return true;
+}
+
+// the node-mask table of the installed wide8 tree from the current instance records, enqueued on `stream` (levels + 1 passes: no read-back)
+int computeNodeMasks(vkrt_scene* s, hipStream_t stream)
+{
+  if(s->dev.layout != 1u || !s->nodeMasks.get())
+    return VKRT_OK;
+  const uint32_t nodes = (uint32_t)(s->info.node_bytes / VKRT_WNODE_BYTES);
+  HIP_TRY(vkrt_launch_node_masks(s->dev, nodes, (uint32_t)s->nodes.size(), s->info.max_depth + 1u, s->nodeMasks.get<uint2>(), stream));
+  return VKRT_OK;
 }
 
 int setDevice(const vkrt_scene* s)
@@ -379,8 +418,10 @@ int launchParams(const vkrt_scene* s, const PushConstantRay* pc, const GlobalUni
 }
 
 static_assert(sizeof(vkrt_ray) == 32 && sizeof(vkrt_hit) == 32, "k_query reads and writes 2 x 16 B per ray");
-// vkrt_intersect / vkrt_occluded: one k_query launch per 2^30 rays on the caller's stream (query.hip); out = hits or occluded flags
-int rayQuery(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, uint32_t seed, void* out, bool anyHit, void* hip_stream, const char* who)
+static_assert(sizeof(vkrt_instance_visibility) == 4 && sizeof(vkrt_query_opts) == 16, "include/vkrt.h");
+// vkrt_intersect / vkrt_occluded (and the _ex pair, whose options are checked by the caller): one k_query launch per 2^30 rays on the
+// caller's stream (query.hip); out = hits or occluded flags
+int rayQuery(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, const vkrt_query_opts& q, void* out, bool anyHit, void* hip_stream, const char* who)
 {
   if(!s)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
@@ -395,8 +436,44 @@ int rayQuery(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, uint32_t seed, voi
     return rc;
   if((rc = setDevice(s)) != VKRT_OK)
     return rc;
-  HIP_TRY(vkrt_launch_query(s->dev, (const float4*)rays, n, seed, anyHit ? nullptr : (float4*)out, anyHit ? (int*)out : nullptr,
+  DevQueryScene qs;
+  static_cast<DevScene&>(qs) = s->dev;
+  qs.nodeMasks = s->nodeMasks.get<const uint2>();
+  qs.cullMask = q.cull_mask;
+  qs.rayFlags = q.ray_flags & (VKRT_RAY_CULL_BACK_FACING | VKRT_RAY_CULL_FRONT_FACING);
+  // the filtering walk only where it can change a result: a facing flag, or a mask that some node's mask misses
+  const bool filter = qs.rayFlags != 0u || !everyMaskMeets(s, q.cull_mask);
+  const bool opaque = (q.ray_flags & VKRT_RAY_OPAQUE) != 0u;
+  HIP_TRY(vkrt_launch_query(qs, (const float4*)rays, n, q.anyhit_seed, filter, opaque, anyHit ? nullptr : (float4*)out, anyHit ? (int*)out : nullptr,
                             (hipStream_t)hip_stream));
+  return VKRT_OK;
+}
+
+// the options of vkrt_intersect_ex / vkrt_occluded_ex (include/vkrt.h)
+int checkQueryOpts(const vkrt_query_opts* q, const char* who)
+{
+  if(!q)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: opts is NULL", who);
+  if(q->struct_size < sizeof(vkrt_query_opts))
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vkrt_query_opts.struct_size %u < %zu (ABI mismatch)", who, q->struct_size, sizeof(vkrt_query_opts));
+  const uint32_t known = VKRT_RAY_OPAQUE | VKRT_RAY_CULL_BACK_FACING | VKRT_RAY_CULL_FRONT_FACING;
+  if(q->ray_flags & ~known)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: ray_flags 0x%x has bits outside OPAQUE | CULL_BACK_FACING | CULL_FRONT_FACING", who, q->ray_flags);
+  if((q->ray_flags & VKRT_RAY_CULL_BACK_FACING) && (q->ray_flags & VKRT_RAY_CULL_FRONT_FACING))
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: ray_flags: CULL_BACK_FACING and CULL_FRONT_FACING together", who);
+  if(q->cull_mask > 0xFFu)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: cull_mask 0x%x > 0xFF", who, q->cull_mask);
+  return VKRT_OK;
+}
+
+// a node range [first, first + count) with its array: the checks vkrt_scene_set/get_instance_visibility share after their own
+int checkVisibilityRange(const vkrt_scene* s, uint32_t first, uint32_t count, const char* who)
+{
+  if(!s)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
+  if((uint64_t)first + count > s->nodes.size())
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: nodes [%u, %llu) outside the scene's %zu nodes", who, first, (unsigned long long)first + count,
+                s->nodes.size());
   return VKRT_OK;
 }
 
@@ -470,9 +547,11 @@ int vkrt_scene_create(const vkrt_scene_desc* d, int device, vkrt_scene** out)
   }
   if((rc = upload(s, d->lights, (size_t)d->light_count, &D.lights)) != VKRT_OK) return bail(rc);
   // instances: object->world rows + inverse (gl_ObjectToWorldEXT / gl_WorldToObjectEXT, rchit:72-76)
+  s->vis.assign(d->node_count, kDefaultVisibility);
+  noteMasks(s);
   std::vector<DevInstance> inst(d->node_count);
   for(uint32_t n = 0; n < d->node_count; n++)
-    makeInstance(d->nodes[n], inst[n]);
+    makeInstance(d->nodes[n], s->vis[n], inst[n]);
   if((rc = upload(s, inst.data(), inst.size(), &D.instances)) != VKRT_OK) return bail(rc);
   // textures: RGBA8 pool + table + sRGB decode table
   float lut[512];
@@ -976,6 +1055,12 @@ int accelBuildOnce(vkrt_scene* s, uint32_t flags, int splitBudget, hipStream_t s
   sceneBounds(s);
   if((rc = traversalSettings(s)) != VKRT_OK)
     return rc;
+  if(s->dev.layout == 1u)
+  {  // the node-mask table of the ray-query filter lives and dies with the tree
+    HIP_TRY(s->nodeMasks.alloc(std::max<size_t>(s->info.node_bytes / VKRT_WNODE_BYTES * 8, 16)));
+    if((rc = computeNodeMasks(s, stream)) != VKRT_OK)
+      return rc;
+  }
   s->info.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   s->built = true;
   return VKRT_OK;
@@ -1058,7 +1143,7 @@ int vkrt_scene_update_nodes(vkrt_scene* s, uint32_t first, uint32_t count, const
     return rc;
   std::vector<DevInstance> inst(count);
   for(uint32_t i = 0; i < count; i++)
-    makeInstance(nodes[i], inst[i]);
+    makeInstance(nodes[i], s->vis[(size_t)first + i], inst[i]);  // (the visibility word stays; the mirrored bit follows the new matrix)
   // Stream-ordered: the records travel as kernel arguments of launches on hip_stream, after whatever the caller enqueued there before
   // (a trace that still reads the old transforms) and before whatever comes after (the refit, the next trace).  The trace entry points'
   // internal lane streams fork from and join to the caller's stream, so ordering on it is all that is needed.
@@ -1102,12 +1187,70 @@ int vkrt_accel_refit(vkrt_scene* s, void* hip_stream)
 
 int vkrt_intersect(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, uint32_t anyhit_seed, vkrt_hit* hits, void* hip_stream)
 {
-  return rayQuery(s, rays, n, anyhit_seed, hits, false, hip_stream, "vkrt_intersect");
+  const vkrt_query_opts q = {sizeof(vkrt_query_opts), 0u, 0xFFu, anyhit_seed};
+  return rayQuery(s, rays, n, q, hits, false, hip_stream, "vkrt_intersect");
 }
 
 int vkrt_occluded(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, uint32_t anyhit_seed, int32_t* occluded, void* hip_stream)
 {
-  return rayQuery(s, rays, n, anyhit_seed, occluded, true, hip_stream, "vkrt_occluded");
+  const vkrt_query_opts q = {sizeof(vkrt_query_opts), 0u, 0xFFu, anyhit_seed};
+  return rayQuery(s, rays, n, q, occluded, true, hip_stream, "vkrt_occluded");
+}
+
+int vkrt_intersect_ex(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, const vkrt_query_opts* opts, vkrt_hit* hits, void* hip_stream)
+{
+  const int rc = checkQueryOpts(opts, "vkrt_intersect_ex");
+  return rc != VKRT_OK ? rc : rayQuery(s, rays, n, *opts, hits, false, hip_stream, "vkrt_intersect_ex");
+}
+
+int vkrt_occluded_ex(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, const vkrt_query_opts* opts, int32_t* occluded, void* hip_stream)
+{
+  const int rc = checkQueryOpts(opts, "vkrt_occluded_ex");
+  return rc != VKRT_OK ? rc : rayQuery(s, rays, n, *opts, occluded, true, hip_stream, "vkrt_occluded_ex");
+}
+
+int vkrt_scene_set_instance_visibility(vkrt_scene* s, uint32_t first, uint32_t count, const vkrt_instance_visibility* vis, void* hip_stream)
+{
+  const char* who = "vkrt_scene_set_instance_visibility";
+  if(count && !vis)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vis is NULL", who);
+  for(uint32_t i = 0; i < count; i++)
+  {
+    if(vis[i].mask == 0)
+      return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: entry %u: mask 0 (hide an instance from every ray with a zero-scale transform)", who, i);
+    if(vis[i].flags & ~(VKRT_INSTANCE_FACING_CULL_DISABLE | VKRT_INSTANCE_FLIP_FACING))
+      return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: entry %u: unknown flag bits 0x%x", who, i, (unsigned)vis[i].flags);
+    if(vis[i].reserved != 0)
+      return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: entry %u: reserved is not 0", who, i);
+  }
+  int rc = checkVisibilityRange(s, first, count, who);
+  if(rc != VKRT_OK || count == 0)
+    return rc;
+  if((rc = setDevice(s)) != VKRT_OK)
+    return rc;
+  // the whole records again, made from the host copies (bit for bit what the device holds, with the new visibility word) and sent as
+  // kernel arguments on hip_stream like vkrt_scene_update_nodes does: stream-ordered, nothing staged, no synchronisation
+  std::vector<DevInstance> inst(count);
+  for(uint32_t i = 0; i < count; i++)
+    makeInstance(s->nodes[(size_t)first + i], vis[i], inst[i]);
+  hipStream_t stream = (hipStream_t)hip_stream;
+  HIP_TRY(vkrt::upload_instances(const_cast<DevInstance*>(s->dev.instances), first, count, inst.data(), stream));
+  std::copy(vis, vis + count, s->vis.begin() + first);
+  noteMasks(s);
+  // the table follows the masks on the same stream (a stale tree too: records and topology are those of its build or last refit)
+  return s->built ? computeNodeMasks(s, stream) : VKRT_OK;
+}
+
+int vkrt_scene_get_instance_visibility(const vkrt_scene* s, uint32_t first, uint32_t count, vkrt_instance_visibility* out)
+{
+  const char* who = "vkrt_scene_get_instance_visibility";
+  if(count && !out)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: out is NULL", who);
+  const int rc = checkVisibilityRange(s, first, count, who);
+  if(rc != VKRT_OK)
+    return rc;
+  std::copy(s->vis.begin() + first, s->vis.begin() + first + count, out);
+  return VKRT_OK;
 }
 
 uint32_t vkrt_shard_rows(const vkrt_shard* sh)
@@ -1494,6 +1637,27 @@ int vkrt_debug_read_accel(vkrt_scene* s, void* nodes, uint64_t nodes_bytes, void
   if(tris_bytes)
     HIP_TRY(hipMemcpy(tris, s->dev.tris, tris_bytes, hipMemcpyDeviceToHost));
   *root_ref = s->dev.rootRef;
+  return VKRT_OK;
+}
+
+int vkrt_debug_read_node_masks(vkrt_scene* s, void* out, uint64_t bytes)
+{
+  if(!s || !out)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "NULL argument");
+  if(!s->built)
+    return fail(VKRT_ERR_NOT_BUILT, "vkrt_debug_read_node_masks before vkrt_accel_build");
+  if(s->dev.layout != 1u)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_debug_read_node_masks: a BVH2 tree has no node-mask table");
+  const uint64_t want = s->info.node_bytes / VKRT_WNODE_BYTES * 8;
+  if(bytes != want)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_debug_read_node_masks: a buffer of %llu bytes for a table of %llu", (unsigned long long)bytes,
+                (unsigned long long)want);
+  const int rc = setDevice(s);
+  if(rc != VKRT_OK)
+    return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  if(bytes)
+    HIP_TRY(hipMemcpy(out, s->nodeMasks.get(), bytes, hipMemcpyDeviceToHost));
   return VKRT_OK;
 }
 

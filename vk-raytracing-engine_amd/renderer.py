@@ -136,6 +136,46 @@ class Renderer:
         st = C.c_void_p(stream.cuda_stream) if stream is not None else None
         _check(self.lib.vkrt_scene_update_nodes(self._h, first, n, arr, st), "vkrt_scene_update_nodes")
 
+    def set_instance_visibility(self, first, masks, flags=None, stream=None):
+        """vkrt_scene_set_instance_visibility for nodes [first, first + n): masks = n ints in 1..255 (the instance masks of the
+        ray-query cull mask); flags = n ints of VKRT_INSTANCE_* bits, or None to keep the nodes' current flags.  Enqueued on `stream`
+        (a torch stream; None = the default stream); queries enqueued after it on that stream see the new values.  Bad values and
+        ranges are refused here, before the call."""
+        m = np.asarray(masks).reshape(-1)
+        first, n = int(first), m.shape[0]
+        nodes = self._prim_mesh.shape[0]
+        if first < 0 or first + n > nodes:
+            raise VkrtError(f"set_instance_visibility: nodes [{first}, {first + n}) outside the scene's {nodes} nodes")
+        if m.dtype.kind not in "iu" or np.any(m < 1) or np.any(m > 255):
+            raise VkrtError("set_instance_visibility: masks must be integers in 1..255 (hide an instance with a zero-scale transform)")
+        if flags is None:
+            f = self.instance_visibility()[1][first:first + n]
+        else:
+            f = np.asarray(flags).reshape(-1)
+            known = abi.VKRT_INSTANCE_FACING_CULL_DISABLE | abi.VKRT_INSTANCE_FLIP_FACING
+            if f.shape[0] != n or f.dtype.kind not in "iu" or np.any(f.astype(np.int64) & ~known) or np.any(f < 0):
+                raise VkrtError(f"set_instance_visibility: flags must be {n} integers of VKRT_INSTANCE_* bits")
+        arr = (abi.InstanceVisibility * max(n, 1))()
+        for i in range(n):
+            arr[i].mask, arr[i].flags, arr[i].reserved = int(m[i]), int(f[i]), 0
+        st = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        _check(self.lib.vkrt_scene_set_instance_visibility(self._h, first, n, arr, st), "vkrt_scene_set_instance_visibility")
+
+    def instance_visibility(self):
+        """(masks, flags): uint8 [nodes] each, the host copy of every node's visibility (vkrt_scene_get_instance_visibility)."""
+        n = self._prim_mesh.shape[0]
+        arr = (abi.InstanceVisibility * max(n, 1))()
+        _check(self.lib.vkrt_scene_get_instance_visibility(self._h, 0, n, arr), "vkrt_scene_get_instance_visibility")
+        return (np.array([arr[i].mask for i in range(n)], np.uint8), np.array([arr[i].flags for i in range(n)], np.uint8))
+
+    def read_node_masks(self):
+        """The wide8 tree's node-mask table (vkrt_debug_read_node_masks): uint8 [nodes, 8], byte s = the OR of the instance masks
+        under child slot s."""
+        nb = int(self.accel_info()["node_bytes"]) // 80 * 8
+        out = np.zeros(max(nb, 8), np.uint8)
+        _check(self.lib.vkrt_debug_read_node_masks(self._h, out.ctypes.data, nb), "vkrt_debug_read_node_masks")
+        return out[:nb].reshape(-1, 8)
+
     def refit(self, stream=None):
         """vkrt_accel_refit: the built tree follows the current node transforms (same topology, new boxes), enqueued on `stream`."""
         st = C.c_void_p(stream.cuda_stream) if stream is not None else None
@@ -327,36 +367,64 @@ class Renderer:
             raise VkrtError(f"{what}: out must be contiguous and {align}-byte aligned")
         return out
 
-    def intersect(self, rays, seed=0, out=None, stream=None):
+    @staticmethod
+    def _query_opts(cull_mask, ray_flags, seed, what):
+        """None for the defaults (the call of vkrt_intersect / vkrt_occluded), else the vkrt_query_opts of the _ex call; refuses what
+        the library would refuse."""
+        if isinstance(cull_mask, bool) or not isinstance(cull_mask, (int, np.integer)) or not 0 <= int(cull_mask) <= 0xFF:
+            raise VkrtError(f"{what}: cull_mask must be an integer in 0..255, got {cull_mask!r}")
+        known = abi.VKRT_RAY_OPAQUE | abi.VKRT_RAY_CULL_BACK_FACING | abi.VKRT_RAY_CULL_FRONT_FACING
+        if isinstance(ray_flags, bool) or not isinstance(ray_flags, (int, np.integer)) or int(ray_flags) < 0 or int(ray_flags) & ~known:
+            raise VkrtError(f"{what}: ray_flags must combine VKRT_RAY_OPAQUE / CULL_BACK_FACING / CULL_FRONT_FACING, got {ray_flags!r}")
+        both = abi.VKRT_RAY_CULL_BACK_FACING | abi.VKRT_RAY_CULL_FRONT_FACING
+        if int(ray_flags) & both == both:
+            raise VkrtError(f"{what}: ray_flags: CULL_BACK_FACING and CULL_FRONT_FACING together")
+        if int(cull_mask) == 0xFF and int(ray_flags) == 0:
+            return None
+        return abi.QueryOpts(C.sizeof(abi.QueryOpts), int(ray_flags), int(cull_mask), int(seed) & 0xFFFFFFFF)
+
+    def intersect(self, rays, seed=0, out=None, stream=None, cull_mask=0xFF, ray_flags=0):
         """Closest hit of every ray (vkrt_intersect), enqueued on `stream` (default: the current stream of the scene's device).
         rays: float32 [N, 8] from pack_rays; seed: the any-hit stage's payload seed (VKRT_OPT_ANYHIT_DISSOLVE); out: an optional
-        float32 / int32 [N, 8] buffer to write into.  Returns a RayHits of views of that buffer."""
+        float32 / int32 [N, 8] buffer to write into.  cull_mask (0..255) / ray_flags (VKRT_RAY_*): the options of vkrt_intersect_ex,
+        against the masks and flags of set_instance_visibility.  Returns a RayHits of views of that buffer."""
         import torch
 
         n = self._query_args(rays, "intersect")
+        opts = self._query_opts(cull_mask, ray_flags, seed, "intersect")
         if stream is None:
             stream = torch.cuda.current_stream(rays.device)
         if out is None:
             with torch.cuda.stream(stream):  # (allocated on the stream that writes it)
                 out = torch.empty((n, 8), dtype=torch.float32, device=rays.device)
         self._query_out(out, (n, 8), "intersect", 16)
-        _check(self.lib.vkrt_intersect(self._h, C.c_void_p(rays.data_ptr()), n, int(seed) & 0xFFFFFFFF, C.c_void_p(out.data_ptr()),
-                                       C.c_void_p(stream.cuda_stream)), "vkrt_intersect")
+        if opts is None:
+            _check(self.lib.vkrt_intersect(self._h, C.c_void_p(rays.data_ptr()), n, int(seed) & 0xFFFFFFFF, C.c_void_p(out.data_ptr()),
+                                           C.c_void_p(stream.cuda_stream)), "vkrt_intersect")
+        else:
+            _check(self.lib.vkrt_intersect_ex(self._h, C.c_void_p(rays.data_ptr()), n, C.byref(opts), C.c_void_p(out.data_ptr()),
+                                              C.c_void_p(stream.cuda_stream)), "vkrt_intersect_ex")
         return RayHits(out)
 
-    def occluded(self, rays, seed=0, out=None, stream=None):
-        """1 where some hit lies in (tmin, tmax), else 0 (vkrt_occluded): int32 [N] (or `out`), enqueued like intersect()."""
+    def occluded(self, rays, seed=0, out=None, stream=None, cull_mask=0xFF, ray_flags=0):
+        """1 where some hit lies in (tmin, tmax), else 0 (vkrt_occluded): int32 [N] (or `out`), enqueued like intersect(), with the
+        same cull_mask / ray_flags options."""
         import torch
 
         n = self._query_args(rays, "occluded")
+        opts = self._query_opts(cull_mask, ray_flags, seed, "occluded")
         if stream is None:
             stream = torch.cuda.current_stream(rays.device)
         if out is None:
             with torch.cuda.stream(stream):
                 out = torch.empty((n,), dtype=torch.int32, device=rays.device)
         self._query_out(out, (n,), "occluded", 4)
-        _check(self.lib.vkrt_occluded(self._h, C.c_void_p(rays.data_ptr()), n, int(seed) & 0xFFFFFFFF, C.c_void_p(out.data_ptr()),
-                                      C.c_void_p(stream.cuda_stream)), "vkrt_occluded")
+        if opts is None:
+            _check(self.lib.vkrt_occluded(self._h, C.c_void_p(rays.data_ptr()), n, int(seed) & 0xFFFFFFFF, C.c_void_p(out.data_ptr()),
+                                          C.c_void_p(stream.cuda_stream)), "vkrt_occluded")
+        else:
+            _check(self.lib.vkrt_occluded_ex(self._h, C.c_void_p(rays.data_ptr()), n, C.byref(opts), C.c_void_p(out.data_ptr()),
+                                             C.c_void_p(stream.cuda_stream)), "vkrt_occluded_ex")
         return out.view(torch.int32)
 
     def trace_rays(self, origins, directions, tmin=0.001, tmax=10000.0, any_hit=False):
