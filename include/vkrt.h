@@ -281,8 +281,8 @@ int vkrt_accel_get_info(const vkrt_scene* scene, vkrt_accel_info* out);
 
 /* ---- moving instances (replaces the update path of the TLAS build: VK_BUILD_ACCELERATION_STRUCTURE_ALLOW_UPDATE_BIT_KHR at
  *      createTopLevelAsGltf :1031-1047, then vkCmdBuildAccelerationStructuresKHR with VK_BUILD_ACCELERATION_STRUCTURE_MODE_UPDATE_KHR).
- *      Rigid motion of whole instances only: no vertex deformation, no topology change.  These entry points came after ABI version 4
- *      without changing it or any struct: detect them by symbol. ---------------------------------------------------------------- */
+ *      Rigid motion of whole instances here, vertex deformation below (vkrt_scene_update_vertices); no topology change.  These entry
+ *      points came after ABI version 4 without changing it or any struct: detect them by symbol. -------------------------------- */
 /* Replace the transforms of nodes [first, first+count) (vkrt_node as at vkrt_scene_create; primMesh must equal the node's
  * existing primMesh).  Enqueued on hip_stream; the array is copied before return.  After this call the scene's tree is stale:
  * trace / G-buffer / hybrid entry points (and the vkrt_debug_* tree hooks) return VKRT_ERR_NOT_BUILT until vkrt_accel_refit or
@@ -290,13 +290,59 @@ int vkrt_accel_get_info(const vkrt_scene* scene, vkrt_accel_info* out);
  * NULL scene give VKRT_ERR_INVALID_ARGUMENT and change nothing; what vkrt_scene_create accepts (a zero scale that hides an
  * instance, a mirroring matrix) is accepted.  A later vkrt_accel_build builds the moved scene. */
 int vkrt_scene_update_nodes(vkrt_scene* scene, uint32_t first, uint32_t count, const vkrt_node* nodes, void* hip_stream);
-/* Refit the built tree to the scene's current node transforms: same topology, same slots, new boxes and triangle records.
+/* Refit the built tree to the scene's current node transforms and vertices: same topology, same slots, new boxes and triangle records.
  * Enqueued on hip_stream.  No host synchronisation and no allocation, except on the first refit of a build.  Everything the build
  * decided stays (layout, record format, split references, any-hit order, traversal stack); options changed since the build take effect
  * at the next vkrt_accel_build.  The image stays a property of the triangle set: a refitted tree traces exactly the pixels and ray
  * counts of a fresh build of the moved scene; only its speed depends on how far the instances moved (vkrt_accel_info.sah_cost).
  * VKRT_ERR_NOT_BUILT before any vkrt_accel_build. */
 int vkrt_accel_refit(vkrt_scene* scene, void* hip_stream);
+
+/* ---- deforming meshes (replaces the update path of the BLAS build: VK_BUILD_ACCELERATION_STRUCTURE_ALLOW_UPDATE_BIT_KHR at
+ *      createBottomLevelASGltf :1001-1011, then vkCmdBuildAccelerationStructuresKHR with VK_BUILD_ACCELERATION_STRUCTURE_MODE_UPDATE_KHR
+ *      on a new vertex buffer -- a skinned character, a cloth, a simulated surface).  This entry point came after ABI version 4 without
+ *      changing it or any existing struct: detect it by symbol. ----------------------------------------------------------------------
+ * New attributes for vertices [first, first+count) of the scene's shared vertex arrays (vkrt_scene_desc: an absolute vertex index, i.e.
+ * a primitive-mesh's vertexOffset already added).  Each of the four arrays is laid out as at vkrt_scene_create with element 0 = vertex
+ * `first`; a NULL array keeps that attribute of every vertex as it is.  Deformation only: index buffers, primitive-meshes, nodes and
+ * materials are untouched, so a mesh that several nodes instance deforms in all of them.
+ * Ordering: enqueued on hip_stream (NULL = default stream) like vkrt_scene_update_nodes -- after what was enqueued there before (a trace
+ * that still reads the old vertices), before what comes after (the refit, the next trace).
+ * VKRT_MEMORY_DEVICE: the arrays are device memory on the scene's device (what the caller's skinning or simulation kernel has just
+ *   written on that stream), float-aligned.  The call neither allocates nor synchronises with the host and returns after the enqueue;
+ *   the arrays must stay valid until the stream has passed the call.  The values are not inspected: a non-finite position is the
+ *   caller's error.  It cannot make any kernel read or write out of bounds (indices do not change), and a later correct update + refit
+ *   repairs the scene completely; what rays return in between is unspecified.
+ * VKRT_MEMORY_HOST: the arrays may be freed or reused on return, as at vkrt_scene_create.  Positions are checked as there (finite)
+ *   before anything changes.  The arrays are staged through a device buffer the scene owns -- allocated (hipMalloc) by the first host
+ *   update and again by one larger than every earlier one, released by vkrt_scene_destroy -- and the call waits for hip_stream before
+ *   it returns.  A caller that must not wait uses VKRT_MEMORY_DEVICE.
+ * Stale tree: with positions given and a built tree, the tree is stale exactly as after vkrt_scene_update_nodes -- trace, G-buffer,
+ *   hybrid, ray-query and vkrt_debug_* tree hooks return VKRT_ERR_NOT_BUILT until vkrt_accel_refit or vkrt_accel_build; one refit serves
+ *   any number of vertex and node updates before it.  An update of normals, tangents or texture coordinates alone does not make the
+ *   tree stale: the next trace shades with them.
+ * vkrt_accel_refit after it: same topology, slots, split references, node-mask table and dissolve flags; new records and boxes;
+ *   vkrt_accel_info.sah_cost is the deformed tree's.  The refitted tree gives bit for bit the pixels, ray counts and hits of a fresh
+ *   scene created from the deformed arrays and built with the same options.  The scene bounds and the large-triangle flag of the
+ *   any-hit order heuristic stay as built (they cannot change a pixel).
+ * vkrt_accel_build after it builds the deformed scene with every builder.  The library keeps a host copy of the positions for the host
+ *   builder and the scene bounds: a host update keeps it current, and after a device update the next vkrt_accel_build downloads the
+ *   positions first (a build synchronises anyway).
+ * Refused with VKRT_ERR_INVALID_ARGUMENT, changing nothing, in this order: a NULL update; struct_size < sizeof(vkrt_vertex_update); a
+ * memory value that is neither of the two; a NULL scene; a range outside the scene's vertices; (host memory) a non-finite position.
+ * Then count == 0 or all four arrays NULL: VKRT_OK, nothing is enqueued, the tree does not become stale.  Then, without a device:
+ * VKRT_ERR_NO_DEVICE. */
+enum vkrt_memory { VKRT_MEMORY_HOST = 0, VKRT_MEMORY_DEVICE = 1 };
+typedef struct vkrt_vertex_update {
+  uint32_t struct_size;     /* sizeof(vkrt_vertex_update) */
+  uint32_t first, count;    /* vertices [first, first+count) */
+  uint32_t memory;          /* vkrt_memory: where the four arrays below live */
+  const float* positions;   /* vec3[count] or NULL = keep */
+  const float* normals;     /* vec3[count] or NULL = keep */
+  const float* tangents;    /* vec4[count] or NULL = keep */
+  const float* texcoords0;  /* vec2[count] or NULL = keep */
+} vkrt_vertex_update;
+int vkrt_scene_update_vertices(vkrt_scene* scene, const vkrt_vertex_update* update, void* hip_stream);
 
 /* ---- ray queries (replaces traceRayEXT on rays of the caller's own, raytrace.rgen:64-97 / VK_KHR_ray_query: a closest-hit and an
  *      occlusion query per ray of a device array).  These entry points came after ABI version 4 without changing it or any
@@ -313,7 +359,7 @@ int vkrt_accel_refit(vkrt_scene* scene, void* hip_stream);
  * payload seed of every ray (0 = what vkrt_debug_trace_rays and the oracle use).  The scheduling options (VKRT_OPT_WF_SHARE,
  * VKRT_OPT_WF_SHARE_FLAGS, VKRT_OPT_TRI_THRESHOLD) apply too; none of them changes a result.
  * Errors, in this order: a NULL scene, or (n > 0) a NULL or misaligned pointer: VKRT_ERR_INVALID_ARGUMENT; n == 0: VKRT_OK, nothing is
- * enqueued; no tree, or a stale one after vkrt_scene_update_nodes: VKRT_ERR_NOT_BUILT; without a device: VKRT_ERR_NO_DEVICE.
+ * enqueued; no tree, or a stale one after vkrt_scene_update_nodes / vkrt_scene_update_vertices: VKRT_ERR_NOT_BUILT; without a device: VKRT_ERR_NO_DEVICE.
  * Counters: a walk cut short adds to vkrt_counters.traversal_faults, like every other walk; no other counter moves. */
 typedef struct vkrt_ray {        /* 32 B */
   float origin[3];    float tmin;

@@ -190,6 +190,13 @@ class QueryOpts(C.Structure):
     _fields_ = [("struct_size", c_u), ("ray_flags", c_u), ("cull_mask", c_u), ("anyhit_seed", c_u)]
 
 
+# deforming meshes (vkrt_scene_update_vertices): the four arrays are host or device pointers, by `memory`
+class VertexUpdate(C.Structure):
+    _fields_ = [("struct_size", c_u), ("first", c_u), ("count", c_u), ("memory", c_u), ("positions", C.c_void_p), ("normals", C.c_void_p),
+                ("tangents", C.c_void_p), ("texcoords0", C.c_void_p)]
+
+
+assert C.sizeof(VertexUpdate) == 48
 assert C.sizeof(Ray) == 32
 assert C.sizeof(Hit) == 32
 assert C.sizeof(InstanceVisibility) == 4
@@ -224,6 +231,7 @@ VKRT_INFO_SPLIT_BUDGET = 101  # read-only: the pre-splitting budget the build us
 # vkrt_instance_flags / vkrt_ray_flags (the gl_RayFlags*EXT values)
 VKRT_INSTANCE_FACING_CULL_DISABLE, VKRT_INSTANCE_FLIP_FACING = 0x1, 0x2
 VKRT_RAY_OPAQUE, VKRT_RAY_CULL_BACK_FACING, VKRT_RAY_CULL_FRONT_FACING = 0x1, 0x10, 0x20
+VKRT_MEMORY_HOST, VKRT_MEMORY_DEVICE = 0, 1  # vkrt_memory
 
 # every symbol include/vkrt.h declares (tests check the built library exports them all)
 VKRT_SYMBOLS = [
@@ -240,6 +248,7 @@ VKRT_SYMBOLS = [
     "vkrt_accel_get_info",
     "vkrt_scene_update_nodes",
     "vkrt_accel_refit",
+    "vkrt_scene_update_vertices",
     "vkrt_intersect",
     "vkrt_occluded",
     "vkrt_scene_set_instance_visibility",
@@ -296,6 +305,8 @@ def declare_vkrt(lib):
     lib.vkrt_scene_update_nodes.restype = C.c_int
     lib.vkrt_accel_refit.argtypes = [C.c_void_p, C.c_void_p]
     lib.vkrt_accel_refit.restype = C.c_int
+    lib.vkrt_scene_update_vertices.argtypes = [C.c_void_p, P(VertexUpdate), C.c_void_p]
+    lib.vkrt_scene_update_vertices.restype = C.c_int
     # (rays, hits, occluded: device pointers)
     lib.vkrt_intersect.argtypes = [C.c_void_p, C.c_void_p, c_u, c_u, C.c_void_p, C.c_void_p]
     lib.vkrt_intersect.restype = C.c_int

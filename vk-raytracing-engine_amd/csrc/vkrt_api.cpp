@@ -30,6 +30,7 @@
 #define VKRT_SPLIT_BUDGET_DEFAULT -1  // automatic (round 5): vkrt_accel_build decides per scene
 #include "lbvh.h"
 #include "refit.h"
+#include "vertex_update.h"
 
 namespace {
 
@@ -61,7 +62,7 @@ struct vkrt_scene
   int device = 0;
   int cuCount = 256;
   // host copies (kept like m_gltfScene keeps its vectors)
-  std::vector<float> positions;
+  std::vector<float> positions;  // (after a device-sourced vkrt_scene_update_vertices: behind the device's until the next build, positionsOnDevice)
   std::vector<uint32_t> indices;
   std::vector<vkrt_prim_mesh> primMeshes;
   std::vector<vkrt_node> nodes;
@@ -93,9 +94,13 @@ struct vkrt_scene
   bool hasLargeTriangles = false;  // some instanced triangle covers more than 1 % of the largest face of the scene's box (any-hit order heuristic)
   bool wavefront = true;  // execution mode the acceleration structure was built for (opt[VKRT_OPT_MODE] at vkrt_accel_build)
   // moving instances (vkrt_scene_update_nodes / vkrt_accel_refit)
-  bool stale = false;      // node transforms changed since the tree was built or refitted: no trace until the next refit or build
+  bool stale = false;      // node transforms or vertex positions changed since the tree was built or refitted: no trace until the next refit or build
   bool refitted = false;   // the tree has been refitted since its build: vkrt_accel_get_info reads the refit's SAH cost from the device
   vkrt::RefitScratch refit;  // level lists + exact node boxes of the current build (allocated at its first refit)
+  // deforming meshes (vkrt_scene_update_vertices)
+  bool positionsOnDevice = false;  // a device-sourced update moved vertices the host copy has not seen: the next build downloads them first
+  vkrt::DevBuf vertexStage;        // staging of host-sourced updates (grown by an update larger than every earlier one)
+  size_t vertexStageBytes = 0;
   // ray-query visibility (vkrt_scene_set_instance_visibility): host copy per node, and which masks occur (bit m of masksPresent[m >> 6])
   std::vector<vkrt_instance_visibility> vis;
   uint64_t masksPresent[4] = {0, 0, 0, 0};
@@ -374,7 +379,7 @@ int checkBuilt(const vkrt_scene* s, const char* who)
   if(!s->built)
     return fail(VKRT_ERR_NOT_BUILT, "%s before vkrt_accel_build", who);
   if(s->stale)
-    return fail(VKRT_ERR_NOT_BUILT, "%s after vkrt_scene_update_nodes: vkrt_accel_refit or vkrt_accel_build first", who);
+    return fail(VKRT_ERR_NOT_BUILT, "%s after vkrt_scene_update_nodes / vkrt_scene_update_vertices: vkrt_accel_refit or vkrt_accel_build first", who);
   return VKRT_OK;
 }
 
@@ -1078,6 +1083,16 @@ int vkrt_accel_build(vkrt_scene* s, uint32_t flags, void* hip_stream)
   if(!s)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "scene is NULL");
   hipStream_t stream = (hipStream_t)hip_stream;
+  if(s->positionsOnDevice)
+  {  // vertices moved by a device-sourced vkrt_scene_update_vertices: the host builder and sceneBounds read the host copy
+    int rc = setDevice(s);
+    if(rc != VKRT_OK)
+      return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if(!s->positions.empty())
+      HIP_TRY(hipMemcpy(s->positions.data(), s->dev.positions, s->positions.size() * sizeof(float), hipMemcpyDeviceToHost));
+    s->positionsOnDevice = false;
+  }
   const bool deviceBuild = flags == 0 || (flags & (VKRT_BUILD_LBVH_GPU | VKRT_BUILD_PLOC_GPU)) != 0;
   if(s->opt[VKRT_OPT_SPLIT_BUDGET] >= 0 || !deviceBuild)
   {
@@ -1182,6 +1197,78 @@ int vkrt_accel_refit(vkrt_scene* s, void* hip_stream)
     return fail(rc, "vkrt_accel_refit: %s", err.c_str());
   s->refitted = true;
   s->stale = false;
+  return VKRT_OK;
+}
+
+int vkrt_scene_update_vertices(vkrt_scene* s, const vkrt_vertex_update* u, void* hip_stream)
+{
+  const char* who = "vkrt_scene_update_vertices";
+  if(!u)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: update is NULL", who);
+  if(u->struct_size < sizeof(vkrt_vertex_update))
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vkrt_vertex_update.struct_size %u < %zu (ABI mismatch)", who, u->struct_size, sizeof(vkrt_vertex_update));
+  if(u->memory != VKRT_MEMORY_HOST && u->memory != VKRT_MEMORY_DEVICE)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: memory %u is neither VKRT_MEMORY_HOST nor VKRT_MEMORY_DEVICE", who, u->memory);
+  if(!s)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
+  const size_t vertexCount = s->positions.size() / 3;
+  if((uint64_t)u->first + u->count > vertexCount)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vertices [%u, %llu) outside the scene's %zu vertices", who, u->first,
+                (unsigned long long)u->first + u->count, vertexCount);
+  const bool host = u->memory == VKRT_MEMORY_HOST;
+  const size_t n = u->count;
+  // the rule of vkrt_scene_create, checked for the whole range before anything changes
+  if(host && u->positions)
+    for(size_t i = 0; i < 3 * n; i++)
+      if(!std::isfinite(u->positions[i]))
+        return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: positions[%zu] (vertex %zu) is not finite", who, i, (size_t)u->first + i / 3);
+  if(n == 0 || (!u->positions && !u->normals && !u->tangents && !u->texcoords0))
+    return VKRT_OK;
+  int rc = setDevice(s);
+  if(rc != VKRT_OK)
+    return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  vkrt::VertexUpdate d;
+  d.first = u->first;
+  d.count = u->count;
+  d.positions = u->positions; d.normals = u->normals; d.tangents = u->tangents; d.texcoords0 = u->texcoords0;
+  if(host)
+  {  // the given arrays, back to back in the scene's staging buffer (16-byte elements first, so every part starts aligned for its loads)
+    const float* src[4] = {u->tangents, u->texcoords0, u->positions, u->normals};
+    const float** dst[4] = {&d.tangents, &d.texcoords0, &d.positions, &d.normals};
+    const size_t width[4] = {4, 2, 3, 3};
+    size_t bytes = 0;
+    for(int k = 0; k < 4; k++)
+      if(src[k]) bytes += n * width[k] * sizeof(float);
+    if(bytes > s->vertexStageBytes)
+    {  // (every earlier host update has waited for its stream: nothing reads the old buffer)
+      s->vertexStageBytes = 0;
+      HIP_TRY(s->vertexStage.alloc(bytes));
+      s->vertexStageBytes = bytes;
+    }
+    size_t at = 0;
+    for(int k = 0; k < 4; k++)
+      if(src[k])
+      {
+        float* part = (float*)(s->vertexStage.get<char>() + at);
+        HIP_TRY(hipMemcpyAsync(part, src[k], n * width[k] * sizeof(float), hipMemcpyHostToDevice, stream));
+        *dst[k] = part;
+        at += n * width[k] * sizeof(float);
+      }
+  }
+  // Stream-ordered like vkrt_scene_update_nodes: one launch on hip_stream, after whatever still reads the old vertices and before the
+  // refit and the next trace (whose internal lane streams fork from and join to the caller's stream).
+  HIP_TRY(vkrt::launch_vertex_update(const_cast<float*>(s->dev.positions), const_cast<float4*>(s->dev.vertexPN), d, stream));
+  if(host)
+  {
+    HIP_TRY(hipStreamSynchronize(stream));  // the caller's arrays and the staging buffer are free again
+    if(u->positions)
+      std::copy(u->positions, u->positions + 3 * n, s->positions.begin() + 3 * (size_t)u->first);
+  }
+  else if(u->positions)
+    s->positionsOnDevice = true;
+  if(u->positions && s->built)
+    s->stale = true;
   return VKRT_OK;
 }
 

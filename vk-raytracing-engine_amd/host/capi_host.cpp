@@ -159,6 +159,51 @@ int vkrt_host_render_gltf_moved(const char* path, int device, int width, int hei
   catch(const std::exception& e) { g_err = e.what(); return 1; }
 }
 
+// vkrt_host_render_gltf with a deforming mesh: build, then `steps` times HelloVkrt::updateVertices(first, ...) + refitAccel, then the
+// frames.  positions / normals: steps x count x 3 floats, tangents: steps x count x 4, texcoords0: steps x count x 2; NULL = kept.
+int vkrt_host_render_gltf_deformed(const char* path, int device, int width, int height, int samples, int depth, int frames, uint32_t seed0,
+                                   const float* eye, const float* center, const float* up, float fov, uint32_t buildFlags, uint32_t first,
+                                   uint32_t count, uint32_t steps, const float* positions, const float* normals, const float* tangents,
+                                   const float* texcoords0, float* rgbaOut)
+{
+  try
+  {
+    HelloVkrt vk(device);
+    vk.setup(width, height);
+    vk.CameraManip.setLookat(Vec3{eye[0], eye[1], eye[2]}, Vec3{center[0], center[1], center[2]}, Vec3{up[0], up[1], up[2]});
+    vk.CameraManip.setFov(fov);
+    vk.loadGltfScene(path);
+    vk.createOffscreenRender();
+    vk.initRayTracing();
+    vk.m_buildFlags = buildFlags;
+    vk.createBottomLevelASGltf();
+    vk.createTopLevelAsGltf();
+    auto step = [&](const float* a, uint32_t k, size_t w) {
+      return a ? std::vector<float>(a + (size_t)k * count * w, a + (size_t)(k + 1) * count * w) : std::vector<float>();
+    };
+    for(uint32_t k = 0; k < steps; k++)
+    {
+      vk.updateVertices(first, step(positions, k, 3), step(normals, k, 3), step(tangents, k, 4), step(texcoords0, k, 2));
+      vk.refitAccel();
+    }
+    vk.m_pcRay.samples = samples;
+    vk.m_pcRay.depth = depth;
+    const float clear[4] = {1, 1, 1, 1};
+    for(int f = 0; f < frames; f++)
+    {
+      vk.updateUniformBuffer();
+      vk.updateFrame();
+      vk.m_seed = seed0 + (uint32_t)f;
+      vk.pathtrace(clear);
+    }
+    std::vector<float> img;
+    vk.downloadImage(img);
+    memcpy(rgbaOut, img.data(), img.size() * sizeof(float));
+    return 0;
+  }
+  catch(const std::exception& e) { g_err = e.what(); return 1; }
+}
+
 // The hybrid sequence of the reference's frame loop (main.cpp:510-561: rasterizeGltf -> raytraceRasterizedScene -> drawPost)
 // through HelloVkrt for ONE rank of a `world`-rank job (setShard): displayOut receives the rank's display strips (rows of its
 // shard x width x rgba32f, after post.frag).  world = 1: the whole image.  GI on, shadows and AO on.

@@ -93,6 +93,41 @@ void HelloVkrt::updateNodeTransforms(uint32_t first, const std::vector<float>& m
   std::copy(nodes.begin(), nodes.end(), m_gltfScene.m_nodes.begin() + first);  // the host copy follows, like m_gltfScene's node matrices
 }
 
+void HelloVkrt::updateVertices(uint32_t first, const std::vector<float>& positions, const std::vector<float>& normals,
+                               const std::vector<float>& tangents, const std::vector<float>& texcoords0)
+{
+  if(!m_scene)
+    throw std::runtime_error("updateVertices before loadGltfScene");
+  const std::vector<float>* src[4] = {&positions, &normals, &tangents, &texcoords0};
+  std::vector<float>* mirror[4] = {&m_gltfScene.m_positions, &m_gltfScene.m_normals, &m_gltfScene.m_tangents, &m_gltfScene.m_texcoords0};
+  const size_t width[4] = {3, 3, 4, 2};
+  size_t count = 0;
+  bool any = false;
+  for(int k = 0; k < 4; k++)
+  {
+    if(src[k]->empty())
+      continue;
+    if(src[k]->size() % width[k] != 0 || (any && src[k]->size() / width[k] != count))
+      throw std::runtime_error("updateVertices: the arrays must hold the same number of vertices (vec3, vec3, vec4, vec2)");
+    count = src[k]->size() / width[k];
+    any = true;
+  }
+  if((uint64_t)first + count > m_gltfScene.vertexCount())
+    throw std::runtime_error("updateVertices: vertex range outside the scene");
+  vkrt_vertex_update u{};
+  u.struct_size = sizeof(u);
+  u.first = first;
+  u.count = (uint32_t)count;
+  u.memory = VKRT_MEMORY_HOST;
+  u.positions = positions.empty() ? nullptr : positions.data();
+  u.normals = normals.empty() ? nullptr : normals.data();
+  u.tangents = tangents.empty() ? nullptr : tangents.data();
+  u.texcoords0 = texcoords0.empty() ? nullptr : texcoords0.data();
+  check(vkrt_scene_update_vertices(m_scene, &u, nullptr), "vkrt_scene_update_vertices");
+  for(int k = 0; k < 4; k++)  // the host copy follows, like m_gltfScene's node matrices
+    std::copy(src[k]->begin(), src[k]->end(), mirror[k]->begin() + (size_t)first * width[k]);
+}
+
 void HelloVkrt::refitAccel()
 {
   if(!m_scene)

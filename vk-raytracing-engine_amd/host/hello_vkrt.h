@@ -44,6 +44,9 @@ public:
   // the reference's TLAS update path (buildTlas(..., update = true) with ALLOW_UPDATE, raytrace_vkpp's animation loop): new transforms
   // for nodes [first, first + matrices.size() / 16) (column-major 4x4 each, primMesh kept), then a refit of the built tree
   void updateNodeTransforms(uint32_t first, const std::vector<float>& matrices);  // vkrt_scene_update_nodes
+  // vkrt_scene_update_vertices from host vectors (vec3 / vec3 / vec4 / vec2 per vertex, an empty vector keeps the attribute)
+  void updateVertices(uint32_t first, const std::vector<float>& positions, const std::vector<float>& normals = {},
+                      const std::vector<float>& tangents = {}, const std::vector<float>& texcoords0 = {});
   void refitAccel();                                                             // vkrt_accel_refit
   void createOffscreenRender();                           // :637-665 (colour image only)
   void updateUniformBuffer();                             // :61-102

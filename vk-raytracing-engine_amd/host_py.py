@@ -36,6 +36,10 @@ def lib():
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                   C.c_void_p, C.c_void_p]
         L.vkrt_host_render_gltf_moved.restype = C.c_int
+        L.vkrt_host_render_gltf_deformed.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vkrt_host_render_gltf_deformed.restype = C.c_int
         L.vkrt_host_render_gltf_hybrid.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_float, C.c_uint32, C.c_uint32, C.c_void_p]
         L.vkrt_host_render_gltf_hybrid.restype = C.c_int
@@ -148,6 +152,35 @@ def render_gltf_moved(path, width, height, first, matrices, samples=1, depth=3, 
                                            p.ctypes.data, fov, build, first, m.shape[1], m.shape[0], m.ctypes.data, img.ctypes.data)
     if rc != 0:
         raise RuntimeError("vkrt_host_render_gltf_moved: " + lib().vkrt_host_last_error().decode())
+    return img
+
+
+def render_gltf_deformed(path, width, height, first, positions, normals=None, tangents=None, texcoords0=None, samples=1, depth=3, frames=1, seed0=0,
+                         eye=(0, 0, 15), center=(0, 0, 0), up=(0, 1, 0), fov=60.0, build=abi.VKRT_BUILD_PLOC_GPU, device=0):
+    """render_gltf after deforming vertices [first, first + count) through the C++ HelloVkrt: positions (steps, count, 3) -- normals
+    (steps, count, 3), tangents (steps, count, 4), texcoords0 (steps, count, 2) or None = kept; each step is
+    updateVertices(first, ...) + refitAccel()."""
+    arrays = []
+    shape = None
+    for a, w in ((positions, 3), (normals, 3), (tangents, 4), (texcoords0, 2)):
+        if a is None:
+            arrays.append(None)
+            continue
+        a = np.ascontiguousarray(a, np.float32)
+        a = a[None] if a.ndim == 2 else a
+        if a.ndim != 3 or a.shape[2] != w or (shape is not None and a.shape[:2] != shape):
+            raise ValueError(f"render_gltf_deformed: an array of shape {a.shape}, expected (steps, count, {w}) with one steps x count")
+        shape = a.shape[:2]
+        arrays.append(a)
+    if shape is None:
+        raise ValueError("render_gltf_deformed: no array given")
+    img = np.zeros((height, width, 4), np.float32)
+    e, c, p = (np.asarray(v, np.float32) for v in (eye, center, up))
+    ptrs = [C.c_void_p(a.ctypes.data) if a is not None else None for a in arrays]
+    rc = lib().vkrt_host_render_gltf_deformed(os.fsencode(path), device, width, height, samples, depth, frames, seed0, e.ctypes.data, c.ctypes.data, p.ctypes.data, fov, build,
+                                              int(first), shape[1], shape[0], *ptrs, img.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("vkrt_host_render_gltf_deformed: " + lib().vkrt_host_last_error().decode())
     return img
 
 

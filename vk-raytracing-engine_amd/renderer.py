@@ -94,6 +94,7 @@ class Renderer:
         del keep
         self.lights_count = int(flat.lights.shape[0])
         self._prim_mesh = np.array(flat.nodes["primMesh"], np.int32)  # update_nodes keeps every node's primMesh
+        self._vertex_count = int(flat.positions.shape[0])
         for k, v in (options or {}).items():
             self.set_option(k, v)
         if build:
@@ -136,6 +137,55 @@ class Renderer:
         st = C.c_void_p(stream.cuda_stream) if stream is not None else None
         _check(self.lib.vkrt_scene_update_nodes(self._h, first, n, arr, st), "vkrt_scene_update_nodes")
 
+    def update_vertices(self, first, positions=None, normals=None, tangents=None, texcoords0=None, stream=None):
+        """vkrt_scene_update_vertices: new attributes for vertices [first, first + n) of the scene's shared vertex arrays (absolute
+        indices, a mesh's vertexOffset included).  positions, normals: (n, 3); tangents: (n, 4); texcoords0: (n, 2); float32; None
+        keeps the attribute.  numpy arrays take the host path (copied before return, the call waits for `stream`); torch tensors on
+        the scene's device take the device path: no copy, no synchronisation, the tensors must live until `stream` has passed the
+        call.  Enqueued on `stream` (a torch stream; None = the default stream).  With positions the tree is stale until refit() or
+        build().  Refused here, before the call: a wrong dtype or shape, a non-contiguous tensor, a tensor on another device, numpy and
+        torch mixed in one call, lengths that differ, a range outside the scene."""
+        import torch
+
+        given = [(k, a, w) for k, a, w in (("positions", positions, 3), ("normals", normals, 3), ("tangents", tangents, 4),
+                                           ("texcoords0", texcoords0, 2)) if a is not None]
+        kinds = set()
+        n = None
+        ptr = {}
+        for k, a, w in given:
+            if isinstance(a, torch.Tensor):
+                kinds.add("torch")
+                if not a.is_cuda or a.device.index != self.device:
+                    raise VkrtError(f"update_vertices: {k} is on {a.device}, the scene is on cuda:{self.device}")
+                if a.dtype != torch.float32:
+                    raise VkrtError(f"update_vertices: {k} is {a.dtype}, expected torch.float32")
+                if not a.is_contiguous():
+                    raise VkrtError(f"update_vertices: {k} must be contiguous")
+                ptr[k] = a.data_ptr()
+            elif isinstance(a, np.ndarray):
+                kinds.add("numpy")
+                if a.dtype != np.float32:
+                    raise VkrtError(f"update_vertices: {k} is {a.dtype}, expected float32")
+                if not a.flags["C_CONTIGUOUS"]:
+                    raise VkrtError(f"update_vertices: {k} must be contiguous")
+                ptr[k] = a.ctypes.data
+            else:
+                raise VkrtError(f"update_vertices: {k} must be a numpy array or a torch tensor, got {type(a).__name__}")
+            if len(kinds) > 1:
+                raise VkrtError(f"update_vertices: {k}: numpy arrays and torch tensors mixed in one call")
+            if a.ndim != 2 or a.shape[1] != w:
+                raise VkrtError(f"update_vertices: {k} has shape {tuple(a.shape)}, expected (n, {w})")
+            if n is not None and a.shape[0] != n:
+                raise VkrtError(f"update_vertices: {k} has {a.shape[0]} vertices, the arrays before it {n}")
+            n = int(a.shape[0])
+        n = n or 0
+        if isinstance(first, bool) or not isinstance(first, (int, np.integer)) or first < 0 or int(first) + n > self._vertex_count:
+            raise VkrtError(f"update_vertices: first: vertices [{first}, {first} + {n}) outside the scene's {self._vertex_count} vertices")
+        u = abi.VertexUpdate(C.sizeof(abi.VertexUpdate), int(first), n, abi.VKRT_MEMORY_DEVICE if "torch" in kinds else abi.VKRT_MEMORY_HOST,
+                             ptr.get("positions"), ptr.get("normals"), ptr.get("tangents"), ptr.get("texcoords0"))
+        st = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        _check(self.lib.vkrt_scene_update_vertices(self._h, C.byref(u), st), "vkrt_scene_update_vertices")
+
     def set_instance_visibility(self, first, masks, flags=None, stream=None):
         """vkrt_scene_set_instance_visibility for nodes [first, first + n): masks = n ints in 1..255 (the instance masks of the
         ray-query cull mask); flags = n ints of VKRT_INSTANCE_* bits, or None to keep the nodes' current flags.  Enqueued on `stream`
@@ -177,7 +227,8 @@ class Renderer:
         return out[:nb].reshape(-1, 8)
 
     def refit(self, stream=None):
-        """vkrt_accel_refit: the built tree follows the current node transforms (same topology, new boxes), enqueued on `stream`."""
+        """vkrt_accel_refit: the built tree follows the current node transforms and vertices (same topology, new boxes), enqueued on
+        `stream`."""
         st = C.c_void_p(stream.cuda_stream) if stream is not None else None
         _check(self.lib.vkrt_accel_refit(self._h, st), "vkrt_accel_refit")
 
