@@ -434,6 +434,57 @@ typedef struct vkrt_query_opts {
 int vkrt_intersect_ex(vkrt_scene* scene, const vkrt_ray* rays, uint32_t n, const vkrt_query_opts* opts, vkrt_hit* hits, void* hip_stream);
 int vkrt_occluded_ex(vkrt_scene* scene, const vkrt_ray* rays, uint32_t n, const vkrt_query_opts* opts, int32_t* occluded, void* hip_stream);
 
+/* ---- shading inputs at the hits of ray queries (what raytrace.rchit:34-113 computes before its BRDF: attribute fetch, world
+ *      transforms, tangent frame, the four texture() taps, normal mapping; Vulkan's hit attributes + buffer references, Embree's
+ *      rtcInterpolate).  With vkrt_intersect and vkrt_occluded it is enough to write a path tracer outside the library.  This entry
+ *      point came after ABI version 4 without changing it or any existing struct: detect it by symbol. ------------------------------
+ * Memory and ordering are those of vkrt_intersect: `hits` and `out` are device memory on the scene's device, 16-byte aligned; the call
+ * is enqueued on hip_stream, allocates nothing, does not synchronise with the host and returns after the enqueue; n may be any
+ * uint32_t.  A vkrt_intersect and a vkrt_hit_surface enqueued on one stream need nothing between them.
+ * A record is a function of (instance, primitive, u, v) of the hit and of the scene's current arrays; t, prim_mesh, triangle and
+ * material of the input are not read.  All arithmetic is that of the path tracer's hit shader: binary32, no contraction, LOD 0.
+ *   position          gl_ObjectToWorldEXT * interpolated position (rchit:70-72): bit for bit the origin the path tracer gives the next ray
+ *   normal            the interpolated vertex normal, normalised, * gl_WorldToObjectEXT, normalised (rchit:74-75)
+ *                     (gl_WorldToObjectEXT: the cofactor inverse of the node's 3x3 in binary64, rounded to binary32, as everywhere in the
+ *                     library; its zero entries carry the signs that form gives them, and a normal component of -0 is a zero)
+ *   texcoord_u/v      the interpolated TEXCOORD_0 (rchit:79)
+ *   shading_normal, tangent, binormal   the frame the shader hands the BRDF.  Without a normal texture, or with VKRT_SURFACE_GEOMETRY
+ *                     alone: `normal`, the Gram-Schmidt tangent and tangent.w * cross(N, T) (rchit:77-78).  With VKRT_SURFACE_MATERIAL and
+ *                     a normal texture: the tap * 2 - 1 carried into that frame, then createCoordinateSystem (rchit:100-106)
+ *   base_color, metallic, roughness     pbrGetBaseColor / pbrGetMetallicRoughness (gltf.glsl:26-45), unclamped as fetched
+ *   emission          emissiveFactor * texture(emissiveTexture), always (the depth / isSpecular rule of rchit:83 is the integrator's)
+ *   alpha             pbrBaseColorFactor.a, times the .a of the base colour tap where the material has that texture (glTF's alpha)
+ *   geometric_normal  normalize(cross(p1 - p0, p2 - p0) * gl_WorldToObjectEXT) on the object-space vertices in index order: the
+ *                     counter-clockwise front face of the visibility section above, carried to world space by the inverse transpose
+ *                     like a vertex normal, so it stays on the front side under mirroring and non-uniform scale.  It is not turned
+ *                     towards any ray: the caller has the direction and takes the sign of the dot product
+ *   material          max(0, materialIndex) of the instance's primitive-mesh;  valid = 1;  reserved = 0
+ * With VKRT_SURFACE_GEOMETRY alone alpha, metallic, roughness, base_color and emission are 0 and no texel is read.
+ * Records that are not hits of this scene have a defined result and read nothing out of bounds: instance < 0 (a miss as
+ * vkrt_intersect writes it), instance >= node_count, primitive outside [0, indexCount / 3) of the instance's primitive-mesh, or a
+ * non-finite u or v give an all-zero record with material = -1 and valid = 0.  Finite u, v outside the triangle are used as given.
+ * No tree is needed: everything read is uploaded at vkrt_scene_create and kept current, in stream order, by vkrt_scene_update_nodes
+ * and vkrt_scene_update_vertices.  The call works before vkrt_accel_build and on a stale tree and never returns VKRT_ERR_NOT_BUILT, so
+ * a caller can follow surface points (instance, primitive, u, v) through motion and deformation.
+ * Errors, in this order, the first four before anything of the scene is read: a NULL scene, or (n > 0) a NULL or misaligned pointer,
+ * or a `fields` value other than the two below: VKRT_ERR_INVALID_ARGUMENT; n == 0: VKRT_OK, nothing is enqueued; without a device:
+ * VKRT_ERR_NO_DEVICE.  No counter moves. */
+enum vkrt_surface_fields {
+  VKRT_SURFACE_GEOMETRY = 0x1,   /* position, geometric and interpolated normal, vertex tangent frame, texture coordinate */
+  VKRT_SURFACE_MATERIAL = 0x2    /* + the four texture() taps: normal mapping, base colour, alpha, metallic, roughness, emission */
+};
+typedef struct vkrt_surface {            /* 128 B, 16-byte aligned, eight float4 */
+  float position[3];         float texcoord_u;
+  float geometric_normal[3]; float texcoord_v;
+  float normal[3];           float alpha;
+  float shading_normal[3];   float metallic;
+  float tangent[3];          float roughness;
+  float binormal[3];         int32_t material;
+  float base_color[3];       int32_t valid;
+  float emission[3];         uint32_t reserved;   /* 0 */
+} vkrt_surface;
+int vkrt_hit_surface(vkrt_scene* scene, const vkrt_hit* hits, uint32_t n, uint32_t fields, vkrt_surface* out, void* hip_stream);
+
 /* ---- path trace (replaces HelloVulkan::pathtrace :1423-1448 = one
  *      vkCmdTraceRaysKHR over raytrace.rgen/.rchit/.rmiss/raytraceShadow.rmiss) ---- */
 uint32_t vkrt_shard_rows(const vkrt_shard* shard); /* rows of the shard's buffer */

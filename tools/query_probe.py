@@ -12,6 +12,14 @@ takes one scalar (tmin, tmax) per call, so in the child run both kernels get eac
 with bounds (1e-4, 0.999) -- the same segment up to those bounds.
 
   python tools/query_probe.py --out profiles/r06_query_probe.json
+
+The surface leg (--surface) times vkrt_hit_surface (k_hit_surface) on the textured bench atrium: the hit records of the camera rays
+(coherent) and of their cosine bounces (incoherent), misses removed, each with VKRT_SURFACE_GEOMETRY and with GEOMETRY | MATERIAL;
+device events around 20 calls after 5 warm-up calls, kernel times from a separate `rocprofv3 --kernel-trace --stats` child run that
+also renders one bench frame, whose k_wf_shade time per record is the yardstick.  --variant-lib PATH measures a second build of the
+library (csrc/Makefile VARIANT=...) in the same run, the two alternating call by call.
+
+  python tools/query_probe.py --surface --out profiles/r06_surface_probe.json
 """
 import argparse
 import csv
@@ -169,6 +177,185 @@ def _kernel_trace(outdir):
     return [(n, d) for _, n, d in rows]
 
 
+# ---- the surface leg ------------------------------------------------------------------------------------------------------------
+HBM_PEAK_GBS = 8000.0
+SURFACE_CASES = (("camera", "geometry", False), ("camera", "material", True), ("diffuse", "geometry", False), ("diffuse", "material", True))
+
+
+def _renderer_of(lib_path, flat, build):
+    """A Renderer on its own copy of the library (None: the product build the package names)."""
+    import ctypes as C
+    from vkrt_amd import abi, renderer
+
+    if lib_path is None:
+        return renderer.Renderer(flat, device=0, build=build)
+    renderer.load_library()
+    saved, renderer._lib = renderer._lib, abi.declare_vkrt(C.CDLL(os.path.abspath(lib_path)))
+    try:
+        return renderer.Renderer(flat, device=0, build=build)  # (keeps the handle it was made with)
+    finally:
+        renderer._lib = saved
+
+
+def _surface_hits(r, sets):
+    """{set: [N, 8] device tensor of the hit records of the set's rays, misses removed}"""
+    import torch
+    from vkrt_amd.renderer import pack_rays
+
+    out = {}
+    for name in ("camera", "diffuse"):
+        o, d, lo, hi = sets[name]
+        rays = pack_rays(torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda(), tmin=torch.from_numpy(lo).cuda(), tmax=torch.from_numpy(hi).cuda())
+        h = r.intersect(rays)
+        out[name] = h.buffer[h.instance >= 0].contiguous()
+    torch.cuda.synchronize()
+    return out
+
+
+def _surface_bytes(flat, hits, material):
+    """Algorithmic bytes per hit: 32 in, 128 out, 3 x 4 index, 3 x 48 vertex, 96 instance; with the material 64 + 16 per issued tap."""
+    b = 32 + 128 + 12 + 144 + 96
+    if not material:
+        return float(b)
+    m = flat.materials[hits[:, 7].contiguous().cpu().numpy().view(np.int32)]
+    taps = sum((m[k] > -1).astype(np.float64) for k in ("pbrBaseColorTexture", "metallicRoughnessTexture", "normalTexture", "emissiveTexture"))
+    return float(b + 64 + 16 * taps.mean())
+
+
+def _surface_child(npz, reps):
+    """Launched under rocprofv3: reps calls per case on the saved hit records, then one bench frame (k_wf_shade)."""
+    import torch
+    from vkrt_amd.flat_scene import FlatScene, make_push_constants
+    from vkrt_amd.renderer import Renderer
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from conftest import default_camera
+
+    z = np.load(npz, allow_pickle=False)
+    flat = FlatScene.load_npz(str(z["scene"]))
+    libs = [None] + ([str(z["variant_lib"])] if str(z["variant_lib"]) else [])
+    rs = [_renderer_of(p, flat, str(z["build"])) for p in libs]
+    for set_name, _, material in SURFACE_CASES:
+        hits = torch.from_numpy(z[set_name]).cuda()
+        for _ in range(reps):
+            for r in rs:  # alternating
+                r.surface(hits, material=material)
+        torch.cuda.synchronize()
+    c = {k: float(z["cam_" + k]) if k == "fov" else tuple(float(x) for x in z["cam_" + k]) for k in ("eye", "center", "up", "fov")}
+    W, H = 1920, 1080
+    pc = make_push_constants(samples=1, depth=8, frame=0, lights_count=len(flat.lights))
+    rs[0].reset_counters()
+    rs[0].pathtrace(pc, default_camera(W, H, **c), W, H, seed=7)
+    torch.cuda.synchronize()
+    with open(str(z["counters_out"]), "w") as f:
+        json.dump(rs[0].counters(), f)
+    for r in rs:
+        r.close()
+
+
+def surface_leg(a):
+    import torch
+    import atrium
+    import vkrt_amd
+
+    flat, info = atrium.build_atrium(262144, seed=1, with_textures=True)
+    cam = dict(info["camera"]) if "camera" in info else dict(atrium.DEFAULT_CAMERA)
+    W, H = 1920, 1080
+    libs = [("plain", None)] + ([(a.variant_name, a.variant_lib)] if a.variant_lib else [])
+    rs = [(name, _renderer_of(p, flat, a.build)) for name, p in libs]
+    r = rs[0][1]
+    sets = ray_sets(flat, cam, W, H, r, a.seed)
+    hits = _surface_hits(r, sets)
+    result = {"source_hash": vkrt_amd.source_hash(), "scene": "atrium 262144 seed 1, textured", "build": a.build, "device": torch.cuda.get_device_name(0),
+              "hbm_peak_GB_s": HBM_PEAK_GBS, "warmup_calls": 5, "timed_calls": 20, "variants": [n for n, _ in libs], "cases": {}}
+    outs = {n: torch.empty((max(h.shape[0] for h in hits.values()), 32), dtype=torch.float32, device="cuda:0") for n, _ in rs}
+    for set_name, what, material in SURFACE_CASES:
+        h = hits[set_name]
+        n = int(h.shape[0])
+        entry = {"hits": n, "algorithmic_bytes_per_hit": round(_surface_bytes(flat, h, material), 1), "events": {}}
+        for _ in range(5):
+            for name, rr in rs:
+                rr.surface(h, material=material, out=outs[name][:n])
+        torch.cuda.synchronize()
+        ms = {name: 0.0 for name, _ in rs}
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(20 * len(rs))]
+        k = 0
+        for _ in range(20):  # the variants alternate call by call, an event pair around every call
+            for name, rr in rs:
+                ev[k][0].record()
+                rr.surface(h, material=material, out=outs[name][:n])
+                ev[k][1].record()
+                k += 1
+        torch.cuda.synchronize()
+        k = 0
+        for _ in range(20):
+            for name, _ in rs:
+                ms[name] += ev[k][0].elapsed_time(ev[k][1])
+                k += 1
+        for name, _ in rs:
+            per = ms[name] / 20
+            entry["events"][name] = {"ms_per_call": round(per, 4), "ns_per_hit": round(per * 1e6 / n, 3), "mhits_per_s": round(n / per * 1e-3, 1)}
+        if len(rs) > 1:  # the variant computes the same records
+            torch.cuda.synchronize()
+            entry["variant_bit_identical"] = bool(torch.equal(outs[rs[0][0]][:n].view(torch.int32), outs[rs[1][0]][:n].view(torch.int32)))
+        result["cases"][set_name + "_" + what] = entry
+        print(set_name, what, json.dumps(entry), flush=True)
+
+    tmp = tempfile.mkdtemp(prefix="surface_probe_")
+    try:
+        scene_npz = os.path.join(tmp, "scene.npz")
+        flat.save_npz(scene_npz)
+        z = {"scene": scene_npz, "build": a.build, "variant_lib": os.path.abspath(a.variant_lib) if a.variant_lib else "",
+             "counters_out": os.path.join(tmp, "counters.json")}
+        for k in ("eye", "center", "up", "fov"):
+            z["cam_" + k] = np.asarray(cam[k], np.float64)
+        for name, h in hits.items():
+            z[name] = h.cpu().numpy()
+        np.savez(os.path.join(tmp, "hits.npz"), **z)
+        prof = os.path.join(tmp, "prof")
+        cmd = [shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3", "--kernel-trace", "--stats", "-d", prof, "-o", "sp", "--output-format", "csv",
+               "--", sys.executable, os.path.abspath(__file__), "--surface-child", os.path.join(tmp, "hits.npz"), "--reps", str(a.reps)]
+        t0 = time.time()
+        rc = subprocess.run(cmd, timeout=900).returncode
+        result["rocprof"] = {"rc": rc, "seconds": round(time.time() - t0, 1), "reps": a.reps}
+        if rc == 0:
+            trace = _kernel_trace(prof)
+            surf = [(n, d) for n, d in trace if "k_hit_surface" in n]
+            per_case = a.reps * len(rs)
+            for ci, (set_name, what, material) in enumerate(SURFACE_CASES):
+                part = surf[ci * per_case:(ci + 1) * per_case]
+                entry = result["cases"][set_name + "_" + what]
+                entry["kernel"] = {}
+                for vi, (name, _) in enumerate(rs):
+                    ds = sorted(d for _, d in part[vi::len(rs)])
+                    if not ds:
+                        continue
+                    med_ns = ds[len(ds) // 2]
+                    nh = entry["hits"]
+                    gbs = entry["algorithmic_bytes_per_hit"] * nh / med_ns
+                    entry["kernel"][name] = {"median_ms": round(med_ns * 1e-6, 4), "ns_per_hit": round(med_ns / nh, 3), "mhits_per_s": round(nh / med_ns * 1e3, 1),
+                                             "algorithmic_GB_s": round(gbs, 1), "share_of_hbm_peak": round(gbs / HBM_PEAK_GBS, 4), "launches": len(ds)}
+            shade = [d for n, d in trace if "k_wf_shade" in n]
+            cnt = json.load(open(z["counters_out"]))
+            records = int(cnt["rays_closest"])  # every closest-hit ray of the frame leaves one record for k_wf_shade (hit or miss)
+            if shade and records:
+                result["k_wf_shade"] = {"frame": "1920x1080, 1 spp, depth 8", "launches": len(shade), "total_ms": round(sum(shade) * 1e-6, 4), "records": records,
+                                        "hits": int(cnt["hits"]), "ns_per_record": round(sum(shade) / records, 3),
+                                        "note": "records = closest-hit rays of the frame, hits and misses; the kernel also evaluates the BRDF and streams the path records"}
+            result["kernel_stats"] = {n: {"calls": c, "total_ms": round(t * 1e-6, 3)} for n, (c, t) in _kernel_stats(prof).items()
+                                      if "k_hit_surface" in n or "k_wf_shade" in n}
+            print("kernel", json.dumps({k: v.get("kernel") for k, v in result["cases"].items()}), flush=True)
+            print("k_wf_shade", json.dumps(result.get("k_wf_shade")), flush=True)
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(result, f, indent=1)
+    print("wrote", a.out)
+    for _, rr in rs:
+        rr.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r06_query_probe.json"))
@@ -177,9 +364,21 @@ def main():
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--reps", type=int, default=5, help="launches of each kernel per set in the rocprofv3 run")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--surface", action="store_true", help="the vkrt_hit_surface leg instead of the ray-query legs")
+    ap.add_argument("--variant-lib", default=None, help="surface leg: a second build of the library to measure beside the product build")
+    ap.add_argument("--variant-name", default="variant")
+    ap.add_argument("--surface-child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
         _child(a.child, a.reps)
+        return
+    if a.surface_child:
+        _surface_child(a.surface_child, a.reps)
+        return
+    if a.surface:
+        if a.out.endswith("r06_query_probe.json"):
+            a.out = os.path.join(ROOT, "profiles", "r06_surface_probe.json")
+        surface_leg(a)
         return
 
     import torch

@@ -181,6 +181,13 @@ class Hit(C.Structure):
                 ("triangle", C.c_int32), ("material", C.c_int32)]
 
 
+# shading inputs at hit records (vkrt_hit_surface): records of a device array, 128 B each = eight float4
+class Surface(C.Structure):
+    _fields_ = [("position", c_f * 3), ("texcoord_u", c_f), ("geometric_normal", c_f * 3), ("texcoord_v", c_f), ("normal", c_f * 3), ("alpha", c_f),
+                ("shading_normal", c_f * 3), ("metallic", c_f), ("tangent", c_f * 3), ("roughness", c_f), ("binormal", c_f * 3), ("material", C.c_int32),
+                ("base_color", c_f * 3), ("valid", C.c_int32), ("emission", c_f * 3), ("reserved", c_u)]
+
+
 # instance visibility and query options (vkrt_scene_set_instance_visibility, vkrt_intersect_ex / vkrt_occluded_ex)
 class InstanceVisibility(C.Structure):
     _fields_ = [("mask", C.c_uint8), ("flags", C.c_uint8), ("reserved", C.c_uint16)]
@@ -199,6 +206,7 @@ class VertexUpdate(C.Structure):
 assert C.sizeof(VertexUpdate) == 48
 assert C.sizeof(Ray) == 32
 assert C.sizeof(Hit) == 32
+assert C.sizeof(Surface) == 128
 assert C.sizeof(InstanceVisibility) == 4
 assert C.sizeof(QueryOpts) == 16
 
@@ -232,6 +240,7 @@ VKRT_INFO_SPLIT_BUDGET = 101  # read-only: the pre-splitting budget the build us
 VKRT_INSTANCE_FACING_CULL_DISABLE, VKRT_INSTANCE_FLIP_FACING = 0x1, 0x2
 VKRT_RAY_OPAQUE, VKRT_RAY_CULL_BACK_FACING, VKRT_RAY_CULL_FRONT_FACING = 0x1, 0x10, 0x20
 VKRT_MEMORY_HOST, VKRT_MEMORY_DEVICE = 0, 1  # vkrt_memory
+VKRT_SURFACE_GEOMETRY, VKRT_SURFACE_MATERIAL = 0x1, 0x2  # vkrt_surface_fields
 
 # every symbol include/vkrt.h declares (tests check the built library exports them all)
 VKRT_SYMBOLS = [
@@ -255,6 +264,7 @@ VKRT_SYMBOLS = [
     "vkrt_scene_get_instance_visibility",
     "vkrt_intersect_ex",
     "vkrt_occluded_ex",
+    "vkrt_hit_surface",
     "vkrt_shard_rows",
     "vkrt_pathtrace",
     "vkrt_pathtrace_frames",
@@ -320,6 +330,9 @@ def declare_vkrt(lib):
     lib.vkrt_intersect_ex.restype = C.c_int
     lib.vkrt_occluded_ex.argtypes = [C.c_void_p, C.c_void_p, c_u, P(QueryOpts), C.c_void_p, C.c_void_p]
     lib.vkrt_occluded_ex.restype = C.c_int
+    # (hits, out: device pointers)
+    lib.vkrt_hit_surface.argtypes = [C.c_void_p, C.c_void_p, c_u, c_u, C.c_void_p, C.c_void_p]
+    lib.vkrt_hit_surface.restype = C.c_int
     lib.vkrt_debug_read_node_masks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     lib.vkrt_debug_read_node_masks.restype = C.c_int
     lib.vkrt_debug_check_accel.argtypes = [C.c_void_p, P(AccelCheck)]

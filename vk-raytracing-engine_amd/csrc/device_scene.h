@@ -130,6 +130,13 @@ struct DevQueryScene : DevScene
   uint32_t cullMask;       // 0..0xFF, launch-uniform
   uint32_t rayFlags;       // VKRT_RAY_CULL_BACK_FACING / VKRT_RAY_CULL_FRONT_FACING or 0
 };
+// The scene of vkrt_hit_surface (k_hit_surface, surface.hip): a hit record names (instance, primitive), not a tree slot, so the kernel
+// resolves it as raytrace.rchit:34-50 does.  The table lives here, not in DevScene, whose layout every other kernel's arguments share.
+struct DevSurfaceScene : DevScene
+{
+  const uint4* primMeshes;  // per primitive-mesh: (firstIndex, vertexOffset, indexCount / 3, max(0, materialIndex)); fixed at vkrt_scene_create
+  uint32_t instanceCount;   // nodes of the scene: the bound of a record's instance
+};
 
 // a traversal could not keep a pending subtree (stack full) or ran into the step bound: the result may be wrong -> make it visible
 #define VKRT_TRAV_FAULT(sc) atomicAdd((sc).faults, 1ull)

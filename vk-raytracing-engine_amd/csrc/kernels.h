@@ -19,6 +19,9 @@ hipError_t vkrt_launch_query(const DevQueryScene& sc, const float4* rays, uint64
 // child nodes' bytes; a node of height h is exact after h passes, so sweeps >= the tree's levels gives the table without reading
 // anything back.  instCount bounds the instance ids of the records.
 hipError_t vkrt_launch_node_masks(const DevScene& sc, uint32_t nodeCount, uint32_t instCount, uint32_t sweeps, uint2* masks, hipStream_t stream);
+// shading inputs at hit records (surface.hip): n vkrt_hit records (2 float4 each) -> n vkrt_surface records (8 float4 each).  material:
+// the four texture taps and the material fields too, else the geometry alone.  Reads no tree.
+hipError_t vkrt_launch_hit_surface(const DevSurfaceScene& sc, const float4* hits, uint32_t n, bool material, float4* out, hipStream_t stream);
 
 // wavefront mode (wavefront.hip)
 struct WfTiming

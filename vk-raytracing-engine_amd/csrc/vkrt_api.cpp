@@ -105,6 +105,8 @@ struct vkrt_scene
   std::vector<vkrt_instance_visibility> vis;
   uint64_t masksPresent[4] = {0, 0, 0, 0};
   vkrt::DevBuf nodeMasks;  // wide8: the node-mask table of the current tree (8 B per node), allocated and computed with it
+  // vkrt_hit_surface: 16 B per primitive-mesh (device_scene.h DevSurfaceScene), uploaded at vkrt_scene_create, released with `allocs`
+  const uint4* surfacePrimMeshes = nullptr;
 };
 
 namespace {
@@ -423,6 +425,7 @@ int launchParams(const vkrt_scene* s, const PushConstantRay* pc, const GlobalUni
 }
 
 static_assert(sizeof(vkrt_ray) == 32 && sizeof(vkrt_hit) == 32, "k_query reads and writes 2 x 16 B per ray");
+static_assert(sizeof(vkrt_surface) == 128, "k_hit_surface writes 8 x 16 B per record");
 static_assert(sizeof(vkrt_instance_visibility) == 4 && sizeof(vkrt_query_opts) == 16, "include/vkrt.h");
 // vkrt_intersect / vkrt_occluded (and the _ex pair, whose options are checked by the caller): one k_query launch per 2^30 rays on the
 // caller's stream (query.hip); out = hits or occluded flags
@@ -551,6 +554,14 @@ int vkrt_scene_create(const vkrt_scene_desc* d, int device, vkrt_scene** out)
     D.vertexPN = (const float4*)pnDev;
   }
   if((rc = upload(s, d->lights, (size_t)d->light_count, &D.lights)) != VKRT_OK) return bail(rc);
+  // the primitive-mesh table of vkrt_hit_surface (rchit:34-40 per record: the tree's triShade has it per slot, a hit record has no slot)
+  {
+    std::vector<uint4> pm(d->prim_mesh_count);
+    for(uint32_t m = 0; m < d->prim_mesh_count; m++)
+      pm[m] = make_uint4(d->prim_meshes[m].firstIndex, d->prim_meshes[m].vertexOffset, d->prim_meshes[m].indexCount / 3u,
+                         (uint32_t)std::max(0, d->prim_meshes[m].materialIndex));
+    if((rc = upload(s, pm.data(), pm.size(), &s->surfacePrimMeshes)) != VKRT_OK) return bail(rc);
+  }
   // instances: object->world rows + inverse (gl_ObjectToWorldEXT / gl_WorldToObjectEXT, rchit:72-76)
   s->vis.assign(d->node_count, kDefaultVisibility);
   noteMasks(s);
@@ -1282,6 +1293,30 @@ int vkrt_occluded(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, uint32_t anyh
 {
   const vkrt_query_opts q = {sizeof(vkrt_query_opts), 0u, 0xFFu, anyhit_seed};
   return rayQuery(s, rays, n, q, occluded, true, hip_stream, "vkrt_occluded");
+}
+
+int vkrt_hit_surface(vkrt_scene* s, const vkrt_hit* hits, uint32_t n, uint32_t fields, vkrt_surface* out, void* hip_stream)
+{
+  if(!s)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_hit_surface: scene is NULL");
+  if(n && (!hits || !out))
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_hit_surface: NULL array");
+  if(n && ((((uintptr_t)hits | (uintptr_t)out) & 15u) != 0u))
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_hit_surface: misaligned array (hits and out: 16 bytes)");
+  if(fields != VKRT_SURFACE_GEOMETRY && fields != (VKRT_SURFACE_GEOMETRY | VKRT_SURFACE_MATERIAL))
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_hit_surface: fields 0x%x is neither VKRT_SURFACE_GEOMETRY nor VKRT_SURFACE_GEOMETRY | VKRT_SURFACE_MATERIAL", fields);
+  if(n == 0)
+    return VKRT_OK;
+  // (no checkBuilt: everything read here is kept current by vkrt_scene_update_nodes / vkrt_scene_update_vertices, the tree is not read)
+  const int rc = setDevice(s);
+  if(rc != VKRT_OK)
+    return rc;
+  DevSurfaceScene ss;
+  static_cast<DevScene&>(ss) = s->dev;
+  ss.primMeshes = s->surfacePrimMeshes;
+  ss.instanceCount = (uint32_t)s->nodes.size();
+  HIP_TRY(vkrt_launch_hit_surface(ss, (const float4*)hits, n, (fields & VKRT_SURFACE_MATERIAL) != 0u, (float4*)out, (hipStream_t)hip_stream));
+  return VKRT_OK;
 }
 
 int vkrt_intersect_ex(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, const vkrt_query_opts* opts, vkrt_hit* hits, void* hip_stream)

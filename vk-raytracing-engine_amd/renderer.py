@@ -78,6 +78,27 @@ class RayHits:
         self.instance, self.primitive, self.prim_mesh, self.triangle, self.material = (i[:, k] for k in range(3, 8))
 
 
+class Surfaces:
+    """Result of Renderer.surface: views of one [N, 32] 4-byte buffer laid out like vkrt_surface.  position, geometric_normal, normal,
+    shading_normal, tangent, binormal, base_color, emission: float32 [N, 3]; texcoord_u, texcoord_v, alpha, metallic, roughness:
+    float32 [N]; material, valid: int32 [N] (material = -1 and valid = 0 where the record was not a hit of the scene: all else 0)."""
+
+    def __init__(self, buffer):
+        import torch
+
+        self.buffer = buffer
+        f, i = buffer.view(torch.float32), buffer.view(torch.int32)
+        (self.position, self.geometric_normal, self.normal, self.shading_normal, self.tangent, self.binormal, self.base_color,
+         self.emission) = (f[:, 4 * k:4 * k + 3] for k in range(8))
+        self.texcoord_u, self.texcoord_v, self.alpha, self.metallic, self.roughness = (f[:, 4 * k + 3] for k in range(5))
+        self.material, self.valid, self.reserved = i[:, 23], i[:, 27], i[:, 31]
+
+    @property
+    def texcoord(self):
+        """[N, 2] view of (texcoord_u, texcoord_v): the two scalars sit four words apart in the record"""
+        return self.buffer.view(self.position.dtype)[:, 3:8:4]
+
+
 class Renderer:
     def __init__(self, flat, device=0, build="ploc", options=None):
         """options: {abi.VKRT_OPT_*: value} applied before the build (per-handle execution options, include/vkrt.h)."""
@@ -477,6 +498,38 @@ class Renderer:
             _check(self.lib.vkrt_occluded_ex(self._h, C.c_void_p(rays.data_ptr()), n, C.byref(opts), C.c_void_p(out.data_ptr()),
                                              C.c_void_p(stream.cuda_stream)), "vkrt_occluded_ex")
         return out.view(torch.int32)
+
+    def surface(self, hits, material=True, out=None, stream=None):
+        """Shading inputs at hit records (vkrt_hit_surface), enqueued on `stream` like intersect(): hits = a RayHits or a float32 /
+        int32 [N, 8] tensor of vkrt_hit records on the scene's device; material=False: the geometry alone (no texel is read, the
+        material fields are 0); out: an optional float32 / int32 [N, 32] buffer to write into.  Needs no tree: it works before
+        build() and between update_nodes / update_vertices and refit().  Returns a Surfaces of views of that buffer."""
+        import torch
+
+        buf = hits.buffer if isinstance(hits, RayHits) else hits
+        if not isinstance(buf, torch.Tensor):
+            raise VkrtError(f"surface: hits must be a RayHits or a torch tensor, got {type(hits).__name__}")
+        if not buf.is_cuda or buf.device.index != self.device:
+            raise VkrtError(f"surface: hits are on {buf.device}, the scene is on cuda:{self.device}")
+        if buf.dtype not in (torch.float32, torch.int32):
+            raise VkrtError(f"surface: hits are {buf.dtype}, expected torch.float32 or torch.int32")
+        if buf.dim() != 2 or buf.shape[1] != 8:
+            raise VkrtError(f"surface: hits have shape {tuple(buf.shape)}, expected [N, 8]")
+        if not buf.is_contiguous() or buf.data_ptr() % 16 != 0:
+            raise VkrtError("surface: hits must be contiguous and 16-byte aligned")
+        if buf.shape[0] >= 1 << 32:
+            raise VkrtError(f"surface: {buf.shape[0]} records, at most 2^32 - 1 per call")
+        n = int(buf.shape[0])
+        fields = abi.VKRT_SURFACE_GEOMETRY | (abi.VKRT_SURFACE_MATERIAL if material else 0)
+        if stream is None:
+            stream = torch.cuda.current_stream(buf.device)
+        if out is None:
+            with torch.cuda.stream(stream):
+                out = torch.empty((n, 32), dtype=torch.float32, device=buf.device)
+        self._query_out(out, (n, 32), "surface", 16)
+        _check(self.lib.vkrt_hit_surface(self._h, C.c_void_p(buf.data_ptr()), n, fields, C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)),
+               "vkrt_hit_surface")
+        return Surfaces(out)
 
     def trace_rays(self, origins, directions, tmin=0.001, tmax=10000.0, any_hit=False):
         o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
