@@ -434,6 +434,33 @@ typedef struct vkrt_query_opts {
 int vkrt_intersect_ex(vkrt_scene* scene, const vkrt_ray* rays, uint32_t n, const vkrt_query_opts* opts, vkrt_hit* hits, void* hip_stream);
 int vkrt_occluded_ex(vkrt_scene* scene, const vkrt_ray* rays, uint32_t n, const vkrt_query_opts* opts, int32_t* occluded, void* hip_stream);
 
+/* ---- multi-hit queries (the any-hit stage of traceRayEXT for a caller without callbacks: Embree's rtcIntersect with a collecting filter,
+ *      OptiX any-hit, trimesh's multiple_hits): the first max_hits candidates along each ray, in order.  Alpha cut-outs and ordered
+ *      blending from vkrt_surface.alpha, lidar multi-return, thickness sums and inside/outside parity need the hits behind the closest
+ *      one; re-tracing with tmin = t of the last hit skips a second surface at exactly that t (the interval is open).  This entry point
+ *      came after ABI version 4 without changing it or any existing struct: detect it by symbol. ------------------------------------
+ * Result: sort the candidates of ray i (the section above: cull mask, facing flags, the dissolve stage with opts->anyhit_seed unless
+ * VKRT_RAY_OPAQUE; the build's VKRT_OPT_WATERTIGHT applies) with t in the open interval (tmin, tmax) by the key (t, flattened triangle
+ * id).  counts[i] = min(max_hits, their number); hits[i * max_hits + j] for j < counts[i] is the j-th of them, with the eight fields
+ * vkrt_intersect writes; for j >= counts[i] it is the miss record of vkrt_intersect (t = tmax, u = v = 0, the five integers -1), so
+ * the whole buffer is defined.  A triangle appears at most once per ray, whatever VKRT_OPT_SPLIT_BUDGET made of it; two triangles at
+ * the same t (coincident faces, decals, doubled instances) both appear, the smaller id first.
+ * Consequences: with max_hits = 1 the call writes bit for bit what vkrt_intersect_ex writes.  The list is a property of the triangle
+ * set: the same under every builder, layout, split budget and scheduling option, and after a refit.  Rays that miss without a walk
+ * (tmin < 0, tmin >= tmax, a zero direction, a non-finite component) and every ray of a call with cull_mask = 0 have count 0.
+ * tmax = +inf is accepted.
+ * Memory and ordering are those of vkrt_intersect: `hits` is device memory, 16-byte aligned, n * max_hits records, ray-major (the
+ * product may pass 2^32: index it with 64 bits); `counts` is NULL or device memory, 4-byte aligned, n words.  The call is enqueued on
+ * hip_stream, allocates nothing, does not synchronise with the host; n may be any uint32_t; only vkrt_counters.traversal_faults may move.
+ * Errors, in this order: what vkrt_intersect_ex refuses of opts; max_hits == 0 or max_hits > VKRT_MULTIHIT_MAX:
+ * VKRT_ERR_INVALID_ARGUMENT; then the checks of vkrt_intersect in their order (a NULL scene; for n > 0 a NULL or misaligned rays or
+ * hits, a misaligned counts; n == 0: VKRT_OK, nothing is enqueued; VKRT_ERR_NOT_BUILT; VKRT_ERR_NO_DEVICE).
+ * Cost: every ray is walked on its own (no shared walk), once, as far as the t of its max_hits-th candidate -- or to tmax when it has
+ * fewer; the list lives in on-chip memory, 20 B x max_hits per ray in flight. */
+#define VKRT_MULTIHIT_MAX 16
+int vkrt_intersect_multi(vkrt_scene* scene, const vkrt_ray* rays, uint32_t n, const vkrt_query_opts* opts, uint32_t max_hits, vkrt_hit* hits,
+                         int32_t* counts, void* hip_stream);
+
 /* ---- shading inputs at the hits of ray queries (what raytrace.rchit:34-113 computes before its BRDF: attribute fetch, world
  *      transforms, tangent frame, the four texture() taps, normal mapping; Vulkan's hit attributes + buffer references, Embree's
  *      rtcInterpolate).  With vkrt_intersect and vkrt_occluded it is enough to write a path tracer outside the library.  This entry

@@ -20,6 +20,15 @@ also renders one bench frame, whose k_wf_shade time per record is the yardstick.
 library (csrc/Makefile VARIANT=...) in the same run, the two alternating call by call.
 
   python tools/query_probe.py --surface --out profiles/r06_surface_probe.json
+
+The multi-hit leg (--multi) times vkrt_intersect_multi (k_query_multi) for K = 1, 2, 4, 8, 16 on the camera rays (coherent) and their
+cosine bounces (incoherent) of the bench atrium against what a caller had to do without it: K passes of vkrt_intersect, pass j with
+tmin = the t of pass j - 1 (a ray that missed gets tmin = tmax and is not walked again).  The rays of every pass are prepared
+beforehand, so the peeling time is that of its K launches alone.  The two alternate call by call, an event pair around each, after
+warm-up calls of every shape; the medians are compared.  --multi-resources (no GPU) compiles multihit.hip with the flags of
+csrc/Makefile and records registers, scratch and static LDS of every k_query_multi instantiation next to the output.
+
+  python tools/query_probe.py --multi-resources && python tools/query_probe.py --multi --out profiles/r06_multihit_probe.json
 """
 import argparse
 import csv
@@ -356,6 +365,125 @@ def surface_leg(a):
         rr.close()
 
 
+# ---- the multi-hit leg -----------------------------------------------------------------------------------------------------------
+MULTI_KS = (1, 2, 4, 8, 16)
+MULTI_RESOURCES = os.path.join(ROOT, "profiles", "r06_multihit_kernel_resources.json")
+
+
+def multi_resources():
+    """Registers, scratch and static LDS of every k_query_multi instantiation from the compiler's metadata (cross-compiles: no GPU)."""
+    import re
+
+    csrc = os.path.join(ROOT, "vk-raytracing-engine_amd", "csrc")
+    tmp = tempfile.mkdtemp(prefix="multihit_isa_")
+    try:
+        asm = os.path.join(tmp, "multihit.s")
+        subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-mllvm",
+                        "-amdgpu-sched-strategy=max-memory-clause", "-fno-slp-vectorize", "--cuda-device-only", "-S", "-o", asm, "multihit.hip"],
+                       cwd=csrc, check=True, stderr=subprocess.DEVNULL)
+        text = open(asm).read()
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    kernels = {}
+    for block in text.split("  - .agpr_count:")[1:]:
+        f = {k: v for k, v in re.findall(r"\.(name|vgpr_count|sgpr_count|private_segment_fixed_size|group_segment_fixed_size|vgpr_spill_count):\s+(\S+)", block)}
+        m = re.match(r"_Z13k_query_multiILb([01])ELi(\d+)EE", f.get("name", ""))
+        if m:
+            kernels[f"{'wide8' if m.group(1) == '1' else 'bvh2'}_tm{m.group(2)}"] = {
+                "vgprs": int(f["vgpr_count"]), "sgprs": int(f["sgpr_count"]), "scratch_bytes": int(f["private_segment_fixed_size"]),
+                "vgpr_spills": int(f["vgpr_spill_count"]), "static_lds_bytes": int(f["group_segment_fixed_size"])}
+    out = {"kernels": kernels, "max_vgprs": max(k["vgprs"] for k in kernels.values()), "max_scratch_bytes": max(k["scratch_bytes"] for k in kernels.values()),
+           "dynamic_lds_bytes_per_wave": "256 x stack words of the tree (2 x (depth + 1) on the wide8 layout) + 1280 x max_hits"}
+    with open(MULTI_RESOURCES, "w") as fh:
+        json.dump(out, fh, indent=1)
+    print("wrote", MULTI_RESOURCES, json.dumps({k: out[k] for k in ("max_vgprs", "max_scratch_bytes")}))
+
+
+def multi_leg(a):
+    import torch
+    import atrium
+    import vkrt_amd
+    from vkrt_amd.renderer import Renderer, pack_rays
+
+    flat, _ = atrium.build_atrium(262144, seed=1, with_textures=False)
+    W, H = 1920, 1080
+    r = Renderer(flat, device=0, build=a.build)
+    info = r.accel_info()
+    sets = ray_sets(flat, dict(atrium.DEFAULT_CAMERA), W, H, r, a.seed)
+    result = {"source_hash": vkrt_amd.source_hash(), "scene": "atrium 262144 seed 1", "triangles": int(info["triangle_count"]), "build": a.build,
+              "device": torch.cuda.get_device_name(0), "warmup_calls": 3, "timed_calls_each": a.multi_calls,
+              "method": "device events around every call, multi-hit and peeling alternating; medians", "sets": {}}
+    if os.path.exists(MULTI_RESOURCES):
+        result["kernel_resources"] = json.load(open(MULTI_RESOURCES))
+    stack_words = 2 * (int(info["max_depth"]) + 1)
+    result["lds_bytes_per_wave"] = {str(k): 256 * stack_words + 1280 * k for k in MULTI_KS}
+    r.reset_counters()
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        return e0, e1
+
+    for name in ("camera", "diffuse"):
+        o, d, lo, hi = sets[name]
+        n = int(o.shape[0])
+        od, dd = torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda()
+        rays = pack_rays(od, dd, tmin=torch.from_numpy(lo).cuda(), tmax=torch.from_numpy(hi).cuda())
+        # the rays of every peeling pass, prepared beforehand
+        passes, cur = [], rays
+        alive = []
+        for _ in range(max(MULTI_KS)):
+            passes.append(cur)
+            h = r.intersect(cur)
+            hit = h.triangle >= 0
+            alive.append(int(hit.sum()))
+            nxt = cur.clone()
+            nxt[:, 3] = torch.where(hit, h.t, cur[:, 7])
+            cur = nxt
+        torch.cuda.synchronize()
+        single = torch.empty((n, 8), dtype=torch.float32, device="cuda:0")
+        entry = {"rays": n, "hits_per_peeling_pass": alive, "k": {}}
+        for k in MULTI_KS:
+            out = torch.empty((n, k, 8), dtype=torch.float32, device="cuda:0")
+            cnt = torch.empty((n,), dtype=torch.int32, device="cuda:0")
+            multi = lambda: r.intersect_multi(rays, k, out=out, counts=cnt)  # noqa: E731
+            peel = lambda: [r.intersect(passes[j], out=single) for j in range(k)]  # noqa: E731
+            for _ in range(3):
+                multi()
+                peel()
+            torch.cuda.synchronize()
+            ev = {"multi": [], "peel": []}
+            for _ in range(a.multi_calls):
+                ev["multi"].append(timed(multi))
+                ev["peel"].append(timed(peel))
+            torch.cuda.synchronize()
+            ms = {w: sorted(e0.elapsed_time(e1) for e0, e1 in ev[w]) for w in ev}
+            med = {w: ms[w][len(ms[w]) // 2] for w in ms}
+            returned = int(cnt.sum())
+            entry["k"][str(k)] = {"multi_ms": round(med["multi"], 4), "peel_ms": round(med["peel"], 4), "ratio_multi_over_peel": round(med["multi"] / med["peel"], 4),
+                                  "multi_ms_min_max": [round(ms["multi"][0], 4), round(ms["multi"][-1], 4)],
+                                  "peel_ms_min_max": [round(ms["peel"][0], 4), round(ms["peel"][-1], 4)],
+                                  "multi_mrays_per_s": round(n / med["multi"] * 1e-3, 1), "hits_returned": returned,
+                                  "multi_mhits_per_s": round(returned / med["multi"] * 1e-3, 1), "full_lists": int((cnt == k).sum())}
+            print(name, k, json.dumps(entry["k"][str(k)]), flush=True)
+        e = [timed(lambda: r.intersect(rays, out=single)) for _ in range(a.multi_calls)]
+        torch.cuda.synchronize()
+        one = sorted(e0.elapsed_time(e1) for e0, e1 in e)
+        entry["intersect_ms"] = round(one[len(one) // 2], 4)
+        entry["k1_over_intersect"] = round(entry["k"]["1"]["multi_ms"] / entry["intersect_ms"], 4)  # (reported, not gated: no shared walk)
+        result["sets"][name] = entry
+    result["traversal_faults"] = int(r.counters()["traversal_faults"])
+    result["required_ratio_le_1"] = {f"{name}_k{k}": result["sets"][name]["k"][str(k)]["ratio_multi_over_peel"] <= 1.0 for name in ("camera", "diffuse")
+                                     for k in (4, 8)}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(result, f, indent=1)
+    print("wrote", a.out, json.dumps(result["required_ratio_le_1"]))
+    r.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r06_query_probe.json"))
@@ -368,7 +496,18 @@ def main():
     ap.add_argument("--variant-lib", default=None, help="surface leg: a second build of the library to measure beside the product build")
     ap.add_argument("--variant-name", default="variant")
     ap.add_argument("--surface-child", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--multi", action="store_true", help="the vkrt_intersect_multi leg: multi-hit calls against peeling with vkrt_intersect")
+    ap.add_argument("--multi-calls", type=int, default=15, help="multi leg: timed calls of each kind per K and ray set")
+    ap.add_argument("--multi-resources", action="store_true", help="registers / scratch / LDS of k_query_multi from the compiler (no GPU)")
     a = ap.parse_args()
+    if a.multi_resources:
+        multi_resources()
+        return
+    if a.multi:
+        if a.out.endswith("r06_query_probe.json"):
+            a.out = os.path.join(ROOT, "profiles", "r06_multihit_probe.json")
+        multi_leg(a)
+        return
     if a.child:
         _child(a.child, a.reps)
         return

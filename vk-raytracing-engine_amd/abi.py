@@ -241,6 +241,7 @@ VKRT_INSTANCE_FACING_CULL_DISABLE, VKRT_INSTANCE_FLIP_FACING = 0x1, 0x2
 VKRT_RAY_OPAQUE, VKRT_RAY_CULL_BACK_FACING, VKRT_RAY_CULL_FRONT_FACING = 0x1, 0x10, 0x20
 VKRT_MEMORY_HOST, VKRT_MEMORY_DEVICE = 0, 1  # vkrt_memory
 VKRT_SURFACE_GEOMETRY, VKRT_SURFACE_MATERIAL = 0x1, 0x2  # vkrt_surface_fields
+VKRT_MULTIHIT_MAX = 16  # the largest max_hits of vkrt_intersect_multi
 
 # every symbol include/vkrt.h declares (tests check the built library exports them all)
 VKRT_SYMBOLS = [
@@ -264,6 +265,7 @@ VKRT_SYMBOLS = [
     "vkrt_scene_get_instance_visibility",
     "vkrt_intersect_ex",
     "vkrt_occluded_ex",
+    "vkrt_intersect_multi",
     "vkrt_hit_surface",
     "vkrt_shard_rows",
     "vkrt_pathtrace",
@@ -330,6 +332,9 @@ def declare_vkrt(lib):
     lib.vkrt_intersect_ex.restype = C.c_int
     lib.vkrt_occluded_ex.argtypes = [C.c_void_p, C.c_void_p, c_u, P(QueryOpts), C.c_void_p, C.c_void_p]
     lib.vkrt_occluded_ex.restype = C.c_int
+    # (rays, hits, counts: device pointers; counts may be NULL)
+    lib.vkrt_intersect_multi.argtypes = [C.c_void_p, C.c_void_p, c_u, P(QueryOpts), c_u, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vkrt_intersect_multi.restype = C.c_int
     # (hits, out: device pointers)
     lib.vkrt_hit_surface.argtypes = [C.c_void_p, C.c_void_p, c_u, c_u, C.c_void_p, C.c_void_p]
     lib.vkrt_hit_surface.restype = C.c_int

@@ -15,6 +15,11 @@ hipError_t vkrt_launch_eval_math(int op, unsigned n, const float* a, const float
 // ray-query filter (sc.cullMask / rayFlags / nodeMasks, VKRT_TM_FILTER); opaque: VKRT_RAY_OPAQUE (no any-hit dissolve stage).
 hipError_t vkrt_launch_query(const DevQueryScene& sc, const float4* rays, uint64_t n, uint32_t seed, bool filter, bool opaque, float4* hits, int* occ,
                              hipStream_t stream);
+// multi-hit ray queries (multihit.hip): the first maxHits (1..VKRT_MULTIHIT_MAX) candidates of every ray in the order (t, triangle id) into
+// hits (maxHits records of 2 float4 per ray, ray-major, miss records behind the count), their number into counts (may be NULL).  seed,
+// filter, opaque: as vkrt_launch_query.  Walks lane by lane; LDS per wave: the stack columns + 5 x maxHits x 64 words.
+hipError_t vkrt_launch_query_multi(const DevQueryScene& sc, const float4* rays, uint64_t n, uint32_t seed, bool filter, bool opaque, uint32_t maxHits,
+                                   float4* hits, int* counts, hipStream_t stream);
 // The node-mask table of a wide8 tree (query.hip): `sweeps` passes over all nodes, each node ORing its leaves' instance masks and its
 // child nodes' bytes; a node of height h is exact after h passes, so sweeps >= the tree's levels gives the table without reading
 // anything back.  instCount bounds the instance ids of the records.

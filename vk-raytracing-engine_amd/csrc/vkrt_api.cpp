@@ -474,6 +474,35 @@ int checkQueryOpts(const vkrt_query_opts* q, const char* who)
   return VKRT_OK;
 }
 
+// vkrt_intersect_multi after its options and max_hits are checked: the checks of rayQuery in their order, then one k_query_multi launch per
+// 2^30 rays on the caller's stream (multihit.hip)
+int rayQueryMulti(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, const vkrt_query_opts& q, uint32_t maxHits, vkrt_hit* hits, int32_t* counts,
+                  void* hip_stream, const char* who)
+{
+  if(!s)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
+  if(n && (!rays || !hits))
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: NULL array", who);
+  if(n && (((uintptr_t)rays & 15u) != 0u || ((uintptr_t)hits & 15u) != 0u || ((uintptr_t)counts & 3u) != 0u))
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: misaligned array (rays and hits: 16 bytes, counts: 4)", who);
+  if(n == 0)
+    return VKRT_OK;
+  int rc = checkBuilt(s, who);
+  if(rc != VKRT_OK)
+    return rc;
+  if((rc = setDevice(s)) != VKRT_OK)
+    return rc;
+  DevQueryScene qs;
+  static_cast<DevScene&>(qs) = s->dev;
+  qs.nodeMasks = s->nodeMasks.get<const uint2>();
+  qs.cullMask = q.cull_mask;
+  qs.rayFlags = q.ray_flags & (VKRT_RAY_CULL_BACK_FACING | VKRT_RAY_CULL_FRONT_FACING);
+  const bool filter = qs.rayFlags != 0u || !everyMaskMeets(s, q.cull_mask);  // (as rayQuery: only where it can change a result)
+  const bool opaque = (q.ray_flags & VKRT_RAY_OPAQUE) != 0u;
+  HIP_TRY(vkrt_launch_query_multi(qs, (const float4*)rays, n, q.anyhit_seed, filter, opaque, maxHits, (float4*)hits, counts, (hipStream_t)hip_stream));
+  return VKRT_OK;
+}
+
 // a node range [first, first + count) with its array: the checks vkrt_scene_set/get_instance_visibility share after their own
 int checkVisibilityRange(const vkrt_scene* s, uint32_t first, uint32_t count, const char* who)
 {
@@ -1329,6 +1358,17 @@ int vkrt_occluded_ex(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, const vkrt
 {
   const int rc = checkQueryOpts(opts, "vkrt_occluded_ex");
   return rc != VKRT_OK ? rc : rayQuery(s, rays, n, *opts, occluded, true, hip_stream, "vkrt_occluded_ex");
+}
+
+int vkrt_intersect_multi(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, const vkrt_query_opts* opts, uint32_t max_hits, vkrt_hit* hits,
+                         int32_t* counts, void* hip_stream)
+{
+  const int rc = checkQueryOpts(opts, "vkrt_intersect_multi");
+  if(rc != VKRT_OK)
+    return rc;
+  if(max_hits == 0u || max_hits > VKRT_MULTIHIT_MAX)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_intersect_multi: max_hits %u outside 1..%d (VKRT_MULTIHIT_MAX)", max_hits, VKRT_MULTIHIT_MAX);
+  return rayQueryMulti(s, rays, n, *opts, max_hits, hits, counts, hip_stream, "vkrt_intersect_multi");
 }
 
 int vkrt_scene_set_instance_visibility(vkrt_scene* s, uint32_t first, uint32_t count, const vkrt_instance_visibility* vis, void* hip_stream)

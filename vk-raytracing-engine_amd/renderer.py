@@ -78,6 +78,25 @@ class RayHits:
         self.instance, self.primitive, self.prim_mesh, self.triangle, self.material = (i[:, k] for k in range(3, 8))
 
 
+class MultiHits:
+    """Result of Renderer.intersect_multi: views of one [N, K, 8] 4-byte buffer of vkrt_hit records, K per ray in the order (t, triangle
+    id), and count, int32 [N]: how many of a ray's records are hits.  t, u, v: float32 [N, K]; instance, primitive, prim_mesh, triangle,
+    material: int32 [N, K].  Records behind a ray's count are misses (-1; t = tmax, u = v = 0)."""
+
+    def __init__(self, buffer, count):
+        import torch
+
+        self.buffer, self.count = buffer, count
+        f, i = buffer.view(torch.float32), buffer.view(torch.int32)
+        self.t, self.u, self.v = f[:, :, 0], f[:, :, 1], f[:, :, 2]
+        self.instance, self.primitive, self.prim_mesh, self.triangle, self.material = (i[:, :, k] for k in range(3, 8))
+
+    def flat(self):
+        """The same records as a RayHits over [N * K, 8] (a view, no copy): record i * K + j is hit j of ray i, so
+        Renderer.surface(h.flat()) is the surface of every returned hit."""
+        return RayHits(self.buffer.view(-1, 8))
+
+
 class Surfaces:
     """Result of Renderer.surface: views of one [N, 32] 4-byte buffer laid out like vkrt_surface.  position, geometric_normal, normal,
     shading_normal, tangent, binormal, base_color, emission: float32 [N, 3]; texcoord_u, texcoord_v, alpha, metallic, roughness:
@@ -477,6 +496,34 @@ class Renderer:
             _check(self.lib.vkrt_intersect_ex(self._h, C.c_void_p(rays.data_ptr()), n, C.byref(opts), C.c_void_p(out.data_ptr()),
                                               C.c_void_p(stream.cuda_stream)), "vkrt_intersect_ex")
         return RayHits(out)
+
+    def intersect_multi(self, rays, max_hits, seed=0, out=None, counts=None, stream=None, cull_mask=0xFF, ray_flags=0):
+        """The first max_hits (1..VKRT_MULTIHIT_MAX) hits along every ray in the order (t, triangle id) (vkrt_intersect_multi), enqueued
+        like intersect() and with its seed / cull_mask / ray_flags.  out: an optional float32 / int32 [N, max_hits, 8] buffer, counts: an
+        optional int32 [N] buffer to write into.  Returns a MultiHits of views of the two."""
+        import torch
+
+        n = self._query_args(rays, "intersect_multi")
+        if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or not 1 <= int(max_hits) <= abi.VKRT_MULTIHIT_MAX:
+            raise VkrtError(f"intersect_multi: max_hits must be an integer in 1..{abi.VKRT_MULTIHIT_MAX}, got {max_hits!r}")
+        k = int(max_hits)
+        opts = self._query_opts(cull_mask, ray_flags, seed, "intersect_multi")
+        if opts is None:
+            opts = abi.QueryOpts(C.sizeof(abi.QueryOpts), 0, 0xFF, int(seed) & 0xFFFFFFFF)
+        if stream is None:
+            stream = torch.cuda.current_stream(rays.device)
+        with torch.cuda.stream(stream):  # (allocated on the stream that writes them)
+            if out is None:
+                out = torch.empty((n, k, 8), dtype=torch.float32, device=rays.device)
+            if counts is None:
+                counts = torch.empty((n,), dtype=torch.int32, device=rays.device)
+        self._query_out(out, (n, k, 8), "intersect_multi", 16)
+        if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32:
+            raise VkrtError("intersect_multi: counts must be an int32 tensor")
+        self._query_out(counts, (n,), "intersect_multi", 4)
+        _check(self.lib.vkrt_intersect_multi(self._h, C.c_void_p(rays.data_ptr()), n, C.byref(opts), k, C.c_void_p(out.data_ptr()),
+                                             C.c_void_p(counts.data_ptr()), C.c_void_p(stream.cuda_stream)), "vkrt_intersect_multi")
+        return MultiHits(out, counts)
 
     def occluded(self, rays, seed=0, out=None, stream=None, cull_mask=0xFF, ray_flags=0):
         """1 where some hit lies in (tmin, tmax), else 0 (vkrt_occluded): int32 [N] (or `out`), enqueued like intersect(), with the
