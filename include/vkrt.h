@@ -461,6 +461,55 @@ int vkrt_occluded_ex(vkrt_scene* scene, const vkrt_ray* rays, uint32_t n, const 
 int vkrt_intersect_multi(vkrt_scene* scene, const vkrt_ray* rays, uint32_t n, const vkrt_query_opts* opts, uint32_t max_hits, vkrt_hit* hits,
                          int32_t* counts, void* hip_stream);
 
+/* ---- closest-point queries (Embree's rtcPointQuery, trimesh's nearest.on_surface, the distance query of collision and
+ *      signed-distance pipelines): per query the nearest point of the scene's surface to a point, within a radius.  Rays cannot
+ *      emulate it.  The result is a vkrt_hit, so vkrt_hit_surface turns it into position, normal and material with nothing in between
+ *      (signed distance: t with the sign of (point - position) . geometric_normal).  This entry point came after ABI version 4 without
+ *      changing it or any existing struct: detect it by symbol. -------------------------------------------------------------------
+ * The triangle: the one the ray tests see, (p0, p0 + e1, p0 + e2) with p0, e1, e2 the binary32 values of its record (vkrt_debug_read_accel:
+ * floats 0-2, 3-5, 6-8 of the 48-B record).  With VKRT_OPT_WATERTIGHT the record holds (p0, p1, p2), and e1 = p1 - p0, e2 = p2 - p0 are
+ * formed in binary32: the bits the default record stores, so a result does not depend on that option.
+ * The point/triangle function (Ericson, Real-Time Collision Detection 5.1.5) runs in binary64 on those binary32 inputs and the
+ * binary32 query point q: no contraction, source order, a dot product a . b = (ax * bx + ay * by) + az * bz.
+ *   ap = q - p0                d1 = e1 . ap    d2 = e2 . ap
+ *   bp = ap - e1               d3 = e1 . bp    d4 = e2 . bp
+ *   cp = ap - e2               d5 = e1 . cp    d6 = e2 . cp
+ *   vc = d1 * d4 - d3 * d2     vb = d5 * d2 - d1 * d6     va = d3 * d6 - d5 * d4
+ * The first of these rows whose condition holds gives the weights (u, v) of vertices 1 and 2:
+ *   1. d1 <= 0 && d2 <= 0                             (0, 0)
+ *   2. d3 >= 0 && d4 <= d3                            (1, 0)
+ *   3. vc <= 0 && d1 >= 0 && d3 <= 0                  (d1 / (d1 - d3), 0)
+ *   4. d6 >= 0 && d5 <= d6                            (0, 1)
+ *   5. vb <= 0 && d2 >= 0 && d6 <= 0                  (0, d2 / (d2 - d6))
+ *   6. va <= 0 && (d4 - d3) >= 0 && (d5 - d6) >= 0    w = (d4 - d3) / ((d4 - d3) + (d5 - d6));  (1 - w, w)
+ *   7. otherwise                                      den = 1 / ((va + vb) + vc);  (vb * den, vc * den)
+ * Then diff = (ap - u * e1) - v * e2 per component and dist2 = diff . diff.  A triangle whose dist2 is NaN is no candidate (a
+ * collinear triangle whose point falls through to row 7).  (Binary32 is not enough: on needle triangles it is wrong by 1e-2 of the
+ * scene's size; binary64 agrees with an 80-bit evaluation to 2e-11.)
+ * Result of query i: among the candidates -- triangles of instances with (mask & cull_mask) != 0 and dist2 < (double)radius * radius,
+ * the comparison strict -- the one with the smallest key (dist2, flattened triangle id).  Its record: t = sqrtf((float)dist2), the
+ * distance; u, v = (float)u, (float)v, as in every other vkrt_hit; the five integers as vkrt_intersect writes them.  Without a
+ * candidate: t = radius, u = v = 0, the five integers -1.  A query misses without a walk when a component of `point` is NaN or
+ * infinite, when radius is NaN, negative or 0, and when cull_mask is 0.  radius = +inf is accepted.
+ * The result is a property of the triangle set: the same under every builder, layout, split budget and scheduling option, and
+ * after a refit.  The walk prunes with a lower bound of the squared point/box distance that carries margins for the binary32
+ * rounding of the boxes, and keeps a box whose bound equals the best dist2, so an equally near triangle with a smaller id is found.
+ * Options: opts may be NULL = {sizeof(vkrt_query_opts), 0, 0xFF, 0}.  ray_flags must be 0 -- a point has no facing and no any-hit
+ * stage, so VKRT_OPT_ANYHIT_DISSOLVE never applies; anyhit_seed is ignored; cull_mask works as in vkrt_intersect_ex.
+ * Memory and ordering are those of vkrt_intersect: `queries` and `hits` are device memory on the scene's device, 16-byte aligned; the
+ * call is enqueued on hip_stream, allocates nothing, does not synchronise with the host; n may be any uint32_t; only
+ * vkrt_counters.traversal_faults may move.
+ * Errors, in this order: what vkrt_intersect_ex refuses of a non-NULL opts, and ray_flags != 0: VKRT_ERR_INVALID_ARGUMENT; then the
+ * checks of vkrt_intersect in their order (a NULL scene; for n > 0 a NULL or misaligned queries or hits; n == 0: VKRT_OK, nothing is
+ * enqueued; VKRT_ERR_NOT_BUILT, also on a stale tree; VKRT_ERR_NO_DEVICE).
+ * Cost: every query walks on its own, nearest box first; the triangle step is binary64. */
+typedef struct vkrt_point_query { /* 16 B */
+  float point[3];
+  float radius;       /* > 0, +inf allowed: only surface points nearer than this are found */
+} vkrt_point_query;
+int vkrt_closest_point(vkrt_scene* scene, const vkrt_point_query* queries, uint32_t n, const vkrt_query_opts* opts, vkrt_hit* hits,
+                       void* hip_stream);
+
 /* ---- shading inputs at the hits of ray queries (what raytrace.rchit:34-113 computes before its BRDF: attribute fetch, world
  *      transforms, tangent frame, the four texture() taps, normal mapping; Vulkan's hit attributes + buffer references, Embree's
  *      rtcInterpolate).  With vkrt_intersect and vkrt_occluded it is enough to write a path tracer outside the library.  This entry
@@ -690,6 +739,11 @@ int vkrt_debug_read_accel(vkrt_scene* scene, void* nodes, uint64_t nodes_bytes, 
  * child slot s (0 for an empty slot).  Other byte counts, a NULL pointer or a BVH2 tree: VKRT_ERR_INVALID_ARGUMENT; no tree:
  * VKRT_ERR_NOT_BUILT (a stale tree is read as it stands: a refit leaves the table valid). */
 int vkrt_debug_read_node_masks(vkrt_scene* scene, void* out, uint64_t bytes);
+/* The work of vkrt_closest_point on n queries of a HOST array (synchronises the device; a test hook like the other vkrt_debug_* calls):
+ * out[0] = nodes visited, out[1] = triangle records tested, summed over the queries, by an instrumented instantiation of the same
+ * walk.  opts and the order of errors as vkrt_closest_point; a NULL out: VKRT_ERR_INVALID_ARGUMENT. */
+int vkrt_debug_closest_point_work(vkrt_scene* scene, const vkrt_point_query* host_queries, uint32_t n, const vkrt_query_opts* opts,
+                                  uint64_t out[2]);
 /* Closest-hit query for n rays: o,d = vec3[n] host arrays; tmin/tmax scalars.
  * Writes t,u,v (float[n]) and the flattened triangle id gid (int32[n], -1 = miss). */
 int vkrt_debug_trace_rays(vkrt_scene* scene, uint32_t n, const float* origins,

@@ -197,6 +197,11 @@ class QueryOpts(C.Structure):
     _fields_ = [("struct_size", c_u), ("ray_flags", c_u), ("cull_mask", c_u), ("anyhit_seed", c_u)]
 
 
+# closest-point queries (vkrt_closest_point): records of a device array, 16 B each
+class PointQuery(C.Structure):
+    _fields_ = [("point", c_f * 3), ("radius", c_f)]
+
+
 # deforming meshes (vkrt_scene_update_vertices): the four arrays are host or device pointers, by `memory`
 class VertexUpdate(C.Structure):
     _fields_ = [("struct_size", c_u), ("first", c_u), ("count", c_u), ("memory", c_u), ("positions", C.c_void_p), ("normals", C.c_void_p),
@@ -266,6 +271,7 @@ VKRT_SYMBOLS = [
     "vkrt_intersect_ex",
     "vkrt_occluded_ex",
     "vkrt_intersect_multi",
+    "vkrt_closest_point",
     "vkrt_hit_surface",
     "vkrt_shard_rows",
     "vkrt_pathtrace",
@@ -286,6 +292,7 @@ VKRT_SYMBOLS = [
     "vkrt_debug_check_accel",
     "vkrt_debug_read_accel",
     "vkrt_debug_read_node_masks",
+    "vkrt_debug_closest_point_work",
     "vkrt_debug_trace_rays",
     "vkrt_debug_eval_math",
 ]
@@ -335,6 +342,12 @@ def declare_vkrt(lib):
     # (rays, hits, counts: device pointers; counts may be NULL)
     lib.vkrt_intersect_multi.argtypes = [C.c_void_p, C.c_void_p, c_u, P(QueryOpts), c_u, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.vkrt_intersect_multi.restype = C.c_int
+    # (queries, hits: device pointers; opts may be NULL)
+    lib.vkrt_closest_point.argtypes = [C.c_void_p, C.c_void_p, c_u, P(QueryOpts), C.c_void_p, C.c_void_p]
+    lib.vkrt_closest_point.restype = C.c_int
+    # (host queries)
+    lib.vkrt_debug_closest_point_work.argtypes = [C.c_void_p, C.c_void_p, c_u, P(QueryOpts), P(C.c_uint64)]
+    lib.vkrt_debug_closest_point_work.restype = C.c_int
     # (hits, out: device pointers)
     lib.vkrt_hit_surface.argtypes = [C.c_void_p, C.c_void_p, c_u, c_u, C.c_void_p, C.c_void_p]
     lib.vkrt_hit_surface.restype = C.c_int

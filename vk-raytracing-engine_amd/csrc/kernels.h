@@ -20,6 +20,11 @@ hipError_t vkrt_launch_query(const DevQueryScene& sc, const float4* rays, uint64
 // filter, opaque: as vkrt_launch_query.  Walks lane by lane; LDS per wave: the stack columns + 5 x maxHits x 64 words.
 hipError_t vkrt_launch_query_multi(const DevQueryScene& sc, const float4* rays, uint64_t n, uint32_t seed, bool filter, bool opaque, uint32_t maxHits,
                                    float4* hits, int* counts, hipStream_t stream);
+// closest-point queries (closest.hip): n queries (one float4 each: point + radius) -> the nearest surface point within the radius as a
+// vkrt_hit (2 float4 each; t = the distance).  filter: walk with sc.cullMask / sc.nodeMasks.  work != NULL: the instrumented kernel adds
+// (nodes visited, triangle records tested) to work[0..1].  Walks lane by lane; LDS per wave: the stack columns.
+hipError_t vkrt_launch_closest_point(const DevQueryScene& sc, const float4* queries, uint64_t n, bool filter, float4* hits, unsigned long long* work,
+                                     hipStream_t stream);
 // The node-mask table of a wide8 tree (query.hip): `sweeps` passes over all nodes, each node ORing its leaves' instance masks and its
 // child nodes' bytes; a node of height h is exact after h passes, so sweeps >= the tree's levels gives the table without reading
 // anything back.  instCount bounds the instance ids of the records.

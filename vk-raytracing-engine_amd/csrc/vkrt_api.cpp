@@ -424,6 +424,24 @@ int launchParams(const vkrt_scene* s, const PushConstantRay* pc, const GlobalUni
   return VKRT_OK;
 }
 
+// The trace set-up every query entry point shares once its own arguments are checked and n > 0: the tree can be traced, the scene's
+// device is current, and the walk's scene carries the call's options.  filter: the filtering walk is needed -- only where it can change
+// a result: a facing flag, or a cull mask that some node's mask misses.
+int querySetup(vkrt_scene* s, const vkrt_query_opts& q, const char* who, DevQueryScene& qs, bool& filter)
+{
+  int rc = checkBuilt(s, who);
+  if(rc != VKRT_OK)
+    return rc;
+  if((rc = setDevice(s)) != VKRT_OK)
+    return rc;
+  static_cast<DevScene&>(qs) = s->dev;
+  qs.nodeMasks = s->nodeMasks.get<const uint2>();
+  qs.cullMask = q.cull_mask;
+  qs.rayFlags = q.ray_flags & (VKRT_RAY_CULL_BACK_FACING | VKRT_RAY_CULL_FRONT_FACING);
+  filter = qs.rayFlags != 0u || !everyMaskMeets(s, q.cull_mask);
+  return VKRT_OK;
+}
+
 static_assert(sizeof(vkrt_ray) == 32 && sizeof(vkrt_hit) == 32, "k_query reads and writes 2 x 16 B per ray");
 static_assert(sizeof(vkrt_surface) == 128, "k_hit_surface writes 8 x 16 B per record");
 static_assert(sizeof(vkrt_instance_visibility) == 4 && sizeof(vkrt_query_opts) == 16, "include/vkrt.h");
@@ -439,18 +457,11 @@ int rayQuery(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, const vkrt_query_o
     return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: misaligned array (rays and hits: 16 bytes, occluded: 4)", who);
   if(n == 0)
     return VKRT_OK;
-  int rc = checkBuilt(s, who);
+  DevQueryScene qs;
+  bool filter;
+  const int rc = querySetup(s, q, who, qs, filter);
   if(rc != VKRT_OK)
     return rc;
-  if((rc = setDevice(s)) != VKRT_OK)
-    return rc;
-  DevQueryScene qs;
-  static_cast<DevScene&>(qs) = s->dev;
-  qs.nodeMasks = s->nodeMasks.get<const uint2>();
-  qs.cullMask = q.cull_mask;
-  qs.rayFlags = q.ray_flags & (VKRT_RAY_CULL_BACK_FACING | VKRT_RAY_CULL_FRONT_FACING);
-  // the filtering walk only where it can change a result: a facing flag, or a mask that some node's mask misses
-  const bool filter = qs.rayFlags != 0u || !everyMaskMeets(s, q.cull_mask);
   const bool opaque = (q.ray_flags & VKRT_RAY_OPAQUE) != 0u;
   HIP_TRY(vkrt_launch_query(qs, (const float4*)rays, n, q.anyhit_seed, filter, opaque, anyHit ? nullptr : (float4*)out, anyHit ? (int*)out : nullptr,
                             (hipStream_t)hip_stream));
@@ -487,19 +498,51 @@ int rayQueryMulti(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, const vkrt_qu
     return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: misaligned array (rays and hits: 16 bytes, counts: 4)", who);
   if(n == 0)
     return VKRT_OK;
-  int rc = checkBuilt(s, who);
+  DevQueryScene qs;
+  bool filter;
+  const int rc = querySetup(s, q, who, qs, filter);
   if(rc != VKRT_OK)
     return rc;
-  if((rc = setDevice(s)) != VKRT_OK)
-    return rc;
-  DevQueryScene qs;
-  static_cast<DevScene&>(qs) = s->dev;
-  qs.nodeMasks = s->nodeMasks.get<const uint2>();
-  qs.cullMask = q.cull_mask;
-  qs.rayFlags = q.ray_flags & (VKRT_RAY_CULL_BACK_FACING | VKRT_RAY_CULL_FRONT_FACING);
-  const bool filter = qs.rayFlags != 0u || !everyMaskMeets(s, q.cull_mask);  // (as rayQuery: only where it can change a result)
   const bool opaque = (q.ray_flags & VKRT_RAY_OPAQUE) != 0u;
   HIP_TRY(vkrt_launch_query_multi(qs, (const float4*)rays, n, q.anyhit_seed, filter, opaque, maxHits, (float4*)hits, counts, (hipStream_t)hip_stream));
+  return VKRT_OK;
+}
+
+static_assert(sizeof(vkrt_point_query) == 16, "k_closest_point reads 16 B per query");
+// the options of vkrt_closest_point: those of vkrt_intersect_ex (NULL = the defaults), and no ray flag -- a point has no facing and no
+// any-hit stage
+int checkPointOpts(const vkrt_query_opts* opts, const char* who, vkrt_query_opts& q)
+{
+  q = vkrt_query_opts{sizeof(vkrt_query_opts), 0u, 0xFFu, 0u};
+  if(!opts)
+    return VKRT_OK;
+  const int rc = checkQueryOpts(opts, who);
+  if(rc != VKRT_OK)
+    return rc;
+  if(opts->ray_flags != 0u)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: ray_flags 0x%x: a point query takes no ray flag", who, opts->ray_flags);
+  q = *opts;
+  return VKRT_OK;
+}
+
+// vkrt_closest_point after its options are checked: the checks of rayQuery in their order, then one k_closest_point launch per 2^30
+// queries on the caller's stream (closest.hip)
+int pointQuery(vkrt_scene* s, const vkrt_point_query* queries, uint32_t n, const vkrt_query_opts& q, vkrt_hit* hits, void* hip_stream, const char* who)
+{
+  if(!s)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
+  if(n && (!queries || !hits))
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: NULL array", who);
+  if(n && ((((uintptr_t)queries | (uintptr_t)hits) & 15u) != 0u))
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: misaligned array (queries and hits: 16 bytes)", who);
+  if(n == 0)
+    return VKRT_OK;
+  DevQueryScene qs;
+  bool filter;
+  const int rc = querySetup(s, q, who, qs, filter);
+  if(rc != VKRT_OK)
+    return rc;
+  HIP_TRY(vkrt_launch_closest_point(qs, (const float4*)queries, n, filter, (float4*)hits, nullptr, (hipStream_t)hip_stream));
   return VKRT_OK;
 }
 
@@ -1371,6 +1414,13 @@ int vkrt_intersect_multi(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, const 
   return rayQueryMulti(s, rays, n, *opts, max_hits, hits, counts, hip_stream, "vkrt_intersect_multi");
 }
 
+int vkrt_closest_point(vkrt_scene* s, const vkrt_point_query* queries, uint32_t n, const vkrt_query_opts* opts, vkrt_hit* hits, void* hip_stream)
+{
+  vkrt_query_opts q;
+  const int rc = checkPointOpts(opts, "vkrt_closest_point", q);
+  return rc != VKRT_OK ? rc : pointQuery(s, queries, n, q, hits, hip_stream, "vkrt_closest_point");
+}
+
 int vkrt_scene_set_instance_visibility(vkrt_scene* s, uint32_t first, uint32_t count, const vkrt_instance_visibility* vis, void* hip_stream)
 {
   const char* who = "vkrt_scene_set_instance_visibility";
@@ -1777,6 +1827,36 @@ int vkrt_debug_trace_rays(vkrt_scene* s, uint32_t n, const float* origins, const
   if(e == hipSuccess) tryHip(hipMemcpy(gid, dG.get(), b1, hipMemcpyDeviceToHost));
   if(e != hipSuccess)
     return fail(VKRT_ERR_HIP, "vkrt_debug_trace_rays: %s", hipGetErrorString(e));
+  return VKRT_OK;
+}
+
+int vkrt_debug_closest_point_work(vkrt_scene* s, const vkrt_point_query* host_queries, uint32_t n, const vkrt_query_opts* opts, uint64_t out[2])
+{
+  const char* who = "vkrt_debug_closest_point_work";
+  vkrt_query_opts q;
+  int rc = checkPointOpts(opts, who, q);
+  if(rc != VKRT_OK)
+    return rc;
+  if(!s || !out || (n && !host_queries))
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "NULL argument");
+  out[0] = out[1] = 0;
+  if(n == 0)
+    return VKRT_OK;
+  DevQueryScene qs;
+  bool filter;
+  if((rc = querySetup(s, q, who, qs, filter)) != VKRT_OK)
+    return rc;
+  vkrt::DevBuf dQ, dH, dW;
+  hipError_t e = hipSuccess;
+  auto tryHip = [&](hipError_t x) { if(e == hipSuccess) e = x; };
+  tryHip(dQ.alloc((size_t)n * sizeof(vkrt_point_query))); tryHip(dH.alloc((size_t)n * sizeof(vkrt_hit))); tryHip(dW.alloc(2 * sizeof(uint64_t)));
+  if(e == hipSuccess) tryHip(hipMemcpy(dQ.get(), host_queries, (size_t)n * sizeof(vkrt_point_query), hipMemcpyHostToDevice));
+  if(e == hipSuccess) tryHip(hipMemset(dW.get(), 0, 2 * sizeof(uint64_t)));
+  if(e == hipSuccess) tryHip(vkrt_launch_closest_point(qs, dQ.get<const float4>(), n, true, dH.get<float4>(), dW.get<unsigned long long>(), nullptr));
+  if(e == hipSuccess) tryHip(hipDeviceSynchronize());
+  if(e == hipSuccess) tryHip(hipMemcpy(out, dW.get(), 2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  if(e != hipSuccess)
+    return fail(VKRT_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
   return VKRT_OK;
 }
 

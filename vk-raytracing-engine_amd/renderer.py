@@ -546,6 +546,79 @@ class Renderer:
                                              C.c_void_p(stream.cuda_stream)), "vkrt_occluded_ex")
         return out.view(torch.int32)
 
+    # ---- closest-point queries (vkrt_closest_point) -------------------------------------------------------------------------------
+    def _point_args(self, points, radius, what):
+        """The float32 [N, 4] query tensor (point.xyz, radius) of a call: `points` itself when it is [N, 4], else [N, 3] points packed
+        with `radius` (a scalar or [N] values).  Refuses what intersect() refuses of its rays."""
+        import torch
+
+        if not isinstance(points, torch.Tensor):
+            raise VkrtError(f"{what}: points must be a torch tensor, got {type(points).__name__}")
+        if not points.is_cuda or points.device.index != self.device:
+            raise VkrtError(f"{what}: points are on {points.device}, the scene is on cuda:{self.device}")
+        if points.dtype != torch.float32:
+            raise VkrtError(f"{what}: points are {points.dtype}, expected torch.float32")
+        if points.dim() != 2 or points.shape[1] not in (3, 4):
+            raise VkrtError(f"{what}: points have shape {tuple(points.shape)}, expected [N, 4] or [N, 3]")
+        if points.shape[0] >= 1 << 32:
+            raise VkrtError(f"{what}: {points.shape[0]} points, at most 2^32 - 1 per call")
+        if points.shape[1] == 3:
+            n = int(points.shape[0])
+            r = torch.as_tensor(radius, dtype=torch.float32, device=points.device)
+            if r.dim() > 0 and r.numel() != n:
+                raise VkrtError(f"{what}: {r.numel()} radii for {n} points")
+            q = torch.empty((n, 4), dtype=torch.float32, device=points.device)
+            q[:, 0:3] = points
+            q[:, 3] = r.reshape(-1) if r.dim() > 0 else r
+            points = q
+        if not points.is_contiguous() or points.data_ptr() % 16 != 0:
+            raise VkrtError(f"{what}: points must be contiguous and 16-byte aligned")
+        return points
+
+    @staticmethod
+    def _point_opts(cull_mask, what):
+        if isinstance(cull_mask, bool) or not isinstance(cull_mask, (int, np.integer)) or not 0 <= int(cull_mask) <= 0xFF:
+            raise VkrtError(f"{what}: cull_mask must be an integer in 0..255, got {cull_mask!r}")
+        return None if int(cull_mask) == 0xFF else abi.QueryOpts(C.sizeof(abi.QueryOpts), 0, int(cull_mask), 0)
+
+    def closest_point(self, points, radius=float("inf"), out=None, stream=None, cull_mask=0xFF):
+        """The nearest point of the scene's surface to every query point, within its radius (vkrt_closest_point), enqueued like
+        intersect().  points: float32 [N, 4] (point.xyz, radius) on the scene's device, or [N, 3] with `radius` a scalar or [N] values;
+        cull_mask (0..255): against the masks of set_instance_visibility.  Returns a RayHits: t = the distance, (instance, primitive, u,
+        v) = the surface point -- what surface() takes -- and -1 / t = radius where nothing lies within the radius."""
+        import torch
+
+        q = self._point_args(points, radius, "closest_point")
+        n = int(q.shape[0])
+        opts = self._point_opts(cull_mask, "closest_point")
+        if stream is None:
+            stream = torch.cuda.current_stream(q.device)
+        if out is None:
+            with torch.cuda.stream(stream):  # (allocated on the stream that writes it)
+                out = torch.empty((n, 8), dtype=torch.float32, device=q.device)
+        self._query_out(out, (n, 8), "closest_point", 16)
+        _check(self.lib.vkrt_closest_point(self._h, C.c_void_p(q.data_ptr()), n, None if opts is None else C.byref(opts),
+                                           C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)), "vkrt_closest_point")
+        return RayHits(out)
+
+    def closest_point_work(self, points, radius=float("inf"), cull_mask=0xFF):
+        """Test hook (vkrt_debug_closest_point_work): the work of closest_point() on these queries -- host arrays, float32 [N, 4] or
+        [N, 3] with `radius` -- as (nodes visited, triangle records tested) in total.  Synchronises."""
+        p = np.asarray(points, np.float32)
+        if p.ndim != 2 or p.shape[1] not in (3, 4):
+            raise VkrtError(f"closest_point_work: points have shape {p.shape}, expected [N, 4] or [N, 3]")
+        if p.shape[1] == 3:
+            q = np.empty((p.shape[0], 4), np.float32)
+            q[:, 0:3] = p
+            q[:, 3] = np.asarray(radius, np.float32)
+            p = q
+        p = np.ascontiguousarray(p)
+        opts = self._point_opts(cull_mask, "closest_point_work")
+        work = (C.c_uint64 * 2)()
+        _check(self.lib.vkrt_debug_closest_point_work(self._h, p.ctypes.data, int(p.shape[0]), None if opts is None else C.byref(opts), work),
+               "vkrt_debug_closest_point_work")
+        return int(work[0]), int(work[1])
+
     def surface(self, hits, material=True, out=None, stream=None):
         """Shading inputs at hit records (vkrt_hit_surface), enqueued on `stream` like intersect(): hits = a RayHits or a float32 /
         int32 [N, 8] tensor of vkrt_hit records on the scene's device; material=False: the geometry alone (no texel is read, the
