@@ -3,12 +3,14 @@
 // the place of the ray/box test and Ericson's point/triangle function, evaluated in binary64, in the place of the ray/triangle test.
 // The result is the smallest key (dist2, flattened triangle id) over the candidates, a property of the triangle set: the walk prunes a
 // box only when its bound EXCEEDS the best dist2 so far, so an equally near triangle with a smaller id is still reached.
-// Functions of its own, lane by lane: the ray walks (traverse.h, traverse_wide.h) are not touched.
+// Functions of its own, lane by lane: the ray walks (traverse.h, traverse_wide.h) are not touched.  The BVH2 loop, the records and the
+// launch loop are those of query_common.h.
 #include <hip/hip_runtime.h>
 
 #include "device_math.h"
 #include "device_scene.h"
 #include "kernels.h"
+#include "query_common.h"
 #include "wf_streams.h"  // wfLoad
 #include "wide_node.h"
 
@@ -127,85 +129,25 @@ VKRT_DEV void cp_test_triangle(const DevQueryScene& sc, CpState& S, unsigned s)
   }
 }
 
-// BVH2: the loop of traverse.h (per-lane stack column in LDS), near child = smaller bound
+// BVH2: the lane walk of query_common.h, near child = smaller bound
 template <bool FILTER, bool COUNT>
 VKRT_DEV void cp_walk_bvh2(const DevQueryScene& sc, CpState& S, int* stk, int stride)
 {
-  const float4* __restrict__ nodes = sc.nodes;
-  const int cap = (int)sc.stackCap;
-  int cur = sc.rootRef;
-  int sp = 0;
-  while(cur != VKRT_TRAV_DONE)
-  {
-    while(cur >= 0)
-    {
-      if(--S.steps == 0u)
-      {
-        VKRT_TRAV_FAULT(sc);
-        return;
-      }
-      const float4 q0 = nodes[cur * VKRT_NODE_QUADS + 0];
-      const float4 q1 = nodes[cur * VKRT_NODE_QUADS + 1];
-      const float4 q2 = nodes[cur * VKRT_NODE_QUADS + 2];
-      const float4 q3 = nodes[cur * VKRT_NODE_QUADS + 3];
-      if(COUNT)
-        S.nodes++;
-      const float b0 = cp_bound(cp_gap(S.qx, q0.x, q0.w, VKRT_CP_PAD_ABS * fmaxf(fabsf(q0.x), fabsf(q0.w))),
-                                cp_gap(S.qy, q0.y, q1.x, VKRT_CP_PAD_ABS * fmaxf(fabsf(q0.y), fabsf(q1.x))),
-                                cp_gap(S.qz, q0.z, q1.y, VKRT_CP_PAD_ABS * fmaxf(fabsf(q0.z), fabsf(q1.y))));
-      const float b1 = cp_bound(cp_gap(S.qx, q1.z, q2.y, VKRT_CP_PAD_ABS * fmaxf(fabsf(q1.z), fabsf(q2.y))),
-                                cp_gap(S.qy, q1.w, q2.z, VKRT_CP_PAD_ABS * fmaxf(fabsf(q1.w), fabsf(q2.z))),
-                                cp_gap(S.qz, q2.x, q2.w, VKRT_CP_PAD_ABS * fmaxf(fabsf(q2.x), fabsf(q2.w))));
-      const bool h0 = !(b0 > S.d2Up), h1 = !(b1 > S.d2Up);
-      const int c0 = __float_as_int(q3.x), c1 = __float_as_int(q3.y);
-      if(h0 && h1)
-      {
-        const bool swap = b1 < b0;
-        const int nearC = swap ? c1 : c0, farC = swap ? c0 : c1;
-        if(sp < cap)
-        {
-          stk[sp * stride] = farC;
-          sp++;
-        }
-        else
-          VKRT_TRAV_FAULT(sc);
-        cur = nearC;
-      }
-      else if(h0)
-        cur = c0;
-      else if(h1)
-        cur = c1;
-      else
-      {
-        if(sp == 0)
-          cur = VKRT_TRAV_DONE;
-        else
-        {
-          sp--;
-          cur = stk[sp * stride];
-        }
-      }
-    }
-    if(cur != VKRT_TRAV_DONE)
-    {
-      if(--S.steps == 0u)
-      {
-        VKRT_TRAV_FAULT(sc);
-        return;
-      }
-      const unsigned code = ~(unsigned)cur;
-      const unsigned first = code >> 3, cnt = (code & 7u) + 1u;
-      for(unsigned k = 0; k < cnt; k++)
-        cp_test_triangle<FILTER, COUNT>(sc, S, first + k);
-      if(sp == 0)
-        cur = VKRT_TRAV_DONE;
-      else
-      {
-        sp--;
-        cur = stk[sp * stride];
-      }
-    }
-  }
+  bvh2_lane_walk(
+      sc, stk, stride, S.steps,
+      [&](float4 q0, float4 q1, float4 q2, bool& h0, bool& h1, float& b0, float& b1) {
+        if(COUNT)
+          S.nodes++;
+        b0 = cp_bound(cp_gap(S.qx, q0.x, q0.w, VKRT_CP_PAD_ABS * fmaxf(fabsf(q0.x), fabsf(q0.w))),
+                      cp_gap(S.qy, q0.y, q1.x, VKRT_CP_PAD_ABS * fmaxf(fabsf(q0.y), fabsf(q1.x))),
+                      cp_gap(S.qz, q0.z, q1.y, VKRT_CP_PAD_ABS * fmaxf(fabsf(q0.z), fabsf(q1.y))));
+        b1 = cp_bound(cp_gap(S.qx, q1.z, q2.y, VKRT_CP_PAD_ABS * fmaxf(fabsf(q1.z), fabsf(q2.y))),
+                      cp_gap(S.qy, q1.w, q2.z, VKRT_CP_PAD_ABS * fmaxf(fabsf(q1.w), fabsf(q2.z))),
+                      cp_gap(S.qz, q2.x, q2.w, VKRT_CP_PAD_ABS * fmaxf(fabsf(q2.x), fabsf(q2.w))));
+        h0 = !(b0 > S.d2Up);
+        h1 = !(b1 > S.d2Up);
+      },
+      [&](unsigned s) { cp_test_triangle<FILTER, COUNT>(sc, S, s); });
 }
 
 #define VKRT_CP_SWAP(i, j)                     \
@@ -341,8 +283,8 @@ VKRT_DEV void cp_walk_wide8(const DevQueryScene& sc, CpState& S, uint2* stk, int
 }
 #undef VKRT_CP_SWAP
 
-// One thread per query, one wave per workgroup.  queries: one float4 each (point, radius); hits: 2 float4 each (vkrt_hit, as k_query writes
-// it, t = the distance).  Queries [first, n).  Dynamic LDS: the stack columns (sc.stackCap x 64 words).  work (COUNT): two totals, nodes
+// One thread per query, one wave per workgroup.  queries: one float4 each (point, radius); hits: 2 float4 each (vkrt_hit, query_common.h
+// query_write_hit, t = the distance).  Queries [first, n).  Dynamic LDS: the stack columns (sc.stackCap x 64 words).  work (COUNT): two totals, nodes
 // visited and triangle records tested.
 template <bool WIDE, bool FILTER, bool COUNT>
 __global__ __launch_bounds__(64)
@@ -371,17 +313,9 @@ void k_closest_point(const DevQueryScene sc, const float4* __restrict__ queries,
       cp_walk_bvh2<FILTER, COUNT>(sc, S, lds_closest + threadIdx.x, 64);
   }
   if(valid && S.slot >= 0)
-  {
-    const float4 c = sc.tris[(size_t)S.slot * VKRT_TRI_QUADS + 2];  // (e2.z, gid | non-opaque flag, instance, primitive)
-    const int inst = __float_as_int(c.z);
-    hits[2 * i] = make_float4(sqrtf((float)S.d2), S.u, S.v, __int_as_float(inst));
-    hits[2 * i + 1] = make_float4(c.w, __int_as_float(sc.instances[inst].primMesh), __int_as_float(S.gid), __uint_as_float(sc.triShade[S.slot].w));
-  }
+    query_write_hit(sc, hits + 2 * i, sqrtf((float)S.d2), S.u, S.v, S.slot, S.gid);
   else
-  {
-    hits[2 * i] = make_float4(q.w, 0.0f, 0.0f, __int_as_float(-1));
-    hits[2 * i + 1] = make_float4(__int_as_float(-1), __int_as_float(-1), __int_as_float(-1), __int_as_float(-1));
-  }
+    query_write_miss(hits + 2 * i, q.w);
   if(COUNT)
   {
     atomicAdd(work, (unsigned long long)S.nodes);
@@ -390,18 +324,14 @@ void k_closest_point(const DevQueryScene sc, const float4* __restrict__ queries,
 }
 
 // n queries from `queries` into hits.  filter: walk with the cull mask (sc.cullMask, sc.nodeMasks).  work != NULL: the instrumented
-// instantiation adds its totals there.  Chunking as vkrt_launch_query: grids of at most 2^24 workgroups (2^30 queries) per launch.
+// instantiation adds its totals there.
 hipError_t vkrt_launch_closest_point(const DevQueryScene& sc, const float4* queries, uint64_t n, bool filter, float4* hits, unsigned long long* work,
                                      hipStream_t stream)
 {
   const size_t lds = (size_t)sc.stackCap * 64 * sizeof(int);
   const bool wide = sc.layout == 1u;
-  const uint64_t chunk = 1ull << 30;
-  for(uint64_t first = 0; first < n; first += chunk)
-  {
-    const uint64_t end = n - first < chunk ? n : first + chunk;
-    const dim3 g((unsigned)((end - first + 63) / 64)), b(64);
-#define VKRT_CP(W, F, C) hipLaunchKernelGGL((k_closest_point<W, F, C>), g, b, lds, stream, sc, queries, first, end, hits, work)
+  return query_launch_chunks(n, [&](uint64_t first, uint64_t end, dim3 g) {
+#define VKRT_CP(W, F, C) hipLaunchKernelGGL((k_closest_point<W, F, C>), g, dim3(64), lds, stream, sc, queries, first, end, hits, work)
     if(work)
     {
       // (one instrumented kernel per layout, with the filter: a cull mask every node meets walks as the unfiltered kernel does)
@@ -416,9 +346,5 @@ hipError_t vkrt_launch_closest_point(const DevQueryScene& sc, const float4* quer
       if(filter) VKRT_CP(false, true, false); else VKRT_CP(false, false, false);
     }
 #undef VKRT_CP
-    const hipError_t e = hipGetLastError();
-    if(e != hipSuccess)
-      return e;
-  }
-  return hipSuccess;
+  });
 }

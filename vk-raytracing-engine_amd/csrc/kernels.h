@@ -10,6 +10,8 @@ hipError_t vkrt_launch_trace_rays(const DevScene& sc, unsigned n, const float* o
                                   float* t, float* u, float* v, int* gid, hipStream_t stream);
 hipError_t vkrt_launch_eval_math(int op, unsigned n, const float* a, const float* b, float* out, hipStream_t stream);
 
+// The three query launches below run one thread per item in chunks of at most 2^30 items (query_common.h query_launch_chunks) and return
+// the first launch error; the ray queries pick their triangle mode there too (query_tri_mode, VKRT_QUERY_TM_SWITCH).
 // ray queries (query.hip): n caller rays (2 float4 each: origin + tmin, direction + tmax) -> closest hits (2 float4 each, vkrt_hit) when
 // hits != NULL, otherwise occluded flags (one int each) into occ.  seed = the any-hit stage's payload seed.  filter: walk with the
 // ray-query filter (sc.cullMask / rayFlags / nodeMasks, VKRT_TM_FILTER); opaque: VKRT_RAY_OPAQUE (no any-hit dissolve stage).

@@ -1,24 +1,18 @@
 // query.hip -- batched ray queries on caller rays (vkrt_intersect / vkrt_occluded, include/vkrt.h): the traversal kernel of the
 // wavefront pipeline (wf_traverse.hip) reading vkrt_ray records and writing vkrt_hit records instead of path-record streams.
 // Built with the flags of wf_traverse.hip (csrc/Makefile) for the same reasons: the walks are the same code.
+// What it shares with multihit.hip and closest.hip -- the invalid-ray rule, the records, the mode dispatch, the launch loop: query_common.h.
 #include <hip/hip_runtime.h>
 
 #include "device_math.h"
 #include "device_scene.h"
 #include "kernels.h"
+#include "query_common.h"
 #include "traverse.h"
 #include "traverse_wide.h"
 #include "traverse_share.h"
 #include "wf_streams.h"  // wfLoad
 #include "wide_node.h"
-
-// A ray the walks never see: tmin < 0, tmin >= tmax (NaN bounds included), a zero direction, a NaN or infinite origin or direction component
-VKRT_DEV bool queryRayValid(float4 r0, float4 r1)
-{
-  const bool finite = isfinite(r0.x) && isfinite(r0.y) && isfinite(r0.z) && isfinite(r1.x) && isfinite(r1.y) && isfinite(r1.z);
-  const bool nonzero = r1.x != 0.0f || r1.y != 0.0f || r1.z != 0.0f;
-  return finite && nonzero && r0.w >= 0.0f && r0.w < r1.w;
-}
 
 // One thread per ray, one wave per workgroup.  rays: 2 float4 per ray (origin, tmin) (direction, tmax); hits: 2 float4 per ray
 // (t, u, v, instance) (primitive, prim_mesh, triangle, material) as int bits; occ: one int per ray (ANYHIT).  Rays [first, n).
@@ -72,63 +66,29 @@ void k_query(const DevQueryScene sc, const float4* __restrict__ rays, uint64_t f
     return;
   }
   if(found)
-  {
-    const float4 c = sc.tris[(size_t)hit.slot * VKRT_TRI_QUADS + 2];  // (e2.z, gid | non-opaque flag, instance, primitive)
-    const int inst = __float_as_int(c.z);
-    hits[2 * i] = make_float4(hit.t, hit.u, hit.v, __int_as_float(inst));
-    hits[2 * i + 1] = make_float4(c.w, __int_as_float(sc.instances[inst].primMesh), __int_as_float(__float_as_int(c.y) & 0x7fffffff),
-                                  __uint_as_float(sc.triShade[hit.slot].w));
-  }
+    query_write_hit(sc, hits + 2 * i, hit.t, hit.u, hit.v, hit.slot, __float_as_int(sc.tris[(size_t)hit.slot * VKRT_TRI_QUADS + 2].y) & 0x7fffffff);
   else
-  {
-    hits[2 * i] = make_float4(r1.w, 0.0f, 0.0f, __int_as_float(-1));
-    hits[2 * i + 1] = make_float4(__int_as_float(-1), __int_as_float(-1), __int_as_float(-1), __int_as_float(-1));
-  }
+    query_write_miss(hits + 2 * i, r1.w);
 }
 
-// n rays from `rays`; hits != NULL: closest hit, else occluded flags into occ.  Grids of at most 2^24 workgroups (2^30 rays) per launch.
-// VKRT_RAY_OPAQUE on a scene built with the dissolve stage: the records carry its flag in their id words, so the walk masks it
-// (VKRT_TM_MASKID) and ignores nothing.
+// n rays from `rays`; hits != NULL: closest hit, else occluded flags into occ.
 hipError_t vkrt_launch_query(const DevQueryScene& sc, const float4* rays, uint64_t n, uint32_t seed, bool filter, bool opaque, float4* hits, int* occ,
                              hipStream_t stream)
 {
   const size_t lds = (size_t)sc.stackCap * 64 * sizeof(int);
   const bool wide = sc.layout == 1u, anyHit = hits == nullptr;
-  const int tm = (sc.watertight ? VKRT_TM_WATERTIGHT : 0) | (sc.dissolve ? (opaque ? VKRT_TM_MASKID : VKRT_TM_DISSOLVE) : 0) |
-                 (filter ? VKRT_TM_FILTER : 0);
-  const uint64_t chunk = 1ull << 30;
-  for(uint64_t first = 0; first < n; first += chunk)
-  {
-    const uint64_t end = n - first < chunk ? n : first + chunk;
-    const dim3 g((unsigned)((end - first + 63) / 64)), b(64);
-#define VKRT_Q(A, W, TM) hipLaunchKernelGGL((k_query<A, W, TM>), g, b, lds, stream, sc, rays, first, end, seed, hits, occ)
-#define VKRT_Q_MODES(A, W)                              \
-  do {                                                  \
-    switch(tm)                                          \
-    {                                                   \
-      case 0: VKRT_Q(A, W, 0); break;                   \
-      case 1: VKRT_Q(A, W, 1); break;                   \
-      case 2: VKRT_Q(A, W, 2); break;                   \
-      case 3: VKRT_Q(A, W, 3); break;                   \
-      case 4: VKRT_Q(A, W, 4); break;                   \
-      case 5: VKRT_Q(A, W, 5); break;                   \
-      case 8: VKRT_Q(A, W, 8); break;                   \
-      case 9: VKRT_Q(A, W, 9); break;                   \
-      case 10: VKRT_Q(A, W, 10); break;                 \
-      case 11: VKRT_Q(A, W, 11); break;                 \
-      case 12: VKRT_Q(A, W, 12); break;                 \
-      default: VKRT_Q(A, W, 13); break;                 \
-    }                                                   \
+  const int tm = query_tri_mode(sc, filter, opaque);
+  return query_launch_chunks(n, [&](uint64_t first, uint64_t end, dim3 g) {
+#define VKRT_Q(A, W, TM) hipLaunchKernelGGL((k_query<A, W, TM>), g, dim3(64), lds, stream, sc, rays, first, end, seed, hits, occ)
+#define VKRT_Q_TM(TM)                                                          \
+  do {                                                                         \
+    if(anyHit) { if(wide) VKRT_Q(true, true, TM); else VKRT_Q(true, false, TM); } \
+    else { if(wide) VKRT_Q(false, true, TM); else VKRT_Q(false, false, TM); }  \
   } while(0)
-    if(anyHit) { if(wide) VKRT_Q_MODES(true, true); else VKRT_Q_MODES(true, false); }
-    else { if(wide) VKRT_Q_MODES(false, true); else VKRT_Q_MODES(false, false); }
-#undef VKRT_Q_MODES
+    VKRT_QUERY_TM_SWITCH(tm, VKRT_Q_TM);
+#undef VKRT_Q_TM
 #undef VKRT_Q
-    const hipError_t e = hipGetLastError();
-    if(e != hipSuccess)
-      return e;
-  }
-  return hipSuccess;
+  });
 }
 
 // One pass of the node-mask table over every node of a wide8 tree (layout: wide_node.h): byte s of node k = OR of the instance masks of

@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -445,22 +446,39 @@ int querySetup(vkrt_scene* s, const vkrt_query_opts& q, const char* who, DevQuer
 static_assert(sizeof(vkrt_ray) == 32 && sizeof(vkrt_hit) == 32, "k_query reads and writes 2 x 16 B per ray");
 static_assert(sizeof(vkrt_surface) == 128, "k_hit_surface writes 8 x 16 B per record");
 static_assert(sizeof(vkrt_instance_visibility) == 4 && sizeof(vkrt_query_opts) == 16, "include/vkrt.h");
+// The argument checks every query entry point starts with, in this order: the scene, then (n > 0) an array that is NULL, then an array
+// that is misaligned.  alignText: the call's list of alignments as its message shows it.
+struct QueryArray
+{
+  const void* p;
+  unsigned align;  // bytes, a power of two
+  bool mayBeNull;
+};
+int checkQueryArrays(const vkrt_scene* s, const char* who, uint32_t n, std::initializer_list<QueryArray> arrays, const char* alignText)
+{
+  if(!s)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
+  if(n == 0)
+    return VKRT_OK;
+  for(const QueryArray& a : arrays)
+    if(!a.p && !a.mayBeNull)
+      return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: NULL array", who);
+  for(const QueryArray& a : arrays)
+    if(((uintptr_t)a.p & (a.align - 1u)) != 0u)
+      return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: misaligned array %s", who, alignText);
+  return VKRT_OK;
+}
+
 // vkrt_intersect / vkrt_occluded (and the _ex pair, whose options are checked by the caller): one k_query launch per 2^30 rays on the
 // caller's stream (query.hip); out = hits or occluded flags
 int rayQuery(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, const vkrt_query_opts& q, void* out, bool anyHit, void* hip_stream, const char* who)
 {
-  if(!s)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
-  if(n && (!rays || !out))
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: NULL array", who);
-  if(n && (((uintptr_t)rays & 15u) != 0u || (!anyHit && ((uintptr_t)out & 15u) != 0u) || (anyHit && ((uintptr_t)out & 3u) != 0u)))
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: misaligned array (rays and hits: 16 bytes, occluded: 4)", who);
-  if(n == 0)
-    return VKRT_OK;
+  int rc = checkQueryArrays(s, who, n, {{rays, 16u, false}, {out, anyHit ? 4u : 16u, false}}, "(rays and hits: 16 bytes, occluded: 4)");
+  if(rc != VKRT_OK || n == 0)
+    return rc;
   DevQueryScene qs;
   bool filter;
-  const int rc = querySetup(s, q, who, qs, filter);
-  if(rc != VKRT_OK)
+  if((rc = querySetup(s, q, who, qs, filter)) != VKRT_OK)
     return rc;
   const bool opaque = (q.ray_flags & VKRT_RAY_OPAQUE) != 0u;
   HIP_TRY(vkrt_launch_query(qs, (const float4*)rays, n, q.anyhit_seed, filter, opaque, anyHit ? nullptr : (float4*)out, anyHit ? (int*)out : nullptr,
@@ -485,23 +503,17 @@ int checkQueryOpts(const vkrt_query_opts* q, const char* who)
   return VKRT_OK;
 }
 
-// vkrt_intersect_multi after its options and max_hits are checked: the checks of rayQuery in their order, then one k_query_multi launch per
-// 2^30 rays on the caller's stream (multihit.hip)
+// vkrt_intersect_multi after its options and max_hits are checked: one k_query_multi launch per 2^30 rays on the caller's stream
+// (multihit.hip)
 int rayQueryMulti(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, const vkrt_query_opts& q, uint32_t maxHits, vkrt_hit* hits, int32_t* counts,
                   void* hip_stream, const char* who)
 {
-  if(!s)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
-  if(n && (!rays || !hits))
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: NULL array", who);
-  if(n && (((uintptr_t)rays & 15u) != 0u || ((uintptr_t)hits & 15u) != 0u || ((uintptr_t)counts & 3u) != 0u))
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: misaligned array (rays and hits: 16 bytes, counts: 4)", who);
-  if(n == 0)
-    return VKRT_OK;
+  int rc = checkQueryArrays(s, who, n, {{rays, 16u, false}, {hits, 16u, false}, {counts, 4u, true}}, "(rays and hits: 16 bytes, counts: 4)");
+  if(rc != VKRT_OK || n == 0)
+    return rc;
   DevQueryScene qs;
   bool filter;
-  const int rc = querySetup(s, q, who, qs, filter);
-  if(rc != VKRT_OK)
+  if((rc = querySetup(s, q, who, qs, filter)) != VKRT_OK)
     return rc;
   const bool opaque = (q.ray_flags & VKRT_RAY_OPAQUE) != 0u;
   HIP_TRY(vkrt_launch_query_multi(qs, (const float4*)rays, n, q.anyhit_seed, filter, opaque, maxHits, (float4*)hits, counts, (hipStream_t)hip_stream));
@@ -525,22 +537,15 @@ int checkPointOpts(const vkrt_query_opts* opts, const char* who, vkrt_query_opts
   return VKRT_OK;
 }
 
-// vkrt_closest_point after its options are checked: the checks of rayQuery in their order, then one k_closest_point launch per 2^30
-// queries on the caller's stream (closest.hip)
+// vkrt_closest_point after its options are checked: one k_closest_point launch per 2^30 queries on the caller's stream (closest.hip)
 int pointQuery(vkrt_scene* s, const vkrt_point_query* queries, uint32_t n, const vkrt_query_opts& q, vkrt_hit* hits, void* hip_stream, const char* who)
 {
-  if(!s)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
-  if(n && (!queries || !hits))
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: NULL array", who);
-  if(n && ((((uintptr_t)queries | (uintptr_t)hits) & 15u) != 0u))
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: misaligned array (queries and hits: 16 bytes)", who);
-  if(n == 0)
-    return VKRT_OK;
+  int rc = checkQueryArrays(s, who, n, {{queries, 16u, false}, {hits, 16u, false}}, "(queries and hits: 16 bytes)");
+  if(rc != VKRT_OK || n == 0)
+    return rc;
   DevQueryScene qs;
   bool filter;
-  const int rc = querySetup(s, q, who, qs, filter);
-  if(rc != VKRT_OK)
+  if((rc = querySetup(s, q, who, qs, filter)) != VKRT_OK)
     return rc;
   HIP_TRY(vkrt_launch_closest_point(qs, (const float4*)queries, n, filter, (float4*)hits, nullptr, (hipStream_t)hip_stream));
   return VKRT_OK;
@@ -1369,19 +1374,15 @@ int vkrt_occluded(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, uint32_t anyh
 
 int vkrt_hit_surface(vkrt_scene* s, const vkrt_hit* hits, uint32_t n, uint32_t fields, vkrt_surface* out, void* hip_stream)
 {
-  if(!s)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_hit_surface: scene is NULL");
-  if(n && (!hits || !out))
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_hit_surface: NULL array");
-  if(n && ((((uintptr_t)hits | (uintptr_t)out) & 15u) != 0u))
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_hit_surface: misaligned array (hits and out: 16 bytes)");
+  int rc = checkQueryArrays(s, "vkrt_hit_surface", n, {{hits, 16u, false}, {out, 16u, false}}, "(hits and out: 16 bytes)");
+  if(rc != VKRT_OK)
+    return rc;
   if(fields != VKRT_SURFACE_GEOMETRY && fields != (VKRT_SURFACE_GEOMETRY | VKRT_SURFACE_MATERIAL))
     return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_hit_surface: fields 0x%x is neither VKRT_SURFACE_GEOMETRY nor VKRT_SURFACE_GEOMETRY | VKRT_SURFACE_MATERIAL", fields);
   if(n == 0)
     return VKRT_OK;
   // (no checkBuilt: everything read here is kept current by vkrt_scene_update_nodes / vkrt_scene_update_vertices, the tree is not read)
-  const int rc = setDevice(s);
-  if(rc != VKRT_OK)
+  if((rc = setDevice(s)) != VKRT_OK)
     return rc;
   DevSurfaceScene ss;
   static_cast<DevScene&>(ss) = s->dev;
