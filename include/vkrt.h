@@ -264,6 +264,12 @@ enum vkrt_option {
                                    (rotated buildings: 0.70-0.82; axis-aligned and finely tessellated scenes: 0.95-1.08) -- two or three
                                    builds of ~13 ms instead of one; VKRT_INFO_SPLIT_BUDGET reports the outcome.  env VKRT_SPLIT_BUDGET */
   VKRT_OPT_LAST            = 14,
+  VKRT_OPT_WF_SAMPLE_SYNC  = 15, /* (appended within ABI 4; VKRT_OPT_LAST keeps naming the last option every ABI-4 library has)  1 (default) = the wavefront
+                                   path tracer keeps all pixels of a frame on the same sample: a path whose sample ends waits, 16 B of state per
+                                   pixel and frame in flight, until a kernel of its own starts the next sample of every pixel in 8x8-tile order,
+                                   so camera rays are traced and their hits shaded as whole tiles; 0 = a pixel starts its next sample in the
+                                   round its sample ends.  Same paths, draws and float operations: no pixel and no counter changes; a timed
+                                   call's shade_ms includes the sample starts.  env VKRT_WF_SAMPLE_SYNC */
   VKRT_INFO_ANYHIT_ORDER   = 100, /* read-only (vkrt_scene_get_option; set is refused): the child-order bits (2 | 4) that the last vkrt_accel_build
                                    resolved VKRT_OPT_WF_SHARE_FLAGS to, i.e. what bit 3 ("automatic") decided for this scene; 0 before a build */
   VKRT_INFO_SPLIT_BUDGET   = 101  /* read-only (ABI 4): the pre-splitting budget the last vkrt_accel_build used -- what VKRT_OPT_SPLIT_BUDGET = -1
@@ -571,8 +577,8 @@ uint32_t vkrt_shard_rows(const vkrt_shard* shard); /* rows of the shard's buffer
  * than every earlier one) grows the working set lazily: one hipStreamSynchronize + hipMalloc inside that call. */
 int vkrt_reserve(vkrt_scene* scene, const vkrt_shard* shard, void* hip_stream);
 /* The same for a caller that knows how many frames it hands to one vkrt_pathtrace_frames call (ABI 4).  The working set holds one
- * set of path-record streams (544 B per pixel of the shard) per frame the library keeps in flight inside a call, plus a 16-B staging
- * plane per pixel and frame in flight: frames_per_call = 1 (a client of vkrt_pathtrace only) sizes it for ONE set -- 1.1 GB at
+ * set of path-record streams (544 B per pixel of the shard) and a 16-B sample-state record per pixel (VKRT_OPT_WF_SAMPLE_SYNC) per frame
+ * the library keeps in flight inside a call, plus a 16-B staging plane per pixel and frame in flight: frames_per_call = 1 (a client of vkrt_pathtrace only) sizes it for ONE set -- 1.1 GB at
  * 1920x1080, 4.5 GB at 3840x2160 --, frames_per_call >= VKRT_OPT_WF_FRAMES_IN_FLIGHT (default 3) for that many: 3.5 GB / 14 GB.
  * vkrt_reserve is vkrt_reserve_frames with frames_per_call = VKRT_OPT_WF_FRAMES_IN_FLIGHT, i.e. the larger figure whatever the
  * client goes on to call.  The working set only grows (a later, larger call or reservation re-allocates it once); it is released by

@@ -162,6 +162,7 @@ struct DevCounters
 #define VKRT_TRACE_PUBLIC_FLAGS 0xFu
 #define VKRT_FLAG_SKIP_DEAD_SHADOW 0x100u  // VKRT_OPT_SKIP_DEAD_SHADOW_RAYS: a diffuse hit whose contribution is exactly zero emits no shadow ray
 #define VKRT_FLAG_STORE_STAGED 0x200u      // frames in flight: `image` is the frame's staging plane; storePixel writes the pixel value unblended
+#define VKRT_FLAG_SAMPLE_SYNC 0x400u       // VKRT_OPT_WF_SAMPLE_SYNC: all pixels of a frame trace sample s before any starts sample s + 1 (wavefront.hip)
 
 struct TraceParams
 {
@@ -182,7 +183,7 @@ struct TraceParams
 };
 
 // Wavefront-mode working set (wavefront.hip): six record streams [parity][type] of SoA float4 planes + their counts, once per
-// frame group (frames in flight), and the staging plane of each group.
+// frame group (frames in flight), the staging plane of each group and the per-pixel sample state of each group.
 struct WfBuffers
 {
   unsigned* ctrl;       // stream counts [parity * 4 + type]; 64 words per lane
@@ -190,4 +191,6 @@ struct WfBuffers
   float4* stage;        // [group][capacity]: pixel values of a frame in flight, shard-local image layout (groups > 1 only)
   uint32_t capacity;    // paths (pixels of the shard, rounded up to whole 8x8 tiles)
   uint32_t groups;      // frame groups the allocation holds
+  float4* sampleState;  // [group][capacity]: (hitValues.xyz, seed) of a pixel between two of its samples, tile-major pixel index of the
+                        // shard (VKRT_FLAG_SAMPLE_SYNC; last member: the fields above keep their kernel-argument offsets)
 };

@@ -124,28 +124,38 @@ VKRT_DEV void segmentTerms(const LaneState& L, f3& contrib, f3& nextWeight)
   nextWeight = L.curWeight * L.prd.weight;
 }
 
-// raytrace.rgen:99-120 -- accumulate the segment, advance depth / sample.  Returns false when the
-// pixel is complete (its value has been stored).
-VKRT_DEV bool advanceSegment(const TraceParams& P, LaneState& L, bool shadowHit, f3 contrib, f3 nextWeight)
+// raytrace.rgen:99-120 -- accumulate the segment, advance depth / sample, up to the point where the next sample would start.
+enum SegmentStep
+{
+  SEG_PIXEL_DONE = 0,  // the pixel is complete (its value has been stored)
+  SEG_CONTINUE = 1,    // the sample goes on with its next segment
+  SEG_SAMPLE_END = 2   // the sample is in hitValues and smpl names the next one, which the caller starts (startSample)
+};
+VKRT_DEV SegmentStep stepSegment(const TraceParams& P, LaneState& L, bool shadowHit, f3 contrib, f3 nextWeight)
 {
   L.stage = 0;
   if(!shadowHit)  // rgen:99-102
     L.hitValue = L.hitValue + contrib;
   L.curWeight = nextWeight;  // rgen:115
   L.prd.depth++;
-  if(!(L.prd.depth < (uint32_t)P.pc.depth))
-  {
-    L.hitValues = L.hitValues + L.hitValue;
-    L.smpl++;
-    if(L.smpl < P.pc.samples)
-      startSample(P, L);
-    else
-    {
-      storePixel(P, L);
-      return false;
-    }
-  }
-  return true;
+  if(L.prd.depth < (uint32_t)P.pc.depth)
+    return SEG_CONTINUE;
+  L.hitValues = L.hitValues + L.hitValue;
+  L.smpl++;
+  if(L.smpl < P.pc.samples)
+    return SEG_SAMPLE_END;
+  storePixel(P, L);
+  return SEG_PIXEL_DONE;
+}
+
+// stepSegment for a path that walks through its samples at its own pace: the next sample starts at once.  Returns false when the
+// pixel is complete (its value has been stored).
+VKRT_DEV bool advanceSegment(const TraceParams& P, LaneState& L, bool shadowHit, f3 contrib, f3 nextWeight)
+{
+  const SegmentStep step = stepSegment(P, L, shadowHit, contrib, nextWeight);
+  if(step == SEG_SAMPLE_END)
+    startSample(P, L);
+  return step != SEG_PIXEL_DONE;
 }
 
 VKRT_DEV bool accumulateAndAdvance(const TraceParams& P, LaneState& L, bool shadowHit)

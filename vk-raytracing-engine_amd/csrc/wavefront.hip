@@ -30,6 +30,14 @@
 //
 // A frame = init + samples * (depth + 1) x (traverse, shade) enqueued back to back on the caller's
 // stream; stream counts stay on the device (no host synchronisation inside a frame).
+//
+// Sample-synchronous schedule (VKRT_OPT_WF_SAMPLE_SYNC, VKRT_FLAG_SAMPLE_SYNC).  A sample takes at most depth + 1 rounds, so the
+// round count above already lets every pixel of a frame trace sample s in the rounds [s (depth + 1), (s + 1) (depth + 1)): a path
+// whose sample ends leaves (hitValues, seed) in its pixel's sample-state record instead of starting the next sample at once, and
+// k_wf_sample_init starts sample s of ALL pixels in front of round s (depth + 1), in tile order like k_wf_init.  The camera rays of
+// a sample are then traced as whole 8x8 tiles per wave instead of scattered among bounce rays of every depth, and their hits are
+// shaded 64 neighbouring pixels to a wave.  Paths, random draws and float operations are those of the other schedule (option 0:
+// pixels walk through their samples at their own pace); only the round in which a ray is traced changes.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdlib>
@@ -102,6 +110,29 @@ VKRT_DEV void storeShadow(const WfBuffers& B, int parity, int type, unsigned i, 
   wfStore(rec(B, parity, type, WF_S3, i), make_float4(contrib.x, contrib.y, contrib.z, 0.0f));
 }
 
+// tile-major index of the lane's pixel in the shard (tile * 64 + inTile of k_wf_init): its sample-state record
+VKRT_DEV unsigned pixelSlot(const TraceParams& P, const LaneState& L)
+{
+  return (((L.lrow >> 3) * P.tilesX + (L.px >> 3)) << 6) | ((L.lrow & 7u) << 3) | (L.px & 7u);
+}
+
+// rgen:99-120 for a segment of the path tracer that is complete (no shadow ray, or the ray is back): the stream the path's next
+// record goes to -- WF_C, or -1 when the pixel is stored or, in the sample-synchronous schedule, waits for k_wf_sample_init
+VKRT_DEV int finishSegment(const TraceParams& P, const WfBuffers& B, LaneState& L, bool shadowHit, f3 contrib, f3 nextWeight)
+{
+  const SegmentStep step = stepSegment(P, L, shadowHit, contrib, nextWeight);
+  if(step == SEG_SAMPLE_END)
+  {
+    if(P.flags & VKRT_FLAG_SAMPLE_SYNC)  // launch-uniform
+    {
+      wfStore(B.sampleState + pixelSlot(P, L), make_float4(L.hitValues.x, L.hitValues.y, L.hitValues.z, __uint_as_float(L.prd.seed)));
+      return -1;
+    }
+    startSample(P, L);
+  }
+  return step == SEG_PIXEL_DONE ? -1 : WF_C;
+}
+
 // Block-aggregated slot assignment in the next round's streams: ballot + popcount inside each wave, wave totals
 // combined through LDS, ONE global atomic per workgroup and stream (the count is a single word: per-wave atomics
 // serialise near 88/us, MI355X_MICROARCH.md "dequeue").  Must be called by every thread of the block; `to` = the stream the
@@ -171,6 +202,48 @@ __global__ __launch_bounds__(WF_BLOCK) void k_wf_init(const TraceParams P, const
   __shared__ unsigned long long red[VKRT_COUNTER_STRIDE * (WF_BLOCK / 64)];
   const unsigned vals[6] = {0, 0, 0, 0, 0, nPixels};
   blockAddCounters(&P.counters->v[blockIdx.x % VKRT_COUNTER_SLOTS][0], vals, 6, red);
+}
+
+// ---- sample init (sample-synchronous schedule): raytrace.rgen:42-60 of sample `smpl` >= 1 for every pixel of the shard ----------
+// The twin of k_wf_init, in front of round `round` = smpl * (depth + 1): one thread per pixel in tile order, so a wave is one 8x8
+// tile.  The C stream of the round's parity is empty here: the traversal launch of round - 1 cleared its count and no path of
+// sample smpl - 1 emitted a record in the shade step of round - 1 (every one of them had ended its sample by then).
+// prd.isSpecular is not part of the sample state.  The other schedule carries the bit of the previous sample's last segment into
+// the new sample, but nothing reads it there: at depth 0 the emission rule of the hit shader (`depth == 0 || isSpecular`, rchit:83)
+// holds whatever the bit says and closestHitTail sets it on both of its branches; a miss leaves it alone but sets depth 100, which
+// decides the shadow-ray test (rgen:79) by itself and ends the sample, so the bit reaches the next sample's depth 0 unread again.
+__global__ __launch_bounds__(WF_BLOCK) void k_wf_sample_init(const TraceParams P, const WfBuffers B, const int round, const int smpl)
+{
+  const unsigned lane = lane_id();
+  const unsigned w = blockIdx.x * blockDim.x + threadIdx.x;  // tile-major work index
+  bool alive = false;
+  LaneState L;
+  if(w < P.tileCount * 64u)
+  {
+    const unsigned tile = P.tileFirst + (w >> 6), inTile = w & 63u;
+    const uint32_t x = (tile % P.tilesX) * 8u + (inTile & 7u);
+    const uint32_t lrow = (tile / P.tilesX) * 8u + (inTile >> 3);
+    if(x < P.fullW && lrow < P.localRows && globalRow(P, lrow) < P.fullH)
+    {
+      const float4 st = wfLoad(B.sampleState + (tile * 64u + inTile));  // == pixelSlot: written once, read once
+      L.px = x; L.lrow = lrow;
+      L.prd.seed = __float_as_uint(st.w);
+      L.prd.isSpecular = false;
+      L.prd.lightDist = 0.0f;
+      L.prd.shadowRayDir = mk3(0.0f);
+      float origin[4];
+      mat4MulVec4(P.viewInverse, 0.0f, 0.0f, 0.0f, 1.0f, origin);
+      L.camOrigin = mk3(origin[0], origin[1], origin[2]);
+      L.hitValues = mk3(st.x, st.y, st.z);
+      L.smpl = smpl;
+      startSample(P, L);
+      alive = true;
+    }
+  }
+  __shared__ unsigned wsum[WF_TYPES * (WF_BLOCK / 64 + 1)];
+  const unsigned slot = claimSlots(B, round & 1, alive ? WF_C : -1, lane, wsum);
+  if(alive)
+    storeClosest(B, round & 1, slot, L);
 }
 
 // ---- hybrid mode: the GI path of raytraceHybrid.rgen:172-282 on the same streams ----------------------------------------------
@@ -294,7 +367,7 @@ VKRT_DEV void shadeHitBlock(const TraceParams& P, const WfBuffers& B, const Hybr
     else if(HYBRID)
       to = advanceSegmentHybrid(P, G, L, false, contrib, nextWeight, 0.0f) ? WF_C : -1;
     else
-      to = advanceSegment(P, L, false, contrib, nextWeight) ? WF_C : -1;
+      to = finishSegment(P, B, L, false, contrib, nextWeight);
   }
   const unsigned slot = claimSlots(B, par ^ 1, to, lane, wsum);
   if(to == WF_C)
@@ -322,13 +395,13 @@ VKRT_DEV void shadeShadowBlock(const TraceParams& P, const WfBuffers& B, const H
   {
     loadCommon(P, B, par, WF_S, qi, L);  // S0 holds the weight after this segment
     const float4 h = wfLoad(rec(B, par, WF_S, WF_H0, qi)), s3 = wfLoad(rec(B, par, WF_S, WF_S3, qi));
-    L.prd.rayOrigin = mk3(0.0f);     // the sample ends here: startSample sets the next ray, or the pixel is stored
+    L.prd.rayOrigin = mk3(0.0f);     // the sample ends here: startSample sets the next ray (now, or in k_wf_sample_init), or the pixel is stored
     L.prd.rayDirection = mk3(0.0f);
     const bool shadowHit = __float_as_int(h.w) >= 0;
     if(HYBRID)
       toClosest = advanceSegmentHybrid(P, G, L, shadowHit, mk3(s3.x, s3.y, s3.z), L.curWeight, L.prd.depth == 1u ? wfLoad(rec(B, par, WF_S, WF_R1, qi)).w : 0.0f);
     else
-      toClosest = advanceSegment(P, L, shadowHit, mk3(s3.x, s3.y, s3.z), L.curWeight);
+      toClosest = finishSegment(P, B, L, shadowHit, mk3(s3.x, s3.y, s3.z), L.curWeight) == WF_C;
   }
   const unsigned slot = claimSlots(B, par ^ 1, toClosest ? WF_C : -1, lane, wsum);
   if(toClosest)
@@ -457,7 +530,8 @@ __global__ __launch_bounds__(WF_BLOCK) void k_wf_blend(const TraceParams P, cons
 size_t vkrt_wf_state_bytes(uint32_t pathCapacity, int groups)
 {
   const size_t g = (size_t)std::max(groups, 1);
-  return g * pathCapacity * 2 * WF_SLOTS * sizeof(float4) + (g > 1 ? g * pathCapacity * sizeof(float4) : 0) + WF_CTRL_BYTES;
+  return g * pathCapacity * 2 * WF_SLOTS * sizeof(float4) + (g > 1 ? g * pathCapacity * sizeof(float4) : 0) + g * pathCapacity * sizeof(float4) +
+         WF_CTRL_BYTES;  // streams + staging planes + sample-state planes + counts
 }
 
 void vkrt_wf_carve(void* base, uint32_t pathCapacity, int groups, WfBuffers* B)
@@ -469,6 +543,8 @@ void vkrt_wf_carve(void* base, uint32_t pathCapacity, int groups, WfBuffers* B)
   B->planes = (float4*)p;
   p += g * pathCapacity * 2 * WF_SLOTS * sizeof(float4);
   B->stage = g > 1 ? (float4*)p : nullptr;
+  p += g > 1 ? g * pathCapacity * sizeof(float4) : 0;
+  B->sampleState = (float4*)p;
   B->capacity = pathCapacity;
   B->groups = (uint32_t)g;
 }
@@ -507,6 +583,22 @@ static void subframeRound(const TraceParams& P, const WfBuffers& B, int r, unsig
   hipLaunchKernelGGL(k_wf_shade, dim3((work + WF_BLOCK - 1) / WF_BLOCK + 3), dim3(WF_BLOCK), 0, stream, P, B, r);
 }
 
+// The launches of a frame between its begin and its blend, in order: the rounds, and in the sample-synchronous schedule one sample
+// init in front of the first round of every sample but the first (whose camera rays subframeBegin made).
+static bool sampleSync(const TraceParams& P) { return (P.flags & VKRT_FLAG_SAMPLE_SYNC) != 0u; }
+static int subframeSteps(const TraceParams& P) { return subframeRounds(P) + ((sampleSync(P) && subframeRounds(P) > 0) ? P.pc.samples - 1 : 0); }
+static void subframeStep(const TraceParams& P, const WfBuffers& B, int step, unsigned travBlock, bool count, hipStream_t stream, WfTiming* timing)
+{
+  if(!sampleSync(P))
+    return subframeRound(P, B, step, travBlock, count, stream, timing);
+  const int perSample = P.pc.depth + 2;  // sample init + depth + 1 rounds; step + 1: as if sample 0 had an init of its own at step -1
+  const int s = (step + 1) / perSample, k = (step + 1) % perSample;
+  if(k != 0)
+    return subframeRound(P, B, s * (P.pc.depth + 1) + k - 1, travBlock, count, stream, timing);
+  const unsigned work = P.tileCount * 64u;
+  hipLaunchKernelGGL(k_wf_sample_init, dim3((work + WF_BLOCK - 1) / WF_BLOCK), dim3(WF_BLOCK), 0, stream, P, B, s * (P.pc.depth + 1), s);
+}
+
 // parameters of frame k of a call (progressive frames of an unchanged camera: main.cpp:503-508, hello_vulkan.cpp:1501-1521)
 static TraceParams frameParams(const TraceParams& P, int k, uint32_t seedStep)
 {
@@ -529,14 +621,14 @@ hipError_t vkrt_launch_wavefront(const TraceParams& P, const WfBuffers& B, const
                                  hipStream_t stream, WfTiming* timing, const WfAsync* async)
 {
   const unsigned travBlock = opt.travBlock == 256 ? 256u : opt.travBlock == 128 ? 128u : 64u;
-  const int rounds = subframeRounds(P);
+  const int steps = subframeSteps(P);  // launches of a frame between its begin and its blend: the rounds and the sample inits
   frames = std::max(frames, 1);
   // Lanes: F frame groups x S tile ranges.  Frames in flight keep every launch at full size, sub-frames cut it into S pieces -- and
   // what overlaps well on this device is few, large launches (profiles/r04_experiments.md #110: two or three full-size lanes reach
   // 0.96-0.97 of linear on a 4K / 8 shard, three third-size lanes 0.90, four quarter-size lanes 0.77): a call with several frames
   // runs them in flight, one lane each; a single frame is split into sub-frames.  Per-kernel timing wants the kernels one after
   // another; tiny frames are not worth splitting.
-  int F = (timing || !async || rounds == 0) ? 1 : std::min(balancedInFlight(frames, opt.inFlight), (int)B.groups);
+  int F = (timing || !async || steps == 0) ? 1 : std::min(balancedInFlight(frames, opt.inFlight), (int)B.groups);
   F = std::max(1, std::min(F, async ? std::min(VKRT_WF_MAX_LANES, async->count) : 1));
   int S = (timing || !async || F > 1) ? 1 : std::max(1, std::min(std::min(VKRT_WF_MAX_LANES, opt.subframes), async->count));
   S = (int)std::min<uint32_t>((uint32_t)S, std::max(1u, P.tileCount / 256u));
@@ -549,7 +641,7 @@ hipError_t vkrt_launch_wavefront(const TraceParams& P, const WfBuffers& B, const
       TraceParams Q = frameParams(P, k, seedStep);
       Q.tileFirst = 0;
       if((e = subframeBegin(Q, B, stream)) != hipSuccess) return e;
-      for(int r = 0; r < rounds; r++) subframeRound(Q, B, r, travBlock, count, stream, timing);
+      for(int r = 0; r < steps; r++) subframeStep(Q, B, r, travBlock, count, stream, timing);
     }
     return hipGetLastError();
   }
@@ -570,6 +662,7 @@ hipError_t vkrt_launch_wavefront(const TraceParams& P, const WfBuffers& B, const
     Bq[q].ctrl = B.ctrl + 64 * q;
     Bq[q].planes = B.planes + (size_t)g * groupQuads + (size_t)2 * WF_SLOTS * ((size_t)tile0[q] * 64u);
     Bq[q].stage = staged ? B.stage + (size_t)g * B.capacity : nullptr;
+    Bq[q].sampleState = B.sampleState + (size_t)g * B.capacity;  // indexed by the pixel's tile in the shard: no offset per tile range
     Bq[q].capacity = tileN[q] * 64u;
     Bq[q].groups = 1;
     laneStream[q] = async->streams[q];
@@ -601,13 +694,13 @@ hipError_t vkrt_launch_wavefront(const TraceParams& P, const WfBuffers& B, const
     }
     forked = q + 1;
   }
-  // Items of a lane's m-th frame: 0 = begin, 1..rounds = the rounds, rounds + 1 = ordered blend (frames in flight only).  The host
+  // Items of a lane's m-th frame: 0 = begin, 1..steps = the rounds and sample inits (subframeStep), steps + 1 = ordered blend (frames in flight only).  The host
   // deals the items of all lanes round-robin -- item i of every lane before item i + 1 of any: enqueueing one lane's hundreds of
   // launches after the other's makes the later lanes start milliseconds late (profiles/r03_experiments.md #106).  The blend of
   // frame k waits for the blend of frame k - 1 (same tiles, another lane) through an event of the pool, one per (frame, tile
   // range), so no record call ever replaces one that still has a wait to come; a lane whose blend would wait for a record the
   // host has not made yet is skipped for a turn (hipStreamWaitEvent refers to the record calls made BEFORE it).
-  const int items = rounds + 1 + (staged ? 1 : 0);
+  const int items = steps + 1 + (staged ? 1 : 0);
   hipEvent_t* evBlend = async->pool;  // [frame k][tile range j]
   int laneFrames[VKRT_WF_MAX_LANES], cursor[VKRT_WF_MAX_LANES];
   std::vector<char> blendRecorded(staged ? (size_t)frames * S : 0, 0);
@@ -640,8 +733,8 @@ hipError_t vkrt_launch_wavefront(const TraceParams& P, const WfBuffers& B, const
       {
         if((e = subframeBegin(Q, Bq[q], st)) != hipSuccess) break;
       }
-      else if(it <= rounds)
-        subframeRound(Q, Bq[q], it - 1, travBlock, count, st, nullptr);
+      else if(it <= steps)
+        subframeStep(Q, Bq[q], it - 1, travBlock, count, st, nullptr);
       else
       {
         // the frame's pixels are staged: blend them into the image behind the blend of frame k - 1
