@@ -193,6 +193,45 @@ def test_gpu_hybrid_sharded_equals_whole_frame(small_scene):
     r.close()
 
 
+@pytest.mark.gpu
+def test_gpu_hybrid_gi_on_streams_equals_gi_in_kernel_with_nrd_planes(small_scene):
+    """The GI path on the wavefront streams (default options) and the one inside k_hybrid (VKRT_OPT_MODE 0) are the same function of
+    the pixel (csrc/hybrid_gi.h): the accumulation image and the nrdRadianceHitDist plane agree word for word after each of two
+    progressive frames, on an image whose height is not a multiple of the 8x8 tile."""
+    from vkrt_amd import abi
+    from vkrt_amd.renderer import Renderer
+
+    flat, camkw = small_scene
+    W, H = 72, 40
+    cam = default_camera(W, H, **camkw)
+    vm = _view_matrix(camkw)
+    L = len(flat.lights)
+
+    def frames(options):
+        r = Renderer(flat, device=0, options=options)
+        g = r.gbuffer_raycast(cam, W, H, lights_count=L, view_matrix=vm)
+        out, acc = [], None
+        for f in range(2):
+            pc = make_push_constants(samples=1, depth=5, frame=f, lights_count=L)
+            pc.useShadows, pc.useAO, pc.useGI = 1, 1, 1
+            acc = r.hybrid_trace(pc, cam, W, H, g, seed=20 + f, accum=acc)
+            out.append({"accum": acc.cpu().numpy().copy(), "nrdRadianceHitDist": g["nrdRadianceHitDist"].cpu().numpy().copy()})
+        r.close()
+        return out
+
+    streams, kernel = frames(None), frames({abi.VKRT_OPT_MODE: 0})
+    for f in range(2):
+        for k in ("accum", "nrdRadianceHitDist"):
+            a, b = streams[f][k].view(np.uint32), kernel[f][k].view(np.uint32)
+            print(f"frame {f} {k}: {int(np.any(a != b, axis=-1).sum())} of {W * H} pixels differ")
+        filled = float((streams[f]["nrdRadianceHitDist"][..., 3] != 0).mean())
+        print(f"frame {f}: nrdRadianceHitDist.w non-zero in {filled:.3f} of the pixels")
+    for f in range(2):
+        for k in ("accum", "nrdRadianceHitDist"):
+            assert np.array_equal(streams[f][k].view(np.uint32), kernel[f][k].view(np.uint32)), (f, k)
+        assert (streams[f]["nrdRadianceHitDist"][..., 3] != 0).mean() >= 0.25  # not a comparison of empty planes
+
+
 # ---- NRD / REBLUR front-end planes (SURVEY 8f row 4; gltf.glsl:156-273) -------------------------------------------------
 @pytest.fixture(scope="module")
 def small_scene():

@@ -6,14 +6,17 @@
 //   k_hybrid   raytraceHybrid.rgen:50-303 (1 shadow ray, 4 AO rays, optional GI path reusing the path tracer's
 //              closest-hit / miss shaders), accumulating into the rgba32f accumulation image (:36-48).
 //   k_post     post.frag:36-58 composite (raster.rgb * rt.a + rt.rgb) and gamma 1/2.2.
-// One thread per pixel; traversal and shading are the path tracer's (traverse*.h, shade.h).  With the wide layout k_hybrid runs one
-// wave per 8x8 tile in lockstep so that its rays use the work-sharing traversal (traverse_share.h).
+// One thread per pixel, in the path tracer's tile order (rgen.h pixelOfWork); traversal and shading are the path tracer's (traverse*.h,
+// shade.h).  With the wide layout k_hybrid runs one wave per 8x8 tile in lockstep so that its rays use the work-sharing traversal
+// (traverse_share.h).  The rules of the GI path and the pixel's store are those of hybrid_gi.h, which the wavefront streams run too
+// (wavefront.hip: the default, k_hybrid then ends after the direct part).
 #include <hip/hip_runtime.h>
 
 #include "device_math.h"
 #include "device_scene.h"
 #include "kernels.h"
 #include "rgen.h"
+#include "hybrid_gi.h"
 #include "shade.h"
 #include "traverse.h"
 #include "traverse_wide.h"
@@ -24,17 +27,11 @@
 struct HybridParams
 {
   TraceParams T;      // scene, pc, camera, launch geometry (image pointer unused)
-  float4* color;      // eOutImage  rgba32f
-  float4* position;   // ePosMap    rgba32f
-  float4* normal;     // eNormMap   rgba32f
-  float2* rough;      // eRoughMap  (rg16f-quantised values held as floats)
-  float4* accum;      // eAccumMap  rgba32f
+  HybridGi G;         // eOutImage, ePosMap, eNormMap (rgba32f), eRoughMap (rg16f-quantised values held as floats), eAccumMap (rgba32f) and
+                      // the optional NRD / REBLUR attachments eInViewZ (r16f values), eInRadHitD (rgba16f values)
   float clearColor[4];
   int lightsCount;
-  // optional NRD / REBLUR front-end attachments (frag_shader.frag:133-136, raytraceHybrid.rgen:273-281); NULL = not requested
-  float4* nrdNormRough;  // eInNormRough rgb10_a2 values
-  float* nrdViewZ;       // eInViewZ     r16f values
-  float4* nrdRadHitD;    // eInRadHitD   rgba16f values
+  float4* nrdNormRough;  // eInNormRough rgb10_a2 values (frag_shader.frag:133-136); NULL = no NRD attachments wanted from k_gbuffer
   float viewMatrix[16];  // pcRaster.viewMatrix (column-major), for viewZ
   uint2* giLater;        // k_hybrid: non-NULL = GI runs afterwards on the wavefront streams; (seed, visibility bits) per pixel go here
 };
@@ -82,20 +79,6 @@ VKRT_DEV bool planeTexCoord(f3 org, f3 dir, f3 p0, f3 p1, f3 p2, const float* tc
   return true;
 }
 
-VKRT_DEV bool pixelOf(const TraceParams& P, uint32_t& x, uint32_t& y, uint32_t& lrow)
-{
-  const unsigned w = blockIdx.x * blockDim.x + threadIdx.x;  // tile-major, as in the path tracer
-  if(w >= P.tileCount * 64u)
-    return false;
-  const unsigned tile = w >> 6, inTile = w & 63u;
-  x = (tile % P.tilesX) * 8u + (inTile & 7u);
-  lrow = (tile / P.tilesX) * 8u + (inTile >> 3);
-  if(x >= P.fullW || lrow >= P.localRows)
-    return false;
-  y = globalRow(P, lrow);
-  return y < P.fullH;
-}
-
 // TM: VKRT_TM_WATERTIGHT and / or VKRT_TM_MASKID (a raster pass has no any-hit stage -- every triangle is opaque here -- but on a scene
 // built for the stage the id words carry its flag, which the tie rule "smallest triangle id" and the exclusive tmax must not see)
 template <bool WIDE, int TM>
@@ -108,10 +91,8 @@ __global__ __launch_bounds__(HY_BLOCK) void k_gbuffer(const HybridParams H)
   unsigned nClosest = 0;
   TravCount tc;
   __shared__ float lut[512];
-  ShadeStats st;
-  st.hits = 0; st.diffuse = 0; st.taps = 0;
-  st.lut = ldsTexelLut(P.sc, lut);
-  if(pixelOf(P, x, y, lrow))
+  ShadeStats st = shadeStatsInit(P.sc, lut);
+  if(pixelOfWork(P, blockIdx.x * blockDim.x + threadIdx.x, 0u, x, y, lrow))
   {
     const size_t p = (size_t)lrow * P.fullW + x;
     float4 oColor = make_float4(H.clearColor[0], H.clearColor[1], H.clearColor[2], H.clearColor[3]);
@@ -119,9 +100,7 @@ __global__ __launch_bounds__(HY_BLOCK) void k_gbuffer(const HybridParams H)
     float2 oRough = make_float2(0.0f, 0.0f);
     float4 oNormRough = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // main.cpp:488-491 clear values
     float oViewZ = 0.0f;
-    float origin[4];
-    mat4MulVec4(P.viewInverse, 0.0f, 0.0f, 0.0f, 1.0f, origin);
-    const f3 org = mk3(origin[0], origin[1], origin[2]), dir = primaryDir(P, x, y);
+    const f3 org = cameraOrigin(P), dir = primaryDir(P, x, y);
     RayHit hit;
     nClosest = 1;
     traverse_any<false, WIDE, TM>(sc, org, dir, 0.001f, 10000.0f, false, lds_stack, (int)threadIdx.x, HY_BLOCK, hit, tc);
@@ -239,12 +218,12 @@ __global__ __launch_bounds__(HY_BLOCK) void k_gbuffer(const HybridParams H)
         oViewZ = quantizeHalf(vz[2]);
       }
     }
-    H.color[p] = oColor; H.position[p] = oPos; H.normal[p] = oNrm; H.rough[p] = oRough;
+    H.G.color[p] = oColor; H.G.position[p] = oPos; H.G.normal[p] = oNrm; H.G.rough[p] = oRough;
     if(H.nrdNormRough)
     {
       H.nrdNormRough[p] = oNormRough;
-      H.nrdViewZ[p] = oViewZ;
-      H.nrdRadHitD[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // frag_shader.frag:136 / clear value
+      H.G.nrdViewZ[p] = oViewZ;
+      H.G.nrdRadHitD[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // frag_shader.frag:136 / clear value
     }
   }
   __shared__ unsigned long long red[VKRT_COUNTER_STRIDE * (HY_BLOCK / 64)];
@@ -295,33 +274,27 @@ __global__ __launch_bounds__(SHARE ? 64 : HY_BLOCK) void k_hybrid(const HybridPa
   unsigned nClosest = 0, nShadow = 0, nPixels = 0;
   TravCount tc;
   __shared__ float lut[512];
-  ShadeStats st;
-  st.hits = 0; st.diffuse = 0; st.taps = 0;
-  st.lut = ldsTexelLut(P.sc, lut);
-  const bool inImage = pixelOf(P, x, y, lrow);
+  ShadeStats st = shadeStatsInit(P.sc, lut);
+  const bool inImage = pixelOfWork(P, blockIdx.x * blockDim.x + threadIdx.x, 0u, x, y, lrow);
   auto anyLane = [](bool c) { return SHARE ? __any(c) != 0 : c; };
   Payload prd;
   prd.seed = 0u;
   prd.isSpecular = false; prd.lightDist = 0.0f; prd.shadowRayDir = mk3(0.0f); prd.depth = 0;
   prd.hitValue = mk3(0.0f); prd.weight = mk3(0.0f); prd.rayOrigin = mk3(0.0f); prd.rayDirection = mk3(0.0f);
-  float4 color = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+  float alpha = 1.0f;  // color.a of rgen: the visibility term of the direct part
   size_t p = 0;
-  f3 worldPos = mk3(0.0f), worldNrm = mk3(0.0f), albedo = mk3(0.0f);
-  float roughness = 0.0f, metalness = 0.0f;
-  bool shaded = false;
+  GbufferPixel g{};  // (a lane outside the image: all zero, not shaded)
+  f3 hitValue = mk3(0.0f);  // the GI path's radiance and hit distance (rgen:172-266)
+  float hitDists = 0.0f;
   if(inImage)
   {
     nPixels = 1;
     p = (size_t)lrow * P.fullW + x;
-    prd.seed = tea((P.flags & 1u) ? (y * P.fullW + x) : (y * x + x), P.seed);  // rgen:55
-    const float4 pixelImg = H.color[p], pixelPos = H.position[p], pixelNorm = H.normal[p];
-    const float2 rm = H.rough[p];
-    worldPos = mk3(pixelPos.x, pixelPos.y, pixelPos.z); worldNrm = mk3(pixelNorm.x, pixelNorm.y, pixelNorm.z);
-    shaded = !(worldPos.x == 0.0f && worldPos.y == 0.0f && worldPos.z == 0.0f && worldNrm.x == 0.0f && worldNrm.y == 0.0f &&
-               worldNrm.z == 0.0f);  // rgen:67
-    albedo = mk3(pixelImg.w, pixelPos.w, pixelNorm.w);
-    roughness = rm.x; metalness = rm.y;
+    prd.seed = pixelSeed(P, x, y);
+    g = loadGbufferPixel(H.G, p);
   }
+  const bool shaded = g.shaded;
+  const f3 worldPos = g.worldPos, worldNrm = g.worldNrm;
   if(anyLane(shaded))
   {
     RayHit hit;
@@ -355,7 +328,7 @@ __global__ __launch_bounds__(SHARE ? 64 : HY_BLOCK) void k_hybrid(const HybridPa
       if(shaded)
       {
         visibility = glsl_max(visibility, 0.01f);
-        color.w *= visibility;
+        alpha *= visibility;
       }
     }
     if(P.pc.useAO == 1)  // rgen:134-169
@@ -379,39 +352,13 @@ __global__ __launch_bounds__(SHARE ? 64 : HY_BLOCK) void k_hybrid(const HybridPa
         }
       }
       if(shaded)
-        color.w *= (1.0f - ao);
+        alpha *= (1.0f - ao);
     }
-    if(P.pc.useGI == 1 && !H.giLater)  // rgen:172-282
+    if(P.pc.useGI == 1 && !H.giLater)  // rgen:172-266
     {
-      f3 curWeight = mk3(0.0f), hitValue = mk3(0.0f);
-      float hitDists = 0.0f;
+      f3 curWeight = mk3(0.0f);
       if(shaded)
-      {
-        f3 direction;
-        const float ratio = metalness * (1.0f - roughness);
-        if(ratio < 0.8f)
-        {
-          prd.isSpecular = false;
-          f3 tangent, binormal;
-          createCoordinateSystem(worldNrm, tangent, binormal);
-          direction = normalize3(samplingHemisphere(prd.seed, tangent, binormal, worldNrm));
-          curWeight = albedo;
-        }
-        else
-        {
-          prd.isSpecular = true;
-          float cam[4];
-          mat4MulVec4(P.viewInverse, 0.0f, 0.0f, 0.0f, 1.0f, cam);
-          const f3 V = normalize3(mk3(cam[0], cam[1], cam[2]) - worldPos);
-          direction = normalize3(glsl_reflect(-V, worldNrm));
-          curWeight = mk3(1.0f);
-        }
-        prd.hitValue = mk3(0.0f);
-        prd.rayOrigin = worldPos;
-        prd.rayDirection = direction;
-        prd.depth = 1;
-        prd.weight = mk3(0.0f);
-      }
+        giFirstRay(P, g, prd, curWeight);
       bool active = shaded && prd.depth < (uint32_t)P.pc.depth;
       while(anyLane(active))
       {
@@ -439,56 +386,17 @@ __global__ __launch_bounds__(SHARE ? 64 : HY_BLOCK) void k_hybrid(const HybridPa
         }
         if(active)
         {
-          if(!shadowHit)
-          {
-            const f3 q = prd.hitValue * curWeight;
-            hitValue = hitValue + mk3(glsl_min(q.x, 10.0f), glsl_min(q.y, 10.0f), glsl_min(q.z, 10.0f));
-          }
-          if(prd.depth == 1u && !prd.isSpecular)  // rgen:253-264
-            hitDists = shadowHit ? 0.5f * prd.lightDist : prd.lightDist;
-          curWeight = curWeight * prd.weight;
-          prd.depth++;
-          active = prd.depth < (uint32_t)P.pc.depth;
-        }
-      }
-      if(shaded)
-      {
-        color.x = hitValue.x; color.y = hitValue.y; color.z = hitValue.z;
-        if(H.nrdRadHitD)
-        {  // rgen:273-281: REBLUR front end, hitDistParams (3, 1, 20, -25), rgba16f store
-          const float viewZ = H.nrdViewZ[p];
-          const float t = glsl_clamp(exp2f(-25.0f * roughness * roughness), 0.0f, 1.0f);
-          const float f = (3.0f + fabsf(viewZ) * 1.0f) * (1.0f * (1.0f - t) + 20.0f * t);
-          float normHitDist = glsl_clamp(hitDists / f, 0.0f, 1.0f);
-          f3 rad = hitValue;
-          const bool bad = isnan(rad.x) || isnan(rad.y) || isnan(rad.z) || isinf(rad.x) || isinf(rad.y) || isinf(rad.z);
-          rad = bad ? mk3(0.0f) : mk3(glsl_clamp(rad.x, 0.0f, 65504.0f), glsl_clamp(rad.y, 0.0f, 65504.0f), glsl_clamp(rad.z, 0.0f, 65504.0f));
-          normHitDist = (isnan(normHitDist) || isinf(normHitDist)) ? 0.0f : glsl_clamp(normHitDist, 0.0f, 1.0f);
-          if(normHitDist != 0.0f)
-            normHitDist = glsl_max(normHitDist, 1e-7f);
-          const float Y = (rad.x * 0.25f + rad.y * 0.5f) + rad.z * 0.25f;
-          const float Co = (rad.x * 0.5f + rad.y * 0.0f) + rad.z * -0.5f;
-          const float Cg = (rad.x * -0.25f + rad.y * 0.5f) + rad.z * -0.25f;
-          H.nrdRadHitD[p] = make_float4(quantizeHalf(Y), quantizeHalf(Co), quantizeHalf(Cg), quantizeHalf(normHitDist));
+          f3 contrib, nextWeight;
+          segmentTerms(prd, curWeight, contrib, nextWeight);
+          active = giSegmentStep(P.pc, prd, curWeight, hitValue, hitDists, shadowHit, contrib, nextWeight, prd.lightDist);
         }
       }
     }
   }
   if(inImage && H.giLater && P.pc.useGI == 1)
-    H.giLater[p] = make_uint2(prd.seed, __float_as_uint(color.w));  // the GI kernels continue from here and write the pixel
+    H.giLater[p] = make_uint2(prd.seed, __float_as_uint(alpha));  // the GI kernels continue from here and write the pixel
   else if(inImage)
-  {
-    // accumulateFrames, rgen:36-48 (all four channels)
-    if(P.pc.frame > 0)
-    {
-      const float a = 1.0f / (float)(P.pc.frame + 1);
-      const float4 old = H.accum[p];
-      H.accum[p] = make_float4(old.x * (1.0f - a) + color.x * a, old.y * (1.0f - a) + color.y * a, old.z * (1.0f - a) + color.z * a,
-                               old.w * (1.0f - a) + color.w * a);
-    }
-    else
-      H.accum[p] = color;
-  }
+    hybridStorePixel(P, H.G, p, shaded && P.pc.useGI == 1, hitValue, hitDists, alpha);
   __shared__ unsigned long long red[VKRT_COUNTER_STRIDE * ((SHARE ? 64 : HY_BLOCK) / 64)];
   const unsigned vals[6] = {nClosest, nShadow, st.hits, st.diffuse, st.taps, nPixels};
   blockAddCounters(&P.counters->v[blockIdx.x % VKRT_COUNTER_SLOTS][0], vals, 6, red);
@@ -519,58 +427,43 @@ __global__ void k_post(int rtMode, int viewAccumulated, int useGI, unsigned n, c
   out[i] = make_float4(powf(m.x, gamma), powf(m.y, gamma), powf(m.z, gamma), powf(m.w, gamma));
 }
 
-hipError_t vkrt_launch_gbuffer(const TraceParams& P, const float clearColor[4], int lightsCount, float* color, float* position, float* normal,
-                               float* rough, const NrdPlanes* nrd, hipStream_t stream)
+hipError_t vkrt_launch_gbuffer(const TraceParams& P, const float clearColor[4], int lightsCount, const HybridGi& G, float* nrdNormRough,
+                               const float* viewMatrix, hipStream_t stream)
 {
   HybridParams H;
   H.T = P;
+  H.G = G;
   H.giLater = nullptr;
-  H.nrdNormRough = nrd ? (float4*)nrd->normRough : nullptr;
-  H.nrdViewZ = nrd ? nrd->viewZ : nullptr;
-  H.nrdRadHitD = nrd ? (float4*)nrd->radHitD : nullptr;
-  for(int k = 0; k < 16; k++) H.viewMatrix[k] = nrd ? nrd->viewMatrix[k] : 0.0f;
-  H.color = (float4*)color; H.position = (float4*)position; H.normal = (float4*)normal; H.rough = (float2*)rough; H.accum = nullptr;
+  H.nrdNormRough = (float4*)nrdNormRough;
+  for(int k = 0; k < 16; k++) H.viewMatrix[k] = nrdNormRough ? viewMatrix[k] : 0.0f;
   for(int k = 0; k < 4; k++) H.clearColor[k] = clearColor[k];
   H.lightsCount = lightsCount;
   const unsigned blocks = (P.tileCount * 64u + HY_BLOCK - 1) / HY_BLOCK;
   const size_t lds = (size_t)P.sc.stackCap * HY_BLOCK * sizeof(int);
-  const int tm = (P.sc.watertight ? VKRT_TM_WATERTIGHT : 0) | (P.sc.dissolve ? VKRT_TM_MASKID : 0);
-#define VKRT_GB_LAUNCH(W, TM) hipLaunchKernelGGL((k_gbuffer<W, TM>), dim3(blocks), dim3(HY_BLOCK), lds, stream, H)
+  const int tm = frame_tri_mode(P.sc, true);
+#define VKRT_GB_WIDE(TM) hipLaunchKernelGGL((k_gbuffer<true, TM>), dim3(blocks), dim3(HY_BLOCK), lds, stream, H)
+#define VKRT_GB_BVH2(TM) hipLaunchKernelGGL((k_gbuffer<false, TM>), dim3(blocks), dim3(HY_BLOCK), lds, stream, H)
   if(P.sc.layout == 1u)
   {
-    switch(tm)
-    {
-      case 0: VKRT_GB_LAUNCH(true, 0); break;
-      case VKRT_TM_WATERTIGHT: VKRT_GB_LAUNCH(true, VKRT_TM_WATERTIGHT); break;
-      case VKRT_TM_MASKID: VKRT_GB_LAUNCH(true, VKRT_TM_MASKID); break;
-      default: VKRT_GB_LAUNCH(true, VKRT_TM_WATERTIGHT | VKRT_TM_MASKID); break;
-    }
+    VKRT_FRAME_TM_SWITCH(tm, VKRT_TM_MASKID, VKRT_GB_WIDE)
   }
   else
   {
-    switch(tm)
-    {
-      case 0: VKRT_GB_LAUNCH(false, 0); break;
-      case VKRT_TM_WATERTIGHT: VKRT_GB_LAUNCH(false, VKRT_TM_WATERTIGHT); break;
-      case VKRT_TM_MASKID: VKRT_GB_LAUNCH(false, VKRT_TM_MASKID); break;
-      default: VKRT_GB_LAUNCH(false, VKRT_TM_WATERTIGHT | VKRT_TM_MASKID); break;
-    }
+    VKRT_FRAME_TM_SWITCH(tm, VKRT_TM_MASKID, VKRT_GB_BVH2)
   }
-#undef VKRT_GB_LAUNCH
+#undef VKRT_GB_BVH2
+#undef VKRT_GB_WIDE
   return hipGetLastError();
 }
 
-hipError_t vkrt_launch_hybrid(const TraceParams& P, const float* color, const float* position, const float* normal, const float* rough, float* accum,
-                              const NrdPlanes* nrd, uint2* giLater, hipStream_t stream)
+hipError_t vkrt_launch_hybrid(const TraceParams& P, const HybridGi& G, uint2* giLater, hipStream_t stream)
 {
   HybridParams H;
   H.T = P;
+  H.G = G;
   H.giLater = giLater;
   H.nrdNormRough = nullptr;
-  H.nrdViewZ = nrd ? nrd->viewZ : nullptr;
-  H.nrdRadHitD = nrd ? (float4*)nrd->radHitD : nullptr;
   for(int k = 0; k < 16; k++) H.viewMatrix[k] = 0.0f;
-  H.color = (float4*)color; H.position = (float4*)position; H.normal = (float4*)normal; H.rough = (float2*)rough; H.accum = (float4*)accum;
   for(int k = 0; k < 4; k++) H.clearColor[k] = 0.0f;
   H.lightsCount = P.pc.lightsCount;
   // with the wide layout and work sharing enabled (the defaults) one wave per workgroup walks its 64 pixels' rays together
@@ -578,30 +471,25 @@ hipError_t vkrt_launch_hybrid(const TraceParams& P, const float* color, const fl
   const unsigned block = share ? 64u : (unsigned)HY_BLOCK;
   const unsigned blocks = (P.tileCount * 64u + block - 1) / block;
   const size_t lds = (size_t)P.sc.stackCap * block * sizeof(int);
-  const int tm = (P.sc.watertight ? VKRT_TM_WATERTIGHT : 0) | (P.sc.dissolve ? VKRT_TM_DISSOLVE : 0);
-#define VKRT_HY_LAUNCH(W, S, TM) hipLaunchKernelGGL((k_hybrid<W, S, TM>), dim3(blocks), dim3(block), lds, stream, H)
-#define VKRT_HY_MODES(W, S)                                                                                                            \
-  switch(tm)                                                                                                                            \
-  {                                                                                                                                     \
-    case 0: VKRT_HY_LAUNCH(W, S, 0); break;                                                                                             \
-    case 1: VKRT_HY_LAUNCH(W, S, 1); break;                                                                                             \
-    case 2: VKRT_HY_LAUNCH(W, S, 2); break;                                                                                             \
-    default: VKRT_HY_LAUNCH(W, S, 3); break;                                                                                            \
-  }
+  const int tm = frame_tri_mode(P.sc, false);
+#define VKRT_HY_SHARE(TM) hipLaunchKernelGGL((k_hybrid<true, true, TM>), dim3(blocks), dim3(block), lds, stream, H)
+#define VKRT_HY_WIDE(TM) hipLaunchKernelGGL((k_hybrid<true, false, TM>), dim3(blocks), dim3(block), lds, stream, H)
+#define VKRT_HY_BVH2(TM) hipLaunchKernelGGL((k_hybrid<false, false, TM>), dim3(blocks), dim3(block), lds, stream, H)
   if(share)
   {
-    VKRT_HY_MODES(true, true)
+    VKRT_FRAME_TM_SWITCH(tm, VKRT_TM_DISSOLVE, VKRT_HY_SHARE)
   }
   else if(P.sc.layout == 1u)
   {
-    VKRT_HY_MODES(true, false)
+    VKRT_FRAME_TM_SWITCH(tm, VKRT_TM_DISSOLVE, VKRT_HY_WIDE)
   }
   else
   {
-    VKRT_HY_MODES(false, false)
+    VKRT_FRAME_TM_SWITCH(tm, VKRT_TM_DISSOLVE, VKRT_HY_BVH2)
   }
-#undef VKRT_HY_MODES
-#undef VKRT_HY_LAUNCH
+#undef VKRT_HY_BVH2
+#undef VKRT_HY_WIDE
+#undef VKRT_HY_SHARE
   return hipGetLastError();
 }
 

@@ -35,9 +35,7 @@ __global__ __launch_bounds__(VKRT_BLOCK, MINW) void k_pathtrace(const TraceParam
   unsigned nClosest = 0, nShadow = 0, nPixels = 0;
   TravCount tc;
   __shared__ float lut[512];
-  ShadeStats st;
-  st.hits = 0; st.diffuse = 0; st.taps = 0;
-  st.lut = ldsTexelLut(P.sc, lut);
+  ShadeStats st = shadeStatsInit(P.sc, lut);
   const uint32_t totalWork = P.tileCount * 64u;
 
   for(;;)
@@ -60,25 +58,16 @@ __global__ __launch_bounds__(VKRT_BLOCK, MINW) void k_pathtrace(const TraceParam
         if(!active)
         {
           const unsigned w = base + (unsigned)__popcll(idleMask & ((1ull << lane) - 1ull));
-          if(w < totalWork)
+          uint32_t x, y, lrow;
+          if(pixelOfWork(P, w, 0u, x, y, lrow))
           {
-            const unsigned tile = w >> 6, inTile = w & 63u;
-            const uint32_t x = (tile % P.tilesX) * 8u + (inTile & 7u);
-            const uint32_t lrow = (tile / P.tilesX) * 8u + (inTile >> 3);
-            if(x < P.fullW && lrow < P.localRows)
-            {
-              const uint32_t y = globalRow(P, lrow);
-              if(y < P.fullH)
-              {
-                startPixel(P, L, x, y, lrow);
-                active = true;
-                nPixels++;
-                if(P.pc.samples <= 0 || P.pc.depth <= 0)
-                {  // degenerate launch: no rays, store the resolved (0/samples) value
-                  storePixel(P, L);
-                  active = false;
-                }
-              }
+            startPixel(P, L, x, y, lrow);
+            active = true;
+            nPixels++;
+            if(P.pc.samples <= 0 || P.pc.depth <= 0)
+            {  // degenerate launch: no rays, store the resolved (0/samples) value
+              storePixel(P, L);
+              active = false;
             }
           }
         }
@@ -141,16 +130,19 @@ __global__ __launch_bounds__(VKRT_BLOCK) void k_trace_rays(DevScene sc, unsigned
   TravCount tc;
   const f3 ro = mk3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rd = mk3(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
   // (test hook: the payload seed of these rays is 0)
-  const int tm = (sc.watertight ? VKRT_TM_WATERTIGHT : 0) | (sc.dissolve ? VKRT_TM_DISSOLVE : 0);
 #define VKRT_DBG(W, TM) traverse_any<false, W, TM>(sc, ro, rd, tmin, tmax, anyHit != 0, lds_stack, (int)threadIdx.x, VKRT_BLOCK, hit, tc, 0u)
+#define VKRT_DBG_WIDE(TM) VKRT_DBG(true, TM)
+#define VKRT_DBG_BVH2(TM) VKRT_DBG(false, TM)
   if(sc.layout == 1u)
   {
-    if(tm == 0) VKRT_DBG(true, 0); else if(tm == 1) VKRT_DBG(true, 1); else if(tm == 2) VKRT_DBG(true, 2); else VKRT_DBG(true, 3);
+    VKRT_FRAME_TM_SWITCH(frame_tri_mode(sc, false), VKRT_TM_DISSOLVE, VKRT_DBG_WIDE)
   }
   else
   {
-    if(tm == 0) VKRT_DBG(false, 0); else if(tm == 1) VKRT_DBG(false, 1); else if(tm == 2) VKRT_DBG(false, 2); else VKRT_DBG(false, 3);
+    VKRT_FRAME_TM_SWITCH(frame_tri_mode(sc, false), VKRT_TM_DISSOLVE, VKRT_DBG_BVH2)
   }
+#undef VKRT_DBG_BVH2
+#undef VKRT_DBG_WIDE
 #undef VKRT_DBG
   if(anyHit)
   {
@@ -188,19 +180,12 @@ hipError_t vkrt_launch_pathtrace(const TraceParams& P, unsigned gridBlocks, bool
 {
   const size_t lds = (size_t)P.sc.stackCap * VKRT_BLOCK * sizeof(int);
   const dim3 g(gridBlocks), b(VKRT_BLOCK);
-  const int tm = (P.sc.watertight ? VKRT_TM_WATERTIGHT : 0) | (P.sc.dissolve ? VKRT_TM_DISSOLVE : 0);
 #define VKRT_MEGA(TM)                                                                        \
   do {                                                                                       \
     if(count) hipLaunchKernelGGL((k_pathtrace<true, 1, TM>), g, b, lds, stream, P);         \
     else hipLaunchKernelGGL((k_pathtrace<false, 3, TM>), g, b, lds, stream, P);             \
   } while(0)
-  switch(tm)
-  {
-    case 0: VKRT_MEGA(0); break;
-    case 1: VKRT_MEGA(1); break;
-    case 2: VKRT_MEGA(2); break;
-    default: VKRT_MEGA(3); break;
-  }
+  VKRT_FRAME_TM_SWITCH(frame_tri_mode(P.sc, false), VKRT_TM_DISSOLVE, VKRT_MEGA)
 #undef VKRT_MEGA
   return hipGetLastError();
 }

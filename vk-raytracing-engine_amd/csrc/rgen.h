@@ -1,6 +1,8 @@
 // rgen.h -- the ray-generation program (reference shaders/raytrace.rgen:24-146) as a per-path state
 // machine shared by the megakernel (pathtrace.hip) and the wavefront kernels (wavefront.hip).
 // One "path" = one pixel; its unit of work is one ray (closest-hit or shadow).
+// Also the pixel front end of every frame kernel (pathtrace.hip, wavefront.hip, hybrid.hip): the tile-major work index -> pixel decode
+// (pixelOfWork) and its inverse (pixelSlot), the seed index rule (pixelSeed), the camera origin and the lane setup of a pixel.
 #pragma once
 #include "device_math.h"
 #include "device_scene.h"
@@ -24,6 +26,42 @@ VKRT_DEV uint32_t globalRow(const TraceParams& P, uint32_t lrow)
     return lrow;
   const uint32_t s = lrow / P.stripRows, r = lrow % P.stripRows;
   return (s * P.shardCount + P.shardIndex) * P.stripRows + r;
+}
+
+// Tile-major work index -> pixel.  Work item w of a launch belongs to the 8x8 tile tileFirst + w / 64 of the shard (tiles row by row,
+// tilesX to a row) and to pixel w % 64 inside it (row by row): column x, shard-local row lrow, global row y.  false: w is past the
+// launch's tiles, or the pixel of a partial tile lies outside the shard or the image.
+VKRT_DEV bool pixelOfWork(const TraceParams& P, unsigned w, unsigned tileFirst, uint32_t& x, uint32_t& y, uint32_t& lrow)
+{
+  if(w >= P.tileCount * 64u)
+    return false;
+  const unsigned tile = tileFirst + (w >> 6), inTile = w & 63u;
+  x = (tile % P.tilesX) * 8u + (inTile & 7u);
+  lrow = (tile / P.tilesX) * 8u + (inTile >> 3);
+  if(x >= P.fullW || lrow >= P.localRows)
+    return false;
+  y = globalRow(P, lrow);
+  return y < P.fullH;
+}
+// ... and back: tile * 64 + inTile of pixel (x, lrow), its tile-major index in the shard (the pixel's sample-state record)
+VKRT_DEV unsigned pixelSlot(const TraceParams& P, uint32_t x, uint32_t lrow)
+{
+  return (((lrow >> 3) * P.tilesX + (x >> 3)) << 6) | ((lrow & 7u) << 3) | (x & 7u);
+}
+
+// the index the pixel's random sequence is seeded with (raytrace.rgen:28, raytraceHybrid.rgen:55; flags bit 0: VKRT_TRACE_SEED_INDEX_ROW_MAJOR)
+VKRT_DEV uint32_t pixelSeed(const TraceParams& P, uint32_t x, uint32_t y)
+{
+  const uint32_t index = (P.flags & 1u) ? (y * P.fullW + x) : (y * x + x);
+  return tea(index, P.seed);
+}
+
+// raytrace.rgen:30 -- viewInverse * (0, 0, 0, 1) (launch-uniform; cheaper to recompute than to carry)
+VKRT_DEV f3 cameraOrigin(const TraceParams& P)
+{
+  float origin[4];
+  mat4MulVec4(P.viewInverse, 0.0f, 0.0f, 0.0f, 1.0f, origin);
+  return mk3(origin[0], origin[1], origin[2]);
 }
 
 // raytrace.rgen:42-60 -- start sample `smpl` of the lane's pixel
@@ -50,18 +88,26 @@ VKRT_DEV void startSample(const TraceParams& P, LaneState& L)
   L.stage = 0;
 }
 
-// raytrace.rgen:27-30 -- bind a pixel to the lane
-VKRT_DEV void startPixel(const TraceParams& P, LaneState& L, uint32_t x, uint32_t y, uint32_t lrow)
+// raytrace.rgen:27-30 -- bind a pixel to the lane: what depends neither on the seed nor on the sum over the samples so far.
+// prd.isSpecular is reset here for every sample the sample-synchronous schedule starts (k_wf_sample_init), while a pixel that walks
+// through its samples at its own pace carries the bit of a sample's last segment into the next sample.  Nothing reads it there: at
+// depth 0 the emission rule of the hit shader (`depth == 0 || isSpecular`, rchit:83) holds whatever the bit says and closestHitTail
+// sets it on both of its branches; a miss leaves it alone but sets depth 100, which decides the shadow-ray test (rgen:79) by itself
+// and ends the sample, so the bit reaches the next sample's depth 0 unread again.
+VKRT_DEV void bindPixel(const TraceParams& P, LaneState& L, uint32_t x, uint32_t lrow)
 {
-  L.px = x; L.lrow = lrow;  // (y == globalRow(P, lrow))
-  const uint32_t index = (P.flags & 1u) ? (y * P.fullW + x) : (y * x + x);
-  L.prd.seed = tea(index, P.seed);
+  L.px = x; L.lrow = lrow;
   L.prd.isSpecular = false;
   L.prd.lightDist = 0.0f;
   L.prd.shadowRayDir = mk3(0.0f);
-  float origin[4];
-  mat4MulVec4(P.viewInverse, 0.0f, 0.0f, 0.0f, 1.0f, origin);
-  L.camOrigin = mk3(origin[0], origin[1], origin[2]);
+  L.camOrigin = cameraOrigin(P);
+}
+
+// raytrace.rgen:27-60 -- the first sample of pixel (x, y), y == globalRow(P, lrow)
+VKRT_DEV void startPixel(const TraceParams& P, LaneState& L, uint32_t x, uint32_t y, uint32_t lrow)
+{
+  bindPixel(P, L, x, lrow);
+  L.prd.seed = pixelSeed(P, x, y);
   L.hitValues = mk3(0.0f);
   L.smpl = 0;
   startSample(P, L);
@@ -117,11 +163,11 @@ VKRT_DEV bool afterClosestRay(const TraceParams& P, LaneState& L, const RayHit& 
 // raytrace.rgen:99-102,115 -- the two products of a finished segment: its clamped radiance contribution and the path
 // weight after it.  Split from the bookkeeping below so the wavefront pipeline can carry (contrib, nextWeight) across
 // the shadow ray instead of (prd.hitValue, curWeight, prd.weight); the float operations are the same.
-VKRT_DEV void segmentTerms(const LaneState& L, f3& contrib, f3& nextWeight)
+VKRT_DEV void segmentTerms(const Payload& prd, f3 curWeight, f3& contrib, f3& nextWeight)
 {
-  const f3 q = L.prd.hitValue * L.curWeight;
+  const f3 q = prd.hitValue * curWeight;
   contrib = mk3(glsl_min(q.x, 10.0f), glsl_min(q.y, 10.0f), glsl_min(q.z, 10.0f));
-  nextWeight = L.curWeight * L.prd.weight;
+  nextWeight = curWeight * prd.weight;
 }
 
 // raytrace.rgen:99-120 -- accumulate the segment, advance depth / sample, up to the point where the next sample would start.
@@ -161,6 +207,6 @@ VKRT_DEV bool advanceSegment(const TraceParams& P, LaneState& L, bool shadowHit,
 VKRT_DEV bool accumulateAndAdvance(const TraceParams& P, LaneState& L, bool shadowHit)
 {
   f3 contrib, nextWeight;
-  segmentTerms(L, contrib, nextWeight);
+  segmentTerms(L.prd, L.curWeight, contrib, nextWeight);
   return advanceSegment(P, L, shadowHit, contrib, nextWeight);
 }

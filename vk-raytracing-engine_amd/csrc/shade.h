@@ -36,6 +36,15 @@ VKRT_DEV const float* ldsTexelLut(const DevScene& sc, float* lds512)
   return lds512;
 }
 
+// the tallies of a thread that is about to shade, with the workgroup's LDS copy of the decode table (same calling rule as ldsTexelLut)
+VKRT_DEV ShadeStats shadeStatsInit(const DevScene& sc, float* lds512)
+{
+  ShadeStats st;
+  st.hits = 0; st.diffuse = 0; st.taps = 0;
+  st.lut = ldsTexelLut(sc, lds512);
+  return st;
+}
+
 struct f4 { float x, y, z, w; };
 
 // Gathers of the hit shader go through buffer descriptors (four SGPRs built from a kernel-argument pointer) with a 32-bit byte

@@ -158,6 +158,23 @@ VKRT_DEV bool tri_test_wt(const WtRay& R, f3 o, f3 p0, f3 p1, f3 p2, float& t, f
 #define VKRT_TM_MASKID 4
 #define VKRT_TM_FILTER 8
 
+// The triangle mode of a frame kernel (path tracing, hybrid, the G-buffer ray cast).  opaque: the walk has no any-hit stage (k_gbuffer)
+// and only masks the stage's flag out of the id words of a scene built for it.
+__host__ __device__ inline int frame_tri_mode(const DevScene& sc, bool opaque)
+{
+  return (sc.watertight ? VKRT_TM_WATERTIGHT : 0) | (sc.dissolve ? (opaque ? VKRT_TM_MASKID : VKRT_TM_DISSOLVE) : 0);
+}
+// X(TM) for the triangle mode tm, a compile-time constant there: the four values frame_tri_mode can give for one `opaque`, whose
+// stage bit is STAGE (VKRT_TM_DISSOLVE or VKRT_TM_MASKID).  (The ray queries have more modes: VKRT_QUERY_TM_SWITCH.)
+#define VKRT_FRAME_TM_SWITCH(tm, STAGE, X)                           \
+  switch(tm)                                                          \
+  {                                                                   \
+    case 0: X(0); break;                                              \
+    case VKRT_TM_WATERTIGHT: X(VKRT_TM_WATERTIGHT); break;            \
+    case STAGE: X(STAGE); break;                                      \
+    default: X((VKRT_TM_WATERTIGHT | STAGE)); break;                  \
+  }
+
 // per-ray constants + one entry point on a 48-byte record (a, b, c)
 template <bool WT> struct TriRay;
 template <> struct TriRay<false>

@@ -1650,14 +1650,9 @@ int gbufferImpl(vkrt_scene* s, const float clearColor[4], int lightsCount, const
   if(P.localRows == 0)
     return VKRT_OK;
   P.sc.gbufferMips = (uint32_t)s->opt[VKRT_OPT_GBUFFER_MIPS];
-  NrdPlanes np{};
-  if(nrd)
-  {
-    np.normRough = nrd->normalRoughness; np.viewZ = nrd->viewZ; np.radHitD = nrd->diffRadianceHitDist;
-    memcpy(np.viewMatrix, viewMatrix, sizeof np.viewMatrix);
-  }
-  HIP_TRY(vkrt_launch_gbuffer(P, clearColor, lightsCount, out->color, out->position, out->normal, out->roughMetal, nrd ? &np : nullptr,
-                              (hipStream_t)hip_stream));
+  const HybridGi G{(float4*)out->color, (float4*)out->position, (float4*)out->normal, (float2*)out->roughMetal, nullptr,
+                   nrd ? (float4*)nrd->diffRadianceHitDist : nullptr, nrd ? nrd->viewZ : nullptr};
+  HIP_TRY(vkrt_launch_gbuffer(P, clearColor, lightsCount, G, nrd ? nrd->normalRoughness : nullptr, viewMatrix, (hipStream_t)hip_stream));
   return VKRT_OK;
 }
 
@@ -1683,11 +1678,8 @@ int hybridImpl(vkrt_scene* s, const PushConstantRay* pc, const GlobalUniforms* c
     return VKRT_OK;
   hipStream_t stream = (hipStream_t)hip_stream;
   HIP_TRY(hipEventRecord(s->evStart, stream));
-  NrdPlanes np{};
-  if(nrd)
-  {
-    np.viewZ = nrd->viewZ; np.radHitD = nrd->diffRadianceHitDist;
-  }
+  const HybridGi G{(float4*)g->color, (float4*)g->position, (float4*)g->normal, (float2*)g->roughMetal, (float4*)accum,
+                   nrd ? (float4*)nrd->diffRadianceHitDist : nullptr, nrd ? nrd->viewZ : nullptr};
   // The GI paths (raytraceHybrid.rgen:172-282) run on the path tracer's wavefront streams when the scene was built for them:
   // k_hybrid does the shadow and AO rays and leaves the per-pixel state for k_hy_gi_init (wavefront.hip).  The megakernel mode
   // keeps the whole rgen in k_hybrid.
@@ -1697,13 +1689,11 @@ int hybridImpl(vkrt_scene* s, const PushConstantRay* pc, const GlobalUniforms* c
     if((rc = ensureWorkingSet(s, P.tileCount * 64u, 1, stream)) != VKRT_OK)
       return rc;
     P.tileFirst = 0;
-    HIP_TRY(vkrt_launch_hybrid(P, g->color, g->position, g->normal, g->roughMetal, accum, nrd ? &np : nullptr, vkrt_wf_hybrid_tmp(s->wf), stream));
-    HybridGi G{(const float4*)g->color, (const float4*)g->position, (const float4*)g->normal, (const float2*)g->roughMetal, (float4*)accum,
-               nrd ? (float4*)nrd->diffRadianceHitDist : nullptr, nrd ? nrd->viewZ : nullptr};
+    HIP_TRY(vkrt_launch_hybrid(P, G, vkrt_wf_hybrid_tmp(s->wf), stream));
     HIP_TRY(vkrt_launch_hybrid_gi(P, s->wf, G, (unsigned)travBlock(s), stream));
   }
   else
-    HIP_TRY(vkrt_launch_hybrid(P, g->color, g->position, g->normal, g->roughMetal, accum, nrd ? &np : nullptr, nullptr, stream));
+    HIP_TRY(vkrt_launch_hybrid(P, G, nullptr, stream));
   HIP_TRY(hipEventRecord(s->evStop, stream));
   s->timed = true;
   s->wfTimed = false;

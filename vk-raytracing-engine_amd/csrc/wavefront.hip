@@ -3,7 +3,8 @@
 // (reference hello_vulkan.cpp:1446) exactly like pathtrace.hip, with the same per-path state machine
 // (rgen.h) and therefore the same results; the work is re-scheduled for gfx950:
 //
-//   k_wf_init          one thread per pixel: rgen prologue (seed, camera ray of sample 0) -> closest-ray stream.
+//   k_wf_init          one thread per pixel, in tile order like every per-pixel kernel here (rgen.h pixelOfWork): rgen prologue
+//                      (seed, camera ray of sample 0) -> closest-ray stream.
 //   k_wf_traverse      one thread per queued ray, batch-synchronous: the 64 rays of a wave start together, so the
 //                      top tree levels are fetched as coalesced/broadcast loads; lanes that finish early take over
 //                      pending subtrees of their neighbours (traverse_share.h).  Workgroups are one wave and
@@ -47,6 +48,7 @@
 #include "device_scene.h"
 #include "kernels.h"
 #include "rgen.h"
+#include "hybrid_gi.h"
 #include "shade.h"
 #include "traverse.h"
 #include "traverse_wide.h"
@@ -73,9 +75,7 @@ VKRT_DEV void loadCommon(const TraceParams& P, const WfBuffers& B, int parity, i
   L.prd.isSpecular = ((flags >> 25) & 1u) != 0u;
   L.hitValues = mk3(s2.x, s2.y, s2.z);
   L.px = pix & 0xffffu; L.lrow = pix >> 16;
-  float origin[4];
-  mat4MulVec4(P.viewInverse, 0.0f, 0.0f, 0.0f, 1.0f, origin);  // rgen:30 (uniform; cheaper to recompute than to carry)
-  L.camOrigin = mk3(origin[0], origin[1], origin[2]);
+  L.camOrigin = cameraOrigin(P);
   L.prd.lightDist = 0.0f;
   L.prd.shadowRayDir = mk3(0.0f);
   L.prd.hitValue = mk3(0.0f);
@@ -110,12 +110,6 @@ VKRT_DEV void storeShadow(const WfBuffers& B, int parity, int type, unsigned i, 
   wfStore(rec(B, parity, type, WF_S3, i), make_float4(contrib.x, contrib.y, contrib.z, 0.0f));
 }
 
-// tile-major index of the lane's pixel in the shard (tile * 64 + inTile of k_wf_init): its sample-state record
-VKRT_DEV unsigned pixelSlot(const TraceParams& P, const LaneState& L)
-{
-  return (((L.lrow >> 3) * P.tilesX + (L.px >> 3)) << 6) | ((L.lrow & 7u) << 3) | (L.px & 7u);
-}
-
 // rgen:99-120 for a segment of the path tracer that is complete (no shadow ray, or the ray is back): the stream the path's next
 // record goes to -- WF_C, or -1 when the pixel is stored or, in the sample-synchronous schedule, waits for k_wf_sample_init
 VKRT_DEV int finishSegment(const TraceParams& P, const WfBuffers& B, LaneState& L, bool shadowHit, f3 contrib, f3 nextWeight)
@@ -125,7 +119,7 @@ VKRT_DEV int finishSegment(const TraceParams& P, const WfBuffers& B, LaneState& 
   {
     if(P.flags & VKRT_FLAG_SAMPLE_SYNC)  // launch-uniform
     {
-      wfStore(B.sampleState + pixelSlot(P, L), make_float4(L.hitValues.x, L.hitValues.y, L.hitValues.z, __uint_as_float(L.prd.seed)));
+      wfStore(B.sampleState + pixelSlot(P, L.px, L.lrow), make_float4(L.hitValues.x, L.hitValues.y, L.hitValues.z, __uint_as_float(L.prd.seed)));
       return -1;
     }
     startSample(P, L);
@@ -176,24 +170,15 @@ __global__ __launch_bounds__(WF_BLOCK) void k_wf_init(const TraceParams P, const
   bool alive = false;
   unsigned nPixels = 0;
   LaneState L;
-  if(w < P.tileCount * 64u)
+  uint32_t x, y, lrow;
+  if(pixelOfWork(P, w, P.tileFirst, x, y, lrow))
   {
-    const unsigned tile = P.tileFirst + (w >> 6), inTile = w & 63u;
-    const uint32_t x = (tile % P.tilesX) * 8u + (inTile & 7u);
-    const uint32_t lrow = (tile / P.tilesX) * 8u + (inTile >> 3);
-    if(x < P.fullW && lrow < P.localRows)
-    {
-      const uint32_t y = globalRow(P, lrow);
-      if(y < P.fullH)
-      {
-        startPixel(P, L, x, y, lrow);
-        nPixels = 1;
-        if(P.pc.samples <= 0 || P.pc.depth <= 0)
-          storePixel(P, L);  // degenerate launch: no rays
-        else
-          alive = true;
-      }
-    }
+    startPixel(P, L, x, y, lrow);
+    nPixels = 1;
+    if(P.pc.samples <= 0 || P.pc.depth <= 0)
+      storePixel(P, L);  // degenerate launch: no rays
+    else
+      alive = true;
   }
   __shared__ unsigned wsum[WF_TYPES * (WF_BLOCK / 64 + 1)];
   const unsigned slot = claimSlots(B, 0, alive ? WF_C : -1, lane, wsum);
@@ -208,37 +193,23 @@ __global__ __launch_bounds__(WF_BLOCK) void k_wf_init(const TraceParams P, const
 // The twin of k_wf_init, in front of round `round` = smpl * (depth + 1): one thread per pixel in tile order, so a wave is one 8x8
 // tile.  The C stream of the round's parity is empty here: the traversal launch of round - 1 cleared its count and no path of
 // sample smpl - 1 emitted a record in the shade step of round - 1 (every one of them had ended its sample by then).
-// prd.isSpecular is not part of the sample state.  The other schedule carries the bit of the previous sample's last segment into
-// the new sample, but nothing reads it there: at depth 0 the emission rule of the hit shader (`depth == 0 || isSpecular`, rchit:83)
-// holds whatever the bit says and closestHitTail sets it on both of its branches; a miss leaves it alone but sets depth 100, which
-// decides the shadow-ray test (rgen:79) by itself and ends the sample, so the bit reaches the next sample's depth 0 unread again.
+// The sample state is (hitValues, seed); the rest of the lane is bindPixel's (rgen.h, which also says why prd.isSpecular is not carried).
 __global__ __launch_bounds__(WF_BLOCK) void k_wf_sample_init(const TraceParams P, const WfBuffers B, const int round, const int smpl)
 {
   const unsigned lane = lane_id();
   const unsigned w = blockIdx.x * blockDim.x + threadIdx.x;  // tile-major work index
   bool alive = false;
   LaneState L;
-  if(w < P.tileCount * 64u)
+  uint32_t x, y, lrow;
+  if(pixelOfWork(P, w, P.tileFirst, x, y, lrow))
   {
-    const unsigned tile = P.tileFirst + (w >> 6), inTile = w & 63u;
-    const uint32_t x = (tile % P.tilesX) * 8u + (inTile & 7u);
-    const uint32_t lrow = (tile / P.tilesX) * 8u + (inTile >> 3);
-    if(x < P.fullW && lrow < P.localRows && globalRow(P, lrow) < P.fullH)
-    {
-      const float4 st = wfLoad(B.sampleState + (tile * 64u + inTile));  // == pixelSlot: written once, read once
-      L.px = x; L.lrow = lrow;
-      L.prd.seed = __float_as_uint(st.w);
-      L.prd.isSpecular = false;
-      L.prd.lightDist = 0.0f;
-      L.prd.shadowRayDir = mk3(0.0f);
-      float origin[4];
-      mat4MulVec4(P.viewInverse, 0.0f, 0.0f, 0.0f, 1.0f, origin);
-      L.camOrigin = mk3(origin[0], origin[1], origin[2]);
-      L.hitValues = mk3(st.x, st.y, st.z);
-      L.smpl = smpl;
-      startSample(P, L);
-      alive = true;
-    }
+    const float4 st = wfLoad(B.sampleState + pixelSlot(P, x, lrow));  // written once, read once
+    bindPixel(P, L, x, lrow);
+    L.prd.seed = __float_as_uint(st.w);
+    L.hitValues = mk3(st.x, st.y, st.z);
+    L.smpl = smpl;
+    startSample(P, L);
+    alive = true;
   }
   __shared__ unsigned wsum[WF_TYPES * (WF_BLOCK / 64 + 1)];
   const unsigned slot = claimSlots(B, round & 1, alive ? WF_C : -1, lane, wsum);
@@ -249,61 +220,17 @@ __global__ __launch_bounds__(WF_BLOCK) void k_wf_sample_init(const TraceParams P
 // ---- hybrid mode: the GI path of raytraceHybrid.rgen:172-282 on the same streams ----------------------------------------------
 // A pixel's GI path is one sample that starts at depth 1 from the G-buffer position; its record is the path tracer's, with the
 // S2 plane (unused: there is no sum over samples) carrying hitDists (.x, rgen:253-264) and the visibility term of the direct
-// part (.y, the alpha of the accumulation image).  HYBRID instantiations of the shade functions end a sample with hybridFinish
-// instead of storePixel and keep hitDists; everything else -- rays, shaders, compaction -- is shared with the path tracer.
-// raytraceHybrid.rgen:266-282 + 36-48: the pixel's GI radiance is complete
-VKRT_DEV void hybridFinish(const TraceParams& P, const HybridGi& G, uint32_t px, uint32_t lrow, bool shaded, f3 hitValue, float hitDists, float alpha)
-{
-  const size_t p = (size_t)lrow * P.fullW + px;
-  float4 color = make_float4(0.0f, 0.0f, 0.0f, alpha);
-  if(shaded)
-  {
-    color.x = hitValue.x; color.y = hitValue.y; color.z = hitValue.z;
-    if(G.nrdRadHitD)
-    {  // REBLUR front end, hitDistParams (3, 1, 20, -25), rgba16f store (same operation order as k_hybrid)
-      const float roughness = G.rough[p].x;
-      const float viewZ = G.nrdViewZ[p];
-      const float t = glsl_clamp(exp2f(-25.0f * roughness * roughness), 0.0f, 1.0f);
-      const float f = (3.0f + fabsf(viewZ) * 1.0f) * (1.0f * (1.0f - t) + 20.0f * t);
-      float normHitDist = glsl_clamp(hitDists / f, 0.0f, 1.0f);
-      f3 rad = hitValue;
-      const bool bad = isnan(rad.x) || isnan(rad.y) || isnan(rad.z) || isinf(rad.x) || isinf(rad.y) || isinf(rad.z);
-      rad = bad ? mk3(0.0f) : mk3(glsl_clamp(rad.x, 0.0f, 65504.0f), glsl_clamp(rad.y, 0.0f, 65504.0f), glsl_clamp(rad.z, 0.0f, 65504.0f));
-      normHitDist = (isnan(normHitDist) || isinf(normHitDist)) ? 0.0f : glsl_clamp(normHitDist, 0.0f, 1.0f);
-      if(normHitDist != 0.0f)
-        normHitDist = glsl_max(normHitDist, 1e-7f);
-      const float Y = (rad.x * 0.25f + rad.y * 0.5f) + rad.z * 0.25f;
-      const float Co = (rad.x * 0.5f + rad.y * 0.0f) + rad.z * -0.5f;
-      const float Cg = (rad.x * -0.25f + rad.y * 0.5f) + rad.z * -0.25f;
-      G.nrdRadHitD[p] = make_float4(quantizeHalf(Y), quantizeHalf(Co), quantizeHalf(Cg), quantizeHalf(normHitDist));
-    }
-  }
-  if(P.pc.frame > 0)  // accumulateFrames, rgen:36-48 (all four channels)
-  {
-    const float a = 1.0f / (float)(P.pc.frame + 1);
-    const float4 old = G.accum[p];
-    G.accum[p] = make_float4(old.x * (1.0f - a) + color.x * a, old.y * (1.0f - a) + color.y * a, old.z * (1.0f - a) + color.z * a,
-                             old.w * (1.0f - a) + color.w * a);
-  }
-  else
-    G.accum[p] = color;
-}
-// rgen:240-266 for one finished segment of the GI path; false = the path (and the pixel) is complete
+// part (.y, the alpha of the accumulation image).  HYBRID instantiations of the shade functions end a sample with hybridStorePixel
+// instead of storePixel and keep hitDists; everything else -- rays, shaders, compaction -- is shared with the path tracer, and the
+// rules of the GI path itself with k_hybrid, which runs it in-kernel in the megakernel mode (hybrid_gi.h).
+// rgen:240-266 for one finished segment of the GI path (hybrid_gi.h); false = the path is complete and the pixel stored
 VKRT_DEV bool advanceSegmentHybrid(const TraceParams& P, const HybridGi& G, LaneState& L, bool shadowHit, f3 contrib, f3 nextWeight, float lightDist)
 {
   L.stage = 0;
-  if(!shadowHit)
-    L.hitValue = L.hitValue + contrib;
-  if(L.prd.depth == 1u && !L.prd.isSpecular)  // rgen:253-264 (only segments that traced a shadow ray get here with depth 1)
-    L.hitValues.x = shadowHit ? 0.5f * lightDist : lightDist;
-  L.curWeight = nextWeight;
-  L.prd.depth++;
-  if(!(L.prd.depth < (uint32_t)P.pc.depth))
-  {
-    hybridFinish(P, G, L.px, L.lrow, true, L.hitValue, L.hitValues.x, L.hitValues.y);
-    return false;
-  }
-  return true;
+  if(giSegmentStep(P.pc, L.prd, L.curWeight, L.hitValue, L.hitValues.x, shadowHit, contrib, nextWeight, lightDist))
+    return true;
+  hybridStorePixel(P, G, (size_t)L.lrow * P.fullW + L.px, true, L.hitValue, L.hitValues.x, L.hitValues.y);
+  return false;
 }
 
 // ---- shade, results of streams C and P: [finish segment k,] rchit / rmiss of the traced closest-hit ray, then the next ray(s) ----
@@ -325,9 +252,7 @@ VKRT_DEV void shadeHitBlock(const TraceParams& P, const WfBuffers& B, const Hybr
   const int type = PAIR ? WF_P : WF_C;
   const unsigned lane = lane_id();
   const unsigned qi = block * WF_BLOCK + threadIdx.x;
-  ShadeStats st;
-  st.hits = 0; st.diffuse = 0; st.taps = 0;
-  st.lut = ldsTexelLut(P.sc, lds.lut);
+  ShadeStats st = shadeStatsInit(P.sc, lds.lut);
   unsigned* wsum = lds.wsum;
   int to = -1;
   LaneState L;
@@ -357,7 +282,7 @@ VKRT_DEV void shadeHitBlock(const TraceParams& P, const WfBuffers& B, const Hybr
       closestHitShaderInst(P.sc, P.pc, hit, (uint32_t)hit.slot, ts, L.prd.rayDirection, L.prd, st);
     else
       missShader(P.pc, L.prd);
-    segmentTerms(L, contrib, nextWeight);
+    segmentTerms(L.prd, L.curWeight, contrib, nextWeight);
     // VKRT_OPT_SKIP_DEAD_SHADOW_RAYS (launch-uniform, path-tracing mode only): rgen:99-102 adds `contrib` when the shadow ray is
     // not occluded; a contribution of exactly (+-0, +-0, +-0) -- light behind the surface and no emission, or a zero weight --
     // leaves hitValue bit for bit as it is either way (x + 0 = x; the sum is never -0), so the ray need not be traced
@@ -443,63 +368,26 @@ __global__ __launch_bounds__(WF_BLOCK) void k_hy_gi_init(const TraceParams P, co
   const unsigned w = blockIdx.x * blockDim.x + threadIdx.x;  // tile-major work index
   bool alive = false;
   LaneState L;
-  if(w < P.tileCount * 64u)
+  uint32_t x, y, lrow;
+  if(pixelOfWork(P, w, P.tileFirst, x, y, lrow))
   {
-    const unsigned tile = P.tileFirst + (w >> 6), inTile = w & 63u;
-    const uint32_t x = (tile % P.tilesX) * 8u + (inTile & 7u);
-    const uint32_t lrow = (tile / P.tilesX) * 8u + (inTile >> 3);
-    if(x < P.fullW && lrow < P.localRows && globalRow(P, lrow) < P.fullH)
+    const size_t p = (size_t)lrow * P.fullW + x;
+    const GbufferPixel g = loadGbufferPixel(G, p);
+    const uint2 t = tmp[p];
+    const float alpha = __uint_as_float(t.y);
+    if(g.shaded)
     {
-      const size_t p = (size_t)lrow * P.fullW + x;
-      const float4 pixelImg = G.color[p], pixelPos = G.position[p], pixelNorm = G.normal[p];
-      const float2 rm = G.rough[p];
-      const uint2 t = tmp[p];
-      const f3 worldPos = mk3(pixelPos.x, pixelPos.y, pixelPos.z), worldNrm = mk3(pixelNorm.x, pixelNorm.y, pixelNorm.z);
-      const bool shaded = !(worldPos.x == 0.0f && worldPos.y == 0.0f && worldPos.z == 0.0f && worldNrm.x == 0.0f && worldNrm.y == 0.0f &&
-                            worldNrm.z == 0.0f);  // rgen:67
-      const float alpha = __uint_as_float(t.y);
-      if(!shaded)
-        hybridFinish(P, G, x, lrow, false, mk3(0.0f), 0.0f, alpha);
-      else
-      {
-        L.px = x; L.lrow = lrow;
-        L.prd.seed = t.x;
-        L.prd.lightDist = 0.0f; L.prd.shadowRayDir = mk3(0.0f);
-        const float roughness = rm.x, metalness = rm.y;
-        const float ratio = metalness * (1.0f - roughness);
-        f3 direction;
-        if(ratio < 0.8f)
-        {
-          L.prd.isSpecular = false;
-          f3 tangent, binormal;
-          createCoordinateSystem(worldNrm, tangent, binormal);
-          direction = normalize3(samplingHemisphere(L.prd.seed, tangent, binormal, worldNrm));
-          L.curWeight = mk3(pixelImg.w, pixelPos.w, pixelNorm.w);  // albedo
-        }
-        else
-        {
-          L.prd.isSpecular = true;
-          float cam[4];
-          mat4MulVec4(P.viewInverse, 0.0f, 0.0f, 0.0f, 1.0f, cam);
-          const f3 V = normalize3(mk3(cam[0], cam[1], cam[2]) - worldPos);
-          direction = normalize3(glsl_reflect(-V, worldNrm));
-          L.curWeight = mk3(1.0f);
-        }
-        L.prd.hitValue = mk3(0.0f);
-        L.prd.rayOrigin = worldPos;
-        L.prd.rayDirection = direction;
-        L.prd.depth = 1;
-        L.prd.weight = mk3(0.0f);
-        L.hitValue = mk3(0.0f);
-        L.hitValues = mk3(0.0f, alpha, 0.0f);  // .x hitDists, .y visibility
-        L.smpl = 0;
-        L.stage = 0;
-        if(L.prd.depth < (uint32_t)P.pc.depth)
-          alive = true;
-        else
-          hybridFinish(P, G, x, lrow, true, mk3(0.0f), 0.0f, alpha);
-      }
+      bindPixel(P, L, x, lrow);
+      L.prd.seed = t.x;
+      giFirstRay(P, g, L.prd, L.curWeight);
+      L.hitValue = mk3(0.0f);
+      L.hitValues = mk3(0.0f, alpha, 0.0f);  // .x hitDists, .y visibility
+      L.smpl = 0;
+      L.stage = 0;
+      alive = L.prd.depth < (uint32_t)P.pc.depth;
     }
+    if(!alive)  // no path to trace: the pixel's value is final
+      hybridStorePixel(P, G, p, g.shaded, mk3(0.0f), 0.0f, alpha);
   }
   __shared__ unsigned wsum[WF_TYPES * (WF_BLOCK / 64 + 1)];
   const unsigned slot = claimSlots(B, 0, alive ? WF_C : -1, lane, wsum);
@@ -512,13 +400,8 @@ __global__ __launch_bounds__(WF_BLOCK) void k_hy_gi_init(const TraceParams P, co
 // store of frame 0.  Launched at the end of a frame on the frame's own lane, behind the blend of the frame before it.
 __global__ __launch_bounds__(WF_BLOCK) void k_wf_blend(const TraceParams P, const float4* stage)
 {
-  const unsigned w = blockIdx.x * blockDim.x + threadIdx.x;
-  if(w >= P.tileCount * 64u)
-    return;
-  const unsigned tile = P.tileFirst + (w >> 6), inTile = w & 63u;
-  const uint32_t x = (tile % P.tilesX) * 8u + (inTile & 7u);
-  const uint32_t lrow = (tile / P.tilesX) * 8u + (inTile >> 3);
-  if(x < P.fullW && lrow < P.localRows && globalRow(P, lrow) < P.fullH)
+  uint32_t x, y, lrow;
+  if(pixelOfWork(P, blockIdx.x * blockDim.x + threadIdx.x, P.tileFirst, x, y, lrow))
   {
     const size_t p = (size_t)lrow * P.fullW + x;
     blendPixel((float4*)P.image + p, stage[p], P.pc.frame);
@@ -563,18 +446,22 @@ static hipError_t subframeBegin(const TraceParams& P, const WfBuffers& B, hipStr
 // a sample takes at most depth + 1 rounds: its first closest-hit ray, then one round per further segment (the shadow ray of
 // segment k travels with the closest-hit ray of segment k + 1), then the shadow ray of its last segment
 static int subframeRounds(const TraceParams& P) { return (P.pc.samples <= 0 || P.pc.depth <= 0) ? 0 : P.pc.samples * (P.pc.depth + 1); }
+// One traversal launch on the records of round r, its geometry for a sub-frame's tiles: workgroups of travBlock threads (64 unless 128
+// or 256 is asked for).  Every path holds one record and a record at most two rays; +4 blocks for the partial tails of the four ray
+// kinds.  One wavefront per workgroup by default: a finished wave frees its slot and LDS without waiting for three others.
+static void launchTraverse(const TraceParams& P, const WfBuffers& B, int r, unsigned travBlock, bool count, hipStream_t stream)
+{
+  const unsigned work = P.tileCount * 64u, tb = (travBlock == 256u || travBlock == 128u) ? travBlock : 64u;
+  vkrt_wf_launch_traverse(P, B, r, tb, count, dim3(2 * ((work + tb - 1) / tb) + 4), (size_t)P.sc.stackCap * tb * sizeof(int), stream);
+}
 // round r: traverse the rays of the records, shade the results into the next round's records
 static void subframeRound(const TraceParams& P, const WfBuffers& B, int r, unsigned travBlock, bool count, hipStream_t stream, WfTiming* timing)
 {
   const unsigned work = P.tileCount * 64u;
-  // every path holds one record and a record at most two rays; +4 blocks for the partial tails of the four ray kinds.
-  // One wavefront per workgroup by default: a finished wave frees its slot and LDS without waiting for three others.
-  const dim3 tg(2 * ((work + travBlock - 1) / travBlock) + 4);
-  const size_t tlds = (size_t)P.sc.stackCap * travBlock * sizeof(int);
   const bool timed = timing && timing->events && 2 * (timing->used + 1) <= timing->capacity;
   if(timed)
     (void)hipEventRecord(timing->events[2 * timing->used], stream);
-  vkrt_wf_launch_traverse(P, B, r, travBlock, count, tg, tlds, stream);
+  launchTraverse(P, B, r, travBlock, count, stream);
   if(timed)
   {
     (void)hipEventRecord(timing->events[2 * timing->used + 1], stream);
@@ -620,7 +507,7 @@ static int balancedInFlight(int frames, int want)
 hipError_t vkrt_launch_wavefront(const TraceParams& P, const WfBuffers& B, const WfOptions& opt, int frames, uint32_t seedStep, bool count,
                                  hipStream_t stream, WfTiming* timing, const WfAsync* async)
 {
-  const unsigned travBlock = opt.travBlock == 256 ? 256u : opt.travBlock == 128 ? 128u : 64u;
+  const unsigned travBlock = (unsigned)opt.travBlock;
   const int steps = subframeSteps(P);  // launches of a frame between its begin and its blend: the rounds and the sample inits
   frames = std::max(frames, 1);
   // Lanes: F frame groups x S tile ranges.  Frames in flight keep every launch at full size, sub-frames cut it into S pieces -- and
@@ -781,12 +668,9 @@ hipError_t vkrt_launch_hybrid_gi(const TraceParams& P, const WfBuffers& B, const
   hipLaunchKernelGGL(k_hy_gi_init, dim3(blocks), dim3(WF_BLOCK), 0, stream, P, B, G, (const uint2*)vkrt_wf_hybrid_tmp(B));
   // the GI path is one sample that starts at depth 1: at most pc.depth - 1 segments, i.e. pc.depth rounds of the paired pipeline
   const int rounds = P.pc.depth;
-  const unsigned tbs = (travBlock == 256u || travBlock == 128u) ? travBlock : 64u;
-  const dim3 tg(2 * ((work + tbs - 1) / tbs) + 4);
-  const size_t tlds = (size_t)P.sc.stackCap * tbs * sizeof(int);
   for(int r = 0; r < rounds; r++)
   {
-    vkrt_wf_launch_traverse(P, B, r, tbs, false, tg, tlds, stream);
+    launchTraverse(P, B, r, travBlock, false, stream);
     hipLaunchKernelGGL(k_wf_shade_hybrid, dim3(blocks + 3), dim3(WF_BLOCK), 0, stream, P, B, G, r);
   }
   return hipGetLastError();

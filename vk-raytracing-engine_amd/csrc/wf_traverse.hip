@@ -124,7 +124,6 @@ void k_wf_traverse(const TraceParams P, const WfBuffers B, const int round)
 void vkrt_wf_launch_traverse(const TraceParams& P, const WfBuffers& B, int r, unsigned travBlock, bool count, dim3 tg, size_t tlds, hipStream_t stream)
 {
   const bool wide = P.sc.layout == 1u;
-  const int tm = (P.sc.watertight ? VKRT_TM_WATERTIGHT : 0) | (P.sc.dissolve ? VKRT_TM_DISSOLVE : 0);
   const dim3 tb(travBlock);
 #define VKRT_TRAV_LAUNCH(C, W, TB, TM) hipLaunchKernelGGL((k_wf_traverse<C, W, TB, TM>), tg, tb, tlds, stream, P, B, r)
 #define VKRT_TRAV_MODES(TB, TM)                                                                                                        \
@@ -132,20 +131,16 @@ void vkrt_wf_launch_traverse(const TraceParams& P, const WfBuffers& B, int r, un
     if(wide) { if(count) VKRT_TRAV_LAUNCH(true, true, TB, TM); else VKRT_TRAV_LAUNCH(false, true, TB, TM); }                           \
     else { if(count) VKRT_TRAV_LAUNCH(true, false, TB, TM); else VKRT_TRAV_LAUNCH(false, false, TB, TM); }                             \
   } while(0)
+#define VKRT_TRAV_64(TM) VKRT_TRAV_MODES(64, TM)
   if(travBlock == 64)
   {
-    switch(tm)
-    {
-      case 0: VKRT_TRAV_MODES(64, 0); break;
-      case 1: VKRT_TRAV_MODES(64, 1); break;
-      case 2: VKRT_TRAV_MODES(64, 2); break;
-      default: VKRT_TRAV_MODES(64, 3); break;
-    }
+    VKRT_FRAME_TM_SWITCH(frame_tri_mode(P.sc, false), VKRT_TM_DISSOLVE, VKRT_TRAV_64)
   }
   else if(travBlock == 128)
     VKRT_TRAV_MODES(128, 0);
   else
     VKRT_TRAV_MODES(256, 0);
+#undef VKRT_TRAV_64
 #undef VKRT_TRAV_MODES
 #undef VKRT_TRAV_LAUNCH
 }
