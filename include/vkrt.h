@@ -270,6 +270,13 @@ enum vkrt_option {
                                    so camera rays are traced and their hits shaded as whole tiles; 0 = a pixel starts its next sample in the
                                    round its sample ends.  Same paths, draws and float operations: no pixel and no counter changes; a timed
                                    call's shade_ms includes the sample starts.  env VKRT_WF_SAMPLE_SYNC */
+  VKRT_OPT_WF_CAMERA_ROUNDS = 16, /* (appended within ABI 4 like option 15)  1 (default) = in the schedule of option 15 the first round of every sample
+                                   traces and shades its camera rays straight from the pixel grid: one wave per 8x8 tile makes the rays from the
+                                   16-B sample state, and the shade step makes the same state again, so the frame has no init kernels and the camera
+                                   rays no path records (96 instead of 256 B moved per pixel and sample in that round); 0 = init kernels write a
+                                   record per camera ray.  Takes effect in path-tracing mode with option 15 = 1, the wide8 layout, 64-thread traversal
+                                   workgroups and work sharing on; anywhere else it resolves to 0 silently.  Same paths, draws and float operations: no
+                                   pixel and no counter changes.  env VKRT_WF_CAMERA_ROUNDS */
   VKRT_INFO_ANYHIT_ORDER   = 100, /* read-only (vkrt_scene_get_option; set is refused): the child-order bits (2 | 4) that the last vkrt_accel_build
                                    resolved VKRT_OPT_WF_SHARE_FLAGS to, i.e. what bit 3 ("automatic") decided for this scene; 0 before a build */
   VKRT_INFO_SPLIT_BUDGET   = 101  /* read-only (ABI 4): the pre-splitting budget the last vkrt_accel_build used -- what VKRT_OPT_SPLIT_BUDGET = -1

@@ -3,7 +3,9 @@
 set, un-overlapped kernel times of single timed frames (VKRT_TRACE_TIME_KERNELS: traverse_ms, shade time per launch) and the frame
 time of six-frame calls with the default frames in flight.  One JSON line per option.
 
-PROBE_SYNC="0,1" picks the options ("none": a library without the option, e.g. an older build selected with VKRT_LIB);
+PROBE_SYNC="0,1" picks the values ("none": the option is left alone, e.g. for an older build selected with VKRT_LIB that lacks it);
+PROBE_OPTION picks the option they are set on (default 15, VKRT_OPT_WF_SAMPLE_SYNC; 16 = VKRT_OPT_WF_CAMERA_ROUNDS: camera rays from
+records / from the pixel grid);
 PROBE_TIMED=0 leaves the timed frames out, so that a kernel trace of the run holds plain frames only (2 single frames and
 1 + PROBE_CALLS calls of six per option)."""
 import json
@@ -35,14 +37,15 @@ def main():
     def pc(frame):
         return make_push_constants(samples=SPP, depth=DEPTH, frame=frame, lights_count=lights)
 
+    option = int(os.environ.get("PROBE_OPTION", abi.VKRT_OPT_WF_SAMPLE_SYNC))
     for opt in os.environ.get("PROBE_SYNC", "0,1").split(","):
         if opt != "none":
-            r.set_option(abi.VKRT_OPT_WF_SAMPLE_SYNC, int(opt))
+            r.set_option(option, int(opt))
         for f in range(2):  # warm-up under this option, and frames 0..7 of the image
             r.pathtrace(pc(f), cam, W, H, seed=f, image=img)
         r.pathtrace_frames(pc(2), cam, W, H, PER_CALL, seed=2, image=img)
         torch.cuda.synchronize()
-        out = {"sample_sync": opt, "lib": os.path.basename(vkrt_amd.LIB_PATH)}
+        out = {"sample_sync" if option == abi.VKRT_OPT_WF_SAMPLE_SYNC else f"option_{option}": opt, "lib": os.path.basename(vkrt_amd.LIB_PATH)}
         if os.environ.get("PROBE_TIMED", "1") != "0":
             tr, sh, tot = [], [], []
             for k in range(3):

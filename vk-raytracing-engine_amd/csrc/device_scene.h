@@ -163,6 +163,8 @@ struct DevCounters
 #define VKRT_FLAG_SKIP_DEAD_SHADOW 0x100u  // VKRT_OPT_SKIP_DEAD_SHADOW_RAYS: a diffuse hit whose contribution is exactly zero emits no shadow ray
 #define VKRT_FLAG_STORE_STAGED 0x200u      // frames in flight: `image` is the frame's staging plane; storePixel writes the pixel value unblended
 #define VKRT_FLAG_SAMPLE_SYNC 0x400u       // VKRT_OPT_WF_SAMPLE_SYNC: all pixels of a frame trace sample s before any starts sample s + 1 (wavefront.hip)
+#define VKRT_FLAG_CAMERA_ROUNDS 0x800u     // VKRT_OPT_WF_CAMERA_ROUNDS (with VKRT_FLAG_SAMPLE_SYNC): the first round of a sample traces and shades its camera
+                                           // rays straight from the pixel grid, without path records (k_wf_traverse_camera, k_wf_shade_camera)
 
 struct TraceParams
 {

@@ -76,6 +76,9 @@ hipError_t vkrt_launch_wavefront(const TraceParams& P, const WfBuffers& B, const
 // tlds = LDS bytes of the per-lane stacks; count = the instrumented instantiation.  Launch errors surface through hipGetLastError.
 void       vkrt_wf_launch_traverse(const TraceParams& P, const WfBuffers& B, int r, unsigned travBlock, bool count, dim3 tg, size_t tlds,
                                    hipStream_t stream);
+// one launch of k_wf_traverse_camera (wf_traverse.hip) for round r, the first round of sample smpl (VKRT_FLAG_CAMERA_ROUNDS): one wave per
+// tile of the sub-frame; tlds = LDS bytes of 64 per-lane stacks
+void       vkrt_wf_launch_traverse_camera(const TraceParams& P, const WfBuffers& B, int r, int smpl, bool count, size_t tlds, hipStream_t stream);
 
 // hybrid mode (hybrid.hip, wavefront.hip)
 struct HybridGi  // the planes of the hybrid passes: one struct for the three launches below

@@ -30,6 +30,7 @@
 #define VKRT_WF_FRAMES_IN_FLIGHT_DEFAULT 3
 #define VKRT_SPLIT_BUDGET_DEFAULT -1  // automatic (round 5): vkrt_accel_build decides per scene
 #define VKRT_WF_SAMPLE_SYNC_DEFAULT 1  // sample-synchronous schedule of the wavefront path tracer (wavefront.hip)
+#define VKRT_WF_CAMERA_ROUNDS_DEFAULT 1  // ... whose camera rays are traced from the pixel grid, without path records (wavefront.hip)
 #include "lbvh.h"
 #include "refit.h"
 #include "vertex_update.h"
@@ -91,8 +92,8 @@ struct vkrt_scene
   int wfTimingRounds = 0;  // rounds per frame of the last timed call (vkrt_last_trace_timing: which gaps are shade launches)
   // execution options (include/vkrt.h vkrt_option); index = option id
   std::vector<hipEvent_t> wfPool;  // events ordering the lanes of one call (kernels.h WfAsync::pool)
-  int opt[VKRT_OPT_WF_SAMPLE_SYNC + 1] = {0, 1, 1, 3, 64, VKRT_WF_SHARE_DEFAULT, VKRT_TRI_THRESHOLD_DEFAULT, 0, VKRT_WF_SHARE_FLAGS_DEFAULT, 1, 0, 0, 0,
-                                          VKRT_WF_FRAMES_IN_FLIGHT_DEFAULT, VKRT_SPLIT_BUDGET_DEFAULT, VKRT_WF_SAMPLE_SYNC_DEFAULT};
+  int opt[VKRT_OPT_WF_CAMERA_ROUNDS + 1] = {0, 1, 1, 3, 64, VKRT_WF_SHARE_DEFAULT, VKRT_TRI_THRESHOLD_DEFAULT, 0, VKRT_WF_SHARE_FLAGS_DEFAULT, 1, 0, 0, 0,
+                                            VKRT_WF_FRAMES_IN_FLIGHT_DEFAULT, VKRT_SPLIT_BUDGET_DEFAULT, VKRT_WF_SAMPLE_SYNC_DEFAULT, VKRT_WF_CAMERA_ROUNDS_DEFAULT};
   bool hasLargeTriangles = false;  // some instanced triangle covers more than 1 % of the largest face of the scene's box (any-hit order heuristic)
   bool wavefront = true;  // execution mode the acceleration structure was built for (opt[VKRT_OPT_MODE] at vkrt_accel_build)
   // moving instances (vkrt_scene_update_nodes / vkrt_accel_refit)
@@ -236,7 +237,8 @@ int clampOption(int option, int v)
     case VKRT_OPT_TRI_THRESHOLD: return std::max(0, std::min(65, v));
     case VKRT_OPT_WF_SHARE_PERIOD: return std::max(0, std::min(255, v));
     case VKRT_OPT_WF_SHARE_FLAGS: return v & 31;
-    case VKRT_OPT_GBUFFER_MIPS: case VKRT_OPT_WATERTIGHT: case VKRT_OPT_SKIP_DEAD_SHADOW_RAYS: case VKRT_OPT_ANYHIT_DISSOLVE: case VKRT_OPT_WF_SAMPLE_SYNC: return v ? 1 : 0;
+    case VKRT_OPT_GBUFFER_MIPS: case VKRT_OPT_WATERTIGHT: case VKRT_OPT_SKIP_DEAD_SHADOW_RAYS: case VKRT_OPT_ANYHIT_DISSOLVE: case VKRT_OPT_WF_SAMPLE_SYNC:
+    case VKRT_OPT_WF_CAMERA_ROUNDS: return v ? 1 : 0;
   }
   return v;
 }
@@ -253,7 +255,8 @@ void optionsFromEnvironment(vkrt_scene* s)
                                                           {"VKRT_GBUFFER_MIPS", VKRT_OPT_GBUFFER_MIPS}, {"VKRT_WATERTIGHT", VKRT_OPT_WATERTIGHT},
                                                           {"VKRT_SKIP_DEAD_SHADOW_RAYS", VKRT_OPT_SKIP_DEAD_SHADOW_RAYS},
                                                           {"VKRT_ANYHIT_DISSOLVE", VKRT_OPT_ANYHIT_DISSOLVE}, {"VKRT_WF_FRAMES_IN_FLIGHT", VKRT_OPT_WF_FRAMES_IN_FLIGHT},
-                                                          {"VKRT_SPLIT_BUDGET", VKRT_OPT_SPLIT_BUDGET}, {"VKRT_WF_SAMPLE_SYNC", VKRT_OPT_WF_SAMPLE_SYNC}};
+                                                          {"VKRT_SPLIT_BUDGET", VKRT_OPT_SPLIT_BUDGET}, {"VKRT_WF_SAMPLE_SYNC", VKRT_OPT_WF_SAMPLE_SYNC},
+                                                          {"VKRT_WF_CAMERA_ROUNDS", VKRT_OPT_WF_CAMERA_ROUNDS}};
   for(const auto& k : ints)
     if((e = getenv(k.name)))
       s->opt[k.option] = clampOption(k.option, atoi(e));
@@ -826,7 +829,7 @@ int vkrt_scene_set_option(vkrt_scene* s, int option, int value)
 {
   if(!s)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "scene is NULL");
-  if(option < VKRT_OPT_MODE || option > VKRT_OPT_WF_SAMPLE_SYNC)
+  if(option < VKRT_OPT_MODE || option > VKRT_OPT_WF_CAMERA_ROUNDS)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "unknown option %d", option);
   if(clampOption(option, value) != value)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "option %d: value %d out of range", option, value);
@@ -848,7 +851,7 @@ int vkrt_scene_get_option(const vkrt_scene* s, int option, int* value)
     *value = s->built ? s->splitResolved : 0;
     return VKRT_OK;
   }
-  if(option < VKRT_OPT_MODE || option > VKRT_OPT_WF_SAMPLE_SYNC)
+  if(option < VKRT_OPT_MODE || option > VKRT_OPT_WF_CAMERA_ROUNDS)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "unknown option %d", option);
   *value = s->opt[option];
   return VKRT_OK;
@@ -1530,6 +1533,11 @@ int vkrt_pathtrace_frames(vkrt_scene* s, const PushConstantRay* pc, const Global
     const uint32_t seedStep = (P.flags & VKRT_TRACE_SAME_SEED_EVERY_FRAME) ? 0u : 1u;
     if(s->opt[VKRT_OPT_WF_SAMPLE_SYNC])
       P.flags |= VKRT_FLAG_SAMPLE_SYNC;  // internal bit (device_scene.h)
+    // camera rounds: only in that schedule, and only where the sharing wave of k_wf_traverse_camera runs (wide8 tree, one-wave traversal
+    // workgroups, sharing on); anywhere else the option resolves to the record path
+    if(s->opt[VKRT_OPT_WF_CAMERA_ROUNDS] && (P.flags & VKRT_FLAG_SAMPLE_SYNC) && s->dev.layout == 1u && travBlock(s) == 64 && s->dev.shareMinIdle != 0u &&
+       s->dev.triThreshold != 0u)
+      P.flags |= VKRT_FLAG_CAMERA_ROUNDS;
     if((rc = ensureWorkingSet(s, P.tileCount * 64u, framesInFlight(s, (int)n_frames), stream)) != VKRT_OK)
       return rc;
     if((rc = ensureEventPool(s, (int)std::min<uint32_t>(n_frames, VKRT_FRAMES_PER_BATCH))) != VKRT_OK)

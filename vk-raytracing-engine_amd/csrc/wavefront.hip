@@ -30,7 +30,7 @@
 // (one record instead of a shadow record followed by a closest record).
 //
 // A frame = init + samples * (depth + 1) x (traverse, shade) enqueued back to back on the caller's
-// stream; stream counts stay on the device (no host synchronisation inside a frame).
+// stream; stream counts stay on the device (no host synchronisation inside a frame).  (Camera rounds, below: no init.)
 //
 // Sample-synchronous schedule (VKRT_OPT_WF_SAMPLE_SYNC, VKRT_FLAG_SAMPLE_SYNC).  A sample takes at most depth + 1 rounds, so the
 // round count above already lets every pixel of a frame trace sample s in the rounds [s (depth + 1), (s + 1) (depth + 1)): a path
@@ -39,6 +39,20 @@
 // a sample are then traced as whole 8x8 tiles per wave instead of scattered among bounce rays of every depth, and their hits are
 // shaded 64 neighbouring pixels to a wave.  Paths, random draws and float operations are those of the other schedule (option 0:
 // pixels walk through their samples at their own pace); only the round in which a ray is traced changes.
+//
+// Camera rounds (VKRT_OPT_WF_CAMERA_ROUNDS, VKRT_FLAG_CAMERA_ROUNDS; the default where the sharing wave runs).  In that schedule the
+// streams are empty in front of a sample's first round -- the round before it traced the last shadow rays of the previous sample and
+// its shade step emitted nothing -- so the round holds camera rays only, one per pixel, and everything in their records but the hit
+// follows from the pixel index, the launch constants and the sample state.  The record is therefore never written:
+//
+//   k_wf_traverse_camera   (wf_traverse.hip) one wave per 8x8 tile: pixel -> sample state (sample 0: the pixel's seed) -> bindPixel +
+//                          startSample -> the walk of k_wf_traverse -> H0 / H1 at the pixel's slot of the C stream.
+//   k_wf_shade_camera      one thread per pixel: the same state again, H0 / H1, then the code of k_wf_shade's C workgroups.
+//
+// A frame then has no k_wf_init and no k_wf_sample_init (a degenerate launch without rounds keeps k_wf_init, which stores its pixels):
+// frame = samples x [(traverse_camera, shade_camera) + depth x (traverse, shade)].  Per pixel and sample the first round moves 96 B
+// (traversal: 16 in, 32 out; shade: 16 + 32 in) instead of 256 B (init: 16 in, 80 out; traversal: 32 in, 32 out; shade: 96 in), and
+// the frame has `samples` launches fewer.  Same functions, draws and float operations: only where a value comes from changes.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdlib>
@@ -246,8 +260,12 @@ struct ShadeLds
   unsigned wsum[WF_TYPES * (WF_BLOCK / 64 + 1)];
 };
 
-template <bool PAIR, bool HYBRID>
-VKRT_DEV void shadeHitBlock(const TraceParams& P, const WfBuffers& B, const HybridGi& G, const int par, const unsigned count, const unsigned block, ShadeLds& lds)
+// CAMERA (k_wf_shade_camera, a camera round of VKRT_FLAG_CAMERA_ROUNDS): the records are the camera rays of sample `smpl`, one per pixel
+// of the launch, and only their H0 / H1 planes exist: record qi belongs to the pixel with tile-major work index qi, and its state is
+// made from the pixel's sample state as k_wf_traverse_camera made the ray (`count` is not read).
+template <bool PAIR, bool HYBRID, bool CAMERA = false>
+VKRT_DEV void shadeHitBlock(const TraceParams& P, const WfBuffers& B, const HybridGi& G, const int par, const unsigned count, const unsigned block, ShadeLds& lds,
+                            const int smpl = 0)
 {
   const int type = PAIR ? WF_P : WF_C;
   const unsigned lane = lane_id();
@@ -257,12 +275,34 @@ VKRT_DEV void shadeHitBlock(const TraceParams& P, const WfBuffers& B, const Hybr
   int to = -1;
   LaneState L;
   f3 contrib = mk3(0.0f), nextWeight = mk3(0.0f);
-  if(qi < count)
+  uint32_t x = 0, y = 0, lrow = 0;
+  if(CAMERA ? pixelOfWork(P, qi, P.tileFirst, x, y, lrow) : qi < count)
   {
-    loadCommon(P, B, par, type, qi, L);
+    if(CAMERA)
+    {
+      bindPixel(P, L, x, lrow);
+      if(smpl == 0)  // launch-uniform: raytrace.rgen:27-28
+      {
+        L.prd.seed = pixelSeed(P, x, y);
+        L.hitValues = mk3(0.0f);
+      }
+      else
+      {
+        const float4 s = wfLoad(B.sampleState + pixelSlot(P, x, lrow));  // this lane is the pixel's only one in the launch: it may write it again below
+        L.prd.seed = __float_as_uint(s.w);
+        L.hitValues = mk3(s.x, s.y, s.z);
+      }
+      L.smpl = smpl;
+      startSample(P, L);
+    }
+    else
+      loadCommon(P, B, par, type, qi, L);
     const float4 h = wfLoad(rec(B, par, type, WF_H0, qi)), t4 = wfLoad(rec(B, par, type, WF_H1, qi));
-    const float4 rd = wfLoad(rec(B, par, type, PAIR ? WF_R2 : WF_R1, qi));
-    L.prd.rayDirection = mk3(rd.x, rd.y, rd.z);  // direction of the closest-hit ray that was traced
+    if(!CAMERA)
+    {
+      const float4 rd = wfLoad(rec(B, par, type, PAIR ? WF_R2 : WF_R1, qi));
+      L.prd.rayDirection = mk3(rd.x, rd.y, rd.z);  // direction of the closest-hit ray that was traced
+    }
     L.prd.rayOrigin = mk3(0.0f);                 // rchit / rmiss do not read it
     if(PAIR)
     {
@@ -359,6 +399,13 @@ __global__ __launch_bounds__(WF_BLOCK) void k_wf_shade_hybrid(const TraceParams 
 {
   shadeRound<true>(P, B, G, round);
 }
+// shade step of a camera round (k_wf_traverse_camera traced it): one thread per pixel of the sub-frame in tile order; reads no stream counts
+__global__ __launch_bounds__(WF_BLOCK) void k_wf_shade_camera(const TraceParams P, const WfBuffers B, const int round, const int smpl)
+{
+  const HybridGi none{};
+  __shared__ ShadeLds lds;
+  shadeHitBlock<false, false, true>(P, B, none, round & 1, 0u, blockIdx.x, lds, smpl);
+}
 
 // First ray of the GI path of every shaded pixel (raytraceHybrid.rgen:172-204), or the pixel's final value when there is no path
 // to trace.  tmp: (seed after the direct part, visibility) per pixel, left by k_hybrid.
@@ -433,19 +480,24 @@ void vkrt_wf_carve(void* base, uint32_t pathCapacity, int groups, WfBuffers* B)
 }
 
 // One sub-frame = the tiles [tileFirst, tileFirst + tileCount) of the shard with their own streams and counts, on one HIP stream.
-// subframeBegin: counts cleared, one closest-ray record per pixel (raytrace.rgen:27-60).
+// a sample takes at most depth + 1 rounds: its first closest-hit ray, then one round per further segment (the shadow ray of
+// segment k travels with the closest-hit ray of segment k + 1), then the shadow ray of its last segment
+static int subframeRounds(const TraceParams& P) { return (P.pc.samples <= 0 || P.pc.depth <= 0) ? 0 : P.pc.samples * (P.pc.depth + 1); }
+// camera rounds (VKRT_FLAG_CAMERA_ROUNDS; the caller sets the bit only with VKRT_FLAG_SAMPLE_SYNC and a tree and workgroup size the
+// sharing wave of k_wf_traverse_camera runs on): no init kernels, the first round of every sample runs the two camera kernels
+static bool cameraRounds(const TraceParams& P) { return (P.flags & VKRT_FLAG_CAMERA_ROUNDS) != 0u && subframeRounds(P) > 0; }
+// subframeBegin: counts cleared, one closest-ray record per pixel (raytrace.rgen:27-60) -- or none: a frame of camera rounds starts
+// from the pixel grid.  (A degenerate launch, no samples or no depth, has no rounds: k_wf_init stores its pixels.)
 static hipError_t subframeBegin(const TraceParams& P, const WfBuffers& B, hipStream_t stream)
 {
   const unsigned work = P.tileCount * 64u;
   const hipError_t e = hipMemsetAsync(B.ctrl, 0, 64, stream);
   if(e != hipSuccess)
     return e;
-  hipLaunchKernelGGL(k_wf_init, dim3((work + WF_BLOCK - 1) / WF_BLOCK), dim3(WF_BLOCK), 0, stream, P, B);
+  if(!cameraRounds(P))
+    hipLaunchKernelGGL(k_wf_init, dim3((work + WF_BLOCK - 1) / WF_BLOCK), dim3(WF_BLOCK), 0, stream, P, B);
   return hipSuccess;
 }
-// a sample takes at most depth + 1 rounds: its first closest-hit ray, then one round per further segment (the shadow ray of
-// segment k travels with the closest-hit ray of segment k + 1), then the shadow ray of its last segment
-static int subframeRounds(const TraceParams& P) { return (P.pc.samples <= 0 || P.pc.depth <= 0) ? 0 : P.pc.samples * (P.pc.depth + 1); }
 // One traversal launch on the records of round r, its geometry for a sub-frame's tiles: workgroups of travBlock threads (64 unless 128
 // or 256 is asked for).  Every path holds one record and a record at most two rays; +4 blocks for the partial tails of the four ray
 // kinds.  One wavefront per workgroup by default: a finished wave frees its slot and LDS without waiting for three others.
@@ -454,28 +506,42 @@ static void launchTraverse(const TraceParams& P, const WfBuffers& B, int r, unsi
   const unsigned work = P.tileCount * 64u, tb = (travBlock == 256u || travBlock == 128u) ? travBlock : 64u;
   vkrt_wf_launch_traverse(P, B, r, tb, count, dim3(2 * ((work + tb - 1) / tb) + 4), (size_t)P.sc.stackCap * tb * sizeof(int), stream);
 }
-// round r: traverse the rays of the records, shade the results into the next round's records
-static void subframeRound(const TraceParams& P, const WfBuffers& B, int r, unsigned travBlock, bool count, hipStream_t stream, WfTiming* timing)
+// round r: traverse the rays of the records, shade the results into the next round's records.  cameraSample >= 0: r is the first
+// round of that sample in a frame of camera rounds -- its rays and their state come from the pixel grid, not from records.
+static void subframeRound(const TraceParams& P, const WfBuffers& B, int r, unsigned travBlock, bool count, hipStream_t stream, WfTiming* timing,
+                          int cameraSample = -1)
 {
   const unsigned work = P.tileCount * 64u;
   const bool timed = timing && timing->events && 2 * (timing->used + 1) <= timing->capacity;
   if(timed)
     (void)hipEventRecord(timing->events[2 * timing->used], stream);
-  launchTraverse(P, B, r, travBlock, count, stream);
+  if(cameraSample >= 0)
+    vkrt_wf_launch_traverse_camera(P, B, r, cameraSample, count, (size_t)P.sc.stackCap * 64u * sizeof(int), stream);
+  else
+    launchTraverse(P, B, r, travBlock, count, stream);
   if(timed)
   {
     (void)hipEventRecord(timing->events[2 * timing->used + 1], stream);
     timing->used++;
   }
-  hipLaunchKernelGGL(k_wf_shade, dim3((work + WF_BLOCK - 1) / WF_BLOCK + 3), dim3(WF_BLOCK), 0, stream, P, B, r);
+  if(cameraSample >= 0)
+    hipLaunchKernelGGL(k_wf_shade_camera, dim3((work + WF_BLOCK - 1) / WF_BLOCK), dim3(WF_BLOCK), 0, stream, P, B, r, cameraSample);
+  else
+    hipLaunchKernelGGL(k_wf_shade, dim3((work + WF_BLOCK - 1) / WF_BLOCK + 3), dim3(WF_BLOCK), 0, stream, P, B, r);
 }
 
 // The launches of a frame between its begin and its blend, in order: the rounds, and in the sample-synchronous schedule one sample
-// init in front of the first round of every sample but the first (whose camera rays subframeBegin made).
+// init in front of the first round of every sample but the first (whose camera rays subframeBegin made) -- unless the frame runs
+// camera rounds, which need no init.
 static bool sampleSync(const TraceParams& P) { return (P.flags & VKRT_FLAG_SAMPLE_SYNC) != 0u; }
-static int subframeSteps(const TraceParams& P) { return subframeRounds(P) + ((sampleSync(P) && subframeRounds(P) > 0) ? P.pc.samples - 1 : 0); }
+static int subframeSteps(const TraceParams& P)
+{
+  return subframeRounds(P) + ((sampleSync(P) && !cameraRounds(P) && subframeRounds(P) > 0) ? P.pc.samples - 1 : 0);
+}
 static void subframeStep(const TraceParams& P, const WfBuffers& B, int step, unsigned travBlock, bool count, hipStream_t stream, WfTiming* timing)
 {
+  if(cameraRounds(P))
+    return subframeRound(P, B, step, travBlock, count, stream, timing, step % (P.pc.depth + 1) == 0 ? step / (P.pc.depth + 1) : -1);
   if(!sampleSync(P))
     return subframeRound(P, B, step, travBlock, count, stream, timing);
   const int perSample = P.pc.depth + 2;  // sample init + depth + 1 rounds; step + 1: as if sample 0 had an init of its own at step -1

@@ -9,6 +9,7 @@
 #include "device_math.h"
 #include "device_scene.h"
 #include "kernels.h"
+#include "rgen.h"
 #include "traverse.h"
 #include "traverse_wide.h"
 #include "traverse_share.h"
@@ -118,6 +119,59 @@ void k_wf_traverse(const TraceParams P, const WfBuffers B, const int round)
   }
 }
 
+// ---- traversal of a camera round (VKRT_FLAG_CAMERA_ROUNDS): one wave per 8x8 tile, rays made from the pixel grid ----------------
+// The first round of sample `smpl` in the sample-synchronous schedule holds camera rays only, one per pixel (wavefront.hip): instead
+// of reading them from records that an init kernel wrote, workgroup b makes the rays of tile tileFirst + b as that kernel would have
+// (bindPixel + startSample of rgen.h on the pixel's sample state; sample 0: the pixel's seed) and leaves their hits in H0 / H1 of
+// slot w, the pixel's tile-major index in the launch, of the C stream.  No other plane of the record is written: k_wf_shade_camera
+// makes the same state again.  A lane outside the shard or the image has no ray and only helps, like the tail lanes of a stream.
+template <bool COUNT, int TM>
+__global__ __launch_bounds__(64)
+__attribute__((amdgpu_waves_per_eu(TM != 0 ? 5 : 1)))
+void k_wf_traverse_camera(const TraceParams P, const WfBuffers B, const int round, const int smpl)
+{
+  extern __shared__ int lds_stack[];
+  const int par = round & 1;
+  if(blockIdx.x == 0 && threadIdx.x == 0)
+    for(int t = 0; t < WF_TYPES; t++) *countOf(B, par ^ 1, t) = 0u;  // next round's counts; this round's shade kernel claims slots from them
+  const unsigned w = blockIdx.x * 64u + threadIdx.x;  // tile-major work index
+  uint32_t x = 0, y = 0, lrow = 0;
+  const bool valid = pixelOfWork(P, w, P.tileFirst, x, y, lrow);
+  f3 o = mk3(0.0f), d = mk3(1.0f, 0.0f, 0.0f);
+  uint32_t raySeed = 0u;
+  if(valid)
+  {
+    LaneState L;
+    bindPixel(P, L, x, lrow);
+    // (launch-uniform branch; the sample state's seed alone decides the ray: hitValues waits for the shade step)
+    L.prd.seed = smpl == 0 ? pixelSeed(P, x, y) : __float_as_uint(((const float*)(B.sampleState + pixelSlot(P, x, lrow)))[3]);
+    L.smpl = smpl;
+    startSample(P, L);
+    o = L.prd.rayOrigin; d = L.prd.rayDirection;
+    raySeed = L.prd.seed;  // any-hit stage: the payload's seed when the ray is traced, after startSample's two draws (S0.w of a record)
+  }
+  // every valid pixel is traced exactly once: one addition per wave to the ray counter, and to the pixel counter in the frame's first round
+  const unsigned nValid = (unsigned)__popcll(__ballot(valid));
+  if(threadIdx.x == 0 && nValid)
+  {
+    atomicAdd(&P.counters->v[blockIdx.x % VKRT_COUNTER_SLOTS][0], (unsigned long long)nValid);
+    if(smpl == 0) atomicAdd(&P.counters->v[blockIdx.x % VKRT_COUNTER_SLOTS][5], (unsigned long long)nValid);
+  }
+  TravCount tc;
+  __shared__ int shareLds[VKRT_SHARE_LDS_WORDS];
+  RayHit hit;
+  uint2* stk = ((uint2*)lds_stack) + threadIdx.x;
+  traverse_wide8_share<COUNT, false, TM>(P.sc, valid, o, d, 0.001f, 10000.0f, stk, shareRes(shareLds), hit, tc, raySeed);
+  if(valid)
+    storeHit(P, B, par, WF_K_CLOSEST_C, w, hit);
+  if(COUNT)
+  {
+    __shared__ unsigned long long red[VKRT_COUNTER_STRIDE];
+    const unsigned vals[10] = {0, 0, 0, 0, 0, 0, tc.nodes, tc.tris, tc.waveNodeSteps, tc.waveTriSteps};
+    blockAddCounters(&P.counters->v[blockIdx.x % VKRT_COUNTER_SLOTS][0], vals, 10, red);
+  }
+}
+
 // One traversal launch: the instantiation for (instrumented?, node layout, workgroup size, triangle mode).  The non-default triangle
 // modes (watertight test, any-hit dissolve stage) are built for the default 64-thread workgroups only (vkrt_accel_build refuses the
 // other sizes with them).
@@ -145,3 +199,14 @@ void vkrt_wf_launch_traverse(const TraceParams& P, const WfBuffers& B, int r, un
 #undef VKRT_TRAV_LAUNCH
 }
 
+// The traversal launch of a camera round: P.tileCount one-wave workgroups; the triangle modes of the 64-thread k_wf_traverse.
+void vkrt_wf_launch_traverse_camera(const TraceParams& P, const WfBuffers& B, int r, int smpl, bool count, size_t tlds, hipStream_t stream)
+{
+#define VKRT_TRAV_CAMERA(TM)                                                                                                           \
+  do {                                                                                                                                 \
+    if(count) hipLaunchKernelGGL((k_wf_traverse_camera<true, TM>), dim3(P.tileCount), dim3(64), tlds, stream, P, B, r, smpl);          \
+    else hipLaunchKernelGGL((k_wf_traverse_camera<false, TM>), dim3(P.tileCount), dim3(64), tlds, stream, P, B, r, smpl);              \
+  } while(0)
+  VKRT_FRAME_TM_SWITCH(frame_tri_mode(P.sc, false), VKRT_TM_DISSOLVE, VKRT_TRAV_CAMERA)
+#undef VKRT_TRAV_CAMERA
+}
