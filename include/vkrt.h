@@ -399,7 +399,8 @@ int vkrt_occluded(vkrt_scene* scene, const vkrt_ray* rays, uint32_t n, uint32_t 
  *   1. (I.mask & cull_mask) != 0,
  *   2. it is not culled by facing: with VKRT_RAY_CULL_BACK_FACING (VKRT_RAY_CULL_FRONT_FACING) back-facing (front-facing) triangles are
  *      not candidates, unless I has VKRT_INSTANCE_FACING_CULL_DISABLE,
- *   3. the any-hit dissolve stage does not ignore it (VKRT_OPT_ANYHIT_DISSOLVE; never with VKRT_RAY_OPAQUE).
+ *   3. the any-hit dissolve stage does not ignore it (VKRT_OPT_ANYHIT_DISSOLVE; never with VKRT_RAY_OPAQUE), nor does the alpha test
+ *      of a VKRT_ALPHA_MASK material ("alpha-tested materials" below; never with VKRT_RAY_OPAQUE).
  * Closest hit and occlusion follow the rules above over the candidates; the filter is a pure function of (ray, triangle), so a result
  * stays a property of the triangle set, independent of builder, layout, split and schedule.
  * Facing is decided in object space: a triangle is FRONT-facing when its object-space vertices p0, p1, p2 (index order) appear
@@ -426,7 +427,7 @@ int vkrt_scene_set_instance_visibility(vkrt_scene* scene, uint32_t first, uint32
 int vkrt_scene_get_instance_visibility(const vkrt_scene* scene, uint32_t first, uint32_t count, vkrt_instance_visibility* out);
 
 enum vkrt_ray_flags {                 /* the gl_RayFlags*EXT values; no other bit is accepted */
-  VKRT_RAY_OPAQUE = 0x1,              /* skip the any-hit dissolve stage, even on a scene built with VKRT_OPT_ANYHIT_DISSOLVE */
+  VKRT_RAY_OPAQUE = 0x1,              /* skip the any-hit stages: dissolve (VKRT_OPT_ANYHIT_DISSOLVE) and the alpha test of MASK materials */
   VKRT_RAY_CULL_BACK_FACING = 0x10,   /* back-facing triangles are not candidates (instances with FACING_CULL_DISABLE excepted) */
   VKRT_RAY_CULL_FRONT_FACING = 0x20   /* front-facing triangles are not candidates (the same) -- not together with CULL_BACK_FACING */
 };
@@ -573,6 +574,42 @@ typedef struct vkrt_surface {            /* 128 B, 16-byte aligned, eight float4
   float emission[3];         uint32_t reserved;   /* 0 */
 } vkrt_surface;
 int vkrt_hit_surface(vkrt_scene* scene, const vkrt_hit* hits, uint32_t n, uint32_t fields, vkrt_surface* out, void* hip_stream);
+
+/* ---- alpha-tested materials (glTF's alphaMode MASK; Vulkan's any-hit shader for cut-out geometry: foliage, fences, fabric edges):
+ *      the texture decides inside the walk whether a candidate counts.  These entry points came after ABI version 4 without changing
+ *      it or any existing struct: detect them by symbol. ------------------------------------------------------------------------
+ * A candidate hit on a triangle whose material is VKRT_ALPHA_MASK is ignored when !(alpha >= cutoff).  alpha is, bit for bit, the
+ * value vkrt_hit_surface(..., VKRT_SURFACE_GEOMETRY | VKRT_SURFACE_MATERIAL) writes into vkrt_surface.alpha for the candidate's
+ * (instance, primitive, u, v), with u, v the floats the walk would put into the vkrt_hit: in binary32 without contraction
+ * b = (1 - u - v, u, v), tu = (uv0.x * b.x + uv1.x * b.y) + uv2.x * b.z and tv likewise, the bilinear LOD-0 REPEAT tap of the base
+ * colour texture, its .a decoded as UNORM (never through the sRGB curve), times pbrBaseColorFactor[3]; a material without a base
+ * colour texture has alpha = pbrBaseColorFactor[3].  A cutoff of 0 admits every candidate; a NaN alpha admits none.
+ * The stage acts in vkrt_intersect, vkrt_occluded, their _ex forms and vkrt_intersect_multi (whose lists then hold admitted candidates
+ * only), as the third filter after the cull mask and the facing flags and beside the dissolve stage of VKRT_OPT_ANYHIT_DISSOLVE: both
+ * may be active, and a candidate is ignored if either says so.  VKRT_RAY_OPAQUE skips both, as gl_RayFlagsOpaqueEXT does.  It does not
+ * act in vkrt_closest_point, vkrt_hit_surface, vkrt_pathtrace*, vkrt_gbuffer_raycast*, vkrt_hybrid_trace* or vkrt_debug_trace_rays:
+ * their results do not depend on any alpha mode.
+ * The decision is a pure function of (ray, triangle), so a result stays a property of the triangle set: the same under every builder,
+ * layout, split budget and scheduling option, and after a refit; vkrt_intersect_multi with max_hits = 1 still writes what
+ * vkrt_intersect_ex writes.  The stage reads the live vertex array: a texture-coordinate update (vkrt_scene_update_vertices with
+ * texcoords0 only) takes effect in the next query, without a refit.
+ * Cost: while no material of the scene is MASK, and for every VKRT_RAY_OPAQUE call, a query launches the kernel it launched before.
+ * Otherwise the walk looks up the material of each candidate that passed the distance test and the other filters (two dependent
+ * loads); a MASK material adds three vertex loads, the material's texture reference and the tap. */
+enum vkrt_alpha_mode { VKRT_ALPHA_OPAQUE = 0, VKRT_ALPHA_MASK = 1 };
+typedef struct vkrt_material_alpha { /* 8 B; every material starts as {VKRT_ALPHA_OPAQUE, 0.5}: the reference's behaviour */
+  uint32_t mode;   /* vkrt_alpha_mode */
+  float    cutoff; /* finite, >= 0 (glTF's alphaCutoff, default 0.5); read for VKRT_ALPHA_MASK only */
+} vkrt_material_alpha;
+/* Set the alpha mode of materials [first, first+count).  The rules of vkrt_scene_set_instance_visibility: the array is copied before
+ * return, the work is enqueued on hip_stream with no host synchronisation and no allocation, and ray queries enqueued on that stream
+ * after it see the new values.  It does not make the tree stale and works on a stale one, and before vkrt_accel_build.  Refused with
+ * VKRT_ERR_INVALID_ARGUMENT, changing nothing, in this order: a NULL array with count > 0; an entry with a mode other than the two or a
+ * cutoff that is NaN, infinite or negative; a NULL scene; a range outside the scene's materials.  Then, without a device:
+ * VKRT_ERR_NO_DEVICE.  The values survive vkrt_accel_build, vkrt_accel_refit, vkrt_scene_update_nodes and vkrt_scene_update_vertices. */
+int vkrt_scene_set_material_alpha(vkrt_scene* scene, uint32_t first, uint32_t count, const vkrt_material_alpha* alpha, void* hip_stream);
+/* Reads the host copy (no synchronisation).  VKRT_ERR_INVALID_ARGUMENT: a NULL array with count > 0, a NULL scene, a range outside. */
+int vkrt_scene_get_material_alpha(const vkrt_scene* scene, uint32_t first, uint32_t count, vkrt_material_alpha* out);
 
 /* ---- path trace (replaces HelloVulkan::pathtrace :1423-1448 = one
  *      vkCmdTraceRaysKHR over raytrace.rgen/.rchit/.rmiss/raytraceShadow.rmiss) ---- */

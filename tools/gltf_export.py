@@ -82,7 +82,8 @@ def export_gltf(flat, path, glb=False, embed=False, write_lights=False, index_ty
             images.append({"uri": name})
         textures.append({"source": i})
     mats = []
-    for m in flat.materials:
+    alpha = getattr(flat, "material_alpha", None)
+    for mi, m in enumerate(flat.materials):
         pbr = {"baseColorFactor": [float(x) for x in m["pbrBaseColorFactor"]], "metallicFactor": float(m["metallicFactor"]),
                "roughnessFactor": float(m["roughnessFactor"])}
         if m["pbrBaseColorTexture"] >= 0:
@@ -94,6 +95,8 @@ def export_gltf(flat, path, glb=False, embed=False, write_lights=False, index_ty
             mj["normalTexture"] = {"index": int(m["normalTexture"])}
         if m["emissiveTexture"] >= 0:
             mj["emissiveTexture"] = {"index": int(m["emissiveTexture"])}
+        if alpha is not None and int(alpha["mode"][mi]) == 1:  # (OPAQUE is glTF's default and takes no cutoff)
+            mj["alphaMode"], mj["alphaCutoff"] = "MASK", float(alpha["cutoff"][mi])
         mats.append(mj)
     if write_lights:
         names = {0: "point", 1: "directional", 2: "spot"}

@@ -29,6 +29,17 @@ warm-up calls of every shape; the medians are compared.  --multi-resources (no G
 csrc/Makefile and records registers, scratch and static LDS of every k_query_multi instantiation next to the output.
 
   python tools/query_probe.py --multi-resources && python tools/query_probe.py --multi --out profiles/r06_multihit_probe.json
+
+The alpha leg (--alpha) measures the alpha-test stage of the ray queries (vkrt_scene_set_material_alpha) on the textured bench atrium
+with the drapery materials (10..13) made VKRT_ALPHA_MASK, cutoff 0.5, over a procedural alpha pattern (a blocky hash in the alpha channel
+of the base-colour textures): vkrt_intersect and vkrt_occluded on the camera, diffuse and shadow sets with the stage, against the same
+calls with every material OPAQUE and -- closest hit only, an occlusion query has no such stand-in -- against the emulation the stage
+replaces: vkrt_intersect_multi with K = 8, vkrt_hit_surface on the 8 records per ray, and a select of the first admitted one.  The
+three alternate call by call (the modes are switched between the calls, outside the timed region); medians.  --alpha-resources (no GPU)
+compiles query.hip and multihit.hip with the flags of csrc/Makefile and records registers, scratch and spills of every instantiation
+with the stage next to its counterpart without it.
+
+  python tools/query_probe.py --alpha-resources && python tools/query_probe.py --alpha --out profiles/alpha_cutout_probe.json
 """
 import argparse
 import csv
@@ -484,6 +495,174 @@ def multi_leg(a):
     r.close()
 
 
+ALPHA_RESOURCES = os.path.join(ROOT, "profiles", "alpha_cutout_kernel_resources.json")
+ALPHA_MATERIALS = (10, 11, 12, 13)  # the drapery of tools/atrium.py
+
+
+def alpha_resources():
+    """Registers, scratch and spills of every k_query / k_query_multi instantiation with the alpha-test stage (VKRT_TM_ALPHA = 16) from the
+    compiler's metadata, each next to the instantiation without the bit (cross-compiles: no GPU), and the units' compile times."""
+    import re
+
+    csrc = os.path.join(ROOT, "vk-raytracing-engine_amd", "csrc")
+    flags = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-mllvm", "-amdgpu-sched-strategy=max-memory-clause",
+             "-fno-slp-vectorize", "--cuda-device-only", "-S"]
+    names = {"vgpr_count": "vgprs", "sgpr_count": "sgprs", "private_segment_fixed_size": "scratch_bytes", "vgpr_spill_count": "vgpr_spills",
+             "sgpr_spill_count": "sgpr_spills_to_vgpr_lanes", "group_segment_fixed_size": "static_lds_bytes"}
+    out = {"hipcc": subprocess.run(["/opt/rocm/bin/hipcc", "--version"], capture_output=True, text=True).stdout.splitlines()[0], "flags": " ".join(flags[:-2]),
+           "note": "tm = the triangle mode (traverse.h): 1 watertight, 2 dissolve, 8 filter, 16 alpha test; the stage is instantiated with the filter only "
+                   "(24..27).  without_stage = the same kernel with tm - 16.  SGPR spills go to VGPR lanes (v_writelane / v_readlane): scratch stays 0.",
+           "kernels": {}, "compile_seconds": {}}
+    tmp = tempfile.mkdtemp(prefix="alpha_isa_")
+    try:
+        for unit, pat in (("query", r"_Z7k_queryILb([01])ELb([01])ELi(\d+)EE"), ("multihit", r"_Z13k_query_multiILb([01])ELi(\d+)EE")):
+            asm = os.path.join(tmp, unit + ".s")
+            t0 = time.time()
+            subprocess.run(["/opt/rocm/bin/hipcc"] + flags + ["-o", asm, unit + ".hip"], cwd=csrc, check=True, stderr=subprocess.DEVNULL)
+            out["compile_seconds"][unit + ".hip"] = round(time.time() - t0, 1)
+            found = {}
+            for block in open(asm).read().split("  - .agpr_count:")[1:]:
+                f = {k: v for k, v in re.findall(r"\.(name|" + "|".join(names) + r"):\s+(\S+)", block)}
+                m = re.match(pat, f.get("name", ""))
+                if m:
+                    g = m.groups()
+                    kind = ("occluded" if g[0] == "1" else "intersect") + ("_wide8" if g[1] == "1" else "_bvh2") if unit == "query" else \
+                        "multi" + ("_wide8" if g[0] == "1" else "_bvh2")
+                    found[(kind, int(g[-1]))] = {names[k]: int(f[k]) for k in names}
+            for (kind, tm), res in sorted(found.items()):
+                if tm & 16:
+                    out["kernels"][f"{kind}_tm{tm}"] = dict(res, without_stage=found[(kind, tm - 16)])
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    ks = out["kernels"].values()
+    out["max_vgprs"] = max(k["vgprs"] for k in ks)
+    out["max_scratch_bytes"] = max(k["scratch_bytes"] for k in ks)
+    out["max_vgpr_spills"] = max(k["vgpr_spills"] for k in ks)
+    with open(ALPHA_RESOURCES, "w") as fh:
+        json.dump(out, fh, indent=1)
+    print("wrote", ALPHA_RESOURCES, json.dumps({k: out[k] for k in ("max_vgprs", "max_scratch_bytes", "max_vgpr_spills", "compile_seconds")}))
+
+
+def _alpha_pattern(h, w, block, salt):
+    """uint8 [h, w]: a hash that is constant over block x block texels -- cut-outs with interiors and edges"""
+    y, x = np.mgrid[0:h, 0:w]
+    v = ((x // block).astype(np.uint64) * np.uint64(73856093)) ^ ((y // block).astype(np.uint64) * np.uint64(19349663)) ^ np.uint64(salt * 83492791)
+    return (((v * np.uint64(2654435761)) >> np.uint64(7)) & np.uint64(255)).astype(np.uint8)
+
+
+def alpha_leg(a):
+    import copy
+
+    import torch
+    import atrium
+    import vkrt_amd
+    from vkrt_amd.renderer import ALPHA_MASK, Renderer, pack_rays
+
+    flat, _ = atrium.build_atrium(262144, seed=1, with_textures=True)
+    flat = copy.copy(flat)
+    flat.materials = flat.materials.copy()
+    flat.textures = [dict(rgba8=np.ascontiguousarray(t["rgba8"]).copy(), is_srgb=t["is_srgb"]) for t in flat.textures]
+    for i in range(4):  # the base-colour textures
+        t = flat.textures[i]["rgba8"]
+        t[:, :, 3] = _alpha_pattern(t.shape[0], t.shape[1], 32, i + 1)
+    for m in ALPHA_MATERIALS:
+        if flat.materials["pbrBaseColorTexture"][m] < 0:
+            flat.materials["pbrBaseColorTexture"][m] = m % 4
+    W, H = 1920, 1080
+    r = Renderer(flat, device=0, build=a.build)
+    sets = ray_sets(flat, dict(atrium.DEFAULT_CAMERA), W, H, r, a.seed)
+    nmat = len(flat.materials)
+    modes = np.zeros(nmat, np.uint32)
+    modes[list(ALPHA_MATERIALS)] = ALPHA_MASK
+    cutoff = 0.5
+    modes_t = torch.from_numpy(modes.astype(np.int64)).cuda()
+    K = 8
+    result = {"source_hash": vkrt_amd.source_hash(), "scene": "atrium 262144 seed 1, textured; materials 10..13 (drapery) MASK, cutoff 0.5, alpha = 32-texel hash blocks",
+              "triangles": int(r.accel_info()["triangle_count"]), "build": a.build, "device": torch.cuda.get_device_name(0), "warmup_calls": 3,
+              "timed_calls_each": a.multi_calls, "emulation": f"intersect_multi K = {K} + surface on {K} records per ray + select",
+              "method": "device events around every call; stage, opaque and emulation alternate call by call, the modes are switched between the calls; medians",
+              "sets": {}}
+    if os.path.exists(ALPHA_RESOURCES):
+        result["kernel_resources"] = {k: v for k, v in json.load(open(ALPHA_RESOURCES)).items() if k.startswith("max_") or k == "compile_seconds"}
+    r.reset_counters()
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        return e0, e1
+
+    def stage(on):
+        r.set_material_alpha(0, modes if on else np.zeros(nmat, np.uint32), cutoff)
+
+    for name in ("camera", "diffuse", "shadow"):
+        o, d, lo, hi = sets[name]
+        n = int(o.shape[0])
+        rays = pack_rays(torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda(), tmin=torch.from_numpy(lo).cuda(), tmax=torch.from_numpy(hi).cuda())
+        hits = torch.empty((n, 8), dtype=torch.float32, device="cuda:0")
+        occ = torch.empty((n,), dtype=torch.int32, device="cuda:0")
+        mh = torch.empty((n, K, 8), dtype=torch.float32, device="cuda:0")
+        cnt = torch.empty((n,), dtype=torch.int32, device="cuda:0")
+        sb = torch.empty((n * K, 32), dtype=torch.float32, device="cuda:0")
+        col = torch.arange(K, device="cuda:0")[None, :]
+        chosen = {}
+
+        def emulate():
+            m = r.intersect_multi(rays, K, out=mh, counts=cnt)
+            s = r.surface(m.flat(), out=sb)
+            masked = modes_t[m.material.clamp(min=0).long()] == ALPHA_MASK
+            adm = (col < cnt[:, None]) & (~masked | (s.alpha.view(n, K) >= cutoff))
+            first = torch.argmax(adm.to(torch.int8), 1)
+            chosen["hit"] = torch.where(adm.any(1)[:, None], mh[torch.arange(n, device="cuda:0"), first].view(torch.int32),
+                                        torch.tensor([0, 0, 0, -1, -1, -1, -1, -1], dtype=torch.int32, device="cuda:0")[None, :])
+            chosen["judged"] = adm.any(1) | (cnt < K)
+
+        calls = {"intersect_stage": (True, lambda: r.intersect(rays, out=hits)), "intersect_opaque": (False, lambda: r.intersect(rays, out=hits)),
+                 "occluded_stage": (True, lambda: r.occluded(rays, out=occ)), "occluded_opaque": (False, lambda: r.occluded(rays, out=occ)),
+                 "emulation": (False, emulate)}
+        for _ in range(3):
+            for on, fn in calls.values():
+                stage(on)
+                fn()
+        torch.cuda.synchronize()
+        ev = {k: [] for k in calls}
+        for _ in range(a.multi_calls):
+            for k, (on, fn) in calls.items():
+                stage(on)
+                ev[k].append(timed(fn))
+        torch.cuda.synchronize()
+        ms = {k: sorted(e0.elapsed_time(e1) for e0, e1 in ev[k]) for k in ev}
+        med = {k: ms[k][len(ms[k]) // 2] for k in ms}
+        # what the stage decided, and that it is what the emulation selects (t, u, v bits and ids; misses: the ids) where the emulation can judge
+        stage(False)
+        plain = r.intersect(rays).buffer.view(torch.int32).clone()
+        stage(True)
+        got = r.intersect(rays).buffer.view(torch.int32).clone()
+        got_occ = r.occluded(rays).clone()
+        torch.cuda.synchronize()
+        judged = chosen["judged"]
+        hit = chosen["hit"][:, 3] >= 0
+        same = torch.where(hit[:, None], got == chosen["hit"], got[:, 3:] .eq(-1).all(1)[:, None].expand(-1, 8)).all(1)
+        entry = {"rays": n, "ms": {k: round(v, 4) for k, v in med.items()}, "ms_min_max": {k: [round(ms[k][0], 4), round(ms[k][-1], 4)] for k in ms},
+                 "mrays_per_s": {k: round(n / v * 1e-3, 1) for k, v in med.items()},
+                 "ratio_intersect_stage_over_opaque": round(med["intersect_stage"] / med["intersect_opaque"], 4),
+                 "ratio_occluded_stage_over_opaque": round(med["occluded_stage"] / med["occluded_opaque"], 4),
+                 "ratio_intersect_stage_over_emulation": round(med["intersect_stage"] / med["emulation"], 4),
+                 "opaque_hits_on_mask_materials": round(float((modes_t[plain[:, 7].clamp(min=0).long()].eq(ALPHA_MASK) & (plain[:, 3] >= 0)).float().mean()), 4),
+                 "rays_the_stage_changes": round(float((got != plain).any(1).float().mean()), 4),
+                 "occluded_fraction_stage": round(float(got_occ.float().mean()), 4),
+                 "emulation_cannot_judge": int((~judged).sum()), "stage_differs_from_emulation_where_judged": int((judged & ~same).sum())}
+        result["sets"][name] = entry
+        print(name, json.dumps(entry), flush=True)
+    result["traversal_faults"] = int(r.counters()["traversal_faults"])
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(result, f, indent=1)
+    print("wrote", a.out)
+    r.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r06_query_probe.json"))
@@ -499,7 +678,17 @@ def main():
     ap.add_argument("--multi", action="store_true", help="the vkrt_intersect_multi leg: multi-hit calls against peeling with vkrt_intersect")
     ap.add_argument("--multi-calls", type=int, default=15, help="multi leg: timed calls of each kind per K and ray set")
     ap.add_argument("--multi-resources", action="store_true", help="registers / scratch / LDS of k_query_multi from the compiler (no GPU)")
+    ap.add_argument("--alpha", action="store_true", help="the alpha-test leg: queries with MASK materials against opaque ones and against the emulation")
+    ap.add_argument("--alpha-resources", action="store_true", help="registers / scratch / spills of the kernels with the alpha-test stage (no GPU)")
     a = ap.parse_args()
+    if a.alpha_resources:
+        alpha_resources()
+        return
+    if a.alpha:
+        if a.out.endswith("r06_query_probe.json"):
+            a.out = os.path.join(ROOT, "profiles", "alpha_cutout_probe.json")
+        alpha_leg(a)
+        return
     if a.multi_resources:
         multi_resources()
         return

@@ -193,6 +193,11 @@ class InstanceVisibility(C.Structure):
     _fields_ = [("mask", C.c_uint8), ("flags", C.c_uint8), ("reserved", C.c_uint16)]
 
 
+# alpha-tested materials (vkrt_scene_set_material_alpha)
+class MaterialAlpha(C.Structure):
+    _fields_ = [("mode", c_u), ("cutoff", c_f)]
+
+
 class QueryOpts(C.Structure):
     _fields_ = [("struct_size", c_u), ("ray_flags", c_u), ("cull_mask", c_u), ("anyhit_seed", c_u)]
 
@@ -214,6 +219,7 @@ assert C.sizeof(Hit) == 32
 assert C.sizeof(Surface) == 128
 assert C.sizeof(InstanceVisibility) == 4
 assert C.sizeof(QueryOpts) == 16
+assert C.sizeof(MaterialAlpha) == 8
 
 # layout contract
 assert C.sizeof(GlobalUniforms) == 192
@@ -248,6 +254,7 @@ VKRT_INSTANCE_FACING_CULL_DISABLE, VKRT_INSTANCE_FLIP_FACING = 0x1, 0x2
 VKRT_RAY_OPAQUE, VKRT_RAY_CULL_BACK_FACING, VKRT_RAY_CULL_FRONT_FACING = 0x1, 0x10, 0x20
 VKRT_MEMORY_HOST, VKRT_MEMORY_DEVICE = 0, 1  # vkrt_memory
 VKRT_SURFACE_GEOMETRY, VKRT_SURFACE_MATERIAL = 0x1, 0x2  # vkrt_surface_fields
+VKRT_ALPHA_OPAQUE, VKRT_ALPHA_MASK = 0, 1  # vkrt_alpha_mode
 VKRT_MULTIHIT_MAX = 16  # the largest max_hits of vkrt_intersect_multi
 
 # every symbol include/vkrt.h declares (tests check the built library exports them all)
@@ -275,6 +282,8 @@ VKRT_SYMBOLS = [
     "vkrt_intersect_multi",
     "vkrt_closest_point",
     "vkrt_hit_surface",
+    "vkrt_scene_set_material_alpha",
+    "vkrt_scene_get_material_alpha",
     "vkrt_shard_rows",
     "vkrt_pathtrace",
     "vkrt_pathtrace_frames",
@@ -353,6 +362,10 @@ def declare_vkrt(lib):
     # (hits, out: device pointers)
     lib.vkrt_hit_surface.argtypes = [C.c_void_p, C.c_void_p, c_u, c_u, C.c_void_p, C.c_void_p]
     lib.vkrt_hit_surface.restype = C.c_int
+    lib.vkrt_scene_set_material_alpha.argtypes = [C.c_void_p, c_u, c_u, P(MaterialAlpha), C.c_void_p]
+    lib.vkrt_scene_set_material_alpha.restype = C.c_int
+    lib.vkrt_scene_get_material_alpha.argtypes = [C.c_void_p, c_u, c_u, P(MaterialAlpha)]
+    lib.vkrt_scene_get_material_alpha.restype = C.c_int
     lib.vkrt_debug_read_node_masks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     lib.vkrt_debug_read_node_masks.restype = C.c_int
     lib.vkrt_debug_check_accel.argtypes = [C.c_void_p, P(AccelCheck)]

@@ -6,6 +6,7 @@
 // all TLAS instances are flattened to ONE world-space BVH.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include "../../include/vkrt_host_device.h"
 #include "device_math.h"
@@ -48,10 +49,12 @@ struct DevTexRef
 struct DevMaterial
 {
   GltfPBRMaterial m;
-  int32_t pad[3];
+  int32_t pad;
+  uint32_t alphaMode;  // vkrt_alpha_mode (vkrt_scene_set_material_alpha); with alphaCutoff one aligned 8-byte load of the ray queries'
+  float alphaCutoff;   // alpha-test stage (traverse.h alpha_ignores), which alone reads the two
   DevTexRef tex[4];
 };
-static_assert(sizeof(DevMaterial) == 128, "DevMaterial");
+static_assert(sizeof(DevMaterial) == 128 && offsetof(DevMaterial, alphaMode) == 56, "DevMaterial");
 // The hit shader's view of a material (shade.h closestHitFront): the factors raytrace.rchit reads and the four texture references
 // in 64 bytes = four aligned 16-byte loads per hit (DevMaterial: eight).
 //   f = (baseColor.xyz, metallic, roughness, emissive.xyz)   ref[2 k], ref[2 k + 1] = reference k (VKRT_TEXREF_*):

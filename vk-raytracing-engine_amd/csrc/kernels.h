@@ -14,14 +14,15 @@ hipError_t vkrt_launch_eval_math(int op, unsigned n, const float* a, const float
 // the first launch error; the ray queries pick their triangle mode there too (query_tri_mode, VKRT_QUERY_TM_SWITCH).
 // ray queries (query.hip): n caller rays (2 float4 each: origin + tmin, direction + tmax) -> closest hits (2 float4 each, vkrt_hit) when
 // hits != NULL, otherwise occluded flags (one int each) into occ.  seed = the any-hit stage's payload seed.  filter: walk with the
-// ray-query filter (sc.cullMask / rayFlags / nodeMasks, VKRT_TM_FILTER); opaque: VKRT_RAY_OPAQUE (no any-hit dissolve stage).
-hipError_t vkrt_launch_query(const DevQueryScene& sc, const float4* rays, uint64_t n, uint32_t seed, bool filter, bool opaque, float4* hits, int* occ,
-                             hipStream_t stream);
+// ray-query filter (sc.cullMask / rayFlags / nodeMasks, VKRT_TM_FILTER); opaque: VKRT_RAY_OPAQUE (no any-hit stage); alpha: some
+// material of the scene is VKRT_ALPHA_MASK (the alpha-test stage, VKRT_TM_ALPHA, unless opaque).
+hipError_t vkrt_launch_query(const DevQueryScene& sc, const float4* rays, uint64_t n, uint32_t seed, bool filter, bool opaque, bool alpha, float4* hits,
+                             int* occ, hipStream_t stream);
 // multi-hit ray queries (multihit.hip): the first maxHits (1..VKRT_MULTIHIT_MAX) candidates of every ray in the order (t, triangle id) into
 // hits (maxHits records of 2 float4 per ray, ray-major, miss records behind the count), their number into counts (may be NULL).  seed,
-// filter, opaque: as vkrt_launch_query.  Walks lane by lane; LDS per wave: the stack columns + 5 x maxHits x 64 words.
-hipError_t vkrt_launch_query_multi(const DevQueryScene& sc, const float4* rays, uint64_t n, uint32_t seed, bool filter, bool opaque, uint32_t maxHits,
-                                   float4* hits, int* counts, hipStream_t stream);
+// filter, opaque, alpha: as vkrt_launch_query.  Walks lane by lane; LDS per wave: the stack columns + 5 x maxHits x 64 words.
+hipError_t vkrt_launch_query_multi(const DevQueryScene& sc, const float4* rays, uint64_t n, uint32_t seed, bool filter, bool opaque, bool alpha,
+                                   uint32_t maxHits, float4* hits, int* counts, hipStream_t stream);
 // closest-point queries (closest.hip): n queries (one float4 each: point + radius) -> the nearest surface point within the radius as a
 // vkrt_hit (2 float4 each; t = the distance).  filter: walk with sc.cullMask / sc.nodeMasks.  work != NULL: the instrumented kernel adds
 // (nodes visited, triangle records tested) to work[0..1].  Walks lane by lane; LDS per wave: the stack columns.
@@ -31,6 +32,9 @@ hipError_t vkrt_launch_closest_point(const DevQueryScene& sc, const float4* quer
 // child nodes' bytes; a node of height h is exact after h passes, so sweeps >= the tree's levels gives the table without reading
 // anything back.  instCount bounds the instance ids of the records.
 hipError_t vkrt_launch_node_masks(const DevScene& sc, uint32_t nodeCount, uint32_t instCount, uint32_t sweeps, uint2* masks, hipStream_t stream);
+// (mode, cutoff bits) of materials [first, first + count) into their DevMaterial records: the pairs travel as kernel arguments of launches
+// on `stream` (stream-ordered, nothing staged, no synchronisation), like the instance records of refit.hip upload_instances
+hipError_t vkrt_launch_material_alpha(DevMaterial* table, uint32_t first, uint32_t count, const uint2* src, hipStream_t stream);
 // shading inputs at hit records (surface.hip): n vkrt_hit records (2 float4 each) -> n vkrt_surface records (8 float4 each).  material:
 // the four texture taps and the material fields too, else the geometry alone.  Reads no tree.
 hipError_t vkrt_launch_hit_surface(const DevSurfaceScene& sc, const float4* hits, uint32_t n, bool material, float4* out, hipStream_t stream);

@@ -86,7 +86,7 @@ VKRT_DEV void multi_test_triangle(const DevScene& sc, const TR& tr, f3 o, f3 d, 
   if(tr.hit(o, d, a, b, c, t, u, v, ccw) && t > tmin)
   {
     const int gid = tri_gid<TM>(c.y);
-    if(L.admits(t, gid) && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, raySeed))
+    if(L.admits(t, gid) && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, raySeed, VKRT_HOOK_UV(TM, u, v)))
       L.insert(t, gid, (int)s, u, v);
   }
 }
@@ -210,12 +210,12 @@ void k_query_multi(const DevQueryScene sc, const float4* __restrict__ rays, uint
 static size_t multiLdsBytes(const DevQueryScene& sc, uint32_t maxHits) { return ((size_t)sc.stackCap + 5u * (size_t)maxHits) * 64 * sizeof(int); }
 
 // n rays from `rays`, maxHits (1..VKRT_MULTIHIT_MAX, checked by the caller) records each into hits, counts may be NULL
-hipError_t vkrt_launch_query_multi(const DevQueryScene& sc, const float4* rays, uint64_t n, uint32_t seed, bool filter, bool opaque, uint32_t maxHits,
-                                   float4* hits, int* counts, hipStream_t stream)
+hipError_t vkrt_launch_query_multi(const DevQueryScene& sc, const float4* rays, uint64_t n, uint32_t seed, bool filter, bool opaque, bool alpha,
+                                   uint32_t maxHits, float4* hits, int* counts, hipStream_t stream)
 {
   const size_t lds = multiLdsBytes(sc, maxHits);
   const bool wide = sc.layout == 1u;
-  const int tm = query_tri_mode(sc, filter, opaque);
+  const int tm = query_tri_mode(sc, filter, opaque, alpha);
   return query_launch_chunks(n, [&](uint64_t first, uint64_t end, dim3 g) {
 #define VKRT_QM(W, TM) hipLaunchKernelGGL((k_query_multi<W, TM>), g, dim3(64), lds, stream, sc, rays, first, end, seed, (int)maxHits, hits, counts)
 #define VKRT_QM_TM(TM) do { if(wide) VKRT_QM(true, TM); else VKRT_QM(false, TM); } while(0)

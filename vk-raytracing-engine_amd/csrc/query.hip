@@ -3,6 +3,7 @@
 // Built with the flags of wf_traverse.hip (csrc/Makefile) for the same reasons: the walks are the same code.
 // What it shares with multihit.hip and closest.hip -- the invalid-ray rule, the records, the mode dispatch, the launch loop: query_common.h.
 #include <hip/hip_runtime.h>
+#include <string.h>
 
 #include "device_math.h"
 #include "device_scene.h"
@@ -72,12 +73,12 @@ void k_query(const DevQueryScene sc, const float4* __restrict__ rays, uint64_t f
 }
 
 // n rays from `rays`; hits != NULL: closest hit, else occluded flags into occ.
-hipError_t vkrt_launch_query(const DevQueryScene& sc, const float4* rays, uint64_t n, uint32_t seed, bool filter, bool opaque, float4* hits, int* occ,
-                             hipStream_t stream)
+hipError_t vkrt_launch_query(const DevQueryScene& sc, const float4* rays, uint64_t n, uint32_t seed, bool filter, bool opaque, bool alpha, float4* hits,
+                             int* occ, hipStream_t stream)
 {
   const size_t lds = (size_t)sc.stackCap * 64 * sizeof(int);
   const bool wide = sc.layout == 1u, anyHit = hits == nullptr;
-  const int tm = query_tri_mode(sc, filter, opaque);
+  const int tm = query_tri_mode(sc, filter, opaque, alpha);
   return query_launch_chunks(n, [&](uint64_t first, uint64_t end, dim3 g) {
 #define VKRT_Q(A, W, TM) hipLaunchKernelGGL((k_query<A, W, TM>), g, dim3(64), lds, stream, sc, rays, first, end, seed, hits, occ)
 #define VKRT_Q_TM(TM)                                                          \
@@ -143,5 +144,35 @@ hipError_t vkrt_launch_node_masks(const DevScene& sc, uint32_t nodeCount, uint32
   for(uint32_t p = 0; p < sweeps; p++)
     hipLaunchKernelGGL(k_node_masks, dim3((nodeCount + 255u) / 256u), dim3(256), 0, stream, sc.nodes, sc.tris, sc.triCount, sc.instances, instCount,
                        nodeCount, masks);
+  return hipGetLastError();
+}
+
+// 256 (mode, cutoff) pairs per launch: 2 KiB of the 4 KiB of kernel arguments
+#define VKRT_ALPHA_PER_LAUNCH 256u
+struct MaterialAlphaBatch
+{
+  uint32_t first, count;
+  uint2 rec[VKRT_ALPHA_PER_LAUNCH];
+};
+__global__ __launch_bounds__(VKRT_ALPHA_PER_LAUNCH) void k_material_alpha(const MaterialAlphaBatch b, DevMaterial* table)
+{
+  if(threadIdx.x < b.count)
+  {
+    DevMaterial& m = table[b.first + threadIdx.x];
+    m.alphaMode = b.rec[threadIdx.x].x;
+    m.alphaCutoff = __uint_as_float(b.rec[threadIdx.x].y);
+  }
+}
+
+hipError_t vkrt_launch_material_alpha(DevMaterial* table, uint32_t first, uint32_t count, const uint2* src, hipStream_t stream)
+{
+  for(uint32_t done = 0; done < count; done += VKRT_ALPHA_PER_LAUNCH)
+  {
+    MaterialAlphaBatch b;
+    b.first = first + done;
+    b.count = count - done < VKRT_ALPHA_PER_LAUNCH ? count - done : VKRT_ALPHA_PER_LAUNCH;
+    memcpy(b.rec, src + done, (size_t)b.count * sizeof(uint2));
+    hipLaunchKernelGGL(k_material_alpha, dim3(1), dim3(VKRT_ALPHA_PER_LAUNCH), 0, stream, b, table);
+  }
   return hipGetLastError();
 }

@@ -109,13 +109,17 @@ VKRT_DEV void bvh2_lane_walk(const DevScene& sc, int* stk, int stride, unsigned&
 }
 
 // The triangle mode of a ray query.  VKRT_RAY_OPAQUE on a scene built with the dissolve stage: the records carry its flag in their id
-// words, so the walk masks it (VKRT_TM_MASKID) and ignores nothing.
-inline int query_tri_mode(const DevScene& sc, bool filter, bool opaque)
+// words, so the walk masks it (VKRT_TM_MASKID) and ignores nothing.  alpha: the scene has a VKRT_ALPHA_MASK material right now; unless
+// the call is opaque the walk then carries the alpha-test stage, always together with the filter (whose defaults reject nothing), which
+// keeps the stage to four more modes instead of eight.
+inline int query_tri_mode(const DevScene& sc, bool filter, bool opaque, bool alpha)
 {
-  return (sc.watertight ? VKRT_TM_WATERTIGHT : 0) | (sc.dissolve ? (opaque ? VKRT_TM_MASKID : VKRT_TM_DISSOLVE) : 0) | (filter ? VKRT_TM_FILTER : 0);
+  const bool stage = alpha && !opaque;
+  return (sc.watertight ? VKRT_TM_WATERTIGHT : 0) | (sc.dissolve ? (opaque ? VKRT_TM_MASKID : VKRT_TM_DISSOLVE) : 0) |
+         (filter || stage ? VKRT_TM_FILTER : 0) | (stage ? VKRT_TM_ALPHA : 0);
 }
 
-// X(TM) for the triangle mode tm, a compile-time constant there: the twelve values query_tri_mode can give
+// X(TM) for the triangle mode tm, a compile-time constant there: the sixteen values query_tri_mode can give
 #define VKRT_QUERY_TM_SWITCH(tm, X) \
   switch(tm)                        \
   {                                 \
@@ -130,7 +134,11 @@ inline int query_tri_mode(const DevScene& sc, bool filter, bool opaque)
     case 10: X(10); break;          \
     case 11: X(11); break;          \
     case 12: X(12); break;          \
-    default: X(13); break; /* case 13 */ \
+    case 13: X(13); break;          \
+    case 24: X(24); break;          \
+    case 25: X(25); break;          \
+    case 26: X(26); break;          \
+    default: X(27); break; /* case 27 */ \
   }
 
 // n items, one thread each, one wave per workgroup, in launches of at most 2^24 workgroups (2^30 items): launch(first, end, grid) starts

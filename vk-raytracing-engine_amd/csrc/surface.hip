@@ -19,7 +19,7 @@ struct SurfaceGeom
 VKRT_DEV void surfaceGeometry(const DevScene& sc, const uint32_t instId, const uint32_t i0, const uint32_t i1, const uint32_t i2, const float u, const float v,
                               SurfaceGeom& g)
 {
-  const f3 b = mk3(1.0f - u - v, u, v);  // rchit:68
+  const f3 b = mk3(1.0f - u - v, u, v);  // rchit:68 (texcoordAt forms the same b)
   const BufView vPN = bufView(sc.vertexPN), vInst = bufView(sc.instances);
   const float4 a0 = bufLoad4(vPN, VKRT_VERTEX_BYTES * i0), b0 = bufLoad4(vPN, VKRT_VERTEX_BYTES * i0 + 16u), tq0 = bufLoad4(vPN, VKRT_VERTEX_BYTES * i0 + 32u);
   const float4 a1 = bufLoad4(vPN, VKRT_VERTEX_BYTES * i1), b1 = bufLoad4(vPN, VKRT_VERTEX_BYTES * i1 + 16u), tq1 = bufLoad4(vPN, VKRT_VERTEX_BYTES * i1 + 32u);
@@ -34,8 +34,7 @@ VKRT_DEV void surfaceGeometry(const DevScene& sc, const uint32_t instId, const u
     in.w2o[0] = q3.x; in.w2o[1] = q3.y; in.w2o[2] = q3.z; in.w2o[3] = q3.w; in.w2o[4] = q4.x; in.w2o[5] = q4.y; in.w2o[6] = q4.z; in.w2o[7] = q4.w;
     in.w2o[8] = q5.x; in.primMesh = __float_as_int(q5.y); in.vis = 0u; in.pad = 0;
   }
-  g.tu = (b0.z * b.x + b1.z * b.y) + b2.z * b.z;
-  g.tv = (b0.w * b.x + b1.w * b.y) + b2.w * b.z;
+  texcoordAt(b0, b1, b2, u, v, g.tu, g.tv);
   const f3 p0 = mk3(a0.x, a0.y, a0.z), p1 = mk3(a1.x, a1.y, a1.z), p2 = mk3(a2.x, a2.y, a2.z);
   const f3 pos = p0 * b.x + p1 * b.y + p2 * b.z;
   g.worldPos = xformPoint(in, pos);
@@ -48,35 +47,6 @@ VKRT_DEV void surfaceGeometry(const DevScene& sc, const uint32_t instId, const u
   g.worldBin = tq0.w * cross3(g.worldNrm, worldTag);
   // the counter-clockwise front face of the object-space triangle, carried to world space like a vertex normal (inverse transpose)
   g.geomNrm = normalize3(xformNormal(in, cross3(p1 - p0, p2 - p0)));
-}
-
-// glTF's alpha: pbrBaseColorFactor.a (DevMaterial; the hit shader's 64-byte record drops it) times the .a of the base colour tap.  The
-// tap is the one closestHitFront takes (same footprint, same texels: merged with its loads).
-VKRT_DEV float surfaceAlpha(const DevScene& sc, const uint32_t matIndex, const float tu, const float tv, const float* lut)
-{
-  const float factor = __uint_as_float(bufLoad1(bufView(sc.materials), 128u * matIndex + 12u));
-  const float4 ref01 = bufLoad4(bufView(sc.shadeMaterials), 64u * matIndex + 32u);
-  const uint32_t dimB = __float_as_uint(ref01.x), baseB = __float_as_uint(ref01.y);
-  const bool wantB = (dimB & 0x8000u) != 0u;
-  // (issued whether or not the material has the texture, exactly as closestHitFront issues it: a tap nobody wants reads record 0)
-  TexTap tB;
-  texFootprint(sc.texQuads ? 0u : (baseB & 0x7fffffffu), (dimB & 0x7fffu) + 1u, ((dimB >> 16) & 0x7fffu) + 1u, (baseB >> 31) != 0u, (dimB >> 31) != 0u, wantB,
-               tu, tv, tB);
-  uint32_t c00, c10, c01, c11;
-  if(sc.texQuads)
-  {
-    const uint32_t rec = (wantB && (dimB >> 31) != 0u) ? tB.i00 + (baseB & 0x7fffffffu) : 0u;
-    const float4 q = bufLoad4(bufView(sc.texQuads), 16u * rec);
-    c00 = __float_as_uint(q.x); c10 = __float_as_uint(q.y); c01 = __float_as_uint(q.z); c11 = __float_as_uint(q.w);
-  }
-  else
-  {
-    const BufView tex = bufView(sc.texels);
-    c00 = bufLoad1(tex, 4u * tB.i00); c10 = bufLoad1(tex, 4u * tB.i10); c01 = bufLoad1(tex, 4u * tB.i01); c11 = bufLoad1(tex, 4u * tB.i11);
-  }
-  if(!wantB)
-    return factor;
-  return factor * texBlend(lut, tB, c00, c10, c01, c11).w;
 }
 
 // One lane per record.  hits: 2 float4 per record (vkrt_hit); out: 8 float4 per record (vkrt_surface).  A record that is not a hit of
@@ -120,7 +90,7 @@ __global__ __launch_bounds__(256) void k_hit_surface(const DevSurfaceScene sc, c
       HitMid mid;
       closestHitFront(sc, hit, (uint32_t)inst, ts, mk3(0.0f, 0.0f, 1.0f), prd, st, mid);
       shadingN = mid.N; tangent = mid.tangent; binormal = mid.binormal;
-      o2.w = surfaceAlpha(sc, ts.w, g.tu, g.tv, st.lut);
+      o2.w = materialAlpha<false>(sc, ts.w, g.tu, g.tv, st.lut);  // texel.h: the value the walks' alpha test compares
       o3.w = mid.metalU;
       o4.w = mid.roughU;
       o6.x = mid.baseColor.x; o6.y = mid.baseColor.y; o6.z = mid.baseColor.z;

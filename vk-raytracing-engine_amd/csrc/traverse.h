@@ -8,6 +8,7 @@
 #pragma once
 #include "device_math.h"
 #include "device_scene.h"
+#include "texel.h"
 
 struct RayHit
 {
@@ -152,11 +153,13 @@ VKRT_DEV bool tri_test_wt(const WtRay& R, f3 o, f3 p0, f3 p1, f3 p2, float& t, f
 // treats every triangle as opaque (the ray-cast G-buffer on a scene built for the stage): the id is masked, no hit is ignored.
 // Bit 3 = the ray-query filter of vkrt_intersect_ex / vkrt_occluded_ex (k_query only): instance masks against the call's cull mask and
 // facing culling (query_rejects), and on the wide8 layout the node-mask table in the node test; the walk's scene is a DevQueryScene.
+// Bit 4 = the alpha-test stage of the ray queries (k_query, k_query_multi; alpha_ignores below), instantiated with bit 3 only.
 // TM = 0 is the product default and compiles to exactly the code it was before.
 #define VKRT_TM_WATERTIGHT 1
 #define VKRT_TM_DISSOLVE 2
 #define VKRT_TM_MASKID 4
 #define VKRT_TM_FILTER 8
+#define VKRT_TM_ALPHA 16
 
 // The triangle mode of a frame kernel (path tracing, hybrid, the G-buffer ray cast).  opaque: the walk has no any-hit stage (k_gbuffer)
 // and only masks the stage's flag out of the id words of a scene built for it.
@@ -207,9 +210,38 @@ VKRT_DEV int tri_gid(float idWord)  // the flattened triangle id of a record (bi
 {
   return (TM & (VKRT_TM_DISSOLVE | VKRT_TM_MASKID)) ? (__float_as_int(idWord) & 0x7fffffff) : __float_as_int(idWord);
 }
-template <int TM>
-VKRT_DEV bool anyhit_ignores(const DevScene& sc, unsigned slot, float idWord, uint32_t raySeed)
+// ---- alpha-test stage (VKRT_TM_ALPHA; include/vkrt.h "alpha-tested materials") ------------------------------------------------------
+// glTF's alphaMode MASK inside the walk: a candidate on a triangle whose material is VKRT_ALPHA_MASK is ignored when
+// !(alpha >= cutoff), alpha = materialAlpha (texel.h) at the candidate's (u, v) -- the floats the walk would put into the vkrt_hit, so
+// the value is bit for bit vkrt_surface.alpha of that hit.  A pure function of (ray, triangle) like the other two filters; a lane that
+// adopted a donor's subtree evaluates the donor's candidate, and (slot, u, v) is all it needs.  Runs per ACCEPTED candidate (after the
+// t / tie test and query_rejects), a divergent slow path of dependent loads: triShade -> (mode, cutoff) -> [MASK only] three vertex
+// quads -> material references -> texels.  An opaque material leaves after the second.  The decode table is read from global memory
+// (sc.srgbLut): the query workgroups' LDS belongs to the stacks and the multi-hit lists.
+VKRT_DEV bool alpha_ignores(const DevScene& sc, unsigned slot, float u, float v)
 {
+  const uint4 ts = sc.triShade[slot];
+  const uint2 mc = *(const uint2*)((const char*)sc.materials + (size_t)ts.w * sizeof(DevMaterial) + offsetof(DevMaterial, alphaMode));
+  if(mc.x == 0u)  // VKRT_ALPHA_OPAQUE
+    return false;
+  const float4 q0 = sc.vertexPN[(size_t)ts.x * VKRT_VERTEX_QUADS + 1], q1 = sc.vertexPN[(size_t)ts.y * VKRT_VERTEX_QUADS + 1],
+               q2 = sc.vertexPN[(size_t)ts.z * VKRT_VERTEX_QUADS + 1];
+  float tu, tv;
+  texcoordAt(q0, q1, q2, u, v, tu, tv);
+  return !(materialAlpha<true>(sc, ts.w, tu, tv, sc.srgbLut) >= __uint_as_float(mc.y));
+}
+
+// (u, v) of a candidate as the hook's last two arguments.  A walk without the alpha stage passes constants: u and v then die where they
+// did before the hook took them, and the walk compiles to the instructions it had.
+#define VKRT_HOOK_UV(TM, u, v) (((TM) & VKRT_TM_ALPHA) ? (u) : 0.0f), (((TM) & VKRT_TM_ALPHA) ? (v) : 0.0f)
+template <int TM>
+VKRT_DEV bool anyhit_ignores(const DevScene& sc, unsigned slot, float idWord, uint32_t raySeed, float u, float v)
+{
+  if constexpr((TM & VKRT_TM_ALPHA) != 0)
+  {
+    if(alpha_ignores(sc, slot, u, v))
+      return true;
+  }
   if(!(TM & VKRT_TM_DISSOLVE) || __float_as_int(idWord) >= 0)
     return false;  // opaque triangle (or the stage is not compiled in)
   const float alpha = sc.materials[sc.triShade[slot].w].m.pbrBaseColorFactor[3];
@@ -371,7 +403,7 @@ VKRT_DEV void traverse(const DevScene& sc, f3 o, f3 d, float tmin, float tmax, b
           {
             if(anyHit)
             {
-              if(t < tmax && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, raySeed))
+              if(t < tmax && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, raySeed, VKRT_HOOK_UV(TM, u, v)))
               {
                 bestSlot = (int)s;
                 bestT = t;
@@ -382,7 +414,7 @@ VKRT_DEV void traverse(const DevScene& sc, f3 o, f3 d, float tmin, float tmax, b
             else
             {
               const int gid = tri_gid<TM>(c.y);
-              if((t < bestT || (t == bestT && gid < bestGid)) && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, raySeed))
+              if((t < bestT || (t == bestT && gid < bestGid)) && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, raySeed, VKRT_HOOK_UV(TM, u, v)))
               {
                 bestT = t; bestU = u; bestV = v; bestSlot = (int)s; bestGid = gid;
               }

@@ -215,7 +215,7 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
           {
             if(ANYHIT)
             {
-              if(t < tmax && !cd.found && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, raySeed))
+              if(t < tmax && !cd.found && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, raySeed, VKRT_HOOK_UV(TM, u, v)))
               {
                 cd.found = true; cd.t = t; cd.slot = (int)s;
               }
@@ -225,7 +225,7 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
               const int gid = tri_gid<TM>(c.y);
               const float rt = cd.found ? cd.t : bt;
               const int rg = cd.found ? cd.gid : bg;
-              if((t < rt || (t == rt && gid < rg)) && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, raySeed))
+              if((t < rt || (t == rt && gid < rg)) && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, raySeed, VKRT_HOOK_UV(TM, u, v)))
               {
                 cd.found = true; cd.t = t; cd.u = u; cd.v = v; cd.slot = (int)s; cd.gid = gid;
               }

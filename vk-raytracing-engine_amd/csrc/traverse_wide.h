@@ -218,7 +218,7 @@ VKRT_DEV bool w8_iterate(const DevScene& sc, W8State<TM>& S, float tmin, uint2* 
       {
         if(ANYHIT)
         {
-          if(t < S.tmax && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, S.raySeed))
+          if(t < S.tmax && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, S.raySeed, VKRT_HOOK_UV(TM, u, v)))
           {
             S.bestSlot = (int)s;
             S.bestT = t;
@@ -228,7 +228,7 @@ VKRT_DEV bool w8_iterate(const DevScene& sc, W8State<TM>& S, float tmin, uint2* 
         else
         {
           const int gid = tri_gid<TM>(c.y);
-          if((t < S.bestT || (t == S.bestT && gid < S.bestGid)) && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, S.raySeed))
+          if((t < S.bestT || (t == S.bestT && gid < S.bestGid)) && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, S.raySeed, VKRT_HOOK_UV(TM, u, v)))
           {
             S.bestT = t; S.bestU = u; S.bestV = v; S.bestSlot = (int)s; S.bestGid = gid;
           }
@@ -297,7 +297,7 @@ VKRT_DEV void traverse_wide8_postpone(const DevScene& sc, f3 o, f3 d, float tmin
     {
       if(ANYHIT)
       {
-        if(t < tmax && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, raySeed))
+        if(t < tmax && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, raySeed, VKRT_HOOK_UV(TM, u, v)))
         {
           bestSlot = (int)s; bestT = t;
           return true;
@@ -306,7 +306,7 @@ VKRT_DEV void traverse_wide8_postpone(const DevScene& sc, f3 o, f3 d, float tmin
       else
       {
         const int gid = tri_gid<TM>(c.y);
-        if((t < bestT || (t == bestT && gid < bestGid)) && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, raySeed))
+        if((t < bestT || (t == bestT && gid < bestGid)) && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, raySeed, VKRT_HOOK_UV(TM, u, v)))
         {
           bestT = t; bestU = u; bestV = v; bestSlot = (int)s; bestGid = gid;
         }

@@ -108,6 +108,10 @@ struct vkrt_scene
   std::vector<vkrt_instance_visibility> vis;
   uint64_t masksPresent[4] = {0, 0, 0, 0};
   vkrt::DevBuf nodeMasks;  // wide8: the node-mask table of the current tree (8 B per node), allocated and computed with it
+  // alpha-tested materials (vkrt_scene_set_material_alpha): host copy per material, and how many are VKRT_ALPHA_MASK right now (> 0: the
+  // ray queries walk with the alpha-test stage)
+  std::vector<vkrt_material_alpha> alpha;
+  uint32_t alphaMasks = 0;
   // vkrt_hit_surface: 16 B per primitive-mesh (device_scene.h DevSurfaceScene), uploaded at vkrt_scene_create, released with `allocs`
   const uint4* surfacePrimMeshes = nullptr;
 };
@@ -272,6 +276,7 @@ void freeAccel(vkrt_scene* s)
   s->stale = false;
 }
 
+constexpr vkrt_material_alpha kDefaultAlpha = {VKRT_ALPHA_OPAQUE, 0.5f};  // glTF's defaults; the reference treats every material as opaque
 constexpr vkrt_instance_visibility kDefaultVisibility = {0xFF, VKRT_INSTANCE_FACING_CULL_DISABLE, 0};  // the reference's TLAS (hello_vulkan.cpp:1040-1041)
 
 // gl_ObjectToWorldEXT / gl_WorldToObjectEXT of one node (rchit:72-76) and its ray-query visibility: the same code at vkrt_scene_create,
@@ -450,6 +455,7 @@ int querySetup(vkrt_scene* s, const vkrt_query_opts& q, const char* who, DevQuer
 static_assert(sizeof(vkrt_ray) == 32 && sizeof(vkrt_hit) == 32, "k_query reads and writes 2 x 16 B per ray");
 static_assert(sizeof(vkrt_surface) == 128, "k_hit_surface writes 8 x 16 B per record");
 static_assert(sizeof(vkrt_instance_visibility) == 4 && sizeof(vkrt_query_opts) == 16, "include/vkrt.h");
+static_assert(sizeof(vkrt_material_alpha) == 8 && sizeof(vkrt_material_alpha) == sizeof(uint2), "k_material_alpha takes (mode, cutoff bits) pairs");
 // The argument checks every query entry point starts with, in this order: the scene, then (n > 0) an array that is NULL, then an array
 // that is misaligned.  alignText: the call's list of alignments as its message shows it.
 struct QueryArray
@@ -485,7 +491,7 @@ int rayQuery(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, const vkrt_query_o
   if((rc = querySetup(s, q, who, qs, filter)) != VKRT_OK)
     return rc;
   const bool opaque = (q.ray_flags & VKRT_RAY_OPAQUE) != 0u;
-  HIP_TRY(vkrt_launch_query(qs, (const float4*)rays, n, q.anyhit_seed, filter, opaque, anyHit ? nullptr : (float4*)out, anyHit ? (int*)out : nullptr,
+  HIP_TRY(vkrt_launch_query(qs, (const float4*)rays, n, q.anyhit_seed, filter, opaque, s->alphaMasks != 0u, anyHit ? nullptr : (float4*)out, anyHit ? (int*)out : nullptr,
                             (hipStream_t)hip_stream));
   return VKRT_OK;
 }
@@ -520,7 +526,7 @@ int rayQueryMulti(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, const vkrt_qu
   if((rc = querySetup(s, q, who, qs, filter)) != VKRT_OK)
     return rc;
   const bool opaque = (q.ray_flags & VKRT_RAY_OPAQUE) != 0u;
-  HIP_TRY(vkrt_launch_query_multi(qs, (const float4*)rays, n, q.anyhit_seed, filter, opaque, maxHits, (float4*)hits, counts, (hipStream_t)hip_stream));
+  HIP_TRY(vkrt_launch_query_multi(qs, (const float4*)rays, n, q.anyhit_seed, filter, opaque, s->alphaMasks != 0u, maxHits, (float4*)hits, counts, (hipStream_t)hip_stream));
   return VKRT_OK;
 }
 
@@ -563,6 +569,17 @@ int checkVisibilityRange(const vkrt_scene* s, uint32_t first, uint32_t count, co
   if((uint64_t)first + count > s->nodes.size())
     return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: nodes [%u, %llu) outside the scene's %zu nodes", who, first, (unsigned long long)first + count,
                 s->nodes.size());
+  return VKRT_OK;
+}
+
+// the same for a material range of vkrt_scene_set/get_material_alpha
+int checkMaterialRange(const vkrt_scene* s, uint32_t first, uint32_t count, const char* who)
+{
+  if(!s)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
+  if((uint64_t)first + count > s->materialCount)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: materials [%u, %llu) outside the scene's %u materials", who, first, (unsigned long long)first + count,
+                s->materialCount);
   return VKRT_OK;
 }
 
@@ -613,6 +630,7 @@ int vkrt_scene_create(const vkrt_scene_desc* d, int device, vkrt_scene** out)
   s->nodes.assign(d->nodes, d->nodes + d->node_count);
   s->lightCount = d->light_count;
   s->materialCount = d->material_count;
+  s->alpha.assign(d->material_count, kDefaultAlpha);
 
   DevScene& D = s->dev;
   if((rc = upload(s, d->positions, 3 * (size_t)d->vertex_count, &D.positions)) != VKRT_OK) return bail(rc);
@@ -725,6 +743,8 @@ int vkrt_scene_create(const vkrt_scene_desc* d, int device, vkrt_scene** out)
   {
     memset(&mats[i], 0, sizeof(DevMaterial));
     mats[i].m = d->materials[i];
+    mats[i].alphaMode = kDefaultAlpha.mode;
+    mats[i].alphaCutoff = kDefaultAlpha.cutoff;
     DevShadeMaterial& sm = shadeMats[i];
     memset(&sm, 0, sizeof(sm));
     for(int k = 0; k < 3; k++)
@@ -1467,6 +1487,45 @@ int vkrt_scene_get_instance_visibility(const vkrt_scene* s, uint32_t first, uint
   if(rc != VKRT_OK)
     return rc;
   std::copy(s->vis.begin() + first, s->vis.begin() + first + count, out);
+  return VKRT_OK;
+}
+
+int vkrt_scene_set_material_alpha(vkrt_scene* s, uint32_t first, uint32_t count, const vkrt_material_alpha* alpha, void* hip_stream)
+{
+  const char* who = "vkrt_scene_set_material_alpha";
+  if(count && !alpha)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: alpha is NULL", who);
+  for(uint32_t i = 0; i < count; i++)
+  {
+    if(alpha[i].mode != VKRT_ALPHA_OPAQUE && alpha[i].mode != VKRT_ALPHA_MASK)
+      return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: entry %u: mode %u is neither VKRT_ALPHA_OPAQUE nor VKRT_ALPHA_MASK", who, i, alpha[i].mode);
+    if(!std::isfinite(alpha[i].cutoff) || alpha[i].cutoff < 0.0f)
+      return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: entry %u: cutoff %g is not a finite number >= 0", who, i, (double)alpha[i].cutoff);
+  }
+  int rc = checkMaterialRange(s, first, count, who);
+  if(rc != VKRT_OK || count == 0)
+    return rc;
+  if((rc = setDevice(s)) != VKRT_OK)
+    return rc;
+  // the pairs travel as kernel arguments on hip_stream like the records of vkrt_scene_set_instance_visibility: stream-ordered, nothing
+  // staged, no synchronisation.  (vkrt_material_alpha is the (mode, cutoff bits) pair the kernel writes.)
+  HIP_TRY(vkrt_launch_material_alpha(const_cast<DevMaterial*>(s->dev.materials), first, count, (const uint2*)alpha, (hipStream_t)hip_stream));
+  std::copy(alpha, alpha + count, s->alpha.begin() + first);
+  s->alphaMasks = 0u;
+  for(const vkrt_material_alpha& a : s->alpha)
+    s->alphaMasks += a.mode == VKRT_ALPHA_MASK ? 1u : 0u;
+  return VKRT_OK;
+}
+
+int vkrt_scene_get_material_alpha(const vkrt_scene* s, uint32_t first, uint32_t count, vkrt_material_alpha* out)
+{
+  const char* who = "vkrt_scene_get_material_alpha";
+  if(count && !out)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: out is NULL", who);
+  const int rc = checkMaterialRange(s, first, count, who);
+  if(rc != VKRT_OK)
+    return rc;
+  std::copy(s->alpha.begin() + first, s->alpha.begin() + first + count, out);
   return VKRT_OK;
 }
 

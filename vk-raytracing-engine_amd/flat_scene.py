@@ -7,7 +7,7 @@ m_materials, m_lights) plus decoded RGBA8 textures.
 """
 import ctypes as C
 from dataclasses import dataclass, field
-from typing import List
+from typing import List, Optional
 
 import numpy as np
 
@@ -30,6 +30,8 @@ PRIM_DTYPE = np.dtype(
     [("firstIndex", "<u4"), ("indexCount", "<u4"), ("vertexOffset", "<u4"), ("vertexCount", "<u4"), ("materialIndex", "<i4")]
 )
 NODE_DTYPE = np.dtype([("worldMatrix", "<f4", 16), ("primMesh", "<i4")])
+ALPHA_DTYPE = np.dtype([("mode", "<u4"), ("cutoff", "<f4")])  # vkrt_material_alpha: glTF's alphaMode (0 OPAQUE, 1 MASK) and alphaCutoff
+assert ALPHA_DTYPE.itemsize == 8
 assert MAT_DTYPE.itemsize == 52 and LIGHT_DTYPE.itemsize == 32 and PRIM_DTYPE.itemsize == 20 and NODE_DTYPE.itemsize == 68
 
 
@@ -58,6 +60,7 @@ class FlatScene:
     lights: np.ndarray  # LIGHT_DTYPE
     nodes: np.ndarray  # NODE_DTYPE
     textures: List[dict] = field(default_factory=list)  # {"rgba8": (H,W,4) u8, "is_srgb": bool}
+    material_alpha: Optional[np.ndarray] = None  # ALPHA_DTYPE per material, or None: every material opaque (Renderer applies it when present)
 
     def __post_init__(self):
         self.positions = np.ascontiguousarray(self.positions, np.float32).reshape(-1, 3)
@@ -69,6 +72,10 @@ class FlatScene:
         self.materials = np.ascontiguousarray(self.materials, MAT_DTYPE)
         self.lights = np.ascontiguousarray(self.lights, LIGHT_DTYPE)
         self.nodes = np.ascontiguousarray(self.nodes, NODE_DTYPE)
+        if self.material_alpha is not None:
+            self.material_alpha = np.ascontiguousarray(self.material_alpha, ALPHA_DTYPE).reshape(-1)
+            if self.material_alpha.shape[0] != self.materials.shape[0]:
+                raise ValueError(f"material_alpha has {self.material_alpha.shape[0]} entries for {self.materials.shape[0]} materials")
 
     # -- stats ---------------------------------------------------------------------------
     @property
@@ -85,6 +92,8 @@ class FlatScene:
         for i, t in enumerate(self.textures):
             d[f"tex{i}_rgba8"] = np.ascontiguousarray(t["rgba8"], np.uint8)
             d[f"tex{i}_srgb"] = np.int32(1 if t["is_srgb"] else 0)
+        if self.material_alpha is not None:
+            d["material_alpha"] = self.material_alpha
         np.savez_compressed(path, **d)
 
     @staticmethod
@@ -94,7 +103,8 @@ class FlatScene:
         for i in range(int(z["texture_count"])):
             tex.append({"rgba8": z[f"tex{i}_rgba8"], "is_srgb": bool(z[f"tex{i}_srgb"])})
         return FlatScene(z["positions"], z["normals"], z["tangents"], z["texcoords0"], z["indices"],
-                         z["prim_meshes"], z["materials"], z["lights"], z["nodes"], tex)
+                         z["prim_meshes"], z["materials"], z["lights"], z["nodes"], tex,
+                         z["material_alpha"] if "material_alpha" in z.files else None)
 
     # -- C ABI marshalling -----------------------------------------------------------------
     def to_desc(self):

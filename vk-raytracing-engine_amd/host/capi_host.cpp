@@ -45,6 +45,12 @@ void vkrt_host_scene_copy(const void* s_, float* pos, float* nrm, float* tan, fl
   memcpy(mats, s->m_materials.data(), s->m_materials.size() * sizeof(GltfPBRMaterial));
   memcpy(lights, s->m_lights.data(), s->m_lights.size() * sizeof(GltfLight));
 }
+// one vkrt_material_alpha per material (counts[4] of them)
+void vkrt_host_scene_material_alpha(const void* s_, vkrt_material_alpha* out)
+{
+  const GltfScene* s = (const GltfScene*)s_;
+  memcpy(out, s->m_materialAlpha.data(), s->m_materialAlpha.size() * sizeof(vkrt_material_alpha));
+}
 void vkrt_host_texture_info(const void* s_, uint32_t i, uint32_t* whs)
 {
   const GltfScene* s = (const GltfScene*)s_;

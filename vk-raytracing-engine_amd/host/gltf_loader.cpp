@@ -507,9 +507,19 @@ GltfScene loadGltf(const std::string& filename)
       for(int k = 0; k < 3; k++) m.emissiveFactor[k] = (float)mj["emissiveFactor"][(size_t)k].number(0.0);
     m.emissiveTexture = textureIndex(mj, "emissiveTexture");
     sc.m_materials.push_back(m);
+    // alphaMode: MASK is the alpha test of the ray queries; BLEND has no counterpart here and is treated as OPAQUE, like the reference
+    // treats every material.  alphaCutoff (default 0.5) is kept as written where it is a finite number >= 0.
+    vkrt_material_alpha a = {VKRT_ALPHA_OPAQUE, 0.5f};
+    if(mj["alphaMode"].string("OPAQUE") == "MASK")
+      a.mode = VKRT_ALPHA_MASK;
+    const float cutoff = (float)mj["alphaCutoff"].number(0.5);
+    if(std::isfinite(cutoff) && cutoff >= 0.f)
+      a.cutoff = cutoff;
+    sc.m_materialAlpha.push_back(a);
   }
   if(sc.m_materials.empty())
     sc.m_materials.push_back(defaultMat());
+  sc.m_materialAlpha.resize(sc.m_materials.size(), vkrt_material_alpha{VKRT_ALPHA_OPAQUE, 0.5f});
 
   // ---- primitive meshes (processMesh, in mesh order; shared attribute sets are cached) -------------------
   std::vector<std::vector<uint32_t>> meshToPrims(g["meshes"].size());

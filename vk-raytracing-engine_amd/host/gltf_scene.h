@@ -29,10 +29,18 @@ struct GltfScene
   std::vector<vkrt_prim_mesh> m_primMeshes;
   std::vector<vkrt_node> m_nodes;
   std::vector<GltfPBRMaterial> m_materials;  // already in shader layout (loadGltfMaterials :207-224)
+  std::vector<vkrt_material_alpha> m_materialAlpha;  // per material: glTF's alphaMode / alphaCutoff (MASK -> VKRT_ALPHA_MASK; OPAQUE and BLEND ->
+                                                     // VKRT_ALPHA_OPAQUE), for vkrt_scene_set_material_alpha; the shader layout has no room for them
   std::vector<GltfLight> m_lights;           // incl. the 8 fallback lights (loadGltfLights :226-325)
   std::vector<TextureImage> m_textures;      // one per glTF texture (:505-509)
   std::string warnings;
 
+  bool hasAlphaMask() const
+  {
+    for(const auto& a : m_materialAlpha)
+      if(a.mode == VKRT_ALPHA_MASK) return true;
+    return false;
+  }
   uint32_t vertexCount() const { return (uint32_t)(m_positions.size() / 3); }
   uint32_t instancedTriangleCount() const
   {

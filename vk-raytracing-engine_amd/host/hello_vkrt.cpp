@@ -42,6 +42,10 @@ void HelloVkrt::loadScene(const GltfScene& scene)
   std::vector<vkrt_texture> tex;
   const vkrt_scene_desc d = m_gltfScene.desc(tex);
   check(vkrt_scene_create(&d, m_device, &m_scene), "vkrt_scene_create");
+  // glTF's alpha modes: the ray queries of this scene test MASK materials against their cutoff (the frame kernels do not read them)
+  if(m_gltfScene.hasAlphaMask())
+    check(vkrt_scene_set_material_alpha(m_scene, 0, (uint32_t)m_gltfScene.m_materialAlpha.size(), m_gltfScene.m_materialAlpha.data(), nullptr),
+          "vkrt_scene_set_material_alpha");
   m_pcRay.lightsCount = (int32_t)m_gltfScene.m_lights.size();  // hello_vulkan.cpp:323-324
 }
 

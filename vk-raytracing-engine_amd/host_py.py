@@ -5,7 +5,7 @@ import os
 import numpy as np
 
 from . import HOST_LIB_PATH, abi
-from .flat_scene import FlatScene, LIGHT_DTYPE, MAT_DTYPE, NODE_DTYPE, PRIM_DTYPE
+from .flat_scene import ALPHA_DTYPE, FlatScene, LIGHT_DTYPE, MAT_DTYPE, NODE_DTYPE, PRIM_DTYPE
 
 _lib = None
 
@@ -24,6 +24,7 @@ def lib():
         L.vkrt_host_free_scene.argtypes = [C.c_void_p]
         L.vkrt_host_scene_counts.argtypes = [C.c_void_p, C.c_void_p]
         L.vkrt_host_scene_copy.argtypes = [C.c_void_p] + [C.c_void_p] * 9
+        L.vkrt_host_scene_material_alpha.argtypes = [C.c_void_p, C.c_void_p]
         L.vkrt_host_texture_info.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.vkrt_host_texture_copy.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.vkrt_host_global_uniforms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.POINTER(abi.GlobalUniforms)]
@@ -103,7 +104,10 @@ def load_gltf(path):
             px = np.zeros((int(whs[1]), int(whs[0]), 4), np.uint8)
             L.vkrt_host_texture_copy(h, i, px.ctypes.data)
             tex.append({"rgba8": px, "is_srgb": bool(whs[2])})
-        return FlatScene(pos, nrm, tan, uv, idx, pm, mats, lights, nd, tex)
+        # glTF's alphaMode / alphaCutoff per material; carried only when the file has a MASK material (else every material is opaque)
+        alpha = np.zeros(M, ALPHA_DTYPE)
+        L.vkrt_host_scene_material_alpha(h, alpha.ctypes.data)
+        return FlatScene(pos, nrm, tan, uv, idx, pm, mats, lights, nd, tex, alpha if np.any(alpha["mode"] != 0) else None)
     finally:
         L.vkrt_host_free_scene(h)
 

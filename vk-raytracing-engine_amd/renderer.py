@@ -29,6 +29,9 @@ def load_library():
     return _lib
 
 
+ALPHA_OPAQUE, ALPHA_MASK = abi.VKRT_ALPHA_OPAQUE, abi.VKRT_ALPHA_MASK  # vkrt_alpha_mode, for Renderer.set_material_alpha
+
+
 class VkrtError(RuntimeError):
     pass
 
@@ -135,8 +138,11 @@ class Renderer:
         self.lights_count = int(flat.lights.shape[0])
         self._prim_mesh = np.array(flat.nodes["primMesh"], np.int32)  # update_nodes keeps every node's primMesh
         self._vertex_count = int(flat.positions.shape[0])
+        self._material_count = int(flat.materials.shape[0])
         for k, v in (options or {}).items():
             self.set_option(k, v)
+        if getattr(flat, "material_alpha", None) is not None:
+            self.set_material_alpha(0, flat.material_alpha["mode"], flat.material_alpha["cutoff"])
         if build:
             self.build(build)
 
@@ -257,6 +263,42 @@ class Renderer:
         arr = (abi.InstanceVisibility * max(n, 1))()
         _check(self.lib.vkrt_scene_get_instance_visibility(self._h, 0, n, arr), "vkrt_scene_get_instance_visibility")
         return (np.array([arr[i].mask for i in range(n)], np.uint8), np.array([arr[i].flags for i in range(n)], np.uint8))
+
+    def set_material_alpha(self, first, modes, cutoffs=0.5, stream=None):
+        """vkrt_scene_set_material_alpha for materials [first, first + n): modes = n ints, ALPHA_OPAQUE or ALPHA_MASK (glTF's alphaMode);
+        cutoffs = one finite number >= 0 for all of them or n of them (glTF's alphaCutoff).  A candidate hit of intersect, occluded
+        and intersect_multi on a MASK material is ignored when its alpha (Surfaces.alpha at that hit) is not >= the cutoff.  Enqueued
+        on `stream` (a torch stream; None = the default stream); queries enqueued after it on that stream see the new values.  Bad
+        values and ranges are refused here, before the call."""
+        m = np.asarray(modes).reshape(-1)
+        if isinstance(first, bool) or not isinstance(first, (int, np.integer)):
+            raise VkrtError(f"set_material_alpha: first must be an integer, got {type(first).__name__}")
+        first, n = int(first), m.shape[0]
+        if first < 0 or first + n > self._material_count:
+            raise VkrtError(f"set_material_alpha: materials [{first}, {first + n}) outside the scene's {self._material_count} materials")
+        if m.dtype.kind not in "iu" or np.any((m != ALPHA_OPAQUE) & (m != ALPHA_MASK)):
+            raise VkrtError("set_material_alpha: modes must be integers, ALPHA_OPAQUE (0) or ALPHA_MASK (1)")
+        c = np.asarray(cutoffs)
+        if c.dtype.kind not in "fiu":
+            raise VkrtError(f"set_material_alpha: cutoffs must be numbers, got {c.dtype}")
+        c = c.astype(np.float32).reshape(-1)
+        if c.shape[0] == 1:
+            c = np.repeat(c, n)
+        if c.shape[0] != n or not np.all(np.isfinite(c)) or np.any(c < 0):
+            raise VkrtError(f"set_material_alpha: cutoffs must be one or {n} finite numbers >= 0")
+        arr = (abi.MaterialAlpha * max(n, 1))()
+        for i in range(n):
+            arr[i].mode, arr[i].cutoff = int(m[i]), float(c[i])
+        st = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        _check(self.lib.vkrt_scene_set_material_alpha(self._h, first, n, arr, st), "vkrt_scene_set_material_alpha")
+
+    def material_alpha(self):
+        """(modes, cutoffs): uint32 and float32 [materials], the host copy of every material's alpha mode
+        (vkrt_scene_get_material_alpha)."""
+        n = self._material_count
+        arr = (abi.MaterialAlpha * max(n, 1))()
+        _check(self.lib.vkrt_scene_get_material_alpha(self._h, 0, n, arr), "vkrt_scene_get_material_alpha")
+        return (np.array([arr[i].mode for i in range(n)], np.uint32), np.array([arr[i].cutoff for i in range(n)], np.float32))
 
     def read_node_masks(self):
         """The wide8 tree's node-mask table (vkrt_debug_read_node_masks): uint8 [nodes, 8], byte s = the OR of the instance masks
