@@ -277,6 +277,13 @@ enum vkrt_option {
                                    record per camera ray.  Takes effect in path-tracing mode with option 15 = 1, the wide8 layout, 64-thread traversal
                                    workgroups and work sharing on; anywhere else it resolves to 0 silently.  Same paths, draws and float operations: no
                                    pixel and no counter changes.  env VKRT_WF_CAMERA_ROUNDS */
+  VKRT_OPT_WF_TRI_LEND = 17, /* (appended within ABI 4 like options 15 and 16)  1 (default) = in a triangle step of the sharing traversal wave (wide8
+                                   layout, work sharing on) a lane with two or more pending triangles lends its last one to a walking lane that
+                                   holds none; the borrower tests it in the same step with the lender's ray and publishes to that ray's result.
+                                   Lanes of the wave that have no work walk along to borrow.  0 = every lane tests its own triangles, one per step.  Closest hit is the minimum over (t, triangle id)
+                                   and any-hit is "exists", whoever runs a test: no pixel, hit record or ray counter changes; tris_tested per
+                                   wave_tri_steps rises, nodes_visited may move with the bound.  Read at vkrt_accel_build, and taken over at once when set on a
+                                   built scene; not built for option 10 and option 12 together, where it resolves to 0 silently.  env VKRT_WF_TRI_LEND */
   VKRT_INFO_ANYHIT_ORDER   = 100, /* read-only (vkrt_scene_get_option; set is refused): the child-order bits (2 | 4) that the last vkrt_accel_build
                                    resolved VKRT_OPT_WF_SHARE_FLAGS to, i.e. what bit 3 ("automatic") decided for this scene; 0 before a build */
   VKRT_INFO_SPLIT_BUDGET   = 101  /* read-only (ABI 4): the pre-splitting budget the last vkrt_accel_build used -- what VKRT_OPT_SPLIT_BUDGET = -1

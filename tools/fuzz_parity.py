@@ -190,6 +190,8 @@ def run_case(seed, verbose=False, hook=None, force_opts=None):
     if rng7.random() < 0.3: opts[abi.VKRT_OPT_WF_SAMPLE_SYNC] = 0
     rng8 = np.random.default_rng([seed, 8])  # camera rays from the pixel grid (the default) or from records
     if rng8.random() < 0.3: opts[abi.VKRT_OPT_WF_CAMERA_ROUNDS] = 0
+    rng9 = np.random.default_rng([seed, 9])  # triangle steps that lend pending triangles to free lanes (the default) or not
+    if rng9.random() < 0.4: opts[abi.VKRT_OPT_WF_TRI_LEND] = 0
     frames_call = rng4.random() < 0.3  # the frames of the sequence in ONE vkrt_pathtrace_frames call, with whatever lanes the draw gives
     if frames_call:
         opts[abi.VKRT_OPT_WF_FRAMES_IN_FLIGHT] = int(rng4.integers(1, 5))

@@ -247,6 +247,7 @@ VKRT_OPT_WATERTIGHT, VKRT_OPT_SKIP_DEAD_SHADOW_RAYS, VKRT_OPT_ANYHIT_DISSOLVE = 
 VKRT_OPT_WF_FRAMES_IN_FLIGHT, VKRT_OPT_SPLIT_BUDGET = 13, 14
 VKRT_OPT_WF_SAMPLE_SYNC = 15
 VKRT_OPT_WF_CAMERA_ROUNDS = 16
+VKRT_OPT_WF_TRI_LEND = 17
 VKRT_INFO_ANYHIT_ORDER = 100  # read-only: what the build resolved the any-hit child order to
 VKRT_INFO_SPLIT_BUDGET = 101  # read-only: the pre-splitting budget the build used (what -1 resolved to)
 # vkrt_instance_flags / vkrt_ray_flags (the gl_RayFlags*EXT values)

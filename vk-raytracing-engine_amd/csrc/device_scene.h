@@ -84,6 +84,7 @@ struct DevTexture
 #define VKRT_NODE_QUADS 4
 #define VKRT_LEAF_MAX 8
 #define VKRT_TRAV_DONE ((int)0x80000000)
+#define VKRT_SHARE_TRI_LEND 0x20u  // DevScene::shareFlags, set by vkrt_accel_build (the public option 8 holds bits 0-4)
 
 // Triangle record, 48 bytes = 3 x float4, in leaf order:
 //   a = (v0.x, v0.y, v0.z, e1.x)  b = (e1.y, e1.z, e2.x, e2.y)  c = (e2.z, gid, inst, prim) (ints as bits)
@@ -120,6 +121,7 @@ struct DevScene
   uint32_t gbufferMips;       // hybrid G-buffer: 1 = implicit-LOD texture() as in a fragment shader (trilinear + 4x anisotropy), 0 = LOD 0
   uint32_t shareFlags;        // bit 0: lanes whose stack is empty also donate the farthest pending child of their current group; bits 1, 2: order of
                               // any-hit walks (traverse.h); bit 4: lanes with nothing else to give donate half of their pending triangles
+                              // VKRT_SHARE_TRI_LEND (internal, VKRT_OPT_WF_TRI_LEND): triangle steps lend pending triangles to free lanes
   uint32_t watertight;        // 1: triangle records hold (p0, p1, p2) and the kernels run the watertight test (VKRT_OPT_WATERTIGHT)
   float sceneLo[3], sceneHi[3];  // world-space bounds of the instanced geometry (conservative; read by the any-hit order heuristic only)
   uint32_t dissolve;          // 1: any-hit alpha / dissolve stage (VKRT_OPT_ANYHIT_DISSOLVE): bit 31 of a record's id word flags a non-opaque triangle

@@ -34,6 +34,11 @@ VKRT_DEV void shareSync()
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+// number of set bits of a wave mask below this lane (v_mbcnt: two instructions, no per-lane mask register)
+VKRT_DEV unsigned laneRank(unsigned long long mask)
+{
+  return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+}
 VKRT_DEV ShareRes shareRes(int* lds320)
 {
   ShareRes r;
@@ -55,7 +60,6 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
   const int cap = (int)(sc.stackCap >> 1);
   const int lane = (int)lane_id();
   const unsigned shareMin = sc.shareMinIdle;
-  const unsigned long long below = (1ull << lane) - 1ull;
   bool farFirst = ANYHIT && anyhit_far_first(sc, o, d, tmax);  // child order of this lane's ray (traverse.h)
 
   res.key[lane] = ((unsigned long long)__float_as_uint(tmax) << 32) | 0xffffffffull;
@@ -71,6 +75,9 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
   int sp = 0, sb = 0, nPost = 0;  // node groups live in [sb, sp), parked triangle groups in [cap - nPost, cap)
   unsigned steps = sc.stepLimit;
   bool busy = G.y != 0u;
+  // triangle lending (the triangle step below); launch-uniform.  Not built where the watertight test and the dissolve stage meet: a borrower
+  // holds a second ray, seed and bound beside its own, and with both stages that is more than the 96 registers of five waves per SIMD
+  const bool lendOn = (TM & (VKRT_TM_WATERTIGHT | VKRT_TM_DISSOLVE)) != (VKRT_TM_WATERTIGHT | VKRT_TM_DISSOLVE) && (sc.shareFlags & VKRT_SHARE_TRI_LEND) != 0u;
 
   for(unsigned iter = 0;; iter++)
   {
@@ -98,7 +105,7 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
       if(donorMask != 0ull)
       {
         const unsigned n = min((unsigned)__popcll(donorMask), (unsigned)__popcll(idleMask));
-        const unsigned giveRank = (unsigned)__popcll(donorMask & below), takeRank = (unsigned)__popcll(idleMask & below);
+        const unsigned giveRank = laneRank(donorMask), takeRank = laneRank(idleMask);
         const bool gives = wants && giveRank < n;
         const bool takes = !busy && takeRank < n;
         uint2 e = make_uint2(0u, 0u);
@@ -172,14 +179,14 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
     }
     // ---- one step of every busy lane's walk (same step as w8run) -----------------------------------------------------
     shareSync();  // results published in the previous step are visible to every lane of the ray
-    if(busy)
+    if(busy || lendOn)  // (with triangle lending the lanes without work walk along, empty-handed, to borrow)
     {
       float bt = tmax;
       int bg = -1;
       bool finished = false;
       bool occluded = false;  // any-hit walks: this lane found an occluder in this step
       if(ANYHIT)
-        finished = __hip_atomic_load(&res.slot[owner], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) >= 0;  // somebody already found an occluder for this ray
+        finished = busy && __hip_atomic_load(&res.slot[owner], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) >= 0;  // somebody already found an occluder for this ray
       else
       {
         const unsigned long long k = __hip_atomic_load(&res.key[owner], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -329,7 +336,104 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
         if(sc.triThreshold > 1u)
           triStep = (unsigned)__popcll(__ballot(T.y != 0u)) * 64u >= sc.triThreshold * (unsigned)__popcll(busyMask) ||
                     __ballot((G.y & 0xff000000u) != 0u) == 0ull;
-        if(T.y != 0u && triStep && !occluded)
+        // triangle lending (VKRT_OPT_WF_TRI_LEND): in a triangle step a walking lane that holds no pending triangle sits the test out while
+        // its neighbour, which came out of one node test with several, tests them one per step.  Here a lane with two or more pending
+        // triangles lends its LAST one (the highest position, so its own order of testing is untouched) to such a free lane: the r-th
+        // lender feeds the r-th free lane, matched by rank among the ballots like donors and idle lanes above (res.donor[] is free between
+        // sharing steps).  The borrower tests that triangle in this step with the lender's ray (origin, direction, home lane, the lender's
+        // view of the ray's bound and tie id and, in the dissolve modes, the seed come by shuffle) and publishes to the ray's home lane as
+        // any lane working on the ray does; nothing of its own walk changes.  Lanes without work walk along empty-handed so that they can
+        // borrow too: two of three free lanes of a triangle step are such lanes.  The result is the minimum over (t, id) / "exists" whoever
+        // tests.  Bench frame: 42.7 M -> 30.3 M triangle wave-steps, lane efficiency 0.40 -> 0.57 (profiles/r09_experiments.md #148-#153).
+        bool lentStep = false;
+        if(lendOn && triStep)  // (launch-uniform; triStep is the same in every lane that is here)
+        {
+          const bool tests = T.y != 0u && !occluded;
+          const unsigned rest1 = T.y & (T.y - 1u);
+          const bool multi = rest1 != 0u && !occluded, isFree = T.y == 0u && !occluded;
+          const unsigned long long lendMask = __ballot(multi), freeMask = __ballot(isFree);
+          const unsigned n = min((unsigned)__popcll(lendMask), (unsigned)__popcll(freeMask));
+          if(n != 0u)
+          {
+            lentStep = true;
+            const unsigned lendRank = laneRank(lendMask), freeRank = laneRank(freeMask);
+            const bool borrows = isFree && freeRank < n;
+            unsigned s = 0u, ls = 0u;
+            if(multi && lendRank < n)
+            {
+              const unsigned hi = 31u - (unsigned)__clz((int)T.y);
+              T.y &= ~(1u << hi);
+              ls = T.x + hi;
+              res.donor[lendRank] = lane;  // r-th lender feeds the r-th free lane
+            }
+            if(tests)
+            {
+              s = T.x + (unsigned)__ffs((int)T.y) - 1u;
+              T.y &= T.y - 1u;
+            }
+            shareSync();
+            const int src = borrows ? res.donor[freeRank] : lane;
+            const unsigned bs = (unsigned)__shfl((int)ls, src);
+            const f3 ro = mk3(__shfl(o.x, src), __shfl(o.y, src), __shfl(o.z, src));
+            const f3 rd = mk3(__shfl(d.x, src), __shfl(d.y, src), __shfl(d.z, src));
+            const int row = __shfl(owner, src);
+            // the lender's view of its ray's best hit, loaded at the top of this step: never below the ray's current one, so no candidate
+            // that could still win is dropped (any-hit walks: tmax)
+            const float rbt = __shfl(bt, src);
+            const int rbg = ANYHIT ? 0 : __shfl(bg, src);
+            uint32_t rseed = raySeed;
+            if(TM & VKRT_TM_DISSOLVE)
+              rseed = (uint32_t)__shfl((int)raySeed, src);
+            if(tests || borrows)
+            {
+              if(borrows)
+              {
+                s = bs;
+                tr.set(rd);  // (watertight: the borrowed ray's shear constants, recomputed rather than shuffled or held beside the lane's own)
+              }
+              const float4* __restrict__ tp = tris + (size_t)s * VKRT_TRI_QUADS;
+              const float4 a = tp[0];
+              const float4 b = tp[1];
+              const float4 c = tp[2];
+              if(COUNT)
+              {
+                tc.tris++;
+                if(lane == __ffsll((long long)__ballot(1)) - 1) tc.waveTriSteps++;
+              }
+              float t, u, v;
+              bool ccw;
+              if(tr.hit(ro, rd, a, b, c, t, u, v, ccw) && t > tmin)
+              {
+                if(ANYHIT)
+                {
+                  if(t < rbt && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, rseed, VKRT_HOOK_UV(TM, u, v)))
+                  {
+                    __hip_atomic_store(&res.slot[row], (int)s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                    if(!borrows)
+                      occluded = true;  // (the lender of an occluder sees it at the top of its next step)
+                  }
+                }
+                else
+                {
+                  const int gid = tri_gid<TM>(c.y);
+                  if((t < rbt || (t == rbt && gid < rbg)) && !query_rejects<TM>(sc, c, ccw) && !anyhit_ignores<TM>(sc, s, c.y, rseed, VKRT_HOOK_UV(TM, u, v)))
+                  {
+                    const unsigned long long mine = ((unsigned long long)__float_as_uint(t) << 32) | (unsigned)gid;
+                    __hip_atomic_fetch_min(&res.key[row], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                    shareSync();
+                    if(__hip_atomic_load(&res.key[row], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) == mine)
+                    {
+                      res.slot[row] = (int)s; res.u[row] = u; res.v[row] = v;
+                    }
+                  }
+                }
+              }
+              if((TM & VKRT_TM_WATERTIGHT) != 0 && borrows)
+                tr.set(d);  // back to the lane's own ray
+            }
+          }
+        }
+        if(!lentStep && T.y != 0u && triStep && !occluded)
         {
           Cand cd = {false, 0.0f, 0.0f, 0.0f, -1, 0};
           testOne(cd);
@@ -348,7 +452,13 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
         }
       }
       if(finished)
-        busy = false;  // (G, T and the stack indices are dead until the lane adopts new work)
+      {
+        if(lendOn && busy)  // (not the lanes that walk along already: they would empty their hands in every iteration)
+        {
+          G.y = 0u; T.y = 0u; sp = 0; sb = 0; nPost = 0;  // empty-handed from here on, where the lane walks along to borrow
+        }
+        busy = false;  // (without lending G, T and the stack indices are dead until the lane adopts new work)
+      }
     }
   }
   shareSync();

@@ -31,6 +31,7 @@
 #define VKRT_SPLIT_BUDGET_DEFAULT -1  // automatic (round 5): vkrt_accel_build decides per scene
 #define VKRT_WF_SAMPLE_SYNC_DEFAULT 1  // sample-synchronous schedule of the wavefront path tracer (wavefront.hip)
 #define VKRT_WF_CAMERA_ROUNDS_DEFAULT 1  // ... whose camera rays are traced from the pixel grid, without path records (wavefront.hip)
+#define VKRT_WF_TRI_LEND_DEFAULT 1  // triangle steps of the sharing wave lend pending triangles to free lanes (traverse_share.h)
 #include "lbvh.h"
 #include "refit.h"
 #include "vertex_update.h"
@@ -92,8 +93,9 @@ struct vkrt_scene
   int wfTimingRounds = 0;  // rounds per frame of the last timed call (vkrt_last_trace_timing: which gaps are shade launches)
   // execution options (include/vkrt.h vkrt_option); index = option id
   std::vector<hipEvent_t> wfPool;  // events ordering the lanes of one call (kernels.h WfAsync::pool)
-  int opt[VKRT_OPT_WF_CAMERA_ROUNDS + 1] = {0, 1, 1, 3, 64, VKRT_WF_SHARE_DEFAULT, VKRT_TRI_THRESHOLD_DEFAULT, 0, VKRT_WF_SHARE_FLAGS_DEFAULT, 1, 0, 0, 0,
-                                            VKRT_WF_FRAMES_IN_FLIGHT_DEFAULT, VKRT_SPLIT_BUDGET_DEFAULT, VKRT_WF_SAMPLE_SYNC_DEFAULT, VKRT_WF_CAMERA_ROUNDS_DEFAULT};
+  int opt[VKRT_OPT_WF_TRI_LEND + 1] = {0, 1, 1, 3, 64, VKRT_WF_SHARE_DEFAULT, VKRT_TRI_THRESHOLD_DEFAULT, 0, VKRT_WF_SHARE_FLAGS_DEFAULT, 1, 0, 0, 0,
+                                            VKRT_WF_FRAMES_IN_FLIGHT_DEFAULT, VKRT_SPLIT_BUDGET_DEFAULT, VKRT_WF_SAMPLE_SYNC_DEFAULT, VKRT_WF_CAMERA_ROUNDS_DEFAULT,
+                                      VKRT_WF_TRI_LEND_DEFAULT};
   bool hasLargeTriangles = false;  // some instanced triangle covers more than 1 % of the largest face of the scene's box (any-hit order heuristic)
   bool wavefront = true;  // execution mode the acceleration structure was built for (opt[VKRT_OPT_MODE] at vkrt_accel_build)
   // moving instances (vkrt_scene_update_nodes / vkrt_accel_refit)
@@ -242,7 +244,7 @@ int clampOption(int option, int v)
     case VKRT_OPT_WF_SHARE_PERIOD: return std::max(0, std::min(255, v));
     case VKRT_OPT_WF_SHARE_FLAGS: return v & 31;
     case VKRT_OPT_GBUFFER_MIPS: case VKRT_OPT_WATERTIGHT: case VKRT_OPT_SKIP_DEAD_SHADOW_RAYS: case VKRT_OPT_ANYHIT_DISSOLVE: case VKRT_OPT_WF_SAMPLE_SYNC:
-    case VKRT_OPT_WF_CAMERA_ROUNDS: return v ? 1 : 0;
+    case VKRT_OPT_WF_CAMERA_ROUNDS: case VKRT_OPT_WF_TRI_LEND: return v ? 1 : 0;
   }
   return v;
 }
@@ -260,7 +262,8 @@ void optionsFromEnvironment(vkrt_scene* s)
                                                           {"VKRT_SKIP_DEAD_SHADOW_RAYS", VKRT_OPT_SKIP_DEAD_SHADOW_RAYS},
                                                           {"VKRT_ANYHIT_DISSOLVE", VKRT_OPT_ANYHIT_DISSOLVE}, {"VKRT_WF_FRAMES_IN_FLIGHT", VKRT_OPT_WF_FRAMES_IN_FLIGHT},
                                                           {"VKRT_SPLIT_BUDGET", VKRT_OPT_SPLIT_BUDGET}, {"VKRT_WF_SAMPLE_SYNC", VKRT_OPT_WF_SAMPLE_SYNC},
-                                                          {"VKRT_WF_CAMERA_ROUNDS", VKRT_OPT_WF_CAMERA_ROUNDS}};
+                                                          {"VKRT_WF_CAMERA_ROUNDS", VKRT_OPT_WF_CAMERA_ROUNDS},
+                                                          {"VKRT_WF_TRI_LEND", VKRT_OPT_WF_TRI_LEND}};
   for(const auto& k : ints)
     if((e = getenv(k.name)))
       s->opt[k.option] = clampOption(k.option, atoi(e));
@@ -849,11 +852,13 @@ int vkrt_scene_set_option(vkrt_scene* s, int option, int value)
 {
   if(!s)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "scene is NULL");
-  if(option < VKRT_OPT_MODE || option > VKRT_OPT_WF_CAMERA_ROUNDS)
+  if(option < VKRT_OPT_MODE || option > VKRT_OPT_WF_TRI_LEND)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "unknown option %d", option);
   if(clampOption(option, value) != value)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "option %d: value %d out of range", option, value);
   s->opt[option] = value;
+  if(option == VKRT_OPT_WF_TRI_LEND && s->built && s->dev.layout == 1u)  // a launch-uniform word of the walk, not a property of the tree: no rebuild needed
+    s->dev.shareFlags = (s->dev.shareFlags & ~VKRT_SHARE_TRI_LEND) | (value ? VKRT_SHARE_TRI_LEND : 0u);
   return VKRT_OK;
 }
 
@@ -871,7 +876,7 @@ int vkrt_scene_get_option(const vkrt_scene* s, int option, int* value)
     *value = s->built ? s->splitResolved : 0;
     return VKRT_OK;
   }
-  if(option < VKRT_OPT_MODE || option > VKRT_OPT_WF_CAMERA_ROUNDS)
+  if(option < VKRT_OPT_MODE || option > VKRT_OPT_WF_TRI_LEND)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "unknown option %d", option);
   *value = s->opt[option];
   return VKRT_OK;
@@ -1051,6 +1056,8 @@ int traversalSettings(vkrt_scene* s)
     s->dev.shareMinIdle = (uint32_t)s->opt[VKRT_OPT_WF_SHARE];
     s->dev.sharePeriodMask = (uint32_t)s->opt[VKRT_OPT_WF_SHARE_PERIOD];
     s->dev.shareFlags |= (uint32_t)s->opt[VKRT_OPT_WF_SHARE_FLAGS] & 17u;  // bit 0: child donation, bit 4: triangle-group donation
+    if(s->opt[VKRT_OPT_WF_TRI_LEND])
+      s->dev.shareFlags |= VKRT_SHARE_TRI_LEND;
   }
   // LDS budget: stackCap * 256 lanes * 4 B must fit a workgroup (160 KiB per CU on gfx950)
   if((size_t)s->dev.stackCap * 256 * 4 > 64 * 1024)
