@@ -740,7 +740,8 @@ int  vkrt_denoiser_reset(vkrt_denoiser* dn);
  * out_rgba32f: W*H rgba32f; .xyz is written at pixels with geometry (G-buffer position or normal non-zero), everything else --
  * .w and the background -- is left untouched, so a host can denoise into a copy of the accumulation plane and hand it to vkrt_post
  * unchanged.  Refused with VKRT_ERR_INVALID_ARGUMENT: struct_size too small, settings out of range, a NULL handle, camera,
- * G-buffer plane, nrd->viewZ, nrd->diffRadianceHitDist or output. */
+ * G-buffer plane, nrd->viewZ, nrd->diffRadianceHitDist or output.  A NaN radiance sample counts as black (the decode clamps with
+ * fmaxf(., 0)) and never reaches the history; an infinite one is the caller's error. */
 int  vkrt_denoise_diffuse(vkrt_denoiser* dn, const vkrt_denoise_settings* settings, const GlobalUniforms* cam, const vkrt_gbuffer* gbuffer,
                           const vkrt_nrd_planes* nrd, float* out_rgba32f, void* hip_stream);
 
