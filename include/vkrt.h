@@ -284,6 +284,15 @@ enum vkrt_option {
                                    and any-hit is "exists", whoever runs a test: no pixel, hit record or ray counter changes; tris_tested per
                                    wave_tri_steps rises, nodes_visited may move with the bound.  Read at vkrt_accel_build, and taken over at once when set on a
                                    built scene; not built for option 10 and option 12 together, where it resolves to 0 silently.  env VKRT_WF_TRI_LEND */
+  VKRT_OPT_ALPHA_TEST = 18, /* (appended within ABI 4 like options 15 to 17)  NOT a scheduling knob: 0 (default) = the frame entry points treat every
+                                   material as opaque, as the reference does; 1 = vkrt_pathtrace*, vkrt_gbuffer_raycast* and vkrt_hybrid_trace* run
+                                   the alpha test of VKRT_ALPHA_MASK materials ("alpha-tested materials" below) on every ray they trace: camera,
+                                   bounce, shadow, AO and GI rays and the G-buffer's primary ray, which passes where a raster pass would discard
+                                   the fragment.  Read by each frame call, not by the builders: it survives builds and refits, and the stage is
+                                   active in a call when the option is 1 and some material is MASK at that moment; otherwise the call launches
+                                   the kernels it launched before.  While active, a wavefront-mode scene with VKRT_OPT_WF_TRAV_BLOCK other than
+                                   64 gets VKRT_ERR_UNSUPPORTED from the frame call, which enqueues nothing.  Options 15 to 17 keep their
+                                   effect (17 resolves to 0 with option 12, as with options 10 + 12).  env VKRT_ALPHA_TEST */
   VKRT_INFO_ANYHIT_ORDER   = 100, /* read-only (vkrt_scene_get_option; set is refused): the child-order bits (2 | 4) that the last vkrt_accel_build
                                    resolved VKRT_OPT_WF_SHARE_FLAGS to, i.e. what bit 3 ("automatic") decided for this scene; 0 before a build */
   VKRT_INFO_SPLIT_BUDGET   = 101  /* read-only (ABI 4): the pre-splitting budget the last vkrt_accel_build used -- what VKRT_OPT_SPLIT_BUDGET = -1
@@ -593,9 +602,11 @@ int vkrt_hit_surface(vkrt_scene* scene, const vkrt_hit* hits, uint32_t n, uint32
  * colour texture has alpha = pbrBaseColorFactor[3].  A cutoff of 0 admits every candidate; a NaN alpha admits none.
  * The stage acts in vkrt_intersect, vkrt_occluded, their _ex forms and vkrt_intersect_multi (whose lists then hold admitted candidates
  * only), as the third filter after the cull mask and the facing flags and beside the dissolve stage of VKRT_OPT_ANYHIT_DISSOLVE: both
- * may be active, and a candidate is ignored if either says so.  VKRT_RAY_OPAQUE skips both, as gl_RayFlagsOpaqueEXT does.  It does not
- * act in vkrt_closest_point, vkrt_hit_surface, vkrt_pathtrace*, vkrt_gbuffer_raycast*, vkrt_hybrid_trace* or vkrt_debug_trace_rays:
- * their results do not depend on any alpha mode.
+ * may be active, and a candidate is ignored if either says so.  VKRT_RAY_OPAQUE skips both, as gl_RayFlagsOpaqueEXT does.  With
+ * VKRT_OPT_ALPHA_TEST = 1 the same rule, with the payload's seed for the dissolve stage, acts on every ray of vkrt_pathtrace*,
+ * vkrt_gbuffer_raycast* (always the LOD-0 tap, whatever VKRT_OPT_GBUFFER_MIPS says) and vkrt_hybrid_trace*; the shading of an admitted
+ * hit is unchanged.  With the option 0 (the default) those results do not depend on any alpha mode.  It never acts in
+ * vkrt_closest_point, vkrt_hit_surface or vkrt_debug_trace_rays.
  * The decision is a pure function of (ray, triangle), so a result stays a property of the triangle set: the same under every builder,
  * layout, split budget and scheduling option, and after a refit; vkrt_intersect_multi with max_hits = 1 still writes what
  * vkrt_intersect_ex writes.  The stage reads the live vertex array: a texture-coordinate update (vkrt_scene_update_vertices with
@@ -610,8 +621,9 @@ typedef struct vkrt_material_alpha { /* 8 B; every material starts as {VKRT_ALPH
 } vkrt_material_alpha;
 /* Set the alpha mode of materials [first, first+count).  The rules of vkrt_scene_set_instance_visibility: the array is copied before
  * return, the work is enqueued on hip_stream with no host synchronisation and no allocation, and ray queries enqueued on that stream
- * after it see the new values.  It does not make the tree stale and works on a stale one, and before vkrt_accel_build.  Refused with
- * VKRT_ERR_INVALID_ARGUMENT, changing nothing, in this order: a NULL array with count > 0; an entry with a mode other than the two or a
+ * after it see the new values, and so do frames (VKRT_OPT_ALPHA_TEST).  It does not make the tree stale and works on a stale one, and
+ * before vkrt_accel_build.  Refused with VKRT_ERR_INVALID_ARGUMENT, changing nothing, in this order: a NULL array with count > 0; an
+ * entry with a mode other than the two or a
  * cutoff that is NaN, infinite or negative; a NULL scene; a range outside the scene's materials.  Then, without a device:
  * VKRT_ERR_NO_DEVICE.  The values survive vkrt_accel_build, vkrt_accel_refit, vkrt_scene_update_nodes and vkrt_scene_update_vertices. */
 int vkrt_scene_set_material_alpha(vkrt_scene* scene, uint32_t first, uint32_t count, const vkrt_material_alpha* alpha, void* hip_stream);

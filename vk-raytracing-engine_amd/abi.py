@@ -248,6 +248,7 @@ VKRT_OPT_WF_FRAMES_IN_FLIGHT, VKRT_OPT_SPLIT_BUDGET = 13, 14
 VKRT_OPT_WF_SAMPLE_SYNC = 15
 VKRT_OPT_WF_CAMERA_ROUNDS = 16
 VKRT_OPT_WF_TRI_LEND = 17
+VKRT_OPT_ALPHA_TEST = 18
 VKRT_INFO_ANYHIT_ORDER = 100  # read-only: what the build resolved the any-hit child order to
 VKRT_INFO_SPLIT_BUDGET = 101  # read-only: the pre-splitting budget the build used (what -1 resolved to)
 # vkrt_instance_flags / vkrt_ray_flags (the gl_RayFlags*EXT values)

@@ -125,8 +125,11 @@ struct DevScene
   uint32_t watertight;        // 1: triangle records hold (p0, p1, p2) and the kernels run the watertight test (VKRT_OPT_WATERTIGHT)
   float sceneLo[3], sceneHi[3];  // world-space bounds of the instanced geometry (conservative; read by the any-hit order heuristic only)
   uint32_t dissolve;          // 1: any-hit alpha / dissolve stage (VKRT_OPT_ANYHIT_DISSOLVE): bit 31 of a record's id word flags a non-opaque triangle
+  uint32_t alphaTest;         // 1: alpha-test stage of the frame kernels (VKRT_OPT_ALPHA_TEST and a MASK material): set per call in the call's copy, 0 in
+                              // the scene's own; sits in what was padding, so every other member keeps its kernel-argument offset
   unsigned long long* faults; // sticky tally of dropped stack pushes + step-limit exits (a walk that was cut short); must stay 0
 };
+static_assert(offsetof(DevScene, alphaTest) == 196 && offsetof(DevScene, faults) == 200 && sizeof(DevScene) == 208, "DevScene");
 // The scene of a ray query with options (k_query, query.hip): the walks receive it as their DevScene and read the fields below only in
 // the triangle modes with VKRT_TM_FILTER (traverse.h query_rejects), so every other walk compiles as it did.
 struct DevQueryScene : DevScene

@@ -79,8 +79,10 @@ VKRT_DEV bool planeTexCoord(f3 org, f3 dir, f3 p0, f3 p1, f3 p2, const float* tc
   return true;
 }
 
-// TM: VKRT_TM_WATERTIGHT and / or VKRT_TM_MASKID (a raster pass has no any-hit stage -- every triangle is opaque here -- but on a scene
-// built for the stage the id words carry its flag, which the tie rule "smallest triangle id" and the exclusive tmax must not see)
+// TM: VKRT_TM_WATERTIGHT and / or VKRT_TM_MASKID (a raster pass has no dissolve stage -- every triangle is opaque to it here -- but on a
+// scene built for the stage the id words carry its flag, which the tie rule "smallest triangle id" and the exclusive tmax must not see)
+// and / or VKRT_TM_ALPHA (VKRT_OPT_ALPHA_TEST): the primary ray passes where frag_shader.frag would `discard` a MASK fragment, decided
+// on the LOD-0 tap of alpha_ignores whatever sc.gbufferMips says
 template <bool WIDE, int TM>
 __global__ __launch_bounds__(HY_BLOCK) void k_gbuffer(const HybridParams H)
 {

@@ -129,17 +129,17 @@ __global__ __launch_bounds__(VKRT_BLOCK) void k_trace_rays(DevScene sc, unsigned
   RayHit hit;
   TravCount tc;
   const f3 ro = mk3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rd = mk3(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
-  // (test hook: the payload seed of these rays is 0)
+  // (test hook: the payload seed of these rays is 0, and the alpha-test stage of the frames is never theirs)
 #define VKRT_DBG(W, TM) traverse_any<false, W, TM>(sc, ro, rd, tmin, tmax, anyHit != 0, lds_stack, (int)threadIdx.x, VKRT_BLOCK, hit, tc, 0u)
 #define VKRT_DBG_WIDE(TM) VKRT_DBG(true, TM)
 #define VKRT_DBG_BVH2(TM) VKRT_DBG(false, TM)
   if(sc.layout == 1u)
   {
-    VKRT_FRAME_TM_SWITCH(frame_tri_mode(sc, false), VKRT_TM_DISSOLVE, VKRT_DBG_WIDE)
+    VKRT_TM_SWITCH4(frame_tri_mode(sc, false), VKRT_TM_DISSOLVE, 0, VKRT_DBG_WIDE)
   }
   else
   {
-    VKRT_FRAME_TM_SWITCH(frame_tri_mode(sc, false), VKRT_TM_DISSOLVE, VKRT_DBG_BVH2)
+    VKRT_TM_SWITCH4(frame_tri_mode(sc, false), VKRT_TM_DISSOLVE, 0, VKRT_DBG_BVH2)
   }
 #undef VKRT_DBG_BVH2
 #undef VKRT_DBG_WIDE
@@ -180,10 +180,12 @@ hipError_t vkrt_launch_pathtrace(const TraceParams& P, unsigned gridBlocks, bool
 {
   const size_t lds = (size_t)P.sc.stackCap * VKRT_BLOCK * sizeof(int);
   const dim3 g(gridBlocks), b(VKRT_BLOCK);
-#define VKRT_MEGA(TM)                                                                        \
-  do {                                                                                       \
-    if(count) hipLaunchKernelGGL((k_pathtrace<true, 1, TM>), g, b, lds, stream, P);         \
-    else hipLaunchKernelGGL((k_pathtrace<false, 3, TM>), g, b, lds, stream, P);             \
+// (With the alpha-test stage the kernel does not fit the 168 VGPRs of MINW = 3 -- its siblings already spill 26 to 28 there -- so those
+// instantiations ask for two waves per SIMD and keep everything in registers.)
+#define VKRT_MEGA(TM)                                                                                        \
+  do {                                                                                                       \
+    if(count) hipLaunchKernelGGL((k_pathtrace<true, 1, TM>), g, b, lds, stream, P);                         \
+    else hipLaunchKernelGGL((k_pathtrace<false, ((TM) & VKRT_TM_ALPHA) ? 2 : 3, TM>), g, b, lds, stream, P); \
   } while(0)
   VKRT_FRAME_TM_SWITCH(frame_tri_mode(P.sc, false), VKRT_TM_DISSOLVE, VKRT_MEGA)
 #undef VKRT_MEGA

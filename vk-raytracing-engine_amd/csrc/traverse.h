@@ -153,7 +153,8 @@ VKRT_DEV bool tri_test_wt(const WtRay& R, f3 o, f3 p0, f3 p1, f3 p2, float& t, f
 // treats every triangle as opaque (the ray-cast G-buffer on a scene built for the stage): the id is masked, no hit is ignored.
 // Bit 3 = the ray-query filter of vkrt_intersect_ex / vkrt_occluded_ex (k_query only): instance masks against the call's cull mask and
 // facing culling (query_rejects), and on the wide8 layout the node-mask table in the node test; the walk's scene is a DevQueryScene.
-// Bit 4 = the alpha-test stage of the ray queries (k_query, k_query_multi; alpha_ignores below), instantiated with bit 3 only.
+// Bit 4 = the alpha-test stage (alpha_ignores below): the ray queries (k_query, k_query_multi) instantiate it with bit 3, the frame
+// kernels (VKRT_OPT_ALPHA_TEST) without it, beside any of the bits 0-2 they have.
 // TM = 0 is the product default and compiles to exactly the code it was before.
 #define VKRT_TM_WATERTIGHT 1
 #define VKRT_TM_DISSOLVE 2
@@ -161,21 +162,33 @@ VKRT_DEV bool tri_test_wt(const WtRay& R, f3 o, f3 p0, f3 p1, f3 p2, float& t, f
 #define VKRT_TM_FILTER 8
 #define VKRT_TM_ALPHA 16
 
-// The triangle mode of a frame kernel (path tracing, hybrid, the G-buffer ray cast).  opaque: the walk has no any-hit stage (k_gbuffer)
-// and only masks the stage's flag out of the id words of a scene built for it.
+// The triangle mode of a frame kernel (path tracing, hybrid, the G-buffer ray cast).  opaque: the walk has no dissolve stage (k_gbuffer)
+// and only masks the stage's flag out of the id words of a scene built for it.  The alpha-test stage is the call's (sc.alphaTest, set
+// by the frame entry points in their copy of the scene) and a real stage in either case: a raster pass discards a MASK fragment.
 __host__ __device__ inline int frame_tri_mode(const DevScene& sc, bool opaque)
 {
-  return (sc.watertight ? VKRT_TM_WATERTIGHT : 0) | (sc.dissolve ? (opaque ? VKRT_TM_MASKID : VKRT_TM_DISSOLVE) : 0);
+  return (sc.watertight ? VKRT_TM_WATERTIGHT : 0) | (sc.dissolve ? (opaque ? VKRT_TM_MASKID : VKRT_TM_DISSOLVE) : 0) | (sc.alphaTest ? VKRT_TM_ALPHA : 0);
 }
-// X(TM) for the triangle mode tm, a compile-time constant there: the four values frame_tri_mode can give for one `opaque`, whose
-// stage bit is STAGE (VKRT_TM_DISSOLVE or VKRT_TM_MASKID).  (The ray queries have more modes: VKRT_QUERY_TM_SWITCH.)
-#define VKRT_FRAME_TM_SWITCH(tm, STAGE, X)                           \
-  switch(tm)                                                          \
+// X(TM) for the triangle mode tm, a compile-time constant there.  VKRT_TM_SWITCH4: the four values of bits 0-2 that frame_tri_mode can
+// give for one `opaque`, whose stage bit is STAGE (VKRT_TM_DISSOLVE or VKRT_TM_MASKID), each with the constant A (0 or VKRT_TM_ALPHA)
+// added; the alpha bit of tm itself is not looked at (vkrt_debug_trace_rays: A = 0).  VKRT_FRAME_TM_SWITCH: the eight modes of a frame
+// kernel.  (The ray queries have their own: VKRT_QUERY_TM_SWITCH.)
+#define VKRT_TM_SWITCH4(tm, STAGE, A, X)                              \
+  switch((tm) & ~VKRT_TM_ALPHA)                                       \
   {                                                                   \
-    case 0: X(0); break;                                              \
-    case VKRT_TM_WATERTIGHT: X(VKRT_TM_WATERTIGHT); break;            \
-    case STAGE: X(STAGE); break;                                      \
-    default: X((VKRT_TM_WATERTIGHT | STAGE)); break;                  \
+    case 0: X((A)); break;                                            \
+    case VKRT_TM_WATERTIGHT: X((VKRT_TM_WATERTIGHT | (A))); break;    \
+    case STAGE: X((STAGE | (A))); break;                              \
+    default: X((VKRT_TM_WATERTIGHT | STAGE | (A))); break;            \
+  }
+#define VKRT_FRAME_TM_SWITCH(tm, STAGE, X)                            \
+  if((tm) & VKRT_TM_ALPHA)                                            \
+  {                                                                   \
+    VKRT_TM_SWITCH4(tm, STAGE, VKRT_TM_ALPHA, X)                      \
+  }                                                                   \
+  else                                                                \
+  {                                                                   \
+    VKRT_TM_SWITCH4(tm, STAGE, 0, X)                                  \
   }
 
 // per-ray constants + one entry point on a 48-byte record (a, b, c)
@@ -218,11 +231,17 @@ VKRT_DEV int tri_gid(float idWord)  // the flattened triangle id of a record (bi
 // t / tie test and query_rejects), a divergent slow path of dependent loads: triShade -> (mode, cutoff) -> [MASK only] three vertex
 // quads -> material references -> texels.  An opaque material leaves after the second.  The decode table is read from global memory
 // (sc.srgbLut): the query workgroups' LDS belongs to the stacks and the multi-hit lists.
+// FRAME (the frame kernels, VKRT_OPT_ALPHA_TEST): the opaque exit is marked as the likely one, which lays the MASK path out of line of
+// the walk's loop.  Most candidates of a frame are on opaque materials; and without the hint k_pathtrace and k_gbuffer<true, watertight>
+// with the stage report a 36-byte private segment that no instruction accesses (a 32-byte SGPR spill slot the register allocator leaves
+// behind + the scavenging slot), with it every frame kernel reports none (profiles/alpha_frames_kernel_resources.json).  The query kernels
+// keep the code they had.
+template <bool FRAME>
 VKRT_DEV bool alpha_ignores(const DevScene& sc, unsigned slot, float u, float v)
 {
   const uint4 ts = sc.triShade[slot];
   const uint2 mc = *(const uint2*)((const char*)sc.materials + (size_t)ts.w * sizeof(DevMaterial) + offsetof(DevMaterial, alphaMode));
-  if(mc.x == 0u)  // VKRT_ALPHA_OPAQUE
+  if(FRAME ? __builtin_expect(mc.x == 0u, 1) : mc.x == 0u)  // VKRT_ALPHA_OPAQUE
     return false;
   const float4 q0 = sc.vertexPN[(size_t)ts.x * VKRT_VERTEX_QUADS + 1], q1 = sc.vertexPN[(size_t)ts.y * VKRT_VERTEX_QUADS + 1],
                q2 = sc.vertexPN[(size_t)ts.z * VKRT_VERTEX_QUADS + 1];
@@ -239,7 +258,7 @@ VKRT_DEV bool anyhit_ignores(const DevScene& sc, unsigned slot, float idWord, ui
 {
   if constexpr((TM & VKRT_TM_ALPHA) != 0)
   {
-    if(alpha_ignores(sc, slot, u, v))
+    if(alpha_ignores<(TM & VKRT_TM_FILTER) == 0>(sc, slot, u, v))
       return true;
   }
   if(!(TM & VKRT_TM_DISSOLVE) || __float_as_int(idWord) >= 0)

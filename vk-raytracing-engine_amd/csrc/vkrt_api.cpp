@@ -93,9 +93,9 @@ struct vkrt_scene
   int wfTimingRounds = 0;  // rounds per frame of the last timed call (vkrt_last_trace_timing: which gaps are shade launches)
   // execution options (include/vkrt.h vkrt_option); index = option id
   std::vector<hipEvent_t> wfPool;  // events ordering the lanes of one call (kernels.h WfAsync::pool)
-  int opt[VKRT_OPT_WF_TRI_LEND + 1] = {0, 1, 1, 3, 64, VKRT_WF_SHARE_DEFAULT, VKRT_TRI_THRESHOLD_DEFAULT, 0, VKRT_WF_SHARE_FLAGS_DEFAULT, 1, 0, 0, 0,
+  int opt[VKRT_OPT_ALPHA_TEST + 1] = {0, 1, 1, 3, 64, VKRT_WF_SHARE_DEFAULT, VKRT_TRI_THRESHOLD_DEFAULT, 0, VKRT_WF_SHARE_FLAGS_DEFAULT, 1, 0, 0, 0,
                                             VKRT_WF_FRAMES_IN_FLIGHT_DEFAULT, VKRT_SPLIT_BUDGET_DEFAULT, VKRT_WF_SAMPLE_SYNC_DEFAULT, VKRT_WF_CAMERA_ROUNDS_DEFAULT,
-                                      VKRT_WF_TRI_LEND_DEFAULT};
+                                      VKRT_WF_TRI_LEND_DEFAULT, 0};
   bool hasLargeTriangles = false;  // some instanced triangle covers more than 1 % of the largest face of the scene's box (any-hit order heuristic)
   bool wavefront = true;  // execution mode the acceleration structure was built for (opt[VKRT_OPT_MODE] at vkrt_accel_build)
   // moving instances (vkrt_scene_update_nodes / vkrt_accel_refit)
@@ -111,7 +111,7 @@ struct vkrt_scene
   uint64_t masksPresent[4] = {0, 0, 0, 0};
   vkrt::DevBuf nodeMasks;  // wide8: the node-mask table of the current tree (8 B per node), allocated and computed with it
   // alpha-tested materials (vkrt_scene_set_material_alpha): host copy per material, and how many are VKRT_ALPHA_MASK right now (> 0: the
-  // ray queries walk with the alpha-test stage)
+  // ray queries walk with the alpha-test stage, and so do the frames with VKRT_OPT_ALPHA_TEST)
   std::vector<vkrt_material_alpha> alpha;
   uint32_t alphaMasks = 0;
   // vkrt_hit_surface: 16 B per primitive-mesh (device_scene.h DevSurfaceScene), uploaded at vkrt_scene_create, released with `allocs`
@@ -244,7 +244,7 @@ int clampOption(int option, int v)
     case VKRT_OPT_WF_SHARE_PERIOD: return std::max(0, std::min(255, v));
     case VKRT_OPT_WF_SHARE_FLAGS: return v & 31;
     case VKRT_OPT_GBUFFER_MIPS: case VKRT_OPT_WATERTIGHT: case VKRT_OPT_SKIP_DEAD_SHADOW_RAYS: case VKRT_OPT_ANYHIT_DISSOLVE: case VKRT_OPT_WF_SAMPLE_SYNC:
-    case VKRT_OPT_WF_CAMERA_ROUNDS: case VKRT_OPT_WF_TRI_LEND: return v ? 1 : 0;
+    case VKRT_OPT_WF_CAMERA_ROUNDS: case VKRT_OPT_WF_TRI_LEND: case VKRT_OPT_ALPHA_TEST: return v ? 1 : 0;
   }
   return v;
 }
@@ -263,7 +263,7 @@ void optionsFromEnvironment(vkrt_scene* s)
                                                           {"VKRT_ANYHIT_DISSOLVE", VKRT_OPT_ANYHIT_DISSOLVE}, {"VKRT_WF_FRAMES_IN_FLIGHT", VKRT_OPT_WF_FRAMES_IN_FLIGHT},
                                                           {"VKRT_SPLIT_BUDGET", VKRT_OPT_SPLIT_BUDGET}, {"VKRT_WF_SAMPLE_SYNC", VKRT_OPT_WF_SAMPLE_SYNC},
                                                           {"VKRT_WF_CAMERA_ROUNDS", VKRT_OPT_WF_CAMERA_ROUNDS},
-                                                          {"VKRT_WF_TRI_LEND", VKRT_OPT_WF_TRI_LEND}};
+                                                          {"VKRT_WF_TRI_LEND", VKRT_OPT_WF_TRI_LEND}, {"VKRT_ALPHA_TEST", VKRT_OPT_ALPHA_TEST}};
   for(const auto& k : ints)
     if((e = getenv(k.name)))
       s->opt[k.option] = clampOption(k.option, atoi(e));
@@ -387,6 +387,20 @@ int framesInFlight(const vkrt_scene* s, int frames) { return std::max(1, std::mi
 
 // traversal workgroup size (the non-default triangle modes exist for the default 64-thread workgroup only)
 int travBlock(const vkrt_scene* s) { return (s->dev.watertight || s->dev.dissolve) ? 64 : s->opt[VKRT_OPT_WF_TRAV_BLOCK]; }
+
+// The alpha-test stage of a frame call (VKRT_OPT_ALPHA_TEST): active when the option is on and some material is MASK right now -- read
+// per call, so nothing of it is a property of the tree.  The call's copy of the scene carries the flag to the launchers
+// (frame_tri_mode); its walks exist for 64-thread traversal workgroups only, like those of the other non-default triangle modes.
+int frameAlphaStage(const vkrt_scene* s, const char* who, TraceParams& P)
+{
+  if(s->opt[VKRT_OPT_ALPHA_TEST] == 0 || s->alphaMasks == 0u)
+    return VKRT_OK;
+  if(s->wavefront && travBlock(s) != 64)
+    return fail(VKRT_ERR_UNSUPPORTED, "%s: VKRT_OPT_ALPHA_TEST with a VKRT_ALPHA_MASK material is built for the default 64-thread traversal workgroups "
+                "(VKRT_OPT_WF_TRAV_BLOCK = %d)", who, travBlock(s));
+  P.sc.alphaTest = 1u;
+  return VKRT_OK;
+}
 
 // the tree can be traced: built, and not moved since (`who` names the caller in the refusal)
 int checkBuilt(const vkrt_scene* s, const char* who)
@@ -852,7 +866,7 @@ int vkrt_scene_set_option(vkrt_scene* s, int option, int value)
 {
   if(!s)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "scene is NULL");
-  if(option < VKRT_OPT_MODE || option > VKRT_OPT_WF_TRI_LEND)
+  if(option < VKRT_OPT_MODE || option > VKRT_OPT_ALPHA_TEST)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "unknown option %d", option);
   if(clampOption(option, value) != value)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "option %d: value %d out of range", option, value);
@@ -876,7 +890,7 @@ int vkrt_scene_get_option(const vkrt_scene* s, int option, int* value)
     *value = s->built ? s->splitResolved : 0;
     return VKRT_OK;
   }
-  if(option < VKRT_OPT_MODE || option > VKRT_OPT_WF_TRI_LEND)
+  if(option < VKRT_OPT_MODE || option > VKRT_OPT_ALPHA_TEST)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "unknown option %d", option);
   *value = s->opt[option];
   return VKRT_OK;
@@ -1586,6 +1600,8 @@ int vkrt_pathtrace_frames(vkrt_scene* s, const PushConstantRay* pc, const Global
     return rc;
   if(P.localRows == 0)
     return VKRT_OK;
+  if((rc = frameAlphaStage(s, "vkrt_pathtrace", P)) != VKRT_OK)
+    return rc;
   if(s->opt[VKRT_OPT_SKIP_DEAD_SHADOW_RAYS])
     P.flags |= VKRT_FLAG_SKIP_DEAD_SHADOW;  // internal bit (device_scene.h)
   P.image = image;
@@ -1723,6 +1739,8 @@ int gbufferImpl(vkrt_scene* s, const float clearColor[4], int lightsCount, const
     return rc;
   if(P.localRows == 0)
     return VKRT_OK;
+  if((rc = frameAlphaStage(s, "vkrt_gbuffer_raycast", P)) != VKRT_OK)
+    return rc;
   P.sc.gbufferMips = (uint32_t)s->opt[VKRT_OPT_GBUFFER_MIPS];
   const HybridGi G{(float4*)out->color, (float4*)out->position, (float4*)out->normal, (float2*)out->roughMetal, nullptr,
                    nrd ? (float4*)nrd->diffRadianceHitDist : nullptr, nrd ? nrd->viewZ : nullptr};
@@ -1750,6 +1768,8 @@ int hybridImpl(vkrt_scene* s, const PushConstantRay* pc, const GlobalUniforms* c
     return rc;
   if(P.localRows == 0)
     return VKRT_OK;
+  if((rc = frameAlphaStage(s, "vkrt_hybrid_trace", P)) != VKRT_OK)
+    return rc;
   hipStream_t stream = (hipStream_t)hip_stream;
   HIP_TRY(hipEventRecord(s->evStart, stream));
   const HybridGi G{(float4*)g->color, (float4*)g->position, (float4*)g->normal, (float2*)g->roughMetal, (float4*)accum,

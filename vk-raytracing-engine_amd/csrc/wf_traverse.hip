@@ -48,9 +48,11 @@ VKRT_DEV void storeHit(const TraceParams& P, const WfBuffers& B, int par, int ki
 }
 
 // ---- traversal: one thread per queued ray, workgroups homogeneous in ray kind -----------------------------------
+// (waves per SIMD: five for the non-default triangle modes of the wide 64-thread kernel, like TM = 0 gets on its own; the instrumented
+// kernels with the alpha-test stage would spill VGPRs at five -- their dissolve / watertight siblings already do -- and ask for four)
 template <bool COUNT, bool WIDE, int TB, int TM = 0>
 __global__ __launch_bounds__(TB)
-__attribute__((amdgpu_waves_per_eu(TM != 0 && WIDE && TB == 64 ? 5 : 1)))
+__attribute__((amdgpu_waves_per_eu(TM != 0 && WIDE && TB == 64 ? (COUNT && (TM & VKRT_TM_ALPHA) != 0 ? 4 : 5) : 1)))
 void k_wf_traverse(const TraceParams P, const WfBuffers B, const int round)
 {
   extern __shared__ int lds_stack[];
@@ -173,8 +175,8 @@ void k_wf_traverse_camera(const TraceParams P, const WfBuffers B, const int roun
 }
 
 // One traversal launch: the instantiation for (instrumented?, node layout, workgroup size, triangle mode).  The non-default triangle
-// modes (watertight test, any-hit dissolve stage) are built for the default 64-thread workgroups only (vkrt_accel_build refuses the
-// other sizes with them).
+// modes (watertight test, any-hit dissolve stage, alpha-test stage) are built for the default 64-thread workgroups only (vkrt_accel_build
+// refuses the other sizes with the first two, the frame entry points with the third).
 void vkrt_wf_launch_traverse(const TraceParams& P, const WfBuffers& B, int r, unsigned travBlock, bool count, dim3 tg, size_t tlds, hipStream_t stream)
 {
   const bool wide = P.sc.layout == 1u;

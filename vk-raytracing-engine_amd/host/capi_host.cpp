@@ -89,6 +89,17 @@ int vkrt_host_parse_config(const char* text, int* out, char* scenePath, int cap)
   catch(const std::exception& e) { g_err = e.what(); return 1; }
 }
 
+// the "alphaTest" key of a config text (AppConfig::alphaTest; absent = 0) -> *out; 1 and the error text when the config does not parse
+int vkrt_host_config_alpha_test(const char* text, int* out)
+{
+  try
+  {
+    *out = parseConfig(text).alphaTest ? 1 : 0;
+    return 0;
+  }
+  catch(const std::exception& e) { g_err = e.what(); return 1; }
+}
+
 // End-to-end through the HelloVulkan-shaped class: load, build, `frames` x (updateUniformBuffer,
 // updateFrame, pathtrace), download.  seed for frame f = seed0 + f.  Returns 0 on success.
 int vkrt_host_render_gltf(const char* path, int device, int width, int height, int samples, int depth, int frames, uint32_t seed0,

@@ -42,7 +42,8 @@ void HelloVkrt::loadScene(const GltfScene& scene)
   std::vector<vkrt_texture> tex;
   const vkrt_scene_desc d = m_gltfScene.desc(tex);
   check(vkrt_scene_create(&d, m_device, &m_scene), "vkrt_scene_create");
-  // glTF's alpha modes: the ray queries of this scene test MASK materials against their cutoff (the frame kernels do not read them)
+  // glTF's alpha modes: the ray queries of this scene test MASK materials against their cutoff, and so do its frames -- path tracing,
+  // the G-buffer ray cast and the hybrid pass -- once m_alphaTest turns VKRT_OPT_ALPHA_TEST on (createTopLevelAsGltf)
   if(m_gltfScene.hasAlphaMask())
     check(vkrt_scene_set_material_alpha(m_scene, 0, (uint32_t)m_gltfScene.m_materialAlpha.size(), m_gltfScene.m_materialAlpha.data(), nullptr),
           "vkrt_scene_set_material_alpha");
@@ -76,6 +77,8 @@ void HelloVkrt::createTopLevelAsGltf()
     check(vkrt_scene_set_option(m_scene, VKRT_OPT_WATERTIGHT, m_watertight ? 1 : 0), "vkrt_scene_set_option(VKRT_OPT_WATERTIGHT)");
   if(m_anyHitDissolve >= 0)
     check(vkrt_scene_set_option(m_scene, VKRT_OPT_ANYHIT_DISSOLVE, m_anyHitDissolve ? 1 : 0), "vkrt_scene_set_option(VKRT_OPT_ANYHIT_DISSOLVE)");
+  if(m_alphaTest)  // (read by every frame call, not by the build; false leaves the environment's VKRT_ALPHA_TEST in place)
+    check(vkrt_scene_set_option(m_scene, VKRT_OPT_ALPHA_TEST, 1), "vkrt_scene_set_option(VKRT_OPT_ALPHA_TEST)");
   if(m_skipDeadShadowRays >= 0)
     check(vkrt_scene_set_option(m_scene, VKRT_OPT_SKIP_DEAD_SHADOW_RAYS, m_skipDeadShadowRays ? 1 : 0), "vkrt_scene_set_option(VKRT_OPT_SKIP_DEAD_SHADOW_RAYS)");
   check(vkrt_accel_build(m_scene, m_buildFlags, nullptr), "vkrt_accel_build");
@@ -388,6 +391,7 @@ AppConfig parseConfig(const std::string& text)
   c.denoise = j["denoise"].boolean(c.denoise);
   if(c.denoise && (c.mode != "hybrid" || !c.useGI))
     throw std::runtime_error("config.json: \"denoise\" needs \"mode\": \"hybrid\" with \"useGI\": true");
+  c.alphaTest = j["alphaTest"].boolean(c.alphaTest);
   if(j.has("watertight")) c.watertight = j["watertight"].boolean(false) ? 1 : 0;
   if(j.has("anyHitDissolve")) c.anyHitDissolve = j["anyHitDissolve"].boolean(false) ? 1 : 0;
   if(j.has("skipDeadShadowRays")) c.skipDeadShadowRays = j["skipDeadShadowRays"].boolean(false) ? 1 : 0;

@@ -101,6 +101,7 @@ public:
   uint32_t m_traceFlags = 0;
   PushConstantPost m_pcPost{1.0f, 0, 0, 0};  // rtMode 0 = hybrid (hello_vulkan.cpp:917), 1 = path tracer
   bool m_denoise = false;         // hybrid mode: denoise the GI term (set before createOffscreenRender)
+  bool m_alphaTest = false;       // VKRT_OPT_ALPHA_TEST: the frames honour glTF alphaMode MASK (set before createTopLevelAsGltf)
   vkrt_denoise_settings m_denoiseSettings{sizeof(vkrt_denoise_settings), 5, 32};
 
 private:
@@ -148,6 +149,7 @@ struct AppConfig
   std::string mode = "pathtrace";
   bool useShadows = true, useAO = true, useGI = false;  // hello_vulkan.cpp:913-915
   bool denoise = false;   // hybrid mode with GI: filter the GI term (vkrt_denoise_diffuse) before drawPost
+  bool alphaTest = false; // both modes: cut-outs of alphaMode MASK materials in the rendered frames (VKRT_OPT_ALPHA_TEST)
   int watertight = -1, anyHitDissolve = -1, skipDeadShadowRays = -1;  // library options (include/vkrt.h): -1 = key absent (environment / library default)
   int framesPerCall = 1;  // > 1: the frame loop hands that many progressive frames to the library at once (HelloVkrt::pathtraceFrames)
   std::string output;

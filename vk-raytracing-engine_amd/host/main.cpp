@@ -180,6 +180,7 @@ int main(int argc, char** argv)
     helloVk.loadGltfScene(scenePath);                           // main.cpp:226
     if(!helloVk.m_gltfScene.warnings.empty()) fprintf(stderr, "warning: %s\n", helloVk.m_gltfScene.warnings.c_str());
     helloVk.m_denoise = cfg.denoise;
+    helloVk.m_alphaTest = cfg.alphaTest;
     helloVk.createOffscreenRender();                            // main.cpp:228
     helloVk.initRayTracing();                                   // main.cpp:235
     helloVk.m_buildFlags = cfg.build == "lbvh" ? VKRT_BUILD_LBVH_GPU : cfg.build == "sah" ? VKRT_BUILD_SAH_HOST : VKRT_BUILD_PLOC_GPU;

@@ -30,6 +30,8 @@ def lib():
         L.vkrt_host_global_uniforms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.POINTER(abi.GlobalUniforms)]
         L.vkrt_host_parse_config.argtypes = [C.c_char_p, C.c_void_p, C.c_char_p, C.c_int]
         L.vkrt_host_parse_config.restype = C.c_int
+        L.vkrt_host_config_alpha_test.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
+        L.vkrt_host_config_alpha_test.restype = C.c_int
         L.vkrt_host_render_gltf.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p]
         L.vkrt_host_render_gltf.restype = C.c_int
@@ -129,6 +131,10 @@ def parse_config(text):
             "skipDeadShadowRays"]
     d = dict(zip(keys, (int(x) for x in out)))
     d["scene_path"] = path.value.decode()
+    alpha = C.c_int(0)
+    if lib().vkrt_host_config_alpha_test(text.encode(), C.byref(alpha)) != 0:
+        raise ValueError(lib().vkrt_host_last_error().decode())
+    d["alphaTest"] = int(alpha.value)
     return d
 
 
