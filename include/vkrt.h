@@ -823,6 +823,22 @@ int vkrt_debug_trace_rays(vkrt_scene* scene, uint32_t n, const float* origins,
  * 4 pow5, 5 1/sqrt-normalise x of (a,b,0)); host arrays in/out. */
 int vkrt_debug_eval_math(int device, int op, uint32_t n, const float* a, const float* b,
                          float* out);
+/* Evaluate the BRDF tail of the hit shader (lobe draw, next-event estimation, cosine / GGX sample, payload outputs) on n records of
+ * HOST arrays (synchronises the device; a test hook like vkrt_debug_eval_math): the device builds the shading inputs the hit shader's
+ * front half hands over for an untextured material and runs the functions the frame kernels run.  Words marked (bits) are integers
+ * stored in the float's bits.
+ *   in : 40 floats per record:
+ *     [0:3] worldPos [3:6] worldNrm [6:9] tangent [9:12] binormal [12:15] worldRayDir
+ *     [15:19] baseColorFactor [19] metallic [20] roughness [21:24] emissive
+ *     [24:27] light.position [27:30] light.color [30] intensity [31] light.type (bits)
+ *     [32] seed (bits) [33] depth (bits) [34] isSpecular (bits) [35] lightsCount (bits) [36:40] pad
+ *   out: 20 floats per record:
+ *     [0:3] hitValue [3:6] rayOrigin [6:9] rayDirection [9:12] weight [12] isSpecular (0.0 or 1.0)
+ *     [13] lightDist [14:17] shadowRayDir [17] seed (bits) [18:20] pad (0)
+ * Every one of the record's lightsCount lights is the record's light, so the index the shader draws always finds it; lightsCount is
+ * 1 to 16, any other value in any record: VKRT_ERR_INVALID_ARGUMENT.  The factors are taken as given (no range check: the clamps are
+ * the shader's).  NULL in or out with n > 0: VKRT_ERR_INVALID_ARGUMENT; n == 0: VKRT_OK. */
+int vkrt_debug_eval_shade(int device, uint32_t n, const float* in, float* out);
 
 #ifdef __cplusplus
 }

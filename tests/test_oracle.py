@@ -48,21 +48,24 @@ def test_sincos_profile_accuracy():
 
 
 def test_shading_agrees_with_numpy_restatement():
+    """The generator's own records (the `default` stratum of tests/shade_records.py): discrete outputs exact, and every record within
+    four times the measured maximum difference (tests/test_shade_records.py holds the other strata and the binary64 twin)."""
     import np_shading
+    import shade_records
 
-    rec = np_shading.random_records(20000, np.random.default_rng(5))
-    a = oracle_py.eval_shade(rec)
-    b = np_shading.shade(rec)
+    rec, a, b, _ = shade_records.evaluate("default")
+    assert rec.shape[0] == 20000
     # discrete outputs are exact: lobe choice, PRNG state, ray origin
     assert np.array_equal(a[:, 12], b[:, 12])
-    assert np.array_equal(a[:, 17].view(np.uint32), b[:, 17].view(np.uint32))
+    assert np.array_equal(a[:, 17].view(np.uint32), np_shading.out_seed(b))
     assert np.array_equal(a[:, 3:6], b[:, 3:6])
+    assert np.isfinite(a[:, :17]).all() and np.isfinite(b[:, :17]).all()
+    shade_records.check_parity("default")  # no quantile: the bar holds for every record
     for lo, hi, name in ((0, 3, "hitValue"), (6, 9, "rayDirection"), (9, 12, "weight"), (13, 14, "lightDist"), (14, 17, "shadowRayDir")):
         x, y = a[:, lo:hi].astype(np.float64), b[:, lo:hi].astype(np.float64)
         scale = np.maximum(np.abs(x), np.abs(y)).max(axis=1, keepdims=True) + 1e-3
         err = np.abs(x - y) / scale
-        # a handful of ill-conditioned samples (grazing specular pdf) may differ more
-        assert np.quantile(err, 0.999) < 2e-4, (name, float(np.quantile(err, 0.999)))
+        assert err.max() < 2e-4, (name, float(err.max()))
         assert np.median(err) < 2e-6, (name, float(np.median(err)))
 
 

@@ -308,6 +308,7 @@ VKRT_SYMBOLS = [
     "vkrt_debug_closest_point_work",
     "vkrt_debug_trace_rays",
     "vkrt_debug_eval_math",
+    "vkrt_debug_eval_shade",
 ]
 
 
@@ -417,4 +418,6 @@ def declare_vkrt(lib):
     lib.vkrt_debug_trace_rays.restype = C.c_int
     lib.vkrt_debug_eval_math.argtypes = [C.c_int, C.c_int, c_u, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.vkrt_debug_eval_math.restype = C.c_int
+    lib.vkrt_debug_eval_shade.argtypes = [C.c_int, c_u, C.c_void_p, C.c_void_p]
+    lib.vkrt_debug_eval_shade.restype = C.c_int
     return lib

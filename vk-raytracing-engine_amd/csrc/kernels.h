@@ -9,6 +9,10 @@ hipError_t vkrt_pathtrace_occupancy(size_t ldsBytes, int* blocksPerCU);
 hipError_t vkrt_launch_trace_rays(const DevScene& sc, unsigned n, const float* o, const float* d, float tmin, float tmax, int anyHit,
                                   float* t, float* u, float* v, int* gid, hipStream_t stream);
 hipError_t vkrt_launch_eval_math(int op, unsigned n, const float* a, const float* b, float* out, hipStream_t stream);
+// vkrt_debug_eval_shade: n records of 40 floats -> 20 floats each, one per thread of 256-thread blocks; lights = scratch of
+// VKRT_EVAL_SHADE_MAX_LIGHTS 32-byte light records (2 float4) per record, written and read by the record's own thread
+#define VKRT_EVAL_SHADE_MAX_LIGHTS 16
+hipError_t vkrt_launch_eval_shade(unsigned n, const float* in, float4* lights, float* out, hipStream_t stream);
 
 // The three query launches below run one thread per item in chunks of at most 2^30 items (query_common.h query_launch_chunks) and return
 // the first launch error; the ray queries pick their triangle mode there too (query_tri_mode, VKRT_QUERY_TM_SWITCH).

@@ -173,6 +173,63 @@ __global__ void k_eval_math(int op, unsigned n, const float* a, const float* b, 
   }
 }
 
+// The BRDF tail of the hit shader on caller records (vkrt_debug_eval_shade; record layout in include/vkrt.h): one record per thread.
+// The thread builds the HitMid closestHitFront hands over for an untextured material and runs closestHitLobe + closestHitTail, the
+// functions of the frame kernels.  lights: VKRT_EVAL_SHADE_MAX_LIGHTS 32-byte records per thread; the thread fills the first
+// lightsCount with the record's light, so whichever index the tail draws finds it.
+__global__ __launch_bounds__(VKRT_BLOCK) void k_eval_shade(unsigned n, const float* in, float4* lights, float* out)
+{
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if(i >= n)
+    return;
+  const float* p = in + 40u * (size_t)i;
+  float* o = out + 20u * (size_t)i;
+  const int lightsCount = __float_as_int(p[35]);
+  if(lightsCount < 1 || lightsCount > VKRT_EVAL_SHADE_MAX_LIGHTS)  // (the host refuses such a batch; never index past the thread's lights)
+  {
+    for(int k = 0; k < 20; k++)
+      o[k] = 0.0f;
+    return;
+  }
+  float4* lq = lights + 2u * VKRT_EVAL_SHADE_MAX_LIGHTS * (size_t)i;
+  const float4 l0 = make_float4(p[24], p[25], p[26], p[27]), l1 = make_float4(p[28], p[29], p[30], p[31]);
+  for(int k = 0; k < lightsCount; k++)
+  {
+    lq[2 * k] = l0;
+    lq[2 * k + 1] = l1;
+  }
+  DevScene sc = {};
+  sc.lights = (const GltfLight*)lq;
+  PushConstantRay pc = {};
+  pc.lightsCount = lightsCount;
+  Payload prd = {};
+  prd.seed = __float_as_uint(p[32]);
+  prd.depth = __float_as_uint(p[33]);
+  prd.isSpecular = __float_as_uint(p[34]) != 0u;
+  HitMid mid;
+  mid.worldPos = mk3(p[0], p[1], p[2]); mid.N = mk3(p[3], p[4], p[5]);
+  mid.tangent = mk3(p[6], p[7], p[8]); mid.binormal = mk3(p[9], p[10], p[11]);
+  mid.V = normalize3(-mk3(p[12], p[13], p[14]));
+  mid.baseColor = mk3(p[15], p[16], p[17]);
+  mid.emittance = (prd.depth == 0 || prd.isSpecular) ? mk3(p[21], p[22], p[23]) : mk3(0.0f);  // rchit:83
+  mid.metalU = p[19]; mid.roughU = p[20];
+  mid.retap = 0u;
+  ShadeStats st;
+  st.hits = 0; st.diffuse = 0; st.taps = 0; st.lut = nullptr;
+  const bool diffuse = closestHitLobe(mid, prd);
+  closestHitTail(sc, pc, mid, diffuse, prd, st);
+  o[0] = prd.hitValue.x; o[1] = prd.hitValue.y; o[2] = prd.hitValue.z;
+  o[3] = prd.rayOrigin.x; o[4] = prd.rayOrigin.y; o[5] = prd.rayOrigin.z;
+  o[6] = prd.rayDirection.x; o[7] = prd.rayDirection.y; o[8] = prd.rayDirection.z;
+  o[9] = prd.weight.x; o[10] = prd.weight.y; o[11] = prd.weight.z;
+  o[12] = prd.isSpecular ? 1.0f : 0.0f;
+  // (the specular branch leaves lightDist / shadowRayDir as the payload held them: 0 here, as in the oracle's record call)
+  o[13] = prd.lightDist;
+  o[14] = prd.shadowRayDir.x; o[15] = prd.shadowRayDir.y; o[16] = prd.shadowRayDir.z;
+  o[17] = __uint_as_float(prd.seed);
+  o[18] = 0.0f; o[19] = 0.0f;
+}
+
 // ---- launch wrappers (called from vkrt_api.cpp) ------------------------------------------------------
 // MINW = minimum waves per SIMD the register allocator must allow: 3 measured +34 % over the unconstrained build and
 // level with 4 (profiles/r01_experiments.md #2, #3), so the product build carries that one variant.
@@ -211,5 +268,11 @@ hipError_t vkrt_launch_trace_rays(const DevScene& sc, unsigned n, const float* o
 hipError_t vkrt_launch_eval_math(int op, unsigned n, const float* a, const float* b, float* out, hipStream_t stream)
 {
   hipLaunchKernelGGL(k_eval_math, dim3((n + 255) / 256), dim3(256), 0, stream, op, n, a, b, out);
+  return hipGetLastError();
+}
+
+hipError_t vkrt_launch_eval_shade(unsigned n, const float* in, float4* lights, float* out, hipStream_t stream)
+{
+  hipLaunchKernelGGL(k_eval_shade, dim3((n + VKRT_BLOCK - 1) / VKRT_BLOCK), dim3(VKRT_BLOCK), 0, stream, n, in, lights, out);
   return hipGetLastError();
 }

@@ -2344,4 +2344,35 @@ int vkrt_debug_eval_math(int device, int op, uint32_t n, const float* a, const f
   return VKRT_OK;
 }
 
+int vkrt_debug_eval_shade(int device, uint32_t n, const float* in, float* out)
+{
+  if(n && (!in || !out))
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "NULL argument");
+  if(vkrt_device_count() <= 0)
+    return fail(VKRT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
+  if(n == 0)
+    return VKRT_OK;
+  for(uint32_t i = 0; i < n; i++)
+  {
+    int32_t lightsCount;
+    memcpy(&lightsCount, in + 40 * (size_t)i + 35, sizeof lightsCount);
+    if(lightsCount < 1 || lightsCount > VKRT_EVAL_SHADE_MAX_LIGHTS)
+      return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_debug_eval_shade: record %u has lightsCount %d (1 to %d)", i, lightsCount, VKRT_EVAL_SHADE_MAX_LIGHTS);
+  }
+  HIP_TRY(hipSetDevice(device));
+  vkrt::DevBuf dIn, dLights, dOut;
+  const size_t inBytes = (size_t)n * 40 * sizeof(float), outBytes = (size_t)n * 20 * sizeof(float);
+  hipError_t e = hipSuccess;
+  auto tryHip = [&](hipError_t x) { if(e == hipSuccess) e = x; };
+  tryHip(dIn.alloc(inBytes)); tryHip(dOut.alloc(outBytes));
+  tryHip(dLights.alloc((size_t)n * VKRT_EVAL_SHADE_MAX_LIGHTS * sizeof(GltfLight)));
+  if(e == hipSuccess) tryHip(hipMemcpy(dIn.get(), in, inBytes, hipMemcpyHostToDevice));
+  if(e == hipSuccess) tryHip(vkrt_launch_eval_shade(n, dIn.get<float>(), dLights.get<float4>(), dOut.get<float>(), nullptr));
+  if(e == hipSuccess) tryHip(hipDeviceSynchronize());
+  if(e == hipSuccess) tryHip(hipMemcpy(out, dOut.get(), outBytes, hipMemcpyDeviceToHost));
+  if(e != hipSuccess)
+    return fail(VKRT_ERR_HIP, "vkrt_debug_eval_shade: %s", hipGetErrorString(e));
+  return VKRT_OK;
+}
+
 }  // extern "C"

@@ -763,3 +763,12 @@ def eval_math(op, a, b=None, device=0):
     out = np.zeros_like(a)
     _check(lib.vkrt_debug_eval_math(device, op, a.size, a.ctypes.data, b.ctypes.data, out.ctypes.data), "vkrt_debug_eval_math")
     return out
+
+
+def eval_shade(records, device=0):
+    """The hit shader's BRDF tail on [n, 40] float32 records -> [n, 20] (layout: include/vkrt.h vkrt_debug_eval_shade)."""
+    lib = load_library()
+    records = np.ascontiguousarray(records, np.float32).reshape(-1, 40)
+    out = np.zeros((records.shape[0], 20), np.float32)
+    _check(lib.vkrt_debug_eval_shade(device, records.shape[0], records.ctypes.data, out.ctypes.data), "vkrt_debug_eval_shade")
+    return out
