@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "device_scene.h"
+#include "wf_schedule.h"
 
 hipError_t vkrt_launch_pathtrace(const TraceParams& P, unsigned gridBlocks, bool count, hipStream_t stream);
 int        vkrt_pathtrace_block_size();
@@ -50,34 +51,25 @@ struct WfTiming
   int capacity;
   int used;             // pairs recorded around k_wf_traverse launches
 };
-// Lanes.  A call renders `frames` progressive frames of one shard.  Its work is dealt to up to VKRT_WF_MAX_LANES lanes, each with its
-// own record streams and its own HIP stream, so that the kernels of different lanes overlap (a draining traversal launch of one lane
-// is filled up by the launches of the others):
-//   * a call of several frames keeps `inFlight` consecutive frames in flight, one lane each (frame k belongs to group k % inFlight).
-//     A frame in flight writes its pixel values into its group's staging plane, and a blend kernel at its end applies
-//     raytrace.rgen:136-141 in frame order (it waits for the blend of frame k - 1): the image is what single-frame calls would
-//     have left, bit for bit.  Every launch keeps its full size;
-//   * a single frame is split spatially into `subframes` tile ranges, one lane each (a pixel is always blended by its own lane).
-#define VKRT_WF_MAX_LANES 8
+// Lanes: a call's work is dealt to up to VKRT_WF_MAX_LANES lanes, each with its own record streams and its own HIP stream; which lanes,
+// which launches and in what order is wf_schedule.h's to say.
 struct WfAsync
 {
   hipStream_t streams[VKRT_WF_MAX_LANES];  // internal streams (created by the caller of vkrt_launch_wavefront)
   hipEvent_t fork, join[VKRT_WF_MAX_LANES];
   int count;                                // usable entries (0/1 = everything on the caller's stream)
   hipEvent_t* pool;                         // events for the blend order of the frames of one call, no timing
-  int poolSize;
+  int poolSize;                             // >= wfPoolEvents(frames) of every call
 };
-// events a call with these parameters takes from WfAsync::pool
-inline int vkrt_wf_pool_events(int frames, int lanes) { return frames * lanes; }
 size_t     vkrt_wf_state_bytes(uint32_t pathCapacity, int groups);
 void       vkrt_wf_carve(void* base, uint32_t pathCapacity, int groups, WfBuffers* B);
 struct WfOptions
 {
   int subframes;   // VKRT_OPT_WF_SUBFRAMES
   int travBlock;   // VKRT_OPT_WF_TRAV_BLOCK (64 / 128 / 256)
-  int inFlight;    // VKRT_OPT_WF_FRAMES_IN_FLIGHT (clamped to the frames of the call and to WfBuffers::groups)
+  int inFlight;    // VKRT_OPT_WF_FRAMES_IN_FLIGHT
 };
-// frames >= 1: frame k uses pc.frame + k and seed + k * seedStep
+// frames >= 1: frame k uses wfFrameParams(P, k, seedStep)
 hipError_t vkrt_launch_wavefront(const TraceParams& P, const WfBuffers& B, const WfOptions& opt, int frames, uint32_t seedStep, bool count,
                                  hipStream_t stream, WfTiming* timing, const WfAsync* async);
 // one launch of k_wf_traverse on the records of round r (wf_traverse.hip): travBlock 64 / 128 / 256 threads per workgroup, tg = grid,

@@ -366,10 +366,14 @@ int ensureWorkingSet(vkrt_scene* s, uint32_t paths, int groups, hipStream_t stre
   return VKRT_OK;
 }
 
-// events that order the lanes of a call of `frames` frames (created once, kept; no device synchronisation)
-int ensureEventPool(vkrt_scene* s, int frames)
+// the working set and the event pool (the events that order the lanes of a call; created once, kept; no device synchronisation) of a
+// wavefront call of `frames` frames, which the launcher sees as batches, on `tiles` 8x8 tiles: wf_schedule.h says how much of each
+int ensureFrameCall(vkrt_scene* s, uint32_t tiles, uint32_t frames, hipStream_t stream)
 {
-  const size_t want = (size_t)vkrt_wf_pool_events(frames, VKRT_WF_MAX_LANES);
+  const int rc = ensureWorkingSet(s, tiles * 64u, wfGroupsWanted(s->opt[VKRT_OPT_WF_FRAMES_IN_FLIGHT], frames), stream);
+  if(rc != VKRT_OK)
+    return rc;
+  const size_t want = (size_t)wfPoolEvents((int)std::min<uint32_t>(frames, VKRT_FRAMES_PER_BATCH));
   while(s->wfPool.size() < want)
   {
     hipEvent_t e;
@@ -380,10 +384,6 @@ int ensureEventPool(vkrt_scene* s, int frames)
   s->wfAsync.poolSize = (int)s->wfPool.size();
   return VKRT_OK;
 }
-
-// frames a call keeps in flight: the option, but never more than the call has
-int framesInFlight(const vkrt_scene* s, int frames) { return std::max(1, std::min(s->opt[VKRT_OPT_WF_FRAMES_IN_FLIGHT], frames)); }
-#define VKRT_FRAMES_PER_BATCH 32  // a longer call is rendered as batches of this many frames (bounds the event pool)
 
 // traversal workgroup size (the non-default triangle modes exist for the default 64-thread workgroup only)
 int travBlock(const vkrt_scene* s) { return (s->dev.watertight || s->dev.dissolve) ? 64 : s->opt[VKRT_OPT_WF_TRAV_BLOCK]; }
@@ -422,6 +422,16 @@ int checkShard(const vkrt_shard* shard)
   return VKRT_OK;
 }
 
+// 8x8 tiles that cover a shard's rows
+int shardTiles(const vkrt_shard* shard, uint32_t& tileCount)
+{
+  const uint64_t tiles = (uint64_t)((shard->full_width + 7) / 8) * ((vkrt_shard_rows(shard) + 7) / 8);
+  if(tiles * 64 >= 0xFFFFFFFFull)
+    return fail(VKRT_ERR_UNSUPPORTED, "launch too large");
+  tileCount = (uint32_t)tiles;
+  return VKRT_OK;
+}
+
 // The TraceParams every trace entry point shares: tree, camera, seed, public flags, the shard's rows and its 8x8 tiles, counters.
 // Callers check the tree (checkBuilt) and the shard (checkShard) first and add what is their own.
 int launchParams(const vkrt_scene* s, const PushConstantRay* pc, const GlobalUniforms* cam, const vkrt_trace_opts* opts, const vkrt_shard* shard,
@@ -443,12 +453,8 @@ int launchParams(const vkrt_scene* s, const PushConstantRay* pc, const GlobalUni
   P.localRows = vkrt_shard_rows(shard);
   P.counters = s->counters;
   P.tilesX = (P.fullW + 7) / 8;
-  const uint64_t tiles = (uint64_t)P.tilesX * ((P.localRows + 7) / 8);
-  if(tiles * 64 >= 0xFFFFFFFFull)
-    return fail(VKRT_ERR_UNSUPPORTED, "launch too large");
-  P.tileCount = (uint32_t)tiles;
   P.tileFirst = 0;
-  return VKRT_OK;
+  return shardTiles(shard, P.tileCount);
 }
 
 // The trace set-up every query entry point shares once its own arguments are checked and n > 0: the tree can be traced, the scene's
@@ -915,19 +921,15 @@ int vkrt_reserve_frames(vkrt_scene* s, const vkrt_shard* shard, uint32_t frames_
     rc = setDevice(s);
   if(rc != VKRT_OK)
     return rc;
-  const uint64_t tiles = (uint64_t)((shard->full_width + 7) / 8) * ((vkrt_shard_rows(shard) + 7) / 8);
-  if(tiles * 64 >= 0xFFFFFFFFull)
-    return fail(VKRT_ERR_UNSUPPORTED, "launch too large");
+  uint32_t tiles = 0;
+  if((rc = shardTiles(shard, tiles)) != VKRT_OK)
+    return rc;
   // the mode that counts is the one the acceleration structure was built for (vkrt_pathtrace and vkrt_hybrid_trace look at
   // s->wavefront, not at an option that may have changed since); before a build, the option is the best guess there is
   const bool wavefront = s->built ? s->wavefront : useWavefront(s);
   if(tiles == 0 || !wavefront)
     return VKRT_OK;  // the megakernel keeps its state in registers / LDS
-  // frame groups: what a call of frames_per_call frames keeps in flight (the balanced share of the option, wavefront.hip)
-  int rc2 = ensureWorkingSet(s, (uint32_t)tiles * 64u, framesInFlight(s, (int)std::min<uint32_t>(frames_per_call, VKRT_FRAMES_PER_BATCH)), (hipStream_t)hip_stream);
-  if(rc2 == VKRT_OK)
-    rc2 = ensureEventPool(s, (int)std::min<uint32_t>(frames_per_call, VKRT_FRAMES_PER_BATCH));
-  return rc2;
+  return ensureFrameCall(s, tiles, frames_per_call, (hipStream_t)hip_stream);
 }
 
 namespace {
@@ -1608,11 +1610,11 @@ int vkrt_pathtrace_frames(vkrt_scene* s, const PushConstantRay* pc, const Global
   P.workCounter = s->workCounter;
 
   const bool count = (P.flags & VKRT_TRACE_COUNT_TRAVERSAL) != 0;
+  const uint32_t seedStep = (P.flags & VKRT_TRACE_SAME_SEED_EVERY_FRAME) ? 0u : 1u;
   if(s->wavefront)
   {
     if(P.fullW > 65535u || P.localRows > 65535u || pc->samples > 65535)
       return fail(VKRT_ERR_UNSUPPORTED, "wavefront mode packs pixel coordinates / sample index in 16 bits");
-    const uint32_t seedStep = (P.flags & VKRT_TRACE_SAME_SEED_EVERY_FRAME) ? 0u : 1u;
     if(s->opt[VKRT_OPT_WF_SAMPLE_SYNC])
       P.flags |= VKRT_FLAG_SAMPLE_SYNC;  // internal bit (device_scene.h)
     // camera rounds: only in that schedule, and only where the sharing wave of k_wf_traverse_camera runs (wide8 tree, one-wave traversal
@@ -1620,15 +1622,13 @@ int vkrt_pathtrace_frames(vkrt_scene* s, const PushConstantRay* pc, const Global
     if(s->opt[VKRT_OPT_WF_CAMERA_ROUNDS] && (P.flags & VKRT_FLAG_SAMPLE_SYNC) && s->dev.layout == 1u && travBlock(s) == 64 && s->dev.shareMinIdle != 0u &&
        s->dev.triThreshold != 0u)
       P.flags |= VKRT_FLAG_CAMERA_ROUNDS;
-    if((rc = ensureWorkingSet(s, P.tileCount * 64u, framesInFlight(s, (int)n_frames), stream)) != VKRT_OK)
-      return rc;
-    if((rc = ensureEventPool(s, (int)std::min<uint32_t>(n_frames, VKRT_FRAMES_PER_BATCH))) != VKRT_OK)
+    if((rc = ensureFrameCall(s, P.tileCount, n_frames, stream)) != VKRT_OK)
       return rc;
     WfTiming* timing = nullptr;
     if(P.flags & VKRT_TRACE_TIME_KERNELS)
     {
-      const size_t wantEv = (size_t)2 * (2 * (size_t)pc->samples * pc->depth) * std::min<uint32_t>(n_frames, 8u);
-      while(s->wfEvents.size() < wantEv && s->wfEvents.size() < 8192)
+      const size_t wantEv = wfTimingEvents(pc->samples, pc->depth, n_frames);
+      while(s->wfEvents.size() < wantEv)
       {
         hipEvent_t e;
         HIP_TRY(hipEventCreate(&e));
@@ -1639,19 +1639,14 @@ int vkrt_pathtrace_frames(vkrt_scene* s, const PushConstantRay* pc, const Global
       timing = &s->wfTiming;
     }
     s->wfTimed = timing != nullptr;
-    s->wfTimingRounds = (pc->samples > 0 && pc->depth > 0) ? pc->samples * (pc->depth + 1) : 0;
+    s->wfTimingRounds = wfRounds(pc->samples, pc->depth);
     HIP_TRY(hipEventRecord(s->evStart, stream));
-    WfOptions wo;
-    wo.subframes = s->opt[VKRT_OPT_WF_SUBFRAMES];
-    wo.travBlock = travBlock(s);
-    wo.inFlight = framesInFlight(s, (int)n_frames);
+    const WfOptions wo{s->opt[VKRT_OPT_WF_SUBFRAMES], travBlock(s), s->opt[VKRT_OPT_WF_FRAMES_IN_FLIGHT]};
     if(timing)
       timing->used = 0;  // one timing record per call: the batches of a long call append to it
     for(uint32_t first = 0; first < n_frames; first += VKRT_FRAMES_PER_BATCH)
     {
-      TraceParams Pb = P;
-      Pb.pc.frame = P.pc.frame + (int)first;
-      Pb.seed = P.seed + first * seedStep;
+      const TraceParams Pb = wfFrameParams(P, first, seedStep);
       HIP_TRY(vkrt_launch_wavefront(Pb, s->wf, wo, (int)std::min<uint32_t>(VKRT_FRAMES_PER_BATCH, n_frames - first), seedStep, count, stream, timing, &s->wfAsync));
     }
     HIP_TRY(hipEventRecord(s->evStop, stream));
@@ -1669,9 +1664,7 @@ int vkrt_pathtrace_frames(vkrt_scene* s, const PushConstantRay* pc, const Global
   HIP_TRY(hipEventRecord(s->evStart, stream));
   for(uint32_t k = 0; k < n_frames; k++)  // the megakernel renders the frames of a call one after another
   {
-    TraceParams Pk = P;
-    Pk.pc.frame = P.pc.frame + (int)k;
-    Pk.seed = P.seed + ((P.flags & VKRT_TRACE_SAME_SEED_EVERY_FRAME) ? 0u : k);
+    const TraceParams Pk = wfFrameParams(P, k, seedStep);
     HIP_TRY(hipMemsetAsync(s->workCounter, 0, sizeof(unsigned int), stream));
     HIP_TRY(vkrt_launch_pathtrace(Pk, grid, count, stream));
   }

@@ -29,8 +29,9 @@
 // (144 instead of 256 on the bench workload), each with ~1.8x the rays, and a diffuse segment moves ~35 % fewer record bytes
 // (one record instead of a shadow record followed by a closest record).
 //
-// A frame = init + samples * (depth + 1) x (traverse, shade) enqueued back to back on the caller's
-// stream; stream counts stay on the device (no host synchronisation inside a frame).  (Camera rounds, below: no init.)
+// The launches of a frame are enqueued back to back; stream counts stay on the device (no host synchronisation inside a frame).
+// How many rounds a frame has, what each of its steps launches in the three schedules and how the frames of a call are dealt to
+// lanes is decided in wf_schedule.h, which the host half of this file only carries out.
 //
 // Sample-synchronous schedule (VKRT_OPT_WF_SAMPLE_SYNC, VKRT_FLAG_SAMPLE_SYNC).  A sample takes at most depth + 1 rounds, so the
 // round count above already lets every pixel of a frame trace sample s in the rounds [s (depth + 1), (s + 1) (depth + 1)): a path
@@ -49,8 +50,7 @@
 //                          startSample -> the walk of k_wf_traverse -> H0 / H1 at the pixel's slot of the C stream.
 //   k_wf_shade_camera      one thread per pixel: the same state again, H0 / H1, then the code of k_wf_shade's C workgroups.
 //
-// A frame then has no k_wf_init and no k_wf_sample_init (a degenerate launch without rounds keeps k_wf_init, which stores its pixels):
-// frame = samples x [(traverse_camera, shade_camera) + depth x (traverse, shade)].  Per pixel and sample the first round moves 96 B
+// A frame then has no k_wf_init and no k_wf_sample_init (wf_schedule.h wfStep).  Per pixel and sample the first round moves 96 B
 // (traversal: 16 in, 32 out; shade: 16 + 32 in) instead of 256 B (init: 16 in, 80 out; traversal: 32 in, 32 out; shade: 96 in), and
 // the frame has `samples` launches fewer.  Same functions, draws and float operations: only where a value comes from changes.
 #include <hip/hip_runtime.h>
@@ -479,24 +479,17 @@ void vkrt_wf_carve(void* base, uint32_t pathCapacity, int groups, WfBuffers* B)
   B->groups = (uint32_t)g;
 }
 
-// One sub-frame = the tiles [tileFirst, tileFirst + tileCount) of the shard with their own streams and counts, on one HIP stream.
-// a sample takes at most depth + 1 rounds: its first closest-hit ray, then one round per further segment (the shadow ray of
-// segment k travels with the closest-hit ray of segment k + 1), then the shadow ray of its last segment
-static int subframeRounds(const TraceParams& P) { return (P.pc.samples <= 0 || P.pc.depth <= 0) ? 0 : P.pc.samples * (P.pc.depth + 1); }
-// camera rounds (VKRT_FLAG_CAMERA_ROUNDS; the caller sets the bit only with VKRT_FLAG_SAMPLE_SYNC and a tree and workgroup size the
-// sharing wave of k_wf_traverse_camera runs on): no init kernels, the first round of every sample runs the two camera kernels
-static bool cameraRounds(const TraceParams& P) { return (P.flags & VKRT_FLAG_CAMERA_ROUNDS) != 0u && subframeRounds(P) > 0; }
-// subframeBegin: counts cleared, one closest-ray record per pixel (raytrace.rgen:27-60) -- or none: a frame of camera rounds starts
-// from the pixel grid.  (A degenerate launch, no samples or no depth, has no rounds: k_wf_init stores its pixels.)
-static hipError_t subframeBegin(const TraceParams& P, const WfBuffers& B, hipStream_t stream)
+// One sub-frame = the tiles [tileFirst, tileFirst + tileCount) of the shard with their own streams and counts, on one HIP stream.  Which
+// launches a call makes for it, and in what order, is wf_schedule.h's to say: the functions below make one launch (or one round) each.
+static unsigned pixelBlocks(const TraceParams& P) { return (P.tileCount * 64u + WF_BLOCK - 1) / WF_BLOCK; }
+// begin: counts cleared and, with `init`, one closest-ray record per pixel (raytrace.rgen:27-60; a degenerate frame, no samples or no
+// depth, has no rounds: k_wf_init stores its pixels).  A frame of camera rounds starts from the pixel grid instead: no init.
+static hipError_t subframeBegin(const TraceParams& P, const WfBuffers& B, bool init, hipStream_t stream)
 {
-  const unsigned work = P.tileCount * 64u;
   const hipError_t e = hipMemsetAsync(B.ctrl, 0, 64, stream);
-  if(e != hipSuccess)
-    return e;
-  if(!cameraRounds(P))
-    hipLaunchKernelGGL(k_wf_init, dim3((work + WF_BLOCK - 1) / WF_BLOCK), dim3(WF_BLOCK), 0, stream, P, B);
-  return hipSuccess;
+  if(e == hipSuccess && init)
+    hipLaunchKernelGGL(k_wf_init, dim3(pixelBlocks(P)), dim3(WF_BLOCK), 0, stream, P, B);
+  return e;
 }
 // One traversal launch on the records of round r, its geometry for a sub-frame's tiles: workgroups of travBlock threads (64 unless 128
 // or 256 is asked for).  Every path holds one record and a record at most two rays; +4 blocks for the partial tails of the four ray
@@ -508,10 +501,8 @@ static void launchTraverse(const TraceParams& P, const WfBuffers& B, int r, unsi
 }
 // round r: traverse the rays of the records, shade the results into the next round's records.  cameraSample >= 0: r is the first
 // round of that sample in a frame of camera rounds -- its rays and their state come from the pixel grid, not from records.
-static void subframeRound(const TraceParams& P, const WfBuffers& B, int r, unsigned travBlock, bool count, hipStream_t stream, WfTiming* timing,
-                          int cameraSample = -1)
+static void subframeRound(const TraceParams& P, const WfBuffers& B, int r, int cameraSample, unsigned travBlock, bool count, hipStream_t stream, WfTiming* timing)
 {
-  const unsigned work = P.tileCount * 64u;
   const bool timed = timing && timing->events && 2 * (timing->used + 1) <= timing->capacity;
   if(timed)
     (void)hipEventRecord(timing->events[2 * timing->used], stream);
@@ -525,98 +516,36 @@ static void subframeRound(const TraceParams& P, const WfBuffers& B, int r, unsig
     timing->used++;
   }
   if(cameraSample >= 0)
-    hipLaunchKernelGGL(k_wf_shade_camera, dim3((work + WF_BLOCK - 1) / WF_BLOCK), dim3(WF_BLOCK), 0, stream, P, B, r, cameraSample);
+    hipLaunchKernelGGL(k_wf_shade_camera, dim3(pixelBlocks(P)), dim3(WF_BLOCK), 0, stream, P, B, r, cameraSample);
   else
-    hipLaunchKernelGGL(k_wf_shade, dim3((work + WF_BLOCK - 1) / WF_BLOCK + 3), dim3(WF_BLOCK), 0, stream, P, B, r);
-}
-
-// The launches of a frame between its begin and its blend, in order: the rounds, and in the sample-synchronous schedule one sample
-// init in front of the first round of every sample but the first (whose camera rays subframeBegin made) -- unless the frame runs
-// camera rounds, which need no init.
-static bool sampleSync(const TraceParams& P) { return (P.flags & VKRT_FLAG_SAMPLE_SYNC) != 0u; }
-static int subframeSteps(const TraceParams& P)
-{
-  return subframeRounds(P) + ((sampleSync(P) && !cameraRounds(P) && subframeRounds(P) > 0) ? P.pc.samples - 1 : 0);
-}
-static void subframeStep(const TraceParams& P, const WfBuffers& B, int step, unsigned travBlock, bool count, hipStream_t stream, WfTiming* timing)
-{
-  if(cameraRounds(P))
-    return subframeRound(P, B, step, travBlock, count, stream, timing, step % (P.pc.depth + 1) == 0 ? step / (P.pc.depth + 1) : -1);
-  if(!sampleSync(P))
-    return subframeRound(P, B, step, travBlock, count, stream, timing);
-  const int perSample = P.pc.depth + 2;  // sample init + depth + 1 rounds; step + 1: as if sample 0 had an init of its own at step -1
-  const int s = (step + 1) / perSample, k = (step + 1) % perSample;
-  if(k != 0)
-    return subframeRound(P, B, s * (P.pc.depth + 1) + k - 1, travBlock, count, stream, timing);
-  const unsigned work = P.tileCount * 64u;
-  hipLaunchKernelGGL(k_wf_sample_init, dim3((work + WF_BLOCK - 1) / WF_BLOCK), dim3(WF_BLOCK), 0, stream, P, B, s * (P.pc.depth + 1), s);
-}
-
-// parameters of frame k of a call (progressive frames of an unchanged camera: main.cpp:503-508, hello_vulkan.cpp:1501-1521)
-static TraceParams frameParams(const TraceParams& P, int k, uint32_t seedStep)
-{
-  TraceParams Q = P;
-  Q.pc.frame = P.pc.frame + k;
-  Q.seed = P.seed + (uint32_t)k * seedStep;
-  return Q;
-}
-
-// frames a call of `frames` frames keeps in flight when the option allows `want`: as many rounds of `want` as the call needs, the frames
-// dealt evenly over them (4 frames, want 3 -> two rounds of 2, not 3 + 1: measured 30.8 against 31.5 ms per frame on a 4K / 8 shard)
-static int balancedInFlight(int frames, int want)
-{
-  want = std::max(1, std::min(want, frames));
-  const int turns = (frames + want - 1) / want;
-  return (frames + turns - 1) / turns;
+    hipLaunchKernelGGL(k_wf_shade, dim3(pixelBlocks(P) + 3), dim3(WF_BLOCK), 0, stream, P, B, r);
 }
 
 hipError_t vkrt_launch_wavefront(const TraceParams& P, const WfBuffers& B, const WfOptions& opt, int frames, uint32_t seedStep, bool count,
                                  hipStream_t stream, WfTiming* timing, const WfAsync* async)
 {
-  const unsigned travBlock = (unsigned)opt.travBlock;
-  const int steps = subframeSteps(P);  // launches of a frame between its begin and its blend: the rounds and the sample inits
-  frames = std::max(frames, 1);
-  // Lanes: F frame groups x S tile ranges.  Frames in flight keep every launch at full size, sub-frames cut it into S pieces -- and
-  // what overlaps well on this device is few, large launches (profiles/r04_experiments.md #110: two or three full-size lanes reach
-  // 0.96-0.97 of linear on a 4K / 8 shard, three third-size lanes 0.90, four quarter-size lanes 0.77): a call with several frames
-  // runs them in flight, one lane each; a single frame is split into sub-frames.  Per-kernel timing wants the kernels one after
-  // another; tiny frames are not worth splitting.
-  int F = (timing || !async || steps == 0) ? 1 : std::min(balancedInFlight(frames, opt.inFlight), (int)B.groups);
-  F = std::max(1, std::min(F, async ? std::min(VKRT_WF_MAX_LANES, async->count) : 1));
-  int S = (timing || !async || F > 1) ? 1 : std::max(1, std::min(std::min(VKRT_WF_MAX_LANES, opt.subframes), async->count));
-  S = (int)std::min<uint32_t>((uint32_t)S, std::max(1u, P.tileCount / 256u));
-  const int L = S * F;
-  hipError_t e;
-  if(L <= 1)
-  {
-    for(int k = 0; k < frames; k++)
-    {
-      TraceParams Q = frameParams(P, k, seedStep);
-      Q.tileFirst = 0;
-      if((e = subframeBegin(Q, B, stream)) != hipSuccess) return e;
-      for(int r = 0; r < steps; r++) subframeStep(Q, B, r, travBlock, count, stream, timing);
-    }
-    return hipGetLastError();
-  }
-  // ---- several lanes ------------------------------------------------------------------------------------------------------
-  // lane q = g * S + j: tile range j of the frames of group g (frames g, g + F, g + 2 F, ...)
-  const bool staged = F > 1;
-  if(staged && vkrt_wf_pool_events(frames, S) > async->poolSize)
-    return hipErrorInvalidValue;  // (the caller sizes the pool: vkrt_api.cpp)
+  const WfCall call{P.pc.samples, P.pc.depth, (P.flags & VKRT_FLAG_SAMPLE_SYNC) != 0u, (P.flags & VKRT_FLAG_CAMERA_ROUNDS) != 0u, P.tileCount, frames,
+                    opt.inFlight, opt.subframes, (int)B.groups, async ? async->count : 0, timing != nullptr};
+  const WfLanes lanes = wfLanes(call);
+  const int L = lanes.F * lanes.S;
+  const bool staged = lanes.F > 1;
+  if(staged && wfPoolEvents(lanes.frames) > async->poolSize)
+    return hipErrorInvalidValue;  // (vkrt_api.cpp sizes the pool with the same function)
+  // a single lane is the caller's stream and B itself; several have internal streams and their slices of B
   hipStream_t laneStream[VKRT_WF_MAX_LANES];
-  uint32_t tile0[VKRT_WF_MAX_LANES], tileN[VKRT_WF_MAX_LANES];
   WfBuffers Bq[VKRT_WF_MAX_LANES];
+  laneStream[0] = stream;
+  Bq[0] = B;
   const size_t groupQuads = (size_t)2 * WF_SLOTS * B.capacity;
-  for(int q = 0; q < L; q++)
+  for(int q = 0; L > 1 && q < L; q++)
   {
-    const int g = q / S, j = q % S;
-    tile0[q] = (uint32_t)((uint64_t)P.tileCount * j / S);
-    tileN[q] = (uint32_t)((uint64_t)P.tileCount * (j + 1) / S) - tile0[q];
+    const int g = q / lanes.S, j = q % lanes.S;
+    const uint32_t tile0 = lanes.tileFirst(j);
     Bq[q].ctrl = B.ctrl + 64 * q;
-    Bq[q].planes = B.planes + (size_t)g * groupQuads + (size_t)2 * WF_SLOTS * ((size_t)tile0[q] * 64u);
+    Bq[q].planes = B.planes + (size_t)g * groupQuads + (size_t)2 * WF_SLOTS * ((size_t)tile0 * 64u);
     Bq[q].stage = staged ? B.stage + (size_t)g * B.capacity : nullptr;
     Bq[q].sampleState = B.sampleState + (size_t)g * B.capacity;  // indexed by the pixel's tile in the shard: no offset per tile range
-    Bq[q].capacity = tileN[q] * 64u;
+    Bq[q].capacity = (lanes.tileFirst(j + 1) - tile0) * 64u;
     Bq[q].groups = 1;
     laneStream[q] = async->streams[q];
   }
@@ -637,8 +566,9 @@ hipError_t vkrt_launch_wavefront(const TraceParams& P, const WfBuffers& B, const
     }
     return first;
   };
-  if((e = hipEventRecord(async->fork, stream)) != hipSuccess) return e;
-  for(int q = 0; q < L; q++)
+  hipError_t e = hipSuccess;
+  if(L > 1 && (e = hipEventRecord(async->fork, stream)) != hipSuccess) return e;
+  for(int q = 0; L > 1 && q < L; q++)
   {
     if((e = hipStreamWaitEvent(laneStream[q], async->fork, 0)) != hipSuccess)
     {
@@ -647,70 +577,45 @@ hipError_t vkrt_launch_wavefront(const TraceParams& P, const WfBuffers& B, const
     }
     forked = q + 1;
   }
-  // Items of a lane's m-th frame: 0 = begin, 1..steps = the rounds and sample inits (subframeStep), steps + 1 = ordered blend (frames in flight only).  The host
-  // deals the items of all lanes round-robin -- item i of every lane before item i + 1 of any: enqueueing one lane's hundreds of
-  // launches after the other's makes the later lanes start milliseconds late (profiles/r03_experiments.md #106).  The blend of
-  // frame k waits for the blend of frame k - 1 (same tiles, another lane) through an event of the pool, one per (frame, tile
-  // range), so no record call ever replaces one that still has a wait to come; a lane whose blend would wait for a record the
-  // host has not made yet is skipped for a turn (hipStreamWaitEvent refers to the record calls made BEFORE it).
-  const int items = steps + 1 + (staged ? 1 : 0);
-  hipEvent_t* evBlend = async->pool;  // [frame k][tile range j]
-  int laneFrames[VKRT_WF_MAX_LANES], cursor[VKRT_WF_MAX_LANES];
-  std::vector<char> blendRecorded(staged ? (size_t)frames * S : 0, 0);
-  int remaining = 0;
-  for(int q = 0; q < L; q++)
-  {
-    laneFrames[q] = (frames - q / S + F - 1) / F;
-    cursor[q] = 0;
-    remaining += laneFrames[q] * items;
-  }
-  e = hipSuccess;
-  while(remaining > 0 && e == hipSuccess)
-  {
-    bool progressed = false;
-    for(int q = 0; q < L && e == hipSuccess; q++)
+  const bool init = !wfCameraRounds(call);
+  const bool all = wfForEachItem(call, lanes, [&](const WfItem& it) {
+    const WfBuffers& Bl = Bq[it.lane];
+    hipStream_t st = laneStream[it.lane];
+    TraceParams Q = wfFrameParams(P, (uint32_t)it.frame, seedStep);
+    Q.tileFirst = lanes.tileFirst(it.range);
+    Q.tileCount = lanes.tileFirst(it.range + 1) - Q.tileFirst;
+    if(staged)
     {
-      if(cursor[q] >= laneFrames[q] * items)
-        continue;
-      const int g = q / S, j = q % S, m = cursor[q] / items, it = cursor[q] % items, k = g + m * F;
-      TraceParams Q = frameParams(P, k, seedStep);
-      Q.tileFirst = tile0[q];
-      Q.tileCount = tileN[q];
-      if(staged)
-      {
-        Q.image = (float*)Bq[q].stage;
-        Q.flags |= VKRT_FLAG_STORE_STAGED;
-      }
-      hipStream_t st = laneStream[q];
-      if(it == 0)
-      {
-        if((e = subframeBegin(Q, Bq[q], st)) != hipSuccess) break;
-      }
-      else if(it <= steps)
-        subframeStep(Q, Bq[q], it - 1, travBlock, count, st, nullptr);
-      else
-      {
-        // the frame's pixels are staged: blend them into the image behind the blend of frame k - 1
-        if(k > 0)
-        {
-          if(!blendRecorded[(size_t)(k - 1) * S + j])
-            continue;
-          if((e = hipStreamWaitEvent(st, evBlend[(k - 1) * S + j], 0)) != hipSuccess) break;
-        }
-        TraceParams R = Q;
-        R.image = P.image;
-        const unsigned work = R.tileCount * 64u;
-        hipLaunchKernelGGL(k_wf_blend, dim3((work + WF_BLOCK - 1) / WF_BLOCK), dim3(WF_BLOCK), 0, st, R, (const float4*)Bq[q].stage);
-        if(k + 1 < frames && (e = hipEventRecord(evBlend[k * S + j], st)) != hipSuccess) break;
-        blendRecorded[(size_t)k * S + j] = 1;
-      }
-      cursor[q]++;
-      remaining--;
-      progressed = true;
+      Q.image = (float*)Bl.stage;
+      Q.flags |= VKRT_FLAG_STORE_STAGED;
     }
-    if(!progressed && e == hipSuccess)
-      e = hipErrorUnknown;  // (cannot happen: the blends follow frame order)
-  }
+    switch(it.kind)
+    {
+    case WfItem::BEGIN:
+      e = subframeBegin(Q, Bl, init, st);
+      break;
+    case WfItem::STEP:
+    {
+      const WfStep s = wfStep(call, it.step);
+      if(s.kind == WfStep::SAMPLE_INIT)
+        hipLaunchKernelGGL(k_wf_sample_init, dim3(pixelBlocks(Q)), dim3(WF_BLOCK), 0, st, Q, Bl, s.round, s.sample);
+      else
+        subframeRound(Q, Bl, s.round, s.sample, (unsigned)opt.travBlock, count, st, timing);
+      break;
+    }
+    case WfItem::BLEND:  // the frame's pixels are staged: blend them into the image behind the blend of the frame before
+      if(it.wait >= 0 && (e = hipStreamWaitEvent(st, async->pool[it.wait], 0)) != hipSuccess)
+        break;
+      Q.image = P.image;
+      hipLaunchKernelGGL(k_wf_blend, dim3(pixelBlocks(Q)), dim3(WF_BLOCK), 0, st, Q, (const float4*)Bl.stage);
+      if(it.record >= 0)
+        e = hipEventRecord(async->pool[it.record], st);
+      break;
+    }
+    return e == hipSuccess;
+  });
+  if(e == hipSuccess && !all)
+    e = hipErrorUnknown;  // (a lane held for ever: tests/test_wf_schedule.py shows there is no such call)
   const hipError_t ej = joinLanes();
   if(e == hipSuccess) e = ej;
   if(e == hipSuccess) e = hipGetLastError();
