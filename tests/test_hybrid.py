@@ -111,15 +111,20 @@ def test_gpu_gbuffer_and_hybrid_match_oracle_cornell(cornell_flat, cornell_oracl
         r.hybrid_trace(pc, cam, W, H, g, seed=40 + f, accum=accum)
         c = r.counters()
         _, cref = cornell_oracle.hybrid(pc, cam, W, H, gnp, seed=40 + f, accum=ref)
-        assert abs(c["rays_shadow"] - cref["rays_shadow"]) <= 8 and abs(c["rays_closest"] - cref["rays_closest"]) <= 8
+        print(f"{kind} frame {f}: rays_shadow {c['rays_shadow']} vs {cref['rays_shadow']}, rays_closest {c['rays_closest']} vs {cref['rays_closest']}")
+        assert c["rays_shadow"] == cref["rays_shadow"] and c["rays_closest"] == cref["rays_closest"]
     out = accum.cpu().numpy()
-    assert _mismatch(out, ref) < 1e-4
+    print(f"{kind}: gbuffer pixels differing {[int(_mismatch(g[k].cpu().numpy(), gref[k]) * W * H + 0.5) for k in gref]}, accum pixels differing {int(_mismatch(out, ref) * W * H + 0.5)} of {W * H}")
+    # measured: no pixel and no ray differs (profiles/hybrid_planes_parity.json), so the share of pixels this comparison once excused
+    # (< 1e-4, counters within 8) is word-for-word equality now, as on the synthetic planes of tests/test_gpu_hybrid_planes.py
+    assert np.array_equal(out.view(np.uint32), ref.view(np.uint32))
     assert float(np.sqrt(np.mean((out - ref) ** 2))) < 1e-3
     # post composite (gamma uses powf: library vs device differ by rounding, not bit-exact)
     comp = r.post(g["color"], accum, rt_mode=0).cpu().numpy()
     want = oracle_py.post(gnp["color"], ref, rt_mode=0)
     bad = np.abs(comp - want) > (2e-5 * np.abs(want) + 1e-6)
-    assert bad.any(axis=-1).mean() < 2e-4  # only the few path-divergent pixels allowed above
+    print(f"{kind}: post texels outside the bar {int(bad.any(axis=-1).sum())}")
+    assert not bad.any()  # (the accumulation image is the oracle's word for word: no path-divergent pixel to excuse)
     r.close()
 
 
@@ -138,6 +143,7 @@ def test_gpu_hybrid_textured_atrium_and_toggles():
     g = r.gbuffer_raycast(cam, W, H)  # all 8 fallback lights, clear colour (1,1,1,1)
     gref = orc.gbuffer(cam, W, H, lights_count=len(flat.lights))
     for k in gref:
+        print(f"atrium gbuffer {k}: pixels differing {int(_mismatch(g[k].cpu().numpy(), gref[k]) * W * H + 0.5)}")
         assert _mismatch(g[k].cpu().numpy(), gref[k]) < 2e-4, k
     gnp = {k: v.cpu().numpy() for k, v in g.items()}
     for sh, ao, gi in ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 1)):
@@ -145,7 +151,8 @@ def test_gpu_hybrid_textured_atrium_and_toggles():
         pc.useShadows, pc.useAO, pc.useGI = sh, ao, gi
         out = r.hybrid_trace(pc, cam, W, H, g, seed=5).cpu().numpy()
         ref, _ = orc.hybrid(pc, cam, W, H, gnp, seed=5)
-        assert _mismatch(out, ref) < 2e-4, (sh, ao, gi)
+        print(f"atrium toggles {(sh, ao, gi)}: accum pixels differing {int(_mismatch(out, ref) * W * H + 0.5)} of {W * H}")
+        assert np.array_equal(out.view(np.uint32), ref.view(np.uint32)), (sh, ao, gi)  # measured 0 of 36864: equality, no share excused
     # the wave-synchronous kernel with work sharing (default) and the one-lane-one-walk kernel are the same function of the pixel
     from vkrt_amd import abi
     pc = make_push_constants(samples=1, depth=6, frame=0, lights_count=len(flat.lights))
@@ -327,6 +334,15 @@ def test_gpu_nrd_planes_match_oracle(small_scene):
     acc_o, rad_o = orc.hybrid_nrd(pc, cam, W, H, gnp, seed=9)
     rad = g["nrdRadianceHitDist"].cpu().numpy()
     r.close()
-    assert np.mean(np.any(acc.cpu().numpy().view(np.uint32) != acc_o.view(np.uint32), axis=-1)) < 1e-3
-    assert np.mean(np.any(rad.view(np.uint32) != rad_o.view(np.uint32), axis=-1)) < 5e-3   # exp2f differs in the last bits between CPU and GPU
+    w_diff = rad.view(np.uint32)[..., 3] != rad_o.view(np.uint32)[..., 3]
+    print(f"nrd: accum pixels differing {int(np.any(acc.cpu().numpy().view(np.uint32) != acc_o.view(np.uint32), axis=-1).sum())}, radiance .xyz "
+          f"{int(np.any(rad.view(np.uint32)[..., :3] != rad_o.view(np.uint32)[..., :3], axis=-1).sum())}, .w {int(w_diff.sum())} of {W * H}; "
+          f"viewZ / normalRoughness words differing {[int((g[k].cpu().numpy().view(np.uint32) != go[k].view(np.uint32)).sum()) for k in ('nrdViewZ', 'nrdNormalRoughness')]}")
+    # measured: no word differs in either plane (profiles/hybrid_planes_parity.json).  accum and the radiance have no transcendental:
+    # word for word.  .w goes through exp2f, whose last bits may differ between the host's and the device's library: word for word or
+    # the adjacent binary16 value (tests/test_gpu_hybrid_planes.py), and never in more pixels than the share this test once allowed.
+    import hybrid_planes as hp
+    assert np.array_equal(acc.cpu().numpy().view(np.uint32), acc_o.view(np.uint32))
+    assert np.array_equal(rad.view(np.uint32)[..., :3], rad_o.view(np.uint32)[..., :3])
+    assert np.all(hp.half_neighbours(rad[..., 3], rad_o[..., 3])) and w_diff.mean() < 5e-3
     assert np.abs(rad - rad_o).max() < 5e-3 * max(1.0, np.abs(rad_o).max())
