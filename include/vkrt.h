@@ -591,6 +591,32 @@ typedef struct vkrt_surface {            /* 128 B, 16-byte aligned, eight float4
 } vkrt_surface;
 int vkrt_hit_surface(vkrt_scene* scene, const vkrt_hit* hits, uint32_t n, uint32_t fields, vkrt_surface* out, void* hip_stream);
 
+/* ---- motion: where a visible surface point was one frame ago (what NRD takes as IN_MV, as world positions), for scenes that
+ *      vkrt_scene_update_nodes and vkrt_scene_update_vertices move and deform.  These entry points came after ABI version 4 without
+ *      changing it or any existing struct: detect them by symbol. ----------------------------------------------------------------
+ * The scene keeps a *previous state*: the node transforms and vertex positions as they were at the last mark.  A frame loop marks,
+ * then updates, then refits, then renders:
+ *     mark -> update nodes / vertices -> refit -> vkrt_gbuffer_raycast_hits -> vkrt_hit_motion -> trace -> vkrt_denoise_diffuse_motion
+ *
+ * vkrt_scene_motion_mark: the node transforms and vertex positions, as they are at this point of hip_stream, become the previous
+ * state: two stream-ordered device-to-device copies (the instance records and the positions).  The first call allocates 96 bytes
+ * per node + 12 bytes per vertex and may synchronise, like the first refit; later calls neither allocate nor synchronise.  Before
+ * any mark the previous state is the current state (the live arrays, nothing allocated).  The snapshot is not part of the tree: it
+ * survives vkrt_accel_build, vkrt_accel_refit and updates of normals, tangents and texture coordinates, and goes with the scene.  A
+ * mark copies all nodes and all positions (no partial snapshots).  Refused with VKRT_ERR_INVALID_ARGUMENT: a NULL scene. */
+int vkrt_scene_motion_mark(vkrt_scene* scene, void* hip_stream);
+/* The surface point of n hit records now (current_rgba32f) and in the previous state (previous_rgba32f): device arrays of n x 4
+ * floats, 16-byte aligned like hits; either may be NULL, not both.  Records are resolved and validated as vkrt_hit_surface does --
+ * (instance, primitive, u, v) are read, t and the other ids are not -- and like it the call needs no tree (it works on a stale one).
+ * A miss, an id outside the scene or a non-finite u or v gives (0, 0, 0, 0); a valid record gives (x, y, z, 1) with, in binary32
+ * without contraction, bw = ((1 - u) - v, u, v), Pk = objectToWorld * (position of vertex k, 1) and
+ *     xyz = ((0 + P0 * bw0) + P1 * bw1) + P2 * bw2
+ * -- current from the live transforms and vertices, previous from the snapshot.  That is the raster stand-in's order (transform the
+ * corners, then interpolate), not raytrace.rchit's: for a record written by vkrt_gbuffer_raycast_hits, current.xyz equals the
+ * G-buffer's position.xyz in every bit, and while nothing moved previous equals current in every bit, which keeps a still frame's
+ * reprojection exactly on the pixel.  One thread per record, on hip_stream, no allocation and no synchronisation. */
+int vkrt_hit_motion(vkrt_scene* scene, const vkrt_hit* hits, uint32_t n, float* current_rgba32f, float* previous_rgba32f, void* hip_stream);
+
 /* ---- alpha-tested materials (glTF's alphaMode MASK; Vulkan's any-hit shader for cut-out geometry: foliage, fences, fabric edges):
  *      the texture decides inside the walk whether a candidate counts.  These entry points came after ABI version 4 without changing
  *      it or any existing struct: detect them by symbol. ------------------------------------------------------------------------
@@ -712,6 +738,15 @@ typedef struct vkrt_nrd_planes {
  * view_matrix = PushConstantRaster.viewMatrix (hello_vulkan.cpp:600), column-major 4x4. */
 int vkrt_gbuffer_raycast_nrd(vkrt_scene* scene, const float clearColor[4], int lightsCount, const GlobalUniforms* cam, const float view_matrix[16],
                              const vkrt_shard* shard, const vkrt_gbuffer* out, const vkrt_nrd_planes* nrd, void* hip_stream);
+/* vkrt_gbuffer_raycast (view_matrix and nrd both NULL) or vkrt_gbuffer_raycast_nrd (both given) that also writes one vkrt_hit per
+ * pixel into hits, a 16-byte aligned device array of rows x full_width records stacked like the planes: a visibility buffer (picking,
+ * vkrt_hit_surface on pixels) and the input of vkrt_hit_motion.  At a pixel with geometry the record is what vkrt_intersect writes for
+ * the primary hit: t of the G-buffer's own ray (origin = the camera, tmin 0.001, tmax 10000), u, v, and the ids, `triangle` without
+ * the dissolve stage's flag; at a background pixel it is the miss record with t = 10000.  The planes are, bit for bit, those of the
+ * call without hits.  Refused with VKRT_ERR_INVALID_ARGUMENT besides what those calls refuse: only one of view_matrix and nrd, hits
+ * NULL or misaligned.  Came after ABI version 4 without changing it: detect it by symbol. */
+int vkrt_gbuffer_raycast_hits(vkrt_scene* scene, const float clearColor[4], int lightsCount, const GlobalUniforms* cam, const float view_matrix[16],
+                              const vkrt_shard* shard, const vkrt_gbuffer* out, const vkrt_nrd_planes* nrd, vkrt_hit* hits, void* hip_stream);
 /* vkrt_hybrid_trace that also writes nrd->diffRadianceHitDist where PushConstantRay.useGI ran (reads nrd->viewZ). */
 int vkrt_hybrid_trace_nrd(vkrt_scene* scene, const PushConstantRay* pc, const GlobalUniforms* cam, const vkrt_trace_opts* opts,
                           const vkrt_shard* shard, const vkrt_gbuffer* gbuffer, const vkrt_nrd_planes* nrd, float* accum_rgba32f_device,
@@ -756,6 +791,18 @@ int  vkrt_denoiser_reset(vkrt_denoiser* dn);
  * fmaxf(., 0)) and never reaches the history; an infinite one is the caller's error. */
 int  vkrt_denoise_diffuse(vkrt_denoiser* dn, const vkrt_denoise_settings* settings, const GlobalUniforms* cam, const vkrt_gbuffer* gbuffer,
                           const vkrt_nrd_planes* nrd, float* out_rgba32f, void* hip_stream);
+/* vkrt_denoise_diffuse for moving and deforming geometry: one more W*H rgba32f plane, prev_position_rgba32f (16-byte aligned), says
+ * where each pixel's surface point was at the previous call -- what vkrt_hit_motion writes as `previous` for the records of
+ * vkrt_gbuffer_raycast_hits.  In the temporal stage Xp = prev.xyz takes the place of the pixel's position in two places: the
+ * projection under the previous call's viewProj, and the plane test d = (previous position plane)[tap] - Xp.  The projection under the
+ * current viewProj, the normal test (the current normal against the stored previous one), the tolerance, the bilinear weights and
+ * everything after the taps are those of the plain call; with prev == position at every pixel (w = 1) the two calls agree bit for bit.
+ * A pixel with geometry whose prev.w == 0 takes no history (a surface that did not exist); a non-finite Xp takes none either.  At
+ * pixels without geometry the plane is not read.  The two calls may be mixed freely on one handle.  Known limit: the normal test
+ * admits about 25 degrees of rotation per frame (N . N_prev >= 0.9); there is no previous-normal plane.  Refused as the plain call,
+ * and a NULL or misaligned prev_position_rgba32f.  Came after ABI version 4 without changing it: detect it by symbol. */
+int  vkrt_denoise_diffuse_motion(vkrt_denoiser* dn, const vkrt_denoise_settings* settings, const GlobalUniforms* cam, const vkrt_gbuffer* gbuffer,
+                                 const vkrt_nrd_planes* nrd, const float* prev_position_rgba32f, float* out_rgba32f, void* hip_stream);
 
 /* ---- counters / timing ------------------------------------------------------------ */
 int vkrt_counters_reset(vkrt_scene* scene, void* hip_stream);

@@ -284,6 +284,8 @@ VKRT_SYMBOLS = [
     "vkrt_intersect_multi",
     "vkrt_closest_point",
     "vkrt_hit_surface",
+    "vkrt_scene_motion_mark",
+    "vkrt_hit_motion",
     "vkrt_scene_set_material_alpha",
     "vkrt_scene_get_material_alpha",
     "vkrt_shard_rows",
@@ -293,11 +295,13 @@ VKRT_SYMBOLS = [
     "vkrt_hybrid_trace",
     "vkrt_gbuffer_raycast_nrd",
     "vkrt_hybrid_trace_nrd",
+    "vkrt_gbuffer_raycast_hits",
     "vkrt_post",
     "vkrt_denoiser_create",
     "vkrt_denoiser_destroy",
     "vkrt_denoiser_reset",
     "vkrt_denoise_diffuse",
+    "vkrt_denoise_diffuse_motion",
     "vkrt_counters_reset",
     "vkrt_counters_read",
     "vkrt_last_trace_ms",
@@ -365,6 +369,11 @@ def declare_vkrt(lib):
     # (hits, out: device pointers)
     lib.vkrt_hit_surface.argtypes = [C.c_void_p, C.c_void_p, c_u, c_u, C.c_void_p, C.c_void_p]
     lib.vkrt_hit_surface.restype = C.c_int
+    # motion (scene, stream) / (scene, hits, n, current, previous, stream: device pointers, either output may be NULL)
+    lib.vkrt_scene_motion_mark.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vkrt_scene_motion_mark.restype = C.c_int
+    lib.vkrt_hit_motion.argtypes = [C.c_void_p, C.c_void_p, c_u, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vkrt_hit_motion.restype = C.c_int
     lib.vkrt_scene_set_material_alpha.argtypes = [C.c_void_p, c_u, c_u, P(MaterialAlpha), C.c_void_p]
     lib.vkrt_scene_set_material_alpha.restype = C.c_int
     lib.vkrt_scene_get_material_alpha.argtypes = [C.c_void_p, c_u, c_u, P(MaterialAlpha)]
@@ -394,6 +403,10 @@ def declare_vkrt(lib):
     lib.vkrt_hybrid_trace_nrd.argtypes = [C.c_void_p, P(PushConstantRay), P(GlobalUniforms), P(TraceOpts), P(Shard), P(Gbuffer), P(NrdPlanes), C.c_void_p,
                                           C.c_void_p]
     lib.vkrt_hybrid_trace_nrd.restype = C.c_int
+    # (view matrix and NRD planes: both NULL or both given; hits: device pointer)
+    lib.vkrt_gbuffer_raycast_hits.argtypes = [C.c_void_p, P(c_f * 4), C.c_int, P(GlobalUniforms), P(c_f * 16), P(Shard), P(Gbuffer), P(NrdPlanes), C.c_void_p,
+                                              C.c_void_p]
+    lib.vkrt_gbuffer_raycast_hits.restype = C.c_int
     lib.vkrt_post.argtypes = [C.c_int, P(PushConstantPost), c_u, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.vkrt_post.restype = C.c_int
     lib.vkrt_denoiser_create.argtypes = [C.c_int, c_u, c_u, P(C.c_void_p)]
@@ -404,6 +417,9 @@ def declare_vkrt(lib):
     lib.vkrt_denoiser_reset.restype = C.c_int
     lib.vkrt_denoise_diffuse.argtypes = [C.c_void_p, P(DenoiseSettings), P(GlobalUniforms), P(Gbuffer), P(NrdPlanes), C.c_void_p, C.c_void_p]
     lib.vkrt_denoise_diffuse.restype = C.c_int
+    lib.vkrt_denoise_diffuse_motion.argtypes = [C.c_void_p, P(DenoiseSettings), P(GlobalUniforms), P(Gbuffer), P(NrdPlanes), C.c_void_p, C.c_void_p,
+                                                C.c_void_p]
+    lib.vkrt_denoise_diffuse_motion.restype = C.c_int
     lib.vkrt_counters_reset.argtypes = [C.c_void_p, C.c_void_p]
     lib.vkrt_counters_reset.restype = C.c_int
     lib.vkrt_counters_read.argtypes = [C.c_void_p, P(Counters)]

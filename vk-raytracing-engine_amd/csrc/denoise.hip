@@ -2,7 +2,8 @@
 // It stands where the reference's commented-out NRD.Denoise call sits (main.cpp:565-602) and consumes the planes that
 // vkrt_gbuffer_raycast_nrd / vkrt_hybrid_trace_nrd write.  Three stages, one thread per pixel in 16x16 tiles:
 //   k_dn_temporal  decode + demodulate the GI radiance, reproject the history with the previous camera, blend colour and moments,
-//                  write the per-pixel guide record (viewZ, dviewZ/dx, dviewZ/dy, oct normal) every later tap reads
+//                  write the per-pixel guide record (viewZ, dviewZ/dx, dviewZ/dy, oct normal) every later tap reads;
+//                  k_dn_motion_temporal is the same stage with the caller's previous-position plane (moving / deforming geometry)
 //   k_dn_variance  variance from the temporal moments (7x7 spatial estimate while the history is short)
 //   k_dn_atrous    one edge-avoiding a-trous iteration (5x5 B3 kernel, step 2^i); iteration 0 feeds the colour history, the last
 //                  one remodulates and writes out.xyz
@@ -114,7 +115,11 @@ __device__ __forceinline__ bool dnValidAt(const DenoiseParams& D, uint32_t q)
 
 }  // namespace
 
-__global__ __launch_bounds__(256) void k_dn_temporal(const DenoiseParams D)
+// The temporal stage.  MOTION (vkrt_denoise_diffuse_motion): the history is looked up where the pixel's surface point was one call ago,
+// Xp = prevPosition[p].xyz -- projected under prevViewProj and held against geomPrev in the plane test -- instead of where it is now;
+// prevPosition[p].w == 0 marks a surface that did not exist then (no history).  Everything else is the one code of both kernels.
+template <bool MOTION>
+__device__ __forceinline__ void dnTemporal(const DenoiseParams& D)
 {
   uint32_t x, y;
   if(!dnPixel(D.W, D.H, x, y))
@@ -154,7 +159,14 @@ __global__ __launch_bounds__(256) void k_dn_temporal(const DenoiseParams D)
   // history: bilinear taps around the reprojected position that pass the plane-distance and normal tests
   float sw = 0.0f, hr = 0.0f, hg = 0.0f, hb = 0.0f, h1 = 0.0f, h2 = 0.0f, maxLen = 0.0f;
   float pxPrev, pyPrev, pxCur, pyCur;
-  if(D.useHistory && dnProject(D.prevViewProj, pos.x, pos.y, pos.z, D.W, D.H, pxPrev, pyPrev) &&
+  float4 Xp = pos;
+  bool existed = true;
+  if(MOTION)
+  {
+    Xp = D.prevPosition[p];
+    existed = !(Xp.w == 0.0f);
+  }
+  if(D.useHistory && existed && dnProject(D.prevViewProj, Xp.x, Xp.y, Xp.z, D.W, D.H, pxPrev, pyPrev) &&
      dnProject(D.curViewProj, pos.x, pos.y, pos.z, D.W, D.H, pxCur, pyCur))
   {
     // q = p + screen-space motion: an unchanged camera lands exactly on the pixel (no rounding blur of the history)
@@ -177,7 +189,7 @@ __global__ __launch_bounds__(256) void k_dn_temporal(const DenoiseParams D)
           const uint32_t gn = __float_as_uint(g.w);
           if(gn == DN_INVALID)
             continue;
-          const float3 d = make_float3(g.x - pos.x, g.y - pos.y, g.z - pos.z);
+          const float3 d = make_float3(g.x - Xp.x, g.y - Xp.y, g.z - Xp.z);
           if(!(fabsf(dnDot(N, d)) <= tol) || !(dnDot(N, dnOctDecode(gn)) >= 0.9f))
             continue;
           const float4 m = D.momPrev[q];
@@ -209,6 +221,9 @@ __global__ __launch_bounds__(256) void k_dn_temporal(const DenoiseParams D)
     D.out[4 * (size_t)p + 2] = ob * f.z;
   }
 }
+
+__global__ __launch_bounds__(256) void k_dn_temporal(const DenoiseParams D) { dnTemporal<false>(D); }
+__global__ __launch_bounds__(256) void k_dn_motion_temporal(const DenoiseParams D) { dnTemporal<true>(D); }
 
 __global__ __launch_bounds__(256) void k_dn_variance(const DenoiseParams D)
 {
@@ -354,7 +369,10 @@ static dim3 dnGrid(uint32_t W, uint32_t H) { return dim3((W + DN_TILE - 1) / DN_
 
 hipError_t vkrt_launch_denoise_temporal(const DenoiseParams& D, bool variance, hipStream_t stream)
 {
-  hipLaunchKernelGGL(k_dn_temporal, dnGrid(D.W, D.H), dim3(DN_TILE, DN_TILE), 0, stream, D);
+  if(D.prevPosition)
+    hipLaunchKernelGGL(k_dn_motion_temporal, dnGrid(D.W, D.H), dim3(DN_TILE, DN_TILE), 0, stream, D);
+  else
+    hipLaunchKernelGGL(k_dn_temporal, dnGrid(D.W, D.H), dim3(DN_TILE, DN_TILE), 0, stream, D);
   if(variance)
     hipLaunchKernelGGL(k_dn_variance, dnGrid(D.W, D.H), dim3(DN_TILE, DN_TILE), 0, stream, D);
   return hipGetLastError();

@@ -15,6 +15,7 @@
 #include "device_math.h"
 #include "device_scene.h"
 #include "kernels.h"
+#include "query_common.h"  // the vkrt_hit / miss record writers
 #include "rgen.h"
 #include "hybrid_gi.h"
 #include "shade.h"
@@ -34,6 +35,7 @@ struct HybridParams
   float4* nrdNormRough;  // eInNormRough rgb10_a2 values (frag_shader.frag:133-136); NULL = no NRD attachments wanted from k_gbuffer
   float viewMatrix[16];  // pcRaster.viewMatrix (column-major), for viewZ
   uint2* giLater;        // k_hybrid: non-NULL = GI runs afterwards on the wavefront streams; (seed, visibility bits) per pixel go here
+  float4* hits;          // k_gbuffer: non-NULL = the primary hit of every pixel as a vkrt_hit too (2 float4 per pixel, vkrt_gbuffer_raycast_hits)
 };
 
 // ---- NRD / REBLUR front-end packing, gltf.glsl:156-273 (same operation order as the oracle) -----------------------------
@@ -109,6 +111,8 @@ __global__ __launch_bounds__(HY_BLOCK) void k_gbuffer(const HybridParams H)
     if(hit.slot >= 0)
     {
       const float4 recq = sc.tris[hit.slot * VKRT_TRI_QUADS + 2];
+      if(H.hits)  // the record vkrt_intersect writes for this ray (the id word without the dissolve stage's flag)
+        query_write_hit(sc, H.hits + 2 * p, hit.t, hit.u, hit.v, hit.slot, __float_as_int(recq.y) & 0x7fffffff);
       const DevInstance in = sc.instances[(uint32_t)__float_as_int(recq.z)];
       const uint4 ts = sc.triShade[hit.slot];
       const uint32_t vi[3] = {ts.x, ts.y, ts.z};
@@ -220,6 +224,8 @@ __global__ __launch_bounds__(HY_BLOCK) void k_gbuffer(const HybridParams H)
         oViewZ = quantizeHalf(vz[2]);
       }
     }
+    else if(H.hits)
+      query_write_miss(H.hits + 2 * p, 10000.0f);
     H.G.color[p] = oColor; H.G.position[p] = oPos; H.G.normal[p] = oNrm; H.G.rough[p] = oRough;
     if(H.nrdNormRough)
     {
@@ -430,12 +436,13 @@ __global__ void k_post(int rtMode, int viewAccumulated, int useGI, unsigned n, c
 }
 
 hipError_t vkrt_launch_gbuffer(const TraceParams& P, const float clearColor[4], int lightsCount, const HybridGi& G, float* nrdNormRough,
-                               const float* viewMatrix, hipStream_t stream)
+                               const float* viewMatrix, float4* hits, hipStream_t stream)
 {
   HybridParams H;
   H.T = P;
   H.G = G;
   H.giLater = nullptr;
+  H.hits = hits;
   H.nrdNormRough = (float4*)nrdNormRough;
   for(int k = 0; k < 16; k++) H.viewMatrix[k] = nrdNormRough ? viewMatrix[k] : 0.0f;
   for(int k = 0; k < 4; k++) H.clearColor[k] = clearColor[k];
@@ -464,6 +471,7 @@ hipError_t vkrt_launch_hybrid(const TraceParams& P, const HybridGi& G, uint2* gi
   H.T = P;
   H.G = G;
   H.giLater = giLater;
+  H.hits = nullptr;
   H.nrdNormRough = nullptr;
   for(int k = 0; k < 16; k++) H.viewMatrix[k] = 0.0f;
   for(int k = 0; k < 4; k++) H.clearColor[k] = 0.0f;

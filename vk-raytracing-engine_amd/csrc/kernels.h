@@ -43,6 +43,15 @@ hipError_t vkrt_launch_material_alpha(DevMaterial* table, uint32_t first, uint32
 // shading inputs at hit records (surface.hip): n vkrt_hit records (2 float4 each) -> n vkrt_surface records (8 float4 each).  material:
 // the four texture taps and the material fields too, else the geometry alone.  Reads no tree.
 hipError_t vkrt_launch_hit_surface(const DevSurfaceScene& sc, const float4* hits, uint32_t n, bool material, float4* out, hipStream_t stream);
+// surface points at hit records, now and at the scene's last vkrt_scene_motion_mark (motion.hip): n vkrt_hit records -> (xyz, 1) per
+// record into cur (from sc.instances / sc.vertexPN) and / or prev (from prevInstances / prevPositions); either may be NULL.  A record
+// that is not a hit of the scene gives (0, 0, 0, 0).  Reads no tree.
+struct DevMotionScene : DevSurfaceScene
+{
+  const DevInstance* prevInstances;  // the snapshot, or sc.instances / sc.positions before any mark
+  const float* prevPositions;        // vec3[]
+};
+hipError_t vkrt_launch_hit_motion(const DevMotionScene& sc, const float4* hits, uint32_t n, float4* cur, float4* prev, hipStream_t stream);
 
 // wavefront mode (wavefront.hip)
 struct WfTiming
@@ -93,8 +102,9 @@ struct HybridGi  // the planes of the hybrid passes: one struct for the three la
 };
 // nrdNormRough != NULL: the NRD attachments are wanted: that plane and G.nrdViewZ are filled too, with viewMatrix = the raster pass's
 // view matrix (column-major)
+// hits != NULL: one vkrt_hit (2 float4) per pixel too, rows stacked like the planes (vkrt_gbuffer_raycast_hits)
 hipError_t vkrt_launch_gbuffer(const TraceParams& P, const float clearColor[4], int lightsCount, const HybridGi& G, float* nrdNormRough,
-                               const float* viewMatrix, hipStream_t stream);
+                               const float* viewMatrix, float4* hits, hipStream_t stream);
 // giLater: non-NULL = the GI part follows on the wavefront streams (vkrt_launch_hybrid_gi): the kernel does shadows + AO only and
 // leaves (seed, visibility) per pixel there instead of writing the accumulation image
 hipError_t vkrt_launch_hybrid(const TraceParams& P, const HybridGi& G, uint2* giLater, hipStream_t stream);
@@ -129,6 +139,8 @@ struct DenoiseParams
   float prevViewProj[16];
   int useHistory;
   int maxHistory;
+  const float4* prevPosition;  // vkrt_denoise_diffuse_motion: where each pixel's surface point was at the previous call (.w == 0: nowhere);
+                               // NULL = the plain call (k_dn_temporal; last member: the fields above keep their kernel-argument offsets)
 };
 struct DenoiseAtrous
 {

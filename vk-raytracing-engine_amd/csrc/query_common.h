@@ -1,4 +1,5 @@
-// query_common.h -- what the query kernels share (query.hip, multihit.hip, closest.hip; nothing else includes it): the rule for a ray
+// query_common.h -- what the query kernels share (query.hip, multihit.hip, closest.hip, motion.hip; hybrid.hip takes the record writers
+// for k_gbuffer's per-pixel hit records, nothing else includes it): the rule for a ray
 // the walks never see, the vkrt_hit and miss record writers, the per-lane BVH2 walk, and on the host side the triangle mode of a ray
 // query, its dispatch and the chunked launch loop.
 // Deliberately NOT here: the wide8 lane loops (traverse_wide8_multi is the twin of w8_iterate on the hot path, cp_walk_wide8 has a group

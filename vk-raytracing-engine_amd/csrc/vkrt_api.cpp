@@ -116,6 +116,12 @@ struct vkrt_scene
   uint32_t alphaMasks = 0;
   // vkrt_hit_surface: 16 B per primitive-mesh (device_scene.h DevSurfaceScene), uploaded at vkrt_scene_create, released with `allocs`
   const uint4* surfacePrimMeshes = nullptr;
+  // vkrt_scene_motion_mark: the instance records (96 B per node) and vertex positions (12 B per vertex) as they were at the last mark, one
+  // allocation made by the first mark and kept until the scene goes; before any mark the previous state is the live arrays
+  vkrt::DevBuf motion;
+  const DevInstance* prevInstances() const { return motion.get() ? motion.get<const DevInstance>() : dev.instances; }
+  const float* prevPositions() const { return motion.get() ? (const float*)(motion.get<const char>() + motionPositionsAt()) : dev.positions; }
+  size_t motionPositionsAt() const { return std::max<size_t>(nodes.size() * sizeof(DevInstance), 16); }
 };
 
 namespace {
@@ -1439,6 +1445,53 @@ int vkrt_hit_surface(vkrt_scene* s, const vkrt_hit* hits, uint32_t n, uint32_t f
   return VKRT_OK;
 }
 
+int vkrt_scene_motion_mark(vkrt_scene* s, void* hip_stream)
+{
+  if(!s)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_scene_motion_mark: scene is NULL");
+  int rc = setDevice(s);
+  if(rc != VKRT_OK)
+    return rc;
+  const size_t instBytes = s->nodes.size() * sizeof(DevInstance), posBytes = s->positions.size() * sizeof(float);
+  if(!s->motion.get())
+  {  // first mark: the one place a mark allocates (and, through hipMalloc, may synchronise)
+    const hipError_t e = s->motion.alloc(s->motionPositionsAt() + std::max<size_t>(posBytes, 16));
+    if(e != hipSuccess)
+      return fail(e == hipErrorOutOfMemory ? VKRT_ERR_OUT_OF_MEMORY : VKRT_ERR_HIP, "vkrt_scene_motion_mark: hipMalloc: %s", hipGetErrorString(e));
+  }
+  // Stream-ordered like the two update calls: the copies read what the updates enqueued before them on hip_stream wrote, and are read
+  // by what comes after (vkrt_hit_motion).  Nothing here depends on the tree, so a build or a refit leaves the snapshot alone.
+  hipStream_t stream = (hipStream_t)hip_stream;
+  if(instBytes)
+    HIP_TRY(hipMemcpyAsync(const_cast<DevInstance*>(s->prevInstances()), s->dev.instances, instBytes, hipMemcpyDeviceToDevice, stream));
+  if(posBytes)
+    HIP_TRY(hipMemcpyAsync(const_cast<float*>(s->prevPositions()), s->dev.positions, posBytes, hipMemcpyDeviceToDevice, stream));
+  return VKRT_OK;
+}
+
+int vkrt_hit_motion(vkrt_scene* s, const vkrt_hit* hits, uint32_t n, float* current, float* previous, void* hip_stream)
+{
+  int rc = checkQueryArrays(s, "vkrt_hit_motion", n, {{hits, 16u, false}, {current, 16u, true}, {previous, 16u, true}},
+                            "(hits, current and previous: 16 bytes)");
+  if(rc != VKRT_OK)
+    return rc;
+  if(!current && !previous)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_hit_motion: current and previous are both NULL");
+  if(n == 0)
+    return VKRT_OK;
+  // (no checkBuilt: like vkrt_hit_surface, nothing read here belongs to the tree)
+  if((rc = setDevice(s)) != VKRT_OK)
+    return rc;
+  DevMotionScene ms;
+  static_cast<DevScene&>(ms) = s->dev;
+  ms.primMeshes = s->surfacePrimMeshes;
+  ms.instanceCount = (uint32_t)s->nodes.size();
+  ms.prevInstances = s->prevInstances();
+  ms.prevPositions = s->prevPositions();
+  HIP_TRY(vkrt_launch_hit_motion(ms, (const float4*)hits, n, (float4*)current, (float4*)previous, (hipStream_t)hip_stream));
+  return VKRT_OK;
+}
+
 int vkrt_intersect_ex(vkrt_scene* s, const vkrt_ray* rays, uint32_t n, const vkrt_query_opts* opts, vkrt_hit* hits, void* hip_stream)
 {
   const int rc = checkQueryOpts(opts, "vkrt_intersect_ex");
@@ -1676,7 +1729,7 @@ int vkrt_pathtrace_frames(vkrt_scene* s, const PushConstantRay* pc, const Global
 
 namespace {
 int gbufferImpl(vkrt_scene* s, const float clearColor[4], int lightsCount, const GlobalUniforms* cam, const float* viewMatrix, const vkrt_shard* shard,
-                const vkrt_gbuffer* out, const vkrt_nrd_planes* nrd, void* hip_stream);
+                const vkrt_gbuffer* out, const vkrt_nrd_planes* nrd, vkrt_hit* hits, void* hip_stream);
 int hybridImpl(vkrt_scene* s, const PushConstantRay* pc, const GlobalUniforms* cam, const vkrt_trace_opts* opts, const vkrt_shard* shard,
                const vkrt_gbuffer* g, const vkrt_nrd_planes* nrd, float* accum, void* hip_stream);
 }  // namespace
@@ -1684,7 +1737,7 @@ int hybridImpl(vkrt_scene* s, const PushConstantRay* pc, const GlobalUniforms* c
 int vkrt_gbuffer_raycast(vkrt_scene* s, const float clearColor[4], int lightsCount, const GlobalUniforms* cam, const vkrt_shard* shard,
                          const vkrt_gbuffer* out, void* hip_stream)
 {
-  return gbufferImpl(s, clearColor, lightsCount, cam, nullptr, shard, out, nullptr, hip_stream);
+  return gbufferImpl(s, clearColor, lightsCount, cam, nullptr, shard, out, nullptr, nullptr, hip_stream);
 }
 
 int vkrt_gbuffer_raycast_nrd(vkrt_scene* s, const float clearColor[4], int lightsCount, const GlobalUniforms* cam, const float viewMatrix[16],
@@ -1694,7 +1747,23 @@ int vkrt_gbuffer_raycast_nrd(vkrt_scene* s, const float clearColor[4], int light
     return VKRT_OK;  // a shard without rows
   if(!nrd || !viewMatrix || !nrd->normalRoughness || !nrd->viewZ || !nrd->diffRadianceHitDist)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "NULL NRD plane / view matrix");
-  return gbufferImpl(s, clearColor, lightsCount, cam, viewMatrix, shard, out, nrd, hip_stream);
+  return gbufferImpl(s, clearColor, lightsCount, cam, viewMatrix, shard, out, nrd, nullptr, hip_stream);
+}
+
+int vkrt_gbuffer_raycast_hits(vkrt_scene* s, const float clearColor[4], int lightsCount, const GlobalUniforms* cam, const float viewMatrix[16],
+                              const vkrt_shard* shard, const vkrt_gbuffer* out, const vkrt_nrd_planes* nrd, vkrt_hit* hits, void* hip_stream)
+{
+  if(s && clearColor && cam && shard && out && hits && (!nrd) == (!viewMatrix) && vkrt_shard_rows(shard) == 0u)
+    return VKRT_OK;  // a shard without rows
+  if((!nrd) != (!viewMatrix))
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_gbuffer_raycast_hits: view_matrix and nrd go together (both NULL or both given)");
+  if(nrd && (!nrd->normalRoughness || !nrd->viewZ || !nrd->diffRadianceHitDist))
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "NULL NRD plane");
+  if(!hits)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_gbuffer_raycast_hits: hits is NULL");
+  if(((uintptr_t)hits & 15u) != 0u)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_gbuffer_raycast_hits: hits is not 16-byte aligned");
+  return gbufferImpl(s, clearColor, lightsCount, cam, viewMatrix, shard, out, nrd, hits, hip_stream);
 }
 
 int vkrt_hybrid_trace(vkrt_scene* s, const PushConstantRay* pc, const GlobalUniforms* cam, const vkrt_trace_opts* opts, const vkrt_shard* shard,
@@ -1715,7 +1784,7 @@ int vkrt_hybrid_trace_nrd(vkrt_scene* s, const PushConstantRay* pc, const Global
 
 namespace {
 int gbufferImpl(vkrt_scene* s, const float clearColor[4], int lightsCount, const GlobalUniforms* cam, const float* viewMatrix, const vkrt_shard* shard,
-                const vkrt_gbuffer* out, const vkrt_nrd_planes* nrd, void* hip_stream)
+                const vkrt_gbuffer* out, const vkrt_nrd_planes* nrd, vkrt_hit* hits, void* hip_stream)
 {
   if(s && clearColor && cam && shard && out && vkrt_shard_rows(shard) == 0u)
     return VKRT_OK;  // a shard without rows: nothing to write, no planes to pass
@@ -1737,7 +1806,7 @@ int gbufferImpl(vkrt_scene* s, const float clearColor[4], int lightsCount, const
   P.sc.gbufferMips = (uint32_t)s->opt[VKRT_OPT_GBUFFER_MIPS];
   const HybridGi G{(float4*)out->color, (float4*)out->position, (float4*)out->normal, (float2*)out->roughMetal, nullptr,
                    nrd ? (float4*)nrd->diffRadianceHitDist : nullptr, nrd ? nrd->viewZ : nullptr};
-  HIP_TRY(vkrt_launch_gbuffer(P, clearColor, lightsCount, G, nrd ? nrd->normalRoughness : nullptr, viewMatrix, (hipStream_t)hip_stream));
+  HIP_TRY(vkrt_launch_gbuffer(P, clearColor, lightsCount, G, nrd ? nrd->normalRoughness : nullptr, viewMatrix, (float4*)hits, (hipStream_t)hip_stream));
   return VKRT_OK;
 }
 
@@ -2249,8 +2318,10 @@ int vkrt_denoiser_reset(vkrt_denoiser* dn)
   return VKRT_OK;
 }
 
-int vkrt_denoise_diffuse(vkrt_denoiser* dn, const vkrt_denoise_settings* settings, const GlobalUniforms* cam, const vkrt_gbuffer* g,
-                         const vkrt_nrd_planes* nrd, float* out, void* hip_stream)
+namespace {
+// vkrt_denoise_diffuse (prevPosition NULL) and vkrt_denoise_diffuse_motion: one call sequence, the temporal kernel differs
+int denoiseImpl(vkrt_denoiser* dn, const vkrt_denoise_settings* settings, const GlobalUniforms* cam, const vkrt_gbuffer* g, const vkrt_nrd_planes* nrd,
+                const float* prevPosition, float* out, void* hip_stream)
 {
   vkrt_denoise_settings st{sizeof(vkrt_denoise_settings), 5, 32};
   if(settings)
@@ -2292,6 +2363,7 @@ int vkrt_denoise_diffuse(vkrt_denoiser* dn, const vkrt_denoise_settings* setting
   memcpy(D.prevViewProj, dn->prevViewProj, sizeof D.prevViewProj);
   D.useHistory = dn->hasHistory ? 1 : 0;
   D.maxHistory = st.max_history;
+  D.prevPosition = (const float4*)prevPosition;
   HIP_TRY(vkrt_launch_denoise_temporal(D, K > 0, stream));
   int in = b;
   for(int i = 0; i < K; i++)
@@ -2311,6 +2383,23 @@ int vkrt_denoise_diffuse(vkrt_denoiser* dn, const vkrt_denoise_settings* setting
   dn->cur ^= 1;
   dn->hasHistory = true;
   return VKRT_OK;
+}
+}  // namespace
+
+int vkrt_denoise_diffuse(vkrt_denoiser* dn, const vkrt_denoise_settings* settings, const GlobalUniforms* cam, const vkrt_gbuffer* g,
+                         const vkrt_nrd_planes* nrd, float* out, void* hip_stream)
+{
+  return denoiseImpl(dn, settings, cam, g, nrd, nullptr, out, hip_stream);
+}
+
+int vkrt_denoise_diffuse_motion(vkrt_denoiser* dn, const vkrt_denoise_settings* settings, const GlobalUniforms* cam, const vkrt_gbuffer* g,
+                                const vkrt_nrd_planes* nrd, const float* prevPosition, float* out, void* hip_stream)
+{
+  if(!prevPosition)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_denoise_diffuse_motion: prev_position_rgba32f is NULL");
+  if(((uintptr_t)prevPosition & 15u) != 0u)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_denoise_diffuse_motion: prev_position_rgba32f is not 16-byte aligned");
+  return denoiseImpl(dn, settings, cam, g, nrd, prevPosition, out, hip_stream);
 }
 
 int vkrt_debug_eval_math(int device, int op, uint32_t n, const float* a, const float* b, float* out)

@@ -142,6 +142,22 @@ void HelloVkrt::refitAccel()
   check(vkrt_accel_refit(m_scene, nullptr), "vkrt_accel_refit");
 }
 
+void HelloVkrt::markMotion()
+{
+  if(!m_scene)
+    throw std::runtime_error("markMotion before loadGltfScene");
+  check(vkrt_scene_motion_mark(m_scene, nullptr), "vkrt_scene_motion_mark");
+  m_motion = true;
+}
+
+void HelloVkrt::freeMotionPlanes()
+{
+  if(m_hitRecords) (void)hipFree(m_hitRecords);
+  if(m_prevPosition) (void)hipFree(m_prevPosition);
+  m_hitRecords = nullptr;
+  m_prevPosition = nullptr;
+}
+
 void HelloVkrt::setShard(uint32_t rank, uint32_t world)
 {
   if(world == 0 || rank >= world)
@@ -163,6 +179,7 @@ void HelloVkrt::createOffscreenRender()
     throw std::runtime_error("createOffscreenRender: hipSetDevice failed");
   if(m_denoiser) vkrt_denoiser_destroy(m_denoiser);
   m_denoiser = nullptr;
+  freeMotionPlanes();  // (of the old size; the next rasterizeGltf after a markMotion allocates them again)
   for(int k = 0; k < 10; k++)
   {
     if(k >= 6 && !m_denoise)
@@ -248,6 +265,19 @@ void HelloVkrt::rasterizeGltf(const float clearColor[4])
   // sharded like the path tracer: every plane holds this rank's strips stacked from row 0 (the ABI's shard semantics)
   const vkrt_shard shard = launchShard();
   const vkrt_gbuffer g{m_offscreenColor, m_positionTexture, m_normalTexture, m_roughnessTexture};
+  if(m_motion)
+  {  // the same pass with a hit record per pixel, then where each pixel's surface point was at the last markMotion
+    const uint32_t n = (uint32_t)((size_t)m_size.width * vkrt_shard_rows(&shard));
+    if(!m_hitRecords && (hipMalloc((void**)&m_hitRecords, std::max<size_t>(n, 1) * sizeof(vkrt_hit)) != hipSuccess ||
+                         hipMalloc((void**)&m_prevPosition, std::max<size_t>(n, 1) * 16) != hipSuccess))
+      throw std::runtime_error("rasterizeGltf: hipMalloc failed");
+    const vkrt_nrd_planes nrd{m_nrdNormRough, m_nrdViewZ, m_nrdRadHitD};
+    const vkrt_mat4 view = CameraManip.getMatrix();
+    check(vkrt_gbuffer_raycast_hits(m_scene, clearColor, m_pcRay.lightsCount, &m_hostUBO, m_denoise ? view.m : nullptr, &shard, &g,
+                                    m_denoise ? &nrd : nullptr, m_hitRecords, nullptr), "vkrt_gbuffer_raycast_hits");
+    check(vkrt_hit_motion(m_scene, m_hitRecords, n, nullptr, m_prevPosition, nullptr), "vkrt_hit_motion");
+    return;
+  }
   if(m_denoise)
   {  // the NRD variant of the raster pass (frag_shader.frag:133-136): pcRaster.viewMatrix = CameraManip.getMatrix() (hello_vulkan.cpp:600)
     const vkrt_nrd_planes nrd{m_nrdNormRough, m_nrdViewZ, m_nrdRadHitD};
@@ -285,6 +315,12 @@ void HelloVkrt::denoise()
     throw std::runtime_error("denoise: hipMemcpyAsync failed");
   const vkrt_gbuffer g{m_offscreenColor, m_positionTexture, m_normalTexture, m_roughnessTexture};
   const vkrt_nrd_planes nrd{m_nrdNormRough, m_nrdViewZ, m_nrdRadHitD};
+  if(m_motion && m_prevPosition)  // (rasterizeGltf filled it for this frame)
+  {
+    check(vkrt_denoise_diffuse_motion(m_denoiser, &m_denoiseSettings, &m_hostUBO, &g, &nrd, m_prevPosition, m_denoisedTexture, nullptr),
+          "vkrt_denoise_diffuse_motion");
+    return;
+  }
   check(vkrt_denoise_diffuse(m_denoiser, &m_denoiseSettings, &m_hostUBO, &g, &nrd, m_denoisedTexture, nullptr), "vkrt_denoise_diffuse");
 }
 
@@ -323,6 +359,8 @@ void HelloVkrt::destroyResources()
   m_scene = nullptr;
   if(m_denoiser) vkrt_denoiser_destroy(m_denoiser);
   m_denoiser = nullptr;
+  freeMotionPlanes();
+  m_motion = false;
   float** planes[10] = {&m_offscreenColor, &m_positionTexture, &m_normalTexture, &m_roughnessTexture, &m_accumulatedTexture, &m_displayImage,
                         &m_nrdNormRough, &m_nrdViewZ, &m_nrdRadHitD, &m_denoisedTexture};
   for(int k = 0; k < 10; k++)

@@ -48,6 +48,11 @@ public:
   void updateVertices(uint32_t first, const std::vector<float>& positions, const std::vector<float>& normals = {},
                       const std::vector<float>& tangents = {}, const std::vector<float>& texcoords0 = {});
   void refitAccel();                                                             // vkrt_accel_refit
+  // vkrt_scene_motion_mark: the transforms and vertices as they are now become the scene's previous state -- call it at the top of an
+  // animated frame, before updateNodeTransforms / updateVertices.  From the first call on the hybrid sequence carries motion: rasterizeGltf
+  // also writes a hit record per pixel and where each pixel's surface point was at the mark (vkrt_gbuffer_raycast_hits, vkrt_hit_motion)
+  // and denoise() reprojects its history with them (vkrt_denoise_diffuse_motion).  Until then the host launches what it always did.
+  void markMotion();
   void createOffscreenRender();                           // :637-665 (colour image only)
   void updateUniformBuffer();                             // :61-102
   void resetFrame();                                      // :1501-1504
@@ -122,6 +127,11 @@ private:
   float* m_nrdRadHitD = nullptr;
   float* m_denoisedTexture = nullptr;
   vkrt_denoiser* m_denoiser = nullptr;
+  // motion (markMotion): a vkrt_hit and the previous world position per pixel, allocated by the first rasterizeGltf after the mark
+  bool m_motion = false;
+  vkrt_hit* m_hitRecords = nullptr;
+  float* m_prevPosition = nullptr;
+  void freeMotionPlanes();
   bool m_blasRequested = false;
   vkrt_shard m_shard{0, 0, 0, 1, 0};  // whole image unless setShard was called
   // updateFrame()'s function-local statics in the reference (:1508-1509)

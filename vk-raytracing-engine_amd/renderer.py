@@ -387,10 +387,14 @@ class Renderer:
         return image
 
     # ---- hybrid mode (reference rtMode == 0) ---------------------------------------------------------
-    def gbuffer_raycast(self, cam, width, height, lights_count=None, clear_color=(1.0, 1.0, 1.0, 1.0), shard=None, stream=None, view_matrix=None):
+    def gbuffer_raycast(self, cam, width, height, lights_count=None, clear_color=(1.0, 1.0, 1.0, 1.0), shard=None, stream=None, view_matrix=None,
+                        hits=False, motion=False):
         """Stand-in for rasterizeGltf: returns dict of torch CUDA planes color/position/normal [rows,W,4], roughMetal [rows,W,2].
         view_matrix (16 floats, column-major pcRaster.viewMatrix): also the NRD front-end planes nrdNormalRoughness [rows,W,4],
-        nrdViewZ [rows,W], nrdRadianceHitDist [rows,W,4] (vkrt_gbuffer_raycast_nrd)."""
+        nrdViewZ [rows,W], nrdRadianceHitDist [rows,W,4] (vkrt_gbuffer_raycast_nrd).
+        hits=True: also "hits" [rows,W,8], one vkrt_hit per pixel (vkrt_gbuffer_raycast_hits; RayHits(g["hits"].view(-1, 8)) names its
+        fields).  motion=True: hits, and "prevPosition" [rows,W,4], where each pixel's surface point was at the last motion_mark()
+        (hit_motion on the same stream): Denoiser.denoise then follows moving and deforming geometry."""
         import torch
 
         shard = shard or whole_image_shard(width, height)
@@ -402,12 +406,22 @@ class Renderer:
         gb = abi.Gbuffer(*(g[k].data_ptr() for k in ("color", "position", "normal", "roughMetal")))
         cc = (C.c_float * 4)(*clear_color)
         n = self.lights_count if lights_count is None else lights_count
+        nrd = vm = None
         if view_matrix is not None:
             g["nrdNormalRoughness"] = torch.zeros((rows, width, 4), dtype=torch.float32, device=dev)
             g["nrdViewZ"] = torch.zeros((rows, width), dtype=torch.float32, device=dev)
             g["nrdRadianceHitDist"] = torch.zeros((rows, width, 4), dtype=torch.float32, device=dev)
             nrd = abi.NrdPlanes(g["nrdNormalRoughness"].data_ptr(), g["nrdViewZ"].data_ptr(), g["nrdRadianceHitDist"].data_ptr())
             vm = (C.c_float * 16)(*[float(v) for v in view_matrix])
+        if hits or motion:
+            g["hits"] = torch.zeros((rows, width, 8), dtype=torch.float32, device=dev)
+            _check(self.lib.vkrt_gbuffer_raycast_hits(self._h, C.byref(cc), n, C.byref(cam), None if vm is None else C.byref(vm), C.byref(shard), C.byref(gb),
+                                                      None if nrd is None else C.byref(nrd), C.c_void_p(g["hits"].data_ptr()),
+                                                      C.c_void_p(stream.cuda_stream)), "vkrt_gbuffer_raycast_hits")
+            if motion:
+                g["prevPosition"] = self.hit_motion(g["hits"].view(-1, 8), current=False, previous=True, stream=stream)[1].view(rows, width, 4)
+            return g
+        if view_matrix is not None:
             _check(self.lib.vkrt_gbuffer_raycast_nrd(self._h, C.byref(cc), n, C.byref(cam), C.byref(vm), C.byref(shard), C.byref(gb), C.byref(nrd),
                                                      C.c_void_p(stream.cuda_stream)), "vkrt_gbuffer_raycast_nrd")
             return g
@@ -661,6 +675,25 @@ class Renderer:
                "vkrt_debug_closest_point_work")
         return int(work[0]), int(work[1])
 
+    def _hits_arg(self, hits, what):
+        """(buffer, n) of a RayHits or a float32 / int32 [N, 8] tensor of vkrt_hit records; refuses what the C ABI cannot take"""
+        import torch
+
+        buf = hits.buffer if isinstance(hits, RayHits) else hits
+        if not isinstance(buf, torch.Tensor):
+            raise VkrtError(f"{what}: hits must be a RayHits or a torch tensor, got {type(hits).__name__}")
+        if not buf.is_cuda or buf.device.index != self.device:
+            raise VkrtError(f"{what}: hits are on {buf.device}, the scene is on cuda:{self.device}")
+        if buf.dtype not in (torch.float32, torch.int32):
+            raise VkrtError(f"{what}: hits are {buf.dtype}, expected torch.float32 or torch.int32")
+        if buf.dim() != 2 or buf.shape[1] != 8:
+            raise VkrtError(f"{what}: hits have shape {tuple(buf.shape)}, expected [N, 8]")
+        if not buf.is_contiguous() or buf.data_ptr() % 16 != 0:
+            raise VkrtError(f"{what}: hits must be contiguous and 16-byte aligned")
+        if buf.shape[0] >= 1 << 32:
+            raise VkrtError(f"{what}: {buf.shape[0]} records, at most 2^32 - 1 per call")
+        return buf, int(buf.shape[0])
+
     def surface(self, hits, material=True, out=None, stream=None):
         """Shading inputs at hit records (vkrt_hit_surface), enqueued on `stream` like intersect(): hits = a RayHits or a float32 /
         int32 [N, 8] tensor of vkrt_hit records on the scene's device; material=False: the geometry alone (no texel is read, the
@@ -668,20 +701,7 @@ class Renderer:
         build() and between update_nodes / update_vertices and refit().  Returns a Surfaces of views of that buffer."""
         import torch
 
-        buf = hits.buffer if isinstance(hits, RayHits) else hits
-        if not isinstance(buf, torch.Tensor):
-            raise VkrtError(f"surface: hits must be a RayHits or a torch tensor, got {type(hits).__name__}")
-        if not buf.is_cuda or buf.device.index != self.device:
-            raise VkrtError(f"surface: hits are on {buf.device}, the scene is on cuda:{self.device}")
-        if buf.dtype not in (torch.float32, torch.int32):
-            raise VkrtError(f"surface: hits are {buf.dtype}, expected torch.float32 or torch.int32")
-        if buf.dim() != 2 or buf.shape[1] != 8:
-            raise VkrtError(f"surface: hits have shape {tuple(buf.shape)}, expected [N, 8]")
-        if not buf.is_contiguous() or buf.data_ptr() % 16 != 0:
-            raise VkrtError("surface: hits must be contiguous and 16-byte aligned")
-        if buf.shape[0] >= 1 << 32:
-            raise VkrtError(f"surface: {buf.shape[0]} records, at most 2^32 - 1 per call")
-        n = int(buf.shape[0])
+        buf, n = self._hits_arg(hits, "surface")
         fields = abi.VKRT_SURFACE_GEOMETRY | (abi.VKRT_SURFACE_MATERIAL if material else 0)
         if stream is None:
             stream = torch.cuda.current_stream(buf.device)
@@ -692,6 +712,36 @@ class Renderer:
         _check(self.lib.vkrt_hit_surface(self._h, C.c_void_p(buf.data_ptr()), n, fields, C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)),
                "vkrt_hit_surface")
         return Surfaces(out)
+
+    # ---- motion (vkrt_scene_motion_mark / vkrt_hit_motion) -----------------------------------------------------------------------
+    def motion_mark(self, stream=None):
+        """vkrt_scene_motion_mark: the node transforms and vertex positions as they are at this point of `stream` (a torch stream;
+        None = the current one) become the scene's previous state -- call it before the frame's update_nodes / update_vertices.  The
+        first call allocates the snapshot; before any call the previous state is the current one."""
+        import torch
+
+        if stream is None:
+            stream = torch.cuda.current_stream(torch.device("cuda", self.device))
+        _check(self.lib.vkrt_scene_motion_mark(self._h, C.c_void_p(stream.cuda_stream)), "vkrt_scene_motion_mark")
+
+    def hit_motion(self, hits, current=True, previous=True, stream=None):
+        """The surface point of hit records now and at the last motion_mark() (vkrt_hit_motion), enqueued on `stream` like
+        intersect(): hits = a RayHits or a float32 / int32 [N, 8] tensor of vkrt_hit records (g["hits"].view(-1, 8) of
+        gbuffer_raycast(hits=True), or a caller's intersect()).  Returns (current, previous): float32 [N, 4] tensors (x, y, z, 1),
+        all zero where the record is not a hit of the scene; None for the one not asked for.  Needs no tree, like surface()."""
+        import torch
+
+        buf, n = self._hits_arg(hits, "hit_motion")
+        if not current and not previous:
+            raise VkrtError("hit_motion: neither current nor previous asked for")
+        if stream is None:
+            stream = torch.cuda.current_stream(buf.device)
+        with torch.cuda.stream(stream):  # (allocated on the stream that writes them)
+            cur = torch.empty((n, 4), dtype=torch.float32, device=buf.device) if current else None
+            prev = torch.empty((n, 4), dtype=torch.float32, device=buf.device) if previous else None
+        _check(self.lib.vkrt_hit_motion(self._h, C.c_void_p(buf.data_ptr()), n, None if cur is None else C.c_void_p(cur.data_ptr()),
+                                        None if prev is None else C.c_void_p(prev.data_ptr()), C.c_void_p(stream.cuda_stream)), "vkrt_hit_motion")
+        return cur, prev
 
     def trace_rays(self, origins, directions, tmin=0.001, tmax=10000.0, any_hit=False):
         o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
@@ -716,7 +766,8 @@ class Denoiser:
         self._h = h
 
     def denoise(self, cam, gbuffer, out=None, iterations=5, max_history=32, stream=None):
-        """gbuffer: the dict Renderer.gbuffer_raycast(view_matrix=...) returns, after hybrid_trace filled its radiance plane.
+        """gbuffer: the dict Renderer.gbuffer_raycast(view_matrix=...) returns, after hybrid_trace filled its radiance plane; with a
+        "prevPosition" plane in it (gbuffer_raycast(motion=True)) the call is vkrt_denoise_diffuse_motion.
         out: torch float32 [H, W, 4] on this device (.xyz written where there is geometry, the rest untouched); a zeroed one
         when None.  Returns out."""
         import torch
@@ -737,6 +788,13 @@ class Denoiser:
         nrd = abi.NrdPlanes(gbuffer["nrdNormalRoughness"].data_ptr() if "nrdNormalRoughness" in gbuffer else None,
                             gbuffer["nrdViewZ"].data_ptr(), gbuffer["nrdRadianceHitDist"].data_ptr())
         st = abi.DenoiseSettings(C.sizeof(abi.DenoiseSettings), int(iterations), int(max_history))
+        if "prevPosition" in gbuffer:  # planes from gbuffer_raycast(motion=True): the history follows moving and deforming geometry
+            t = gbuffer["prevPosition"]
+            if tuple(t.shape) != (H, W, 4) or t.dtype != torch.float32 or not t.is_contiguous():
+                raise VkrtError(f"denoise: plane prevPosition is {tuple(t.shape)}, the denoiser was made for {(H, W, 4)}")
+            _check(self.lib.vkrt_denoise_diffuse_motion(self._h, C.byref(st), C.byref(cam), C.byref(gb), C.byref(nrd), C.c_void_p(t.data_ptr()),
+                                                        C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)), "vkrt_denoise_diffuse_motion")
+            return out
         _check(self.lib.vkrt_denoise_diffuse(self._h, C.byref(st), C.byref(cam), C.byref(gb), C.byref(nrd), C.c_void_p(out.data_ptr()),
                                              C.c_void_p(stream.cuda_stream)), "vkrt_denoise_diffuse")
         return out
