@@ -856,6 +856,13 @@ int vkrt_debug_read_accel(vkrt_scene* scene, void* nodes, uint64_t nodes_bytes, 
  * child slot s (0 for an empty slot).  Other byte counts, a NULL pointer or a BVH2 tree: VKRT_ERR_INVALID_ARGUMENT; no tree:
  * VKRT_ERR_NOT_BUILT (a stale tree is read as it stands: a refit leaves the table valid). */
 int vkrt_debug_read_node_masks(vkrt_scene* scene, void* out, uint64_t bytes);
+/* Which triangle sits in every slot of the installed tree (synchronises the device; a test hook like the other vkrt_debug_* calls, no
+ * kernel of its own): out[k] = the flattened triangle id of slot k -- instances in node order, each instance's triangles in index
+ * order; the id word of the slot's 48-B record without its non-opaque flag -- for the slots of vkrt_debug_read_accel's triangle
+ * records, in that order, either layout, any builder (bytes == vkrt_accel_info.triangle_bytes / 48 * 4).  A triangle with several
+ * references (VKRT_OPT_SPLIT_BUDGET) appears once per slot it owns.  Other byte counts or a NULL pointer:
+ * VKRT_ERR_INVALID_ARGUMENT; no tree, or a stale one: VKRT_ERR_NOT_BUILT. */
+int vkrt_debug_read_triangle_ids(vkrt_scene* scene, uint32_t* out, uint64_t bytes);
 /* The work of vkrt_closest_point on n queries of a HOST array (synchronises the device; a test hook like the other vkrt_debug_* calls):
  * out[0] = nodes visited, out[1] = triangle records tested, summed over the queries, by an instrumented instantiation of the same
  * walk.  opts and the order of errors as vkrt_closest_point; a NULL out: VKRT_ERR_INVALID_ARGUMENT. */

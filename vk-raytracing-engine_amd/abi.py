@@ -309,6 +309,7 @@ VKRT_SYMBOLS = [
     "vkrt_debug_check_accel",
     "vkrt_debug_read_accel",
     "vkrt_debug_read_node_masks",
+    "vkrt_debug_read_triangle_ids",
     "vkrt_debug_closest_point_work",
     "vkrt_debug_trace_rays",
     "vkrt_debug_eval_math",
@@ -380,6 +381,8 @@ def declare_vkrt(lib):
     lib.vkrt_scene_get_material_alpha.restype = C.c_int
     lib.vkrt_debug_read_node_masks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     lib.vkrt_debug_read_node_masks.restype = C.c_int
+    lib.vkrt_debug_read_triangle_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+    lib.vkrt_debug_read_triangle_ids.restype = C.c_int
     lib.vkrt_debug_check_accel.argtypes = [C.c_void_p, P(AccelCheck)]
     lib.vkrt_debug_check_accel.restype = C.c_int
     lib.vkrt_debug_read_accel.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, P(C.c_int32)]

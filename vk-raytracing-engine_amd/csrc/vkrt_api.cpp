@@ -2053,6 +2053,30 @@ int vkrt_debug_read_node_masks(vkrt_scene* s, void* out, uint64_t bytes)
   return VKRT_OK;
 }
 
+int vkrt_debug_read_triangle_ids(vkrt_scene* s, uint32_t* out, uint64_t bytes)
+{
+  if(!s || !out)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "NULL argument");
+  int rc = checkBuilt(s, "vkrt_debug_read_triangle_ids");
+  if(rc == VKRT_OK)
+    rc = setDevice(s);
+  if(rc != VKRT_OK)
+    return rc;
+  const uint64_t slots = s->info.triangle_bytes / 48, want = slots * 4;
+  if(bytes != want)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_debug_read_triangle_ids: a buffer of %llu bytes for %llu slots (%llu bytes)",
+                (unsigned long long)bytes, (unsigned long long)slots, (unsigned long long)want);
+  HIP_TRY(hipDeviceSynchronize());
+  if(slots)
+  {
+    // word 9 of every 48-B record: the flattened triangle id (bit 31: the non-opaque flag of the any-hit stage)
+    std::vector<uint32_t> rec((size_t)slots * 12);
+    HIP_TRY(hipMemcpy(rec.data(), s->dev.tris, (size_t)slots * 48, hipMemcpyDeviceToHost));
+    for(uint64_t k = 0; k < slots; k++) out[k] = rec[(size_t)k * 12 + 9] & 0x7fffffffu;
+  }
+  return VKRT_OK;
+}
+
 int vkrt_debug_check_accel(vkrt_scene* s, vkrt_accel_check* out)
 {
   if(!s || !out)

@@ -308,6 +308,14 @@ class Renderer:
         _check(self.lib.vkrt_debug_read_node_masks(self._h, out.ctypes.data, nb), "vkrt_debug_read_node_masks")
         return out[:nb].reshape(-1, 8)
 
+    def read_triangle_ids(self):
+        """The flattened triangle id of every slot of the installed tree (vkrt_debug_read_triangle_ids): uint32 [slots], in the
+        order of read_accel()["tris"]."""
+        nb = int(self.accel_info()["triangle_bytes"]) // 48 * 4
+        out = np.zeros(max(nb, 4) // 4, np.uint32)
+        _check(self.lib.vkrt_debug_read_triangle_ids(self._h, out.ctypes.data, nb), "vkrt_debug_read_triangle_ids")
+        return out[: nb // 4]
+
     def refit(self, stream=None):
         """vkrt_accel_refit: the built tree follows the current node transforms and vertices (same topology, new boxes), enqueued on
         `stream`."""
