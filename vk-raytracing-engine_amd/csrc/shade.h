@@ -37,12 +37,29 @@ VKRT_DEV const float* ldsTexelLut(const DevScene& sc, float* lds512)
   return lds512;
 }
 
-// the tallies of a thread that is about to shade, with the workgroup's LDS copy of the decode table (same calling rule as ldsTexelLut)
+// ... by a workgroup of exactly BLOCK threads (a divisor of 512): 512 / BLOCK loads at constant offsets per thread, no loop over blockDim.x
+template <unsigned BLOCK>
+VKRT_DEV const float* ldsTexelLutBlock(const DevScene& sc, float* lds512)
+{
+  static_assert(512u % BLOCK == 0u, "the table is 512 entries");
+#pragma unroll
+  for(unsigned k = 0; k < 512u / BLOCK; k++)
+    lds512[threadIdx.x + k * BLOCK] = sc.srgbLut[threadIdx.x + k * BLOCK];
+  __syncthreads();
+  return lds512;
+}
+
+// the tallies of a thread that is about to shade, with the workgroup's LDS copy of the decode table (same calling rule as ldsTexelLut;
+// BLOCK != 0: the workgroup's size, known at compile time)
+template <unsigned BLOCK = 0u>
 VKRT_DEV ShadeStats shadeStatsInit(const DevScene& sc, float* lds512)
 {
   ShadeStats st;
   st.hits = 0; st.diffuse = 0; st.taps = 0;
-  st.lut = ldsTexelLut(sc, lds512);
+  if constexpr(BLOCK != 0u)
+    st.lut = ldsTexelLutBlock<BLOCK>(sc, lds512);
+  else
+    st.lut = ldsTexelLut(sc, lds512);
   return st;
 }
 
@@ -327,51 +344,46 @@ VKRT_DEV void closestHitFront(const DevScene& sc, const RayHit& hit, const uint3
   const float tu = (b0.z * b.x + b1.z * b.y) + b2.z * b.z;
   const float tv = (b0.w * b.x + b1.w * b.y) + b2.w * b.z;
 
-  // The four texture() calls of rchit:83-113 (emissive, normal, base colour, metallic-roughness): footprints first, then
-  // all sixteen texel loads, then the decode, so the loads overlap instead of forming four dependent round trips.
-  // A tap the reference would not issue reads texel 0 and is discarded.
+  // The four texture() calls of rchit:83-113 (emissive, normal, base colour, metallic-roughness): footprint and texel loads of each
+  // tap here, the decode further down, so the loads overlap instead of forming four dependent round trips.  A tap that no lane of
+  // the wave wants (a wave-uniform test: the emissive one in nearly every bounce round, all four on untextured surfaces) is not
+  // formed at all; where some lane wants it, a lane the reference would not issue it for reads texel 0 and discards it.
   const bool emits = prd.depth == 0 || prd.isSpecular;  // rchit:83
   const bool wantE = emits && mat.emissiveTexture > -1, wantN = mat.normalTexture > -1;
   const bool wantB = mat.pbrBaseColorTexture > -1, wantM = mat.metallicRoughnessTexture > -1;
   st.taps += (wantE ? 1u : 0u) + (wantN ? 1u : 0u) + (wantB ? 1u : 0u) + (wantM ? 1u : 0u);
   TexTap tE, tN, tB, tM;
-  // (with a footprint pool the tap's texel number is relative to the texture: the pool's record number is added below)
-#define VKRT_FOOTPRINT(dim, base, want, tap)                                                                                           \
-  texFootprint(sc.texQuads ? 0u : ((base) & 0x7fffffffu), ((dim) & 0x7fffu) + 1u, (((dim) >> 16) & 0x7fffu) + 1u, ((base) >> 31) != 0u, \
-               ((dim) >> 31) != 0u, want, tu, tv, tap)
-  VKRT_FOOTPRINT(dimE, baseE, wantE, tE);
-  VKRT_FOOTPRINT(dimN, baseN, wantN, tN);
-  VKRT_FOOTPRINT(dimB, baseB, wantB, tB);
-  VKRT_FOOTPRINT(dimM, baseM, wantM, tM);
-#undef VKRT_FOOTPRINT
-  uint32_t e00, e10, e01, e11, n00, n10, n01, n11, c00, c10, c01, c11, r00, r10, r01, r11;
-  if(sc.texQuads)
-  {
-    // one 16-byte record per tap: the 2x2 footprint at (x0, y0) with the wrap already applied (DevScene::texQuads); the record
-    // number is the texture's first record + the level-0 texel number of i00 inside the texture
-    const BufView quads = bufView(sc.texQuads);
-#define VKRT_QUAD(dim, base, tap, want, a, b, c, d)                                                                                    \
+  uint32_t e00 = 0u, e10 = 0u, e01 = 0u, e11 = 0u, n00 = 0u, n10 = 0u, n01 = 0u, n11 = 0u;
+  uint32_t c00 = 0u, c10 = 0u, c01 = 0u, c11 = 0u, r00 = 0u, r10 = 0u, r01 = 0u, r11 = 0u;
+  // with a footprint pool (sc.texQuads) one 16-byte record per tap: the 2x2 footprint at (x0, y0) with the wrap already applied; the
+  // record number is the texture's first record + the level-0 texel number of i00 inside the texture.  Without: four texel loads.
+  const bool pool = sc.texQuads != nullptr;
+  const BufView gather = bufView(pool ? (const void*)sc.texQuads : (const void*)sc.texels);
+#define VKRT_TAP(dim, base, want, tap, a, b, c, d)                                                                                     \
+  if(__ballot(want) != 0ull)                                                                                                           \
   {                                                                                                                                    \
-    const uint32_t rec_ = ((want) && ((dim) >> 31) != 0u) ? tap.i00 + ((base) & 0x7fffffffu) : 0u;                                        \
-    const float4 v_ = bufLoad4(quads, 16u * rec_);                                                                                     \
-    a = __float_as_uint(v_.x); b = __float_as_uint(v_.y); c = __float_as_uint(v_.z); d = __float_as_uint(v_.w);                        \
+    const uint32_t w_ = ((dim) & 0x7fffu) + 1u, h_ = (((dim) >> 16) & 0x7fffu) + 1u;                                                   \
+    const bool live_ = (want) && ((dim) >> 31) != 0u;                                                                                  \
+    int x0_, y0_;                                                                                                                      \
+    texFootprintOrigin(w_, h_, ((base) >> 31) != 0u, ((dim) >> 31) != 0u, tu, tv, tap, x0_, y0_);                                      \
+    if(pool)                                                                                                                           \
+    {                                                                                                                                  \
+      const uint32_t rec_ = live_ ? ((uint32_t)y0_ * w_ + (uint32_t)x0_) + ((base) & 0x7fffffffu) : 0u;                                 \
+      const float4 v_ = bufLoad4(gather, 16u * rec_);                                                                                  \
+      a = __float_as_uint(v_.x); b = __float_as_uint(v_.y); c = __float_as_uint(v_.z); d = __float_as_uint(v_.w);                      \
+    }                                                                                                                                  \
+    else                                                                                                                               \
+    {                                                                                                                                  \
+      texFootprintTexels((base) & 0x7fffffffu, w_, h_, live_, x0_, y0_, tap);                                                          \
+      a = bufLoad1(gather, 4u * tap.i00); b = bufLoad1(gather, 4u * tap.i10);                                                          \
+      c = bufLoad1(gather, 4u * tap.i01); d = bufLoad1(gather, 4u * tap.i11);                                                          \
+    }                                                                                                                                  \
   }
-    VKRT_QUAD(dimE, baseE, tE, wantE, e00, e10, e01, e11)
-    VKRT_QUAD(dimN, baseN, tN, wantN, n00, n10, n01, n11)
-    VKRT_QUAD(dimB, baseB, tB, wantB, c00, c10, c01, c11)
-    VKRT_QUAD(dimM, baseM, tM, wantM, r00, r10, r01, r11)
-#undef VKRT_QUAD
-  }
-  else
-  {
-    const BufView tex = bufView(sc.texels);
-#define VKRT_TEXEL(i) bufLoad1(tex, 4u * (i))
-    e00 = VKRT_TEXEL(tE.i00); e10 = VKRT_TEXEL(tE.i10); e01 = VKRT_TEXEL(tE.i01); e11 = VKRT_TEXEL(tE.i11);
-    n00 = VKRT_TEXEL(tN.i00); n10 = VKRT_TEXEL(tN.i10); n01 = VKRT_TEXEL(tN.i01); n11 = VKRT_TEXEL(tN.i11);
-    c00 = VKRT_TEXEL(tB.i00); c10 = VKRT_TEXEL(tB.i10); c01 = VKRT_TEXEL(tB.i01); c11 = VKRT_TEXEL(tB.i11);
-    r00 = VKRT_TEXEL(tM.i00); r10 = VKRT_TEXEL(tM.i10); r01 = VKRT_TEXEL(tM.i01); r11 = VKRT_TEXEL(tM.i11);
-#undef VKRT_TEXEL
-  }
+  VKRT_TAP(dimE, baseE, wantE, tE, e00, e10, e01, e11)
+  VKRT_TAP(dimN, baseN, wantN, tN, n00, n10, n01, n11)
+  VKRT_TAP(dimB, baseB, wantB, tB, c00, c10, c01, c11)
+  VKRT_TAP(dimM, baseM, wantM, tM, r00, r10, r01, r11)
+#undef VKRT_TAP
 
   const f3 pos = mk3(a0.x, a0.y, a0.z) * b.x + mk3(a1.x, a1.y, a1.z) * b.y + mk3(a2.x, a2.y, a2.z) * b.z;
   const f3 worldPos = xformPoint(in, pos);

@@ -39,7 +39,8 @@ struct TexTap
   uint32_t lutBase;             // 0: sRGB decode, 256: UNORM decode (rgb; alpha is always UNORM)
   bool white;                   // index out of range: 1x1 white dummy (hello_vulkan.cpp:468-472)
 };
-VKRT_DEV void texFootprint(uint32_t offset, uint32_t width, uint32_t height, bool srgb, bool valid, bool want, float u, float v, TexTap& t)
+// first half: the weights, lutBase / white, and the wrapped texel (x0, y0) of the footprint's corner
+VKRT_DEV void texFootprintOrigin(uint32_t width, uint32_t height, bool srgb, bool valid, float u, float v, TexTap& t, int& x0, int& y0)
 {
   float fx = u * (float)width - 0.5f;
   float fy = v * (float)height - 0.5f;
@@ -47,15 +48,24 @@ VKRT_DEV void texFootprint(uint32_t offset, uint32_t width, uint32_t height, boo
   if(!(fabsf(fy) < 1.0e9f)) fy = 0.0f;
   const float flx = floorf(fx), fly = floorf(fy);
   t.ax = fx - flx; t.ay = fy - fly;
+  x0 = wrapi((int)flx, (int)width); y0 = wrapi((int)fly, (int)height);
+  t.lutBase = srgb ? 0u : 256u;
+  t.white = !valid;
+}
+// second half: the four texel indices of the footprint at (x0, y0), or texel 0 four times for a tap nobody wants
+VKRT_DEV void texFootprintTexels(uint32_t offset, uint32_t width, uint32_t height, bool live, int x0, int y0, TexTap& t)
+{
   const int w = (int)width, h = (int)height;
-  const int x0 = wrapi((int)flx, w), y0 = wrapi((int)fly, h);
   const int x1 = x0 + 1 == w ? 0 : x0 + 1, y1 = y0 + 1 == h ? 0 : y0 + 1;
-  const bool live = want && valid;
   const uint32_t r0 = offset + (uint32_t)y0 * width, r1 = offset + (uint32_t)y1 * width;
   t.i00 = live ? r0 + (uint32_t)x0 : 0u; t.i10 = live ? r0 + (uint32_t)x1 : 0u;
   t.i01 = live ? r1 + (uint32_t)x0 : 0u; t.i11 = live ? r1 + (uint32_t)x1 : 0u;
-  t.lutBase = srgb ? 0u : 256u;
-  t.white = !valid;
+}
+VKRT_DEV void texFootprint(uint32_t offset, uint32_t width, uint32_t height, bool srgb, bool valid, bool want, float u, float v, TexTap& t)
+{
+  int x0, y0;
+  texFootprintOrigin(width, height, srgb, valid, u, v, t, x0, y0);
+  texFootprintTexels(offset, width, height, want && valid, x0, y0, t);
 }
 VKRT_DEV f4 texelDecode(const float* lut, uint32_t p, uint32_t base)
 {

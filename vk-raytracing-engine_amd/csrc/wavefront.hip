@@ -260,6 +260,21 @@ struct ShadeLds
   unsigned wsum[WF_TYPES * (WF_BLOCK / 64 + 1)];
 };
 
+// pixelOfWork (rgen.h) where 64 consecutive work items are one wave, as in the 256-thread workgroups here: the tile is the wave's, so
+// its column and row -- two integer divisions -- are found once on the scalar unit instead of in every lane.  Same x, y, lrow.
+VKRT_DEV bool pixelOfWave(const TraceParams& P, unsigned w, unsigned tileFirst, uint32_t& x, uint32_t& y, uint32_t& lrow)
+{
+  if(w >= P.tileCount * 64u)
+    return false;
+  const unsigned tile = (unsigned)__builtin_amdgcn_readfirstlane((int)(tileFirst + (w >> 6))), inTile = w & 63u;
+  x = (tile % P.tilesX) * 8u + (inTile & 7u);
+  lrow = (tile / P.tilesX) * 8u + (inTile >> 3);
+  if(x >= P.fullW || lrow >= P.localRows)
+    return false;
+  y = globalRow(P, lrow);
+  return y < P.fullH;
+}
+
 // CAMERA (k_wf_shade_camera, a camera round of VKRT_FLAG_CAMERA_ROUNDS): the records are the camera rays of sample `smpl`, one per pixel
 // of the launch, and only their H0 / H1 planes exist: record qi belongs to the pixel with tile-major work index qi, and its state is
 // made from the pixel's sample state as k_wf_traverse_camera made the ray (`count` is not read).
@@ -270,13 +285,13 @@ VKRT_DEV void shadeHitBlock(const TraceParams& P, const WfBuffers& B, const Hybr
   const int type = PAIR ? WF_P : WF_C;
   const unsigned lane = lane_id();
   const unsigned qi = block * WF_BLOCK + threadIdx.x;
-  ShadeStats st = shadeStatsInit(P.sc, lds.lut);
+  ShadeStats st = shadeStatsInit<WF_BLOCK>(P.sc, lds.lut);
   unsigned* wsum = lds.wsum;
   int to = -1;
   LaneState L;
   f3 contrib = mk3(0.0f), nextWeight = mk3(0.0f);
   uint32_t x = 0, y = 0, lrow = 0;
-  if(CAMERA ? pixelOfWork(P, qi, P.tileFirst, x, y, lrow) : qi < count)
+  if(CAMERA ? pixelOfWave(P, qi, P.tileFirst, x, y, lrow) : qi < count)
   {
     if(CAMERA)
     {
@@ -288,7 +303,8 @@ VKRT_DEV void shadeHitBlock(const TraceParams& P, const WfBuffers& B, const Hybr
       }
       else
       {
-        const float4 s = wfLoad(B.sampleState + pixelSlot(P, x, lrow));  // this lane is the pixel's only one in the launch: it may write it again below
+        // (pixelSlot(P, x, lrow) is the pixel's tile-major index in the shard, which is what qi counts from the launch's first tile)
+        const float4 s = wfLoad(B.sampleState + (P.tileFirst * 64u + qi));  // this lane is the pixel's only one in the launch: it may write it again below
         L.prd.seed = __float_as_uint(s.w);
         L.hitValues = mk3(s.x, s.y, s.z);
       }
@@ -337,8 +353,10 @@ VKRT_DEV void shadeHitBlock(const TraceParams& P, const WfBuffers& B, const Hybr
   const unsigned slot = claimSlots(B, par ^ 1, to, lane, wsum);
   if(to == WF_C)
     storeClosest(B, par ^ 1, slot, L);
-  else if(to >= 0)
-    storeShadow(B, par ^ 1, to, slot, L, contrib, nextWeight);
+  else if(to == WF_P)  // (one call per stream: with the type a constant every plane's base is uniform and a store needs the lane's 32-bit offset only)
+    storeShadow(B, par ^ 1, WF_P, slot, L, contrib, nextWeight);
+  else if(to == WF_S)
+    storeShadow(B, par ^ 1, WF_S, slot, L, contrib, nextWeight);
   if(P.flags & VKRT_FLAG_COUNT_WORK)  // launch-uniform: hit / lobe / texture-tap tallies are instrumentation, not needed for the ray rate
   {
     __shared__ unsigned long long red[VKRT_COUNTER_STRIDE * (WF_BLOCK / 64)];
@@ -375,6 +393,15 @@ VKRT_DEV void shadeShadowBlock(const TraceParams& P, const WfBuffers& B, const H
 
 // One launch shades the three result streams of a round: the heavy workgroups (C, then P) are dispatched first, the light
 // shadow-result workgroups fill in behind them.
+// WF_SCALAR_FP32 on the shade kernels: with frames in flight they are bound by VALU issue, where a packed FP32 instruction takes the two
+// slots of the two scalar ones it replaces and the v_mov_b32 that pair its operands in adjacent registers come on top (k_wf_shade: 661
+// moves with packed FP32, 437 without; profiles/shade_isa.json).  The attribute takes the packed opcodes from these kernels' target, so
+// the SLP vectoriser, which the unit keeps for its other kernels, finds nothing to form there.  Same operations, same results.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define WF_SCALAR_FP32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define WF_SCALAR_FP32  // (the host pass only sees the kernels' stubs, and its target has no such feature)
+#endif
 template <bool HYBRID>
 VKRT_DEV void shadeRound(const TraceParams& P, const WfBuffers& B, const HybridGi& G, const int round)
 {
@@ -390,17 +417,17 @@ VKRT_DEV void shadeRound(const TraceParams& P, const WfBuffers& B, const HybridG
   else if((blk -= nP) < nS)
     shadeShadowBlock<HYBRID>(P, B, G, par, cS, blk, lds);
 }
-__global__ __launch_bounds__(WF_BLOCK) void k_wf_shade(const TraceParams P, const WfBuffers B, const int round)
+WF_SCALAR_FP32 __global__ __launch_bounds__(WF_BLOCK) void k_wf_shade(const TraceParams P, const WfBuffers B, const int round)
 {
   const HybridGi none{};
   shadeRound<false>(P, B, none, round);
 }
-__global__ __launch_bounds__(WF_BLOCK) void k_wf_shade_hybrid(const TraceParams P, const WfBuffers B, const HybridGi G, const int round)
+WF_SCALAR_FP32 __global__ __launch_bounds__(WF_BLOCK) void k_wf_shade_hybrid(const TraceParams P, const WfBuffers B, const HybridGi G, const int round)
 {
   shadeRound<true>(P, B, G, round);
 }
 // shade step of a camera round (k_wf_traverse_camera traced it): one thread per pixel of the sub-frame in tile order; reads no stream counts
-__global__ __launch_bounds__(WF_BLOCK) void k_wf_shade_camera(const TraceParams P, const WfBuffers B, const int round, const int smpl)
+WF_SCALAR_FP32 __global__ __launch_bounds__(WF_BLOCK) void k_wf_shade_camera(const TraceParams P, const WfBuffers B, const int round, const int smpl)
 {
   const HybridGi none{};
   __shared__ ShadeLds lds;
