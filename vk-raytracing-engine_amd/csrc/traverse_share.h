@@ -39,6 +39,22 @@ VKRT_DEV unsigned laneRank(unsigned long long mask)
 {
   return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
 }
+// A cursor into a lane's stack column is the LDS address of an entry: 32 bits, in bytes, the lane's column folded in once -- the
+// operand ds_read_b64 / ds_write_b64 take as it is.  (As entry indices the cursors cost a shift-add per access, and the parked end
+// a subtraction before it: four to six instructions of every iteration, profiles/r11_experiments.md #158.)
+typedef unsigned vkrt_u32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) vkrt_u32x2* ShareStk;
+VKRT_DEV uint2 stkLoad(ShareStk p)
+{
+  const vkrt_u32x2 e = *p;
+  return make_uint2(e.x, e.y);
+}
+VKRT_DEV void stkStore(ShareStk p, uint2 e)
+{
+  vkrt_u32x2 w;
+  w.x = e.x; w.y = e.y;
+  *p = w;
+}
 VKRT_DEV ShareRes shareRes(int* lds320)
 {
   ShareRes r;
@@ -52,13 +68,14 @@ template <bool COUNT, bool ANYHIT, int TM = 0>
 VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, float tmin, float tmax, uint2* stk, ShareRes res, RayHit& hit,
                                    TravCount& tc, uint32_t raySeed = 0u)
 {
-  TriRay<(TM & VKRT_TM_WATERTIGHT) != 0> tr;
+  // (the `[isa: ...]` comments name the regions tools/isa_blocks.py --loops-json attributes instructions to: each holds to the next one)
+  TriRay<(TM & VKRT_TM_WATERTIGHT) != 0> tr;  // [isa: prologue_epilogue]
   tr.set(d);
   const float4* __restrict__ nodes = sc.nodes;
   const float4* __restrict__ tris = sc.tris;
   const int stride = 64;
-  const int cap = (int)(sc.stackCap >> 1);
   const int lane = (int)lane_id();
+  const ShareStk stkBase = (ShareStk)stk, stkCap = stkBase + (int)(sc.stackCap >> 1) * stride;  // the lane's column: [stkBase, stkCap)
   const unsigned shareMin = sc.shareMinIdle;
   bool farFirst = ANYHIT && anyhit_far_first(sc, o, d, tmax);  // child order of this lane's ray (traverse.h)
 
@@ -67,24 +84,33 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
   shareSync();  // adopting lanes read res.*[owner] of other lanes
 
   int owner = lane;  // home lane of the ray this lane is working on
+  // where every step of the walk looks first: the ray's key (closest) or slot (any) in res, as an address kept beside `owner`
+  unsigned long long* ownerKey = res.key + lane;
+  int* ownerSlot = res.slot + lane;
   f3 id = mk3(safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
   bool px = !(id.x < 0.0f), py = !(id.y < 0.0f), pz = !(id.z < 0.0f);
   unsigned oct4 = ((px ? 1u : 0u) | (py ? 2u : 0u) | (pz ? 4u : 0u)) * 0x01010101u;  // octinv in every byte (w8_test_children)
   uint2 G = make_uint2(0u, (valid && sc.rootRef != VKRT_TRAV_DONE) ? 0x80000000u : 0u);
   uint2 T = make_uint2(0u, 0u);
-  int sp = 0, sb = 0, nPost = 0;  // node groups live in [sb, sp), parked triangle groups in [cap - nPost, cap)
-  unsigned steps = sc.stepLimit;
+  ShareStk sp = stkBase, sb = stkBase, top = stkCap;  // node groups live in [sb, sp), parked triangle groups in [top, stkCap)
+  // Step bound (termination safety net): one count for the wave, kept by the scalar unit with the loop counter, instead of one per
+  // lane that every adoption had to reset.  Every iteration either finishes a busy lane or takes at least one lane one node test or
+  // one triangle test further (when no lane has node work left the triangle step is taken), and the 64 rays of a wave have at most
+  // nodes + triangles tests each: at most 2 x 64 x (nodes + triangles) + 64 iterations, which 64 x stepLimit =
+  // 64 x (4 x (nodes + triangles) + 64) covers twice.  Looser than the per-lane count, finite; a wave that reaches it faults.
   bool busy = G.y != 0u;
+  const unsigned iterLimit = sc.stepLimit > 0x03ffffffu ? 0xffffffffu : sc.stepLimit * 64u;
   // triangle lending (the triangle step below); launch-uniform.  Not built where the watertight test and the dissolve stage meet: a borrower
   // holds a second ray, seed and bound beside its own, and with both stages that is more than the 96 registers of five waves per SIMD
   const bool lendOn = (TM & (VKRT_TM_WATERTIGHT | VKRT_TM_DISSOLVE)) != (VKRT_TM_WATERTIGHT | VKRT_TM_DISSOLVE) && (sc.shareFlags & VKRT_SHARE_TRI_LEND) != 0u;
 
-  for(unsigned iter = 0;; iter++)
+  for(unsigned iter = 0;; iter++)  // [isa: bookkeeping]
   {
     const unsigned long long busyMask = __ballot(busy);
-    if(busyMask == 0ull)
+    if(busyMask == 0ull || iter >= iterLimit)  // (one exit: a lane that leaves with work in its hands has met the bound)
       break;
     // ---- work sharing (every 4th step): idle lanes adopt the oldest pending node group of busy lanes ---------------------
+    // [isa: sharing_step]
     if((iter & sc.sharePeriodMask) == sc.sharePeriodMask && (unsigned)__popcll(~busyMask) >= shareMin)
     {
       // donors: lanes with a pending group on their stack give the oldest one (largest, farthest subtree); with shareFlags bit 0
@@ -95,10 +121,10 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
       // Sponza-like drapery half of all steps were such triangle-only steps at 16 % lane efficiency (profiles/r04_experiments.md
       // #113, #116).  (A second matching round, so that lanes giving node work can give triangles in the same step, costs more per
       // step than it saves: -2.7 % on the uniform scene, #116b.)
-      const bool giveStack = busy && sp - sb >= 1;
+      const bool giveStack = busy && sp > sb;
       const bool giveChild = (sc.shareFlags & 1u) != 0u && busy && !giveStack && (G.y & 0xff000000u & ((G.y & 0xff000000u) - 1u)) != 0u;
       const bool mayTris = (sc.shareFlags & 16u) != 0u && busy && !giveStack && !giveChild;
-      const bool giveParked = mayTris && nPost > 0;
+      const bool giveParked = mayTris && top < stkCap;
       const bool giveTris = mayTris && !giveParked && (T.y & (T.y - 1u)) != 0u;
       const bool wants = giveStack || giveChild || giveParked || giveTris;
       const unsigned long long donorMask = __ballot(wants), idleMask = ~busyMask;
@@ -113,8 +139,8 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
         {
           if(giveStack)
           {
-            e = stk[sb * stride];
-            sb++;
+            e = stkLoad(sb);
+            sb += stride;
           }
           else if(giveChild)
           {
@@ -126,9 +152,9 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
           }
           else if(giveParked)
           {
-            e = stk[(cap - nPost) * stride];
+            e = stkLoad(top);
             e.x |= 0x80000000u;  // bit 31 of the base marks the entry as a triangle group
-            nPost--;
+            top += stride;
           }
           else
           {
@@ -148,6 +174,7 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
         const float ix = __shfl(id.x, src), iy = __shfl(id.y, src), iz = __shfl(id.z, src);
         const float tm = __shfl(tmax, src);
         const int ow = __shfl(owner, src);
+        const unsigned o4 = (unsigned)__shfl((int)oct4, src);  // (the taker keeps the donor's octant word instead of building it again)
         if(TM & VKRT_TM_DISSOLVE)
         {
           const uint32_t sd = (uint32_t)__shfl((int)raySeed, src);  // the any-hit stage decides per (ray seed, triangle)
@@ -159,7 +186,7 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
           tr.set(d);  // (watertight: the adopted ray's shear constants, recomputed rather than shuffled)
           farFirst = ANYHIT && anyhit_far_first(sc, o, d, tmax);
           px = !(id.x < 0.0f); py = !(id.y < 0.0f); pz = !(id.z < 0.0f);
-          oct4 = ((px ? 1u : 0u) | (py ? 2u : 0u) | (pz ? 4u : 0u)) * 0x01010101u;
+          oct4 = o4;
           if(ex & 0x80000000u)  // a triangle group of the donor's ray: nothing to walk, only to test
           {
             G = make_uint2(0u, 0u);
@@ -170,14 +197,15 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
             G = make_uint2(ex, ey);
             T = make_uint2(0u, 0u);
           }
-          sp = 0; sb = 0; nPost = 0;
+          sp = stkBase; sb = stkBase; top = stkCap;
           owner = ow;
-          steps = sc.stepLimit;
+          ownerKey = res.key + ow; ownerSlot = res.slot + ow;
           busy = true;
         }
       }
     }
     // ---- one step of every busy lane's walk (same step as w8run) -----------------------------------------------------
+    // [isa: bookkeeping]
     shareSync();  // results published in the previous step are visible to every lane of the ray
     if(busy || lendOn)  // (with triangle lending the lanes without work walk along, empty-handed, to borrow)
     {
@@ -186,10 +214,10 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
       bool finished = false;
       bool occluded = false;  // any-hit walks: this lane found an occluder in this step
       if(ANYHIT)
-        finished = busy && __hip_atomic_load(&res.slot[owner], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) >= 0;  // somebody already found an occluder for this ray
+        finished = busy && __hip_atomic_load(ownerSlot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) >= 0;  // somebody already found an occluder for this ray
       else
       {
-        const unsigned long long k = __hip_atomic_load(&res.key[owner], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        const unsigned long long k = __hip_atomic_load(ownerKey, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
         bt = __uint_as_float((unsigned)(k >> 32));
         bg = (int)(unsigned)k;
       }
@@ -203,7 +231,7 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
           float t, u, v;
           int slot, gid;
         };
-        auto testOne = [&](Cand& cd) {
+        auto testOne = [&](Cand& cd) {  // [isa: triangle_test]
           const unsigned i = (unsigned)__ffs((int)T.y) - 1u;
           T.y &= T.y - 1u;
           const unsigned s = T.x + i;
@@ -239,6 +267,7 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
             }
           }
         };
+        // [isa: bookkeeping]
         // publish an improvement: LDS atomic minimum on (t, id), the winner leaves its payload.  Called where the candidate was found,
         // by the lanes that found one: the lanes of a site run it in lockstep, and the sequences of two sites never interleave.
         auto publish = [&](const Cand& cd) {
@@ -246,7 +275,7 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
             return;
           if(ANYHIT)
           {
-            __hip_atomic_store(&res.slot[owner], cd.slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            __hip_atomic_store(ownerSlot, cd.slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
             occluded = true;
           }
           else
@@ -254,9 +283,9 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
             // (t bits, triangle id) is unique per candidate, so "the minimum is mine" identifies exactly one winner among the
             // lanes publishing for this ray in this step; it alone writes the payload.  Keys only decrease.
             const unsigned long long mine = ((unsigned long long)__float_as_uint(cd.t) << 32) | (unsigned)cd.gid;
-            __hip_atomic_fetch_min(&res.key[owner], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            __hip_atomic_fetch_min(ownerKey, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
             shareSync();  // every lane's minimum has been applied before anyone checks who won
-            if(__hip_atomic_load(&res.key[owner], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) == mine)
+            if(__hip_atomic_load(ownerKey, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) == mine)
             {
               res.slot[owner] = cd.slot; res.u[owner] = cd.u; res.v[owner] = cd.v;
             }
@@ -279,19 +308,21 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
           G.y &= ~(1u << bitIdx);
           if(G.y & 0xff000000u)
           {
-            if(__builtin_expect(sp + nPost >= cap && nPost > VKRT_W8_POSTPONE_ROOM, 0))
+            bool full = sp >= top;  // (one comparison on the way every push takes; the rare block makes its own)
+            if(__builtin_expect(full && top < stkCap - VKRT_W8_POSTPONE_ROOM * stride, 0))
             {
               // a triangle group parked beyond its reserved room sits where this node group has to go: test it out now
               const uint2 keep = T;
-              T = stk[(cap - nPost) * stride];
-              nPost--;
+              T = stkLoad(top);
+              top += stride;
               flushT();
               T = keep;
+              full = sp >= top;
             }
-            if(sp + nPost < cap)
+            if(!full)
             {
-              stk[sp * stride] = G;
-              sp++;
+              stkStore(sp, G);
+              sp += stride;
             }
             else
               VKRT_TRAV_FAULT(sc);
@@ -303,10 +334,10 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
           {
             if(T.y != 0u)
             {
-              if(__builtin_expect(nPost < VKRT_W8_MAX_POSTPONED && sp + nPost < cap, 1))
+              if(__builtin_expect(top > stkCap - VKRT_W8_MAX_POSTPONED * stride && sp < top, 1))
               {
-                nPost++;
-                stk[(cap - nPost) * stride] = T;
+                top -= stride;
+                stkStore(top, T);
               }
               else
               {
@@ -320,21 +351,22 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
         }
         if((G.y & 0xff000000u) == 0u && sp > sb)
         {
-          sp--;
-          G = stk[sp * stride];
+          sp -= stride;
+          G = stkLoad(sp);
         }
-        if(T.y == 0u && nPost > 0)
+        if(T.y == 0u && top < stkCap)
         {
-          T = stk[(cap - nPost) * stride];
-          nPost--;
+          T = stkLoad(top);
+          top += stride;
         }
         // triangle step: with triThreshold > 1 the wave tests triangles only when that many of 64 walking lanes hold a pending group
         // (the share of the lanes still busy, so that the thin tail of a wave is not left waiting for a count it cannot reach), or
         // none of them has node work left.  1 = every iteration (experiment #57); default 32: with eight parked groups per lane the
         // triangle step runs at 45 % instead of 29 % lane efficiency for 1.5 % more node visits (profiles/r04_experiments.md #118)
+        const unsigned long long hasTMask = __ballot(T.y != 0u);  // one vote for the triangle step and for the lending below
         bool triStep = true;
         if(sc.triThreshold > 1u)
-          triStep = (unsigned)__popcll(__ballot(T.y != 0u)) * 64u >= sc.triThreshold * (unsigned)__popcll(busyMask) ||
+          triStep = (unsigned)__popcll(hasTMask) * 64u >= sc.triThreshold * (unsigned)__popcll(busyMask) ||
                     __ballot((G.y & 0xff000000u) != 0u) == 0ull;
         // triangle lending (VKRT_OPT_WF_TRI_LEND): in a triangle step a walking lane that holds no pending triangle sits the test out while
         // its neighbour, which came out of one node test with several, tests them one per step.  Here a lane with two or more pending
@@ -345,13 +377,14 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
         // any lane working on the ray does; nothing of its own walk changes.  Lanes without work walk along empty-handed so that they can
         // borrow too: two of three free lanes of a triangle step are such lanes.  The result is the minimum over (t, id) / "exists" whoever
         // tests.  Bench frame: 42.7 M -> 30.3 M triangle wave-steps, lane efficiency 0.40 -> 0.57 (profiles/r09_experiments.md #148-#153).
-        bool lentStep = false;
+        bool lentStep = false;  // [isa: lending]
         if(lendOn && triStep)  // (launch-uniform; triStep is the same in every lane that is here)
         {
           const bool tests = T.y != 0u && !occluded;
           const unsigned rest1 = T.y & (T.y - 1u);
           const bool multi = rest1 != 0u && !occluded, isFree = T.y == 0u && !occluded;
-          const unsigned long long lendMask = __ballot(multi), freeMask = __ballot(isFree);
+          // (a closest-hit walk has no `occluded`: its free lanes are the lanes here that hold no triangle)
+          const unsigned long long lendMask = __ballot(multi), freeMask = ANYHIT ? __ballot(isFree) : (__ballot(true) & ~hasTMask);
           const unsigned n = min((unsigned)__popcll(lendMask), (unsigned)__popcll(freeMask));
           if(n != 0u)
           {
@@ -391,7 +424,7 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
                 s = bs;
                 tr.set(rd);  // (watertight: the borrowed ray's shear constants, recomputed rather than shuffled or held beside the lane's own)
               }
-              const float4* __restrict__ tp = tris + (size_t)s * VKRT_TRI_QUADS;
+              const float4* __restrict__ tp = tris + (size_t)s * VKRT_TRI_QUADS;  // [isa: triangle_test]
               const float4 a = tp[0];
               const float4 b = tp[1];
               const float4 c = tp[2];
@@ -428,12 +461,12 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
                   }
                 }
               }
-              if((TM & VKRT_TM_WATERTIGHT) != 0 && borrows)
+              if((TM & VKRT_TM_WATERTIGHT) != 0 && borrows)  // [isa: lending]
                 tr.set(d);  // back to the lane's own ray
             }
           }
         }
-        if(!lentStep && T.y != 0u && triStep && !occluded)
+        if(!lentStep && T.y != 0u && triStep && !occluded)  // [isa: bookkeeping]
         {
           Cand cd = {false, 0.0f, 0.0f, 0.0f, -1, 0};
           testOne(cd);
@@ -443,24 +476,21 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
         //  test -- did not pay: 4110 -> 4082 / 4078 Mrays/s on the strip scene, profiles/r04_experiments.md #116c)
         if(ANYHIT && occluded)
           finished = true;
-        else if((G.y & 0xff000000u) == 0u && T.y == 0u && nPost == 0)
+        else if((G.y & 0xff000000u) == 0u && T.y == 0u && top == stkCap)
           finished = true;  // (sp == sb here: the refill above would have popped otherwise)
-        else if(--steps == 0u)
-        {
-          VKRT_TRAV_FAULT(sc);
-          finished = true;
-        }
       }
       if(finished)
       {
         if(lendOn && busy)  // (not the lanes that walk along already: they would empty their hands in every iteration)
         {
-          G.y = 0u; T.y = 0u; sp = 0; sb = 0; nPost = 0;  // empty-handed from here on, where the lane walks along to borrow
+          G.y = 0u; T.y = 0u; sp = stkBase; sb = stkBase; top = stkCap;  // empty-handed from here on, where the lane walks along to borrow
         }
-        busy = false;  // (without lending G, T and the stack indices are dead until the lane adopts new work)
+        busy = false;  // (without lending G, T and the stack cursors are dead until the lane adopts new work)
       }
     }
   }
+  if(__builtin_expect(busy, 0))  // [isa: prologue_epilogue]
+    VKRT_TRAV_FAULT(sc);
   shareSync();
   hit.t = __uint_as_float((unsigned)(res.key[lane] >> 32)); hit.u = res.u[lane]; hit.v = res.v[lane]; hit.slot = res.slot[lane];
   if(ANYHIT)
