@@ -8,6 +8,8 @@ import re
 import vkrt_amd
 from vkrt_amd import abi
 
+from test_scene_options import option_env, option_table
+
 
 def _read(*parts):
     return open(os.path.join(vkrt_amd.REPO_ROOT, *parts)).read()
@@ -28,11 +30,11 @@ def test_default_is_off_and_the_env_hook_is_documented():
     start = hdr.index("VKRT_OPT_ALPHA_TEST = 18")
     doc = hdr[start:hdr.index("*/", start)]
     assert "0 (default)" in doc and "env VKRT_ALPHA_TEST" in doc and "VKRT_ERR_UNSUPPORTED" in doc
-    api = _read("vk-raytracing-engine_amd", "csrc", "vkrt_api.cpp")
-    assert '{"VKRT_ALPHA_TEST", VKRT_OPT_ALPHA_TEST}' in api
-    # the last initialiser of the option table is the new option's default
-    table = re.search(r"int opt\[VKRT_OPT_ALPHA_TEST \+ 1\] = \{([^}]*)\}", api)
-    assert table and table.group(1).split(",")[-1].strip() == "0" and len(table.group(1).split(",")) == 19
+    assert option_env(abi.VKRT_OPT_ALPHA_TEST) == "VKRT_ALPHA_TEST"
+    # the last row of the option table is the new option's, and its default is off
+    table = option_table()
+    assert table.shim_option_last() == abi.VKRT_OPT_ALPHA_TEST and table.shim_option_rows() == 19
+    assert table.shim_option_default(abi.VKRT_OPT_ALPHA_TEST) == 0
     assert "`VKRT_OPT_ALPHA_TEST` / `VKRT_ALPHA_TEST` | 0 |" in _read("README.md")
     # the section on alpha-tested materials no longer says that frames never depend on the modes
     section = hdr[hdr.index("alpha-tested materials"):hdr.index("enum vkrt_alpha_mode")]

@@ -7,6 +7,8 @@ import re
 import vkrt_amd
 from vkrt_amd import abi
 
+from test_scene_options import option_env, option_table
+
 
 def _read(*parts):
     return open(os.path.join(vkrt_amd.REPO_ROOT, *parts)).read()
@@ -27,10 +29,8 @@ def test_default_is_the_headers_and_the_env_hook_is_documented():
     doc = hdr[start:hdr.index("*/", start)]
     m = re.search(r"(\d) \(default\)", doc)
     assert m and "env VKRT_WF_CAMERA_ROUNDS" in doc
-    api = _read("vk-raytracing-engine_amd", "csrc", "vkrt_api.cpp")
-    d = re.search(r"#define VKRT_WF_CAMERA_ROUNDS_DEFAULT (\d)", api)
-    assert d and d.group(1) == m.group(1)
-    assert '{"VKRT_WF_CAMERA_ROUNDS", VKRT_OPT_WF_CAMERA_ROUNDS}' in api
+    assert option_table().shim_option_default(abi.VKRT_OPT_WF_CAMERA_ROUNDS) == int(m.group(1))
+    assert option_env(abi.VKRT_OPT_WF_CAMERA_ROUNDS) == "VKRT_WF_CAMERA_ROUNDS"
     assert "`VKRT_OPT_WF_CAMERA_ROUNDS` / `VKRT_WF_CAMERA_ROUNDS` | %s |" % m.group(1) in _read("README.md")
 
 

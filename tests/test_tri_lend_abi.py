@@ -1,11 +1,13 @@
 """CPU-side checks of VKRT_OPT_WF_TRI_LEND (triangle steps of the sharing traversal wave lend pending triangles to free lanes,
-csrc/traverse_share.h): the option's number and default in the header, the Python constants, the library's sources and the README
+csrc/traverse_share.h): the option's number and default in the header, the Python constants, the library's option table and the README
 agree, and the option costs no LDS of its own."""
 import os
 import re
 
 import vkrt_amd
 from vkrt_amd import abi
+
+from test_scene_options import option_env, option_table
 
 
 def _read(*parts):
@@ -28,18 +30,17 @@ def test_default_is_the_headers_and_the_env_hook_is_documented():
     doc = hdr[start:hdr.index("*/", start)]
     m = re.search(r"(\d) \(default\)", doc)
     assert m and "env VKRT_WF_TRI_LEND" in doc
-    api = _read("vk-raytracing-engine_amd", "csrc", "vkrt_api.cpp")
-    d = re.search(r"#define VKRT_WF_TRI_LEND_DEFAULT (\d)", api)
-    assert d and d.group(1) == m.group(1)
-    assert '{"VKRT_WF_TRI_LEND", VKRT_OPT_WF_TRI_LEND}' in api
+    table = option_table()
+    assert table.shim_option_default(abi.VKRT_OPT_WF_TRI_LEND) == int(m.group(1))
+    assert option_env(abi.VKRT_OPT_WF_TRI_LEND) == "VKRT_WF_TRI_LEND"
     assert "`VKRT_OPT_WF_TRI_LEND` / `VKRT_WF_TRI_LEND` | %s |" % m.group(1) in _read("README.md")
 
 
 def test_option_eight_keeps_its_default_and_mask():
     """the switch travels in a bit of DevScene::shareFlags above the five that VKRT_OPT_WF_SHARE_FLAGS owns"""
-    api = _read("vk-raytracing-engine_amd", "csrc", "vkrt_api.cpp")
-    assert re.search(r"#define VKRT_WF_SHARE_FLAGS_DEFAULT 25\b", api)
-    assert "case VKRT_OPT_WF_SHARE_FLAGS: return v & 31;" in api
+    table = option_table()
+    assert table.shim_option_default(abi.VKRT_OPT_WF_SHARE_FLAGS) == 25
+    assert [table.shim_clamp_option(abi.VKRT_OPT_WF_SHARE_FLAGS, v) for v in (-1, 31, 32, 57, 255)] == [31, 31, 0, 25, 31]  # v & 31
     dev = _read("vk-raytracing-engine_amd", "csrc", "device_scene.h")
     m = re.search(r"#define VKRT_SHARE_TRI_LEND (0x[0-9a-fA-F]+)u", dev)
     assert m and int(m.group(1), 16) & 31 == 0 and bin(int(m.group(1), 16)).count("1") == 1

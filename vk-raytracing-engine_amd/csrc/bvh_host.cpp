@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 
 namespace vkrt {
 
@@ -652,6 +653,190 @@ void collapse_wide8(const BuiltBvh& b2, const std::vector<FlatTri>& tris, BuiltW
   cx.emit(0, kids, 0);
   out.nodeCount = (uint32_t)(out.nodes.size() / VKRT_WNODE_DWORDS);
   out.sahCost = (float)(cx.sahSum / cx.rootArea);
+}
+
+// ---- vkrt_debug_check_accel on host arrays ------------------------------------------------------------------------------------------
+void check_tree(uint32_t layout, int32_t rootRef, const void* nodeWords, uint32_t N, const float* tris, uint32_t T, uint32_t triangleCount,
+                bool watertight, vkrt_accel_check& out)
+{
+  constexpr int32_t kTravDone = (int32_t)0x80000000;  // device_scene.h VKRT_TRAV_DONE
+  memset(&out, 0, sizeof out);
+  out.layout = layout;
+  std::vector<uint32_t> seen(T, 0u);
+  std::vector<uint8_t> reached(N, 0);
+  struct Bound { float lo[3], hi[3]; };
+  std::vector<Bound> chain;  // boxes of the slots on the path from the root
+  // slots per triangle id: a triangle with one slot must lie inside every box above that slot (its vertices do: convexity); the slots
+  // of a pre-split triangle (VKRT_OPT_SPLIT_BUDGET) are checked together at the end: `reach[slot]` = intersection of the chain
+  auto gidOf = [&](uint32_t slot) { uint32_t g; memcpy(&g, &tris[(size_t)slot * 12 + 9], 4); return g & 0x7fffffffu; };
+  auto decode = [&](uint32_t slot) { return unpack_triangle(&tris[(size_t)slot * 12], watertight); };
+  const uint32_t gidCount = triangleCount;
+  std::vector<uint32_t> slotsOfGid(gidCount, 0u);
+  for(uint32_t k = 0; k < T; k++)
+  {
+    const uint32_t g = gidOf(k);
+    if(g < gidCount) slotsOfGid[g]++; else out.bad_references++;
+  }
+  std::vector<Bound> reach(T);
+  for(Bound& b : reach)
+    for(int k = 0; k < 3; k++) { b.lo[k] = -INFINITY; b.hi[k] = INFINITY; }
+  auto checkTriangle = [&](uint32_t slot) {
+    out.triangles_referenced++;
+    if(slot >= T) { out.bad_references++; return; }
+    if(seen[slot]++) { out.triangles_repeated++; return; }
+    const uint32_t g = gidOf(slot);
+    const bool single = g < gidCount && slotsOfGid[g] == 1u;
+    for(const Bound& b : chain)
+      for(int k = 0; k < 3; k++)
+      {
+        reach[slot].lo[k] = std::max(reach[slot].lo[k], b.lo[k]);
+        reach[slot].hi[k] = std::min(reach[slot].hi[k], b.hi[k]);
+      }
+    if(!single)
+      return;
+    const FlatTri ft = decode(slot);
+    for(const float* p : {ft.v0, ft.p1, ft.p2})
+      for(const Bound& b : chain)
+        for(int k = 0; k < 3; k++)
+          if(!(p[k] >= b.lo[k] && p[k] <= b.hi[k])) { out.box_violations++; break; }
+  };
+  if(layout == 1u)
+  {
+    const uint32_t* nodes = (const uint32_t*)nodeWords;
+    struct Item { uint32_t node, depth; size_t chainLen; Bound b; bool hasBound; };
+    std::vector<Item> stack;
+    if(rootRef != kTravDone && N)
+      stack.push_back(Item{0u, 1u, 0, Bound{}, false});
+    while(!stack.empty())
+    {
+      const Item it = stack.back();
+      stack.pop_back();
+      chain.resize(it.chainLen);
+      if(it.hasBound) chain.push_back(it.b);
+      if(it.node >= N || reached[it.node]++) { out.bad_references++; continue; }
+      out.nodes_reached++;
+      out.max_depth = std::max(out.max_depth, it.depth);
+      const uint32_t* n = &nodes[(size_t)it.node * 20];
+      float org[3];
+      memcpy(org, n, 12);
+      const uint32_t ew = n[3], imask = ew >> 24, childBase = n[4], triBase = n[5];
+      double cell[3];
+      for(int k = 0; k < 3; k++) cell[k] = std::ldexp(1.0, (int)((ew >> (8 * k)) & 255u) - 127);
+      for(int slot = 0; slot < 8; slot++)
+      {
+        const uint32_t meta = (n[6 + (slot >> 2)] >> (8 * (slot & 3))) & 255u;
+        if(meta == 0u)
+        {
+          if(imask & (1u << slot)) out.bad_references++;
+          continue;
+        }
+        Bound b;
+        for(int k = 0; k < 3; k++)
+        {
+          const uint32_t ql = (n[8 + 2 * k + (slot >> 2)] >> (8 * (slot & 3))) & 255u;
+          const uint32_t qh = (n[14 + 2 * k + (slot >> 2)] >> (8 * (slot & 3))) & 255u;
+          b.lo[k] = (float)((double)org[k] + ql * cell[k]);  // (exact in double; the kernel pads its own float arithmetic)
+          b.hi[k] = (float)((double)org[k] + qh * cell[k]);
+          if((double)b.lo[k] > (double)org[k] + ql * cell[k]) b.lo[k] = std::nextafter(b.lo[k], -INFINITY);
+          if((double)b.hi[k] < (double)org[k] + qh * cell[k]) b.hi[k] = std::nextafter(b.hi[k], INFINITY);
+        }
+        const bool internal = (imask >> slot) & 1u;
+        if(internal)
+        {
+          if(meta != (0x20u | (24u + (uint32_t)slot))) out.bad_references++;
+          const uint32_t rank = (uint32_t)__builtin_popcount(imask & ((1u << slot) - 1u));
+          stack.push_back(Item{childBase + rank, it.depth + 1u, chain.size(), b, true});
+        }
+        else
+        {
+          const uint32_t unary = meta >> 5, off = meta & 31u;
+          const uint32_t cnt = (uint32_t)__builtin_popcount(unary);
+          if(unary != (1u << cnt) - 1u || cnt == 0u || off + cnt > 24u) out.bad_references++;
+          chain.push_back(b);
+          for(uint32_t t = 0; t < cnt; t++) checkTriangle(triBase + off + t);
+          chain.pop_back();
+        }
+      }
+    }
+  }
+  else
+  {
+    const float* nodes = (const float*)nodeWords;
+    struct Item { int32_t ref; uint32_t depth; size_t chainLen; Bound b; bool hasBound; };
+    std::vector<Item> stack;
+    if(rootRef != kTravDone)
+      stack.push_back(Item{rootRef, 1u, 0, Bound{}, false});
+    while(!stack.empty())
+    {
+      const Item it = stack.back();
+      stack.pop_back();
+      chain.resize(it.chainLen);
+      if(it.hasBound) chain.push_back(it.b);
+      if(it.ref < 0)
+      {  // leaf: ~(first slot << 3 | count - 1)
+        const uint32_t code = (uint32_t)~it.ref, first = code >> 3, cnt = (code & 7u) + 1u;
+        out.max_depth = std::max(out.max_depth, it.depth - 1u);
+        for(uint32_t t = 0; t < cnt; t++) checkTriangle(first + t);
+        continue;
+      }
+      if((uint32_t)it.ref >= N || reached[(uint32_t)it.ref]++) { out.bad_references++; continue; }
+      out.nodes_reached++;
+      out.max_depth = std::max(out.max_depth, it.depth);
+      const float* n = &nodes[(size_t)it.ref * 16];
+      for(int c = 0; c < 2; c++)
+      {
+        Bound b;
+        for(int k = 0; k < 3; k++) { b.lo[k] = n[6 * c + k]; b.hi[k] = n[6 * c + 3 + k]; }
+        int32_t ref;
+        memcpy(&ref, &n[12 + c], 4);
+        stack.push_back(Item{ref, it.depth + 1u, chain.size(), b, true});
+      }
+    }
+  }
+  for(uint32_t t = 0; t < T; t++)
+    if(!seen[t]) out.triangles_missing++;
+  // pre-split triangles: every lattice point of the triangle must be reachable through at least one of its slots
+  {
+    std::vector<uint32_t> first(gidCount + 1, 0u), fill(gidCount, 0u), bySlot(T);
+    for(uint32_t g = 0; g < gidCount; g++) first[g + 1] = first[g] + slotsOfGid[g];
+    for(uint32_t k = 0; k < T; k++)
+    {
+      const uint32_t g = gidOf(k);
+      if(g < gidCount) bySlot[first[g] + fill[g]++] = k;
+    }
+    for(uint32_t g = 0; g < gidCount; g++)
+    {
+      if(slotsOfGid[g] == 0u) { out.triangles_uncovered++; continue; }  // an instanced triangle the tree does not hold at all
+      if(slotsOfGid[g] == 1u) continue;
+      out.triangles_split++;
+      const FlatTri ft = decode(bySlot[first[g]]);
+      const float* v[3] = {ft.v0, ft.p1, ft.p2};
+      bool covered = true;
+      const int n = 8;  // lattice: barycentric (i, j, n - i - j) / n
+      for(int i = 0; i <= n && covered; i++)
+        for(int j = 0; i + j <= n && covered; j++)
+        {
+          double p[3];
+          for(int k = 0; k < 3; k++) p[k] = ((double)v[0][k] * (n - i - j) + (double)v[1][k] * i + (double)v[2][k] * j) / n;
+          bool inSome = false;
+          for(uint32_t q = first[g]; q < first[g + 1] && !inSome; q++)
+          {
+            if(!seen[bySlot[q]]) continue;
+            const Bound& b = reach[bySlot[q]];
+            bool in = true;
+            // (the lattice point is rounded from double; a piece's box is padded by 8 ulp of the coordinates: allow as much)
+            for(int k = 0; k < 3; k++)
+            {
+              const double tol = 1e-6 * std::max(1.0, std::fabs(p[k]));
+              in = in && p[k] >= (double)b.lo[k] - tol && p[k] <= (double)b.hi[k] + tol;
+            }
+            inSome = in;
+          }
+          covered = inSome;
+        }
+      if(!covered) out.triangles_uncovered++;
+    }
+  }
 }
 
 }  // namespace vkrt

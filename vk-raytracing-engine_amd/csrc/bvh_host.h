@@ -1,4 +1,4 @@
-// bvh_host.h -- host-side geometry flattening and BVH2 construction (see bvh_host.cpp).
+// bvh_host.h -- host-side geometry flattening, BVH construction and the tree check of vkrt_debug_check_accel (see bvh_host.cpp).
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -72,5 +72,10 @@ void build_wide8_host(const std::vector<FlatTri>& tris, BuiltWide8& out, bool wa
 // SAH-optimal collapse of an existing binary tree whose leaves hold <= 3 triangles each (ideally 1).
 // triCount0Box: bounds of the first triangle, used only when the binary root is a leaf.
 void collapse_wide8(const BuiltBvh& b2, const std::vector<FlatTri>& tris, BuiltWide8& out, bool watertight = false);
+
+// What vkrt_debug_check_accel reports (include/vkrt.h), from host copies of a tree: layout 0 = BVH2 (16 floats per node), 1 = wide8
+// (20 dwords per node); `tris` holds slotCount 48-byte records, whose ids lie below triangleCount.
+void check_tree(uint32_t layout, int32_t rootRef, const void* nodeWords, uint32_t nodeCount, const float* tris, uint32_t slotCount,
+                uint32_t triangleCount, bool watertight, vkrt_accel_check& out);
 
 }  // namespace vkrt

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/vkrt.h"
 #include "device_scene.h"
@@ -49,7 +50,41 @@ private:
   std::unique_ptr<void, Free> p_;
 };
 
-// Scratch of one build: typed allocations of at least 16 bytes, all freed when the arena goes.
+// One event / one stream, destroyed by the destructor or when another owner is moved over it.
+class DevEvent
+{
+public:
+  hipError_t create(unsigned flags = hipEventDefault)
+  {
+    hipEvent_t e = nullptr;
+    const hipError_t rc = hipEventCreateWithFlags(&e, flags);
+    p_.reset(rc == hipSuccess ? e : nullptr);
+    return rc;
+  }
+  hipEvent_t get() const { return p_.get(); }
+
+private:
+  struct Destroy { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
+  std::unique_ptr<std::remove_pointer_t<hipEvent_t>, Destroy> p_;
+};
+class DevStream
+{
+public:
+  hipError_t create(unsigned flags)
+  {
+    hipStream_t q = nullptr;
+    const hipError_t rc = hipStreamCreateWithFlags(&q, flags);
+    p_.reset(rc == hipSuccess ? q : nullptr);
+    return rc;
+  }
+  hipStream_t get() const { return p_.get(); }
+
+private:
+  struct Destroy { void operator()(hipStream_t q) const { (void)hipStreamDestroy(q); } };
+  std::unique_ptr<std::remove_pointer_t<hipStream_t>, Destroy> p_;
+};
+
+// Typed allocations of at least 16 bytes, all freed when the arena goes: the scratch of one build, the tables of one scene.
 struct DevArena
 {
   std::vector<DevBuf> bufs;

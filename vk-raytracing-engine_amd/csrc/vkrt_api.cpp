@@ -22,16 +22,10 @@
 #include "dev_buffer.h"
 #include "device_scene.h"
 #include "kernels.h"
+#include "scene_options.h"
+#include "scene_pack.h"
 #include "wide_node.h"
 
-#define VKRT_TRI_THRESHOLD_DEFAULT 32
-#define VKRT_WF_SHARE_DEFAULT 16
-#define VKRT_WF_SHARE_FLAGS_DEFAULT 25
-#define VKRT_WF_FRAMES_IN_FLIGHT_DEFAULT 3
-#define VKRT_SPLIT_BUDGET_DEFAULT -1  // automatic (round 5): vkrt_accel_build decides per scene
-#define VKRT_WF_SAMPLE_SYNC_DEFAULT 1  // sample-synchronous schedule of the wavefront path tracer (wavefront.hip)
-#define VKRT_WF_CAMERA_ROUNDS_DEFAULT 1  // ... whose camera rays are traced from the pixel grid, without path records (wavefront.hip)
-#define VKRT_WF_TRI_LEND_DEFAULT 1  // triangle steps of the sharing wave lend pending triangles to free lanes (traverse_share.h)
 #include "lbvh.h"
 #include "refit.h"
 #include "vertex_update.h"
@@ -73,29 +67,30 @@ struct vkrt_scene
   uint32_t lightCount = 0, materialCount = 0;
   std::vector<float> materialAlpha;  // pbrBaseColorFactor.a per material (the any-hit stage's dissolve), host copy for the host builder
   // device allocations
-  std::vector<void*> allocs;
+  vkrt::DevArena tables;  // what vkrt_scene_create uploads, and the counters
   DevScene dev{};
   vkrt::TreeBuffers accel;  // the built tree (dev.nodes / tris / triShade point into it)
   bool built = false;
   vkrt_accel_info info{};
   unsigned int* workCounter = nullptr;
   DevCounters* counters = nullptr;
-  hipEvent_t evStart = nullptr, evStop = nullptr;
+  vkrt::DevEvent evStart, evStop;
   bool timed = false;
-  // wavefront mode working set
-  void* wfMem = nullptr;
+  // wavefront mode working set; WfAsync and WfTiming are the raw views the launchers take, filled from the owners beside them
+  vkrt::DevBuf wfMem;
   WfBuffers wf{};
+  vkrt::DevStream wfStreams[VKRT_WF_MAX_LANES];
+  vkrt::DevEvent wfFork, wfJoin[VKRT_WF_MAX_LANES];
   WfAsync wfAsync{};
+  std::vector<vkrt::DevEvent> wfEventOwners;
   std::vector<hipEvent_t> wfEvents;
   WfTiming wfTiming{};
   bool wfTimed = false;
   int splitResolved = 0;  // the budget the last vkrt_accel_build used (VKRT_INFO_SPLIT_BUDGET): what -1 resolved to
   int wfTimingRounds = 0;  // rounds per frame of the last timed call (vkrt_last_trace_timing: which gaps are shade launches)
-  // execution options (include/vkrt.h vkrt_option); index = option id
-  std::vector<hipEvent_t> wfPool;  // events ordering the lanes of one call (kernels.h WfAsync::pool)
-  int opt[VKRT_OPT_ALPHA_TEST + 1] = {0, 1, 1, 3, 64, VKRT_WF_SHARE_DEFAULT, VKRT_TRI_THRESHOLD_DEFAULT, 0, VKRT_WF_SHARE_FLAGS_DEFAULT, 1, 0, 0, 0,
-                                            VKRT_WF_FRAMES_IN_FLIGHT_DEFAULT, VKRT_SPLIT_BUDGET_DEFAULT, VKRT_WF_SAMPLE_SYNC_DEFAULT, VKRT_WF_CAMERA_ROUNDS_DEFAULT,
-                                      VKRT_WF_TRI_LEND_DEFAULT, 0};
+  std::vector<vkrt::DevEvent> wfPoolOwners;  // events ordering the lanes of one call (kernels.h WfAsync::pool)
+  std::vector<hipEvent_t> wfPool;
+  int opt[vkrt::kOptionLast + 1];  // execution options (include/vkrt.h vkrt_option); index = option id, values from scene_options.h
   bool hasLargeTriangles = false;  // some instanced triangle covers more than 1 % of the largest face of the scene's box (any-hit order heuristic)
   bool wavefront = true;  // execution mode the acceleration structure was built for (opt[VKRT_OPT_MODE] at vkrt_accel_build)
   // moving instances (vkrt_scene_update_nodes / vkrt_accel_refit)
@@ -114,7 +109,7 @@ struct vkrt_scene
   // ray queries walk with the alpha-test stage, and so do the frames with VKRT_OPT_ALPHA_TEST)
   std::vector<vkrt_material_alpha> alpha;
   uint32_t alphaMasks = 0;
-  // vkrt_hit_surface: 16 B per primitive-mesh (device_scene.h DevSurfaceScene), uploaded at vkrt_scene_create, released with `allocs`
+  // vkrt_hit_surface: 16 B per primitive-mesh (device_scene.h DevSurfaceScene), uploaded at vkrt_scene_create, released with `tables`
   const uint4* surfacePrimMeshes = nullptr;
   // vkrt_scene_motion_mark: the instance records (96 B per node) and vertex positions (12 B per vertex) as they were at the last mark, one
   // allocation made by the first mark and kept until the scene goes; before any mark the previous state is the live arrays
@@ -129,151 +124,19 @@ namespace {
 template <typename T>
 int upload(vkrt_scene* s, const T* src, size_t count, const T** dst)
 {
-  void* p = nullptr;
-  const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
-  HIP_TRY(hipMalloc(&p, bytes));
-  s->allocs.push_back(p);
+  T* p = nullptr;
+  HIP_TRY(s->tables.alloc(&p, count));
   if(count)
     HIP_TRY(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
-  *dst = (const T*)p;
+  *dst = p;
   return VKRT_OK;
 }
 
-// node transforms: vkrt_scene_create and vkrt_scene_update_nodes refuse the same ones
-int checkTransform(const vkrt_node& n, uint32_t i)
-{
-  for(int k = 0; k < 16; k++)
-    if(!std::isfinite(n.worldMatrix[k]))
-      return fail(VKRT_ERR_INVALID_ARGUMENT, "node %u: worldMatrix[%d] is not finite", i, k);
-  return VKRT_OK;
-}
-
-int validate(const vkrt_scene_desc* d)
-{
-  if(!d)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "desc is NULL");
-  if(d->struct_size != sizeof(vkrt_scene_desc))
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_scene_desc.struct_size %u != %zu (ABI mismatch)", d->struct_size,
-                sizeof(vkrt_scene_desc));
-  if(d->vertex_count && (!d->positions || !d->normals || !d->tangents || !d->texcoords0))
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "vertex arrays missing");
-  if(d->index_count && !d->indices)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "indices missing");
-  if(d->material_count == 0 || !d->materials)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "at least one material is required (nvh::GltfScene appends a default one)");
-  if(d->light_count == 0 || !d->lights)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "at least one light is required (hello_vulkan.cpp:247 adds 8 fallback lights)");
-  if((d->prim_mesh_count && !d->prim_meshes) || (d->node_count && !d->nodes) || (d->texture_count && !d->textures))
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "array pointer missing");
-  for(uint32_t i = 0; i < d->prim_mesh_count; i++)
-  {
-    const vkrt_prim_mesh& p = d->prim_meshes[i];
-    if((uint64_t)p.firstIndex + p.indexCount > d->index_count || (uint64_t)p.vertexOffset + p.vertexCount > d->vertex_count)
-      return fail(VKRT_ERR_INVALID_ARGUMENT, "primMesh %u: range outside the index/vertex arrays", i);
-    if(p.materialIndex >= (int32_t)d->material_count)
-      return fail(VKRT_ERR_INVALID_ARGUMENT, "primMesh %u: materialIndex %d out of range", i, p.materialIndex);
-    const uint32_t triIdx = (p.indexCount / 3) * 3;
-    for(uint32_t k = 0; k < triIdx; k++)
-      if(d->indices[p.firstIndex + k] >= p.vertexCount)
-        return fail(VKRT_ERR_INVALID_ARGUMENT, "primMesh %u: index %u >= vertexCount %u", i, d->indices[p.firstIndex + k],
-                    p.vertexCount);
-  }
-  for(uint32_t i = 0; i < d->node_count; i++)
-  {
-    if(d->nodes[i].primMesh < 0 || (uint32_t)d->nodes[i].primMesh >= d->prim_mesh_count)
-      return fail(VKRT_ERR_INVALID_ARGUMENT, "node %u: primMesh %d out of range", i, d->nodes[i].primMesh);
-    if(checkTransform(d->nodes[i], i) != VKRT_OK)
-      return VKRT_ERR_INVALID_ARGUMENT;
-  }
-  // the builders compare and quantise boxes: NaN / inf coordinates have no place in an acceleration structure (a Vulkan driver is
-  // free to drop such triangles; here they are refused up front)
-  for(size_t i = 0; i < (size_t)d->vertex_count * 3; i++)
-    if(!std::isfinite(d->positions[i]))
-      return fail(VKRT_ERR_INVALID_ARGUMENT, "positions[%zu] (vertex %zu) is not finite", i, i / 3);
-  for(uint32_t i = 0; i < d->material_count; i++)
-  {
-    const GltfPBRMaterial& m = d->materials[i];
-    const int32_t t[4] = {m.pbrBaseColorTexture, m.metallicRoughnessTexture, m.normalTexture, m.emissiveTexture};
-    for(int k = 0; k < 4; k++)
-      if(t[k] >= (int32_t)d->texture_count && d->texture_count > 0)
-        return fail(VKRT_ERR_INVALID_ARGUMENT, "material %u: texture index %d out of range", i, t[k]);
-  }
-  for(uint32_t i = 0; i < d->texture_count; i++)
-    if(!d->textures[i].rgba8 || d->textures[i].width == 0 || d->textures[i].height == 0)
-      return fail(VKRT_ERR_INVALID_ARGUMENT, "texture %u: empty", i);
-  return VKRT_OK;
-}
-
-// Mip chain of one RGBA8 image as nvvk::cmdGenerateMipmaps builds it (hello_vulkan.cpp:496): level L is blitted from level
-// L - 1 with VK_FILTER_LINEAR to max(1, size / 2).  vkCmdBlitImage semantics: destination texel centre x + 0.5 maps to the
-// unnormalised source coordinate (x + 0.5) * srcSize / dstSize, filtered bilinearly around it with clamp-to-edge; an sRGB
-// image is filtered in linear space and re-encoded.  Even sizes reduce to the 2x2 box average.
-float srgbEncode(float c) { return c <= 0.0031308f ? 12.92f * c : 1.055f * powf(c, 1.0f / 2.4f) - 0.055f; }
-void downsampleLevel(const uint32_t* src, uint32_t sw, uint32_t sh, uint32_t* dst, uint32_t dw, uint32_t dh, bool srgb, const float* lut512)
-{
-  for(uint32_t y = 0; y < dh; y++)
-    for(uint32_t x = 0; x < dw; x++)
-    {
-      const float fu = ((float)x + 0.5f) * ((float)sw / (float)dw) - 0.5f, fv = ((float)y + 0.5f) * ((float)sh / (float)dh) - 0.5f;
-      const float flx = floorf(fu), fly = floorf(fv), ax = fu - flx, ay = fv - fly;
-      auto cl = [](int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); };
-      const int x0 = cl((int)flx, (int)sw), x1 = cl((int)flx + 1, (int)sw), y0 = cl((int)fly, (int)sh), y1 = cl((int)fly + 1, (int)sh);
-      const uint32_t p[4] = {src[(size_t)y0 * sw + x0], src[(size_t)y0 * sw + x1], src[(size_t)y1 * sw + x0], src[(size_t)y1 * sw + x1]};
-      uint32_t out = 0;
-      for(int c = 0; c < 4; c++)
-      {
-        const uint32_t base = (srgb && c < 3) ? 0u : 256u;
-        const float t00 = lut512[base + ((p[0] >> (8 * c)) & 255u)], t10 = lut512[base + ((p[1] >> (8 * c)) & 255u)];
-        const float t01 = lut512[base + ((p[2] >> (8 * c)) & 255u)], t11 = lut512[base + ((p[3] >> (8 * c)) & 255u)];
-        float v = (t00 * (1.0f - ax) + t10 * ax) * (1.0f - ay) + (t01 * (1.0f - ax) + t11 * ax) * ay;
-        if(srgb && c < 3) v = srgbEncode(v);
-        v = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);
-        out |= (uint32_t)(v * 255.0f + 0.5f) << (8 * c);
-      }
-      dst[(size_t)y * dw + x] = out;
-    }
-}
+// a refusal of scene_pack.h's checks, whose reason is in err
+int failWith(int code, const std::string& err) { return fail(code, "%s", err.c_str()); }
 
 // execution mode: wavefront pipeline (default) or the single persistent megakernel
 bool useWavefront(const vkrt_scene* s) { return s->opt[VKRT_OPT_MODE] == 1; }
-
-int clampOption(int option, int v)
-{
-  switch(option)
-  {
-    case VKRT_OPT_MODE: case VKRT_OPT_BVH_LAYOUT: return v ? 1 : 0;
-    case VKRT_OPT_WF_SUBFRAMES: case VKRT_OPT_WF_FRAMES_IN_FLIGHT: return std::max(1, std::min(VKRT_WF_MAX_LANES, v));
-    case VKRT_OPT_SPLIT_BUDGET: return std::max(-1, std::min(100, v));  // -1 = automatic (vkrt_accel_build)
-    case VKRT_OPT_WF_TRAV_BLOCK: return v == 256 ? 256 : v == 128 ? 128 : 64;
-    case VKRT_OPT_WF_SHARE: return std::max(0, std::min(64, v));
-    case VKRT_OPT_TRI_THRESHOLD: return std::max(0, std::min(65, v));
-    case VKRT_OPT_WF_SHARE_PERIOD: return std::max(0, std::min(255, v));
-    case VKRT_OPT_WF_SHARE_FLAGS: return v & 31;
-    case VKRT_OPT_GBUFFER_MIPS: case VKRT_OPT_WATERTIGHT: case VKRT_OPT_SKIP_DEAD_SHADOW_RAYS: case VKRT_OPT_ANYHIT_DISSOLVE: case VKRT_OPT_WF_SAMPLE_SYNC:
-    case VKRT_OPT_WF_CAMERA_ROUNDS: case VKRT_OPT_WF_TRI_LEND: case VKRT_OPT_ALPHA_TEST: return v ? 1 : 0;
-  }
-  return v;
-}
-
-// Initial option values: the process-wide test hooks documented in include/vkrt.h, read once per scene handle.
-void optionsFromEnvironment(vkrt_scene* s)
-{
-  const char* e;
-  if((e = getenv("VKRT_MODE")) && !strcmp(e, "mega")) s->opt[VKRT_OPT_MODE] = 0;
-  if((e = getenv("VKRT_BVH")) && !strcmp(e, "bvh2")) s->opt[VKRT_OPT_BVH_LAYOUT] = 0;
-  const struct { const char* name; int option; } ints[] = {{"VKRT_WF_SUBFRAMES", VKRT_OPT_WF_SUBFRAMES}, {"VKRT_WF_TRAV_BLOCK", VKRT_OPT_WF_TRAV_BLOCK},
-                                                          {"VKRT_WF_SHARE", VKRT_OPT_WF_SHARE}, {"VKRT_TRI_THRESHOLD", VKRT_OPT_TRI_THRESHOLD},
-                                                          {"VKRT_WF_SHARE_PERIOD", VKRT_OPT_WF_SHARE_PERIOD}, {"VKRT_WF_SHARE_FLAGS", VKRT_OPT_WF_SHARE_FLAGS},
-                                                          {"VKRT_GBUFFER_MIPS", VKRT_OPT_GBUFFER_MIPS}, {"VKRT_WATERTIGHT", VKRT_OPT_WATERTIGHT},
-                                                          {"VKRT_SKIP_DEAD_SHADOW_RAYS", VKRT_OPT_SKIP_DEAD_SHADOW_RAYS},
-                                                          {"VKRT_ANYHIT_DISSOLVE", VKRT_OPT_ANYHIT_DISSOLVE}, {"VKRT_WF_FRAMES_IN_FLIGHT", VKRT_OPT_WF_FRAMES_IN_FLIGHT},
-                                                          {"VKRT_SPLIT_BUDGET", VKRT_OPT_SPLIT_BUDGET}, {"VKRT_WF_SAMPLE_SYNC", VKRT_OPT_WF_SAMPLE_SYNC},
-                                                          {"VKRT_WF_CAMERA_ROUNDS", VKRT_OPT_WF_CAMERA_ROUNDS},
-                                                          {"VKRT_WF_TRI_LEND", VKRT_OPT_WF_TRI_LEND}, {"VKRT_ALPHA_TEST", VKRT_OPT_ALPHA_TEST}};
-  for(const auto& k : ints)
-    if((e = getenv(k.name)))
-      s->opt[k.option] = clampOption(k.option, atoi(e));
-}
 
 void freeAccel(vkrt_scene* s)
 {
@@ -283,27 +146,6 @@ void freeAccel(vkrt_scene* s)
   s->refit = vkrt::RefitScratch{};
   s->refitted = false;
   s->stale = false;
-}
-
-constexpr vkrt_material_alpha kDefaultAlpha = {VKRT_ALPHA_OPAQUE, 0.5f};  // glTF's defaults; the reference treats every material as opaque
-constexpr vkrt_instance_visibility kDefaultVisibility = {0xFF, VKRT_INSTANCE_FACING_CULL_DISABLE, 0};  // the reference's TLAS (hello_vulkan.cpp:1040-1041)
-
-// gl_ObjectToWorldEXT / gl_WorldToObjectEXT of one node (rchit:72-76) and its ray-query visibility: the same code at vkrt_scene_create,
-// vkrt_scene_update_nodes and vkrt_scene_set_instance_visibility, so that a moved scene's records are bit for bit those of a scene
-// created with the moved nodes
-void makeInstance(const vkrt_node& node, const vkrt_instance_visibility& vis, DevInstance& in)
-{
-  memset(&in, 0, sizeof in);
-  for(int r = 0; r < 3; r++)
-    for(int c = 0; c < 4; c++)
-      in.o2w[r * 4 + c] = node.worldMatrix[c * 4 + r];
-  vkrt::invert3x3_rows(in.o2w, in.w2o);
-  in.primMesh = node.primMesh;
-  // facing: a mirroring transform turns the world-space winding around (traverse.h query_rejects); decided in double on the matrix
-  const float* m = in.o2w;
-  const double det = (double)m[0] * ((double)m[5] * m[10] - (double)m[6] * m[9]) - (double)m[1] * ((double)m[4] * m[10] - (double)m[6] * m[8]) +
-                     (double)m[2] * ((double)m[4] * m[9] - (double)m[5] * m[8]);
-  in.vis = (uint32_t)vis.mask | ((uint32_t)vis.flags << 8) | (det < 0.0 ? VKRT_VIS_MIRRORED : 0u);
 }
 
 void noteMasks(vkrt_scene* s)
@@ -348,26 +190,43 @@ int ensureWorkingSet(vkrt_scene* s, uint32_t paths, int groups, hipStream_t stre
   // (16384 x 16384 pixels in one shard, ~146 GB of streams) would wrap it silently
   if(paths >= (1u << 28))
     return fail(VKRT_ERR_UNSUPPORTED, "wavefront mode: %u path records in one shard (limit 2^28 - 1: split the launch into shards)", paths);
-  if(!s->wfMem || s->wf.capacity < paths || (int)s->wf.groups < groups)
+  if(!s->wfMem.get() || s->wf.capacity < paths || (int)s->wf.groups < groups)
   {
     HIP_TRY(hipStreamSynchronize(stream));  // an earlier frame may still be using the smaller buffer
-    if(s->wfMem) (void)hipFree(s->wfMem);
-    s->wfMem = nullptr;
     paths = std::max(paths, s->wf.capacity);
     groups = std::max(groups, (int)s->wf.groups);
     s->wf = WfBuffers{};
-    HIP_TRY(hipMalloc(&s->wfMem, vkrt_wf_state_bytes(paths, groups)));
-    vkrt_wf_carve(s->wfMem, paths, groups, &s->wf);
+    HIP_TRY(s->wfMem.alloc(vkrt_wf_state_bytes(paths, groups)));
+    vkrt_wf_carve(s->wfMem.get(), paths, groups, &s->wf);
   }
   if(s->wfAsync.count == 0)
-  {
-    HIP_TRY(hipEventCreateWithFlags(&s->wfAsync.fork, hipEventDisableTiming));
+  {  // (a call that fails half-way keeps what it created; the next one creates the rest)
+    if(!s->wfFork.get())
+      HIP_TRY(s->wfFork.create(hipEventDisableTiming));
     for(int j = 0; j < VKRT_WF_MAX_LANES; j++)
     {
-      HIP_TRY(hipStreamCreateWithFlags(&s->wfAsync.streams[j], hipStreamNonBlocking));
-      HIP_TRY(hipEventCreateWithFlags(&s->wfAsync.join[j], hipEventDisableTiming));
+      if(!s->wfStreams[j].get())
+        HIP_TRY(s->wfStreams[j].create(hipStreamNonBlocking));
+      if(!s->wfJoin[j].get())
+        HIP_TRY(s->wfJoin[j].create(hipEventDisableTiming));
+      s->wfAsync.streams[j] = s->wfStreams[j].get();
+      s->wfAsync.join[j] = s->wfJoin[j].get();
     }
+    s->wfAsync.fork = s->wfFork.get();
     s->wfAsync.count = VKRT_WF_MAX_LANES;
+  }
+  return VKRT_OK;
+}
+
+// at least `want` events with `flags` in an owner list and in the raw array a launcher takes
+int growEvents(std::vector<vkrt::DevEvent>& owners, std::vector<hipEvent_t>& raw, size_t want, unsigned flags)
+{
+  while(raw.size() < want)
+  {
+    vkrt::DevEvent e;
+    HIP_TRY(e.create(flags));
+    raw.push_back(e.get());
+    owners.push_back(std::move(e));
   }
   return VKRT_OK;
 }
@@ -379,13 +238,8 @@ int ensureFrameCall(vkrt_scene* s, uint32_t tiles, uint32_t frames, hipStream_t 
   const int rc = ensureWorkingSet(s, tiles * 64u, wfGroupsWanted(s->opt[VKRT_OPT_WF_FRAMES_IN_FLIGHT], frames), stream);
   if(rc != VKRT_OK)
     return rc;
-  const size_t want = (size_t)wfPoolEvents((int)std::min<uint32_t>(frames, VKRT_FRAMES_PER_BATCH));
-  while(s->wfPool.size() < want)
-  {
-    hipEvent_t e;
-    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    s->wfPool.push_back(e);
-  }
+  if(const int rc = growEvents(s->wfPoolOwners, s->wfPool, (size_t)wfPoolEvents((int)std::min<uint32_t>(frames, VKRT_FRAMES_PER_BATCH)), hipEventDisableTiming); rc != VKRT_OK)
+    return rc;
   s->wfAsync.pool = s->wfPool.data();
   s->wfAsync.poolSize = (int)s->wfPool.size();
   return VKRT_OK;
@@ -632,9 +486,10 @@ int vkrt_scene_create(const vkrt_scene_desc* d, int device, vkrt_scene** out)
   if(!out)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "out is NULL");
   *out = nullptr;
-  int rc = validate(d);
+  std::string err;
+  int rc = vkrt::validate_scene(d, err);
   if(rc != VKRT_OK)
-    return rc;
+    return failWith(rc, err);
   const int ndev = vkrt_device_count();
   if(ndev <= 0)
     return fail(VKRT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
@@ -642,7 +497,7 @@ int vkrt_scene_create(const vkrt_scene_desc* d, int device, vkrt_scene** out)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "device %d out of range [0,%d)", device, ndev);
   vkrt_scene* s = new vkrt_scene();
   s->device = device;
-  optionsFromEnvironment(s);
+  vkrt::initial_options(s->opt);
   auto bail = [&](int code) {
     vkrt_scene_destroy(s);
     return code;
@@ -659,170 +514,37 @@ int vkrt_scene_create(const vkrt_scene_desc* d, int device, vkrt_scene** out)
   s->nodes.assign(d->nodes, d->nodes + d->node_count);
   s->lightCount = d->light_count;
   s->materialCount = d->material_count;
-  s->alpha.assign(d->material_count, kDefaultAlpha);
+  s->alpha.assign(d->material_count, vkrt::kDefaultAlpha);
+  for(uint32_t i = 0; i < d->material_count; i++)
+    s->materialAlpha.push_back(d->materials[i].pbrBaseColorFactor[3]);
+  s->vis.assign(d->node_count, vkrt::kDefaultVisibility);
+  noteMasks(s);
 
+  // VKRT_TEX_QUADS=0 (test hook): no footprint pool
+  const char* quadEnv = getenv("VKRT_TEX_QUADS");
+  vkrt::PackedScene packed;
+  if((rc = vkrt::pack_scene(d, !(quadEnv && atoi(quadEnv) == 0), packed, err)) != VKRT_OK)
+    return bail(failWith(rc, err));
   DevScene& D = s->dev;
+  const float *pn = nullptr, *lut = nullptr;
+  const uint32_t *pm = nullptr, *quads = nullptr;
   if((rc = upload(s, d->positions, 3 * (size_t)d->vertex_count, &D.positions)) != VKRT_OK) return bail(rc);
   if((rc = upload(s, d->indices, (size_t)d->index_count, &D.indices)) != VKRT_OK) return bail(rc);
-  // (normals / uv travel inside vertexPN; the ePrimLookup indirection of hello_vulkan.cpp:363-368 is resolved per triangle
-  // at build time into triShade, so neither is uploaded in its raw form)
-  // interleaved (position, normal, uv, tangent) records for the closest-hit attribute fetch (rchit:41-66)
-  {
-    std::vector<float> pn((size_t)d->vertex_count * 4 * VKRT_VERTEX_QUADS);
-    for(uint32_t v = 0; v < d->vertex_count; v++)
-    {
-      float* o = &pn[(size_t)v * 4 * VKRT_VERTEX_QUADS];
-      o[0] = d->positions[3 * (size_t)v]; o[1] = d->positions[3 * (size_t)v + 1]; o[2] = d->positions[3 * (size_t)v + 2];
-      o[3] = d->normals[3 * (size_t)v]; o[4] = d->normals[3 * (size_t)v + 1]; o[5] = d->normals[3 * (size_t)v + 2];
-      o[6] = d->texcoords0[2 * (size_t)v]; o[7] = d->texcoords0[2 * (size_t)v + 1];
-      for(int k = 0; k < 4; k++) o[8 + k] = d->tangents[4 * (size_t)v + k];
-    }
-    const float* pnDev = nullptr;
-    if((rc = upload(s, pn.data(), pn.size(), &pnDev)) != VKRT_OK) return bail(rc);
-    D.vertexPN = (const float4*)pnDev;
-  }
+  if((rc = upload(s, packed.vertexPN.data(), packed.vertexPN.size(), &pn)) != VKRT_OK) return bail(rc);
   if((rc = upload(s, d->lights, (size_t)d->light_count, &D.lights)) != VKRT_OK) return bail(rc);
-  // the primitive-mesh table of vkrt_hit_surface (rchit:34-40 per record: the tree's triShade has it per slot, a hit record has no slot)
-  {
-    std::vector<uint4> pm(d->prim_mesh_count);
-    for(uint32_t m = 0; m < d->prim_mesh_count; m++)
-      pm[m] = make_uint4(d->prim_meshes[m].firstIndex, d->prim_meshes[m].vertexOffset, d->prim_meshes[m].indexCount / 3u,
-                         (uint32_t)std::max(0, d->prim_meshes[m].materialIndex));
-    if((rc = upload(s, pm.data(), pm.size(), &s->surfacePrimMeshes)) != VKRT_OK) return bail(rc);
-  }
-  // instances: object->world rows + inverse (gl_ObjectToWorldEXT / gl_WorldToObjectEXT, rchit:72-76)
-  s->vis.assign(d->node_count, kDefaultVisibility);
-  noteMasks(s);
-  std::vector<DevInstance> inst(d->node_count);
-  for(uint32_t n = 0; n < d->node_count; n++)
-    makeInstance(d->nodes[n], s->vis[n], inst[n]);
-  if((rc = upload(s, inst.data(), inst.size(), &D.instances)) != VKRT_OK) return bail(rc);
-  // textures: RGBA8 pool + table + sRGB decode table
-  float lut[512];
-  for(int i = 0; i < 256; i++)
-  {
-    const float c = (float)i / 255.0f;
-    lut[i] = (c <= 0.04045f) ? c / 12.92f : powf((c + 0.055f) / 1.055f, 2.4f);
-    lut[256 + i] = c;
-  }
-  std::vector<DevTexture> table(d->texture_count);
-  std::vector<uint32_t> mipTable((size_t)d->texture_count * VKRT_MAX_MIPS, 0u);
-  std::vector<uint32_t> pool;
-  // footprint pool (DevScene::texQuads): 16 bytes per level-0 texel; built when it stays below 2 GiB and VKRT_TEX_QUADS=0 is not set
-  // (test hook: the path tracer then gathers the four texels of a tap one by one, as it did up to round 3; same values either way)
-  std::vector<uint32_t> quadFirst(d->texture_count, 0u);
-  uint64_t quadTotal = 1;  // record 0 = white dummy (hits without a texture read it and discard it)
-  for(uint32_t t = 0; t < d->texture_count; t++)
-  {
-    quadFirst[t] = (uint32_t)std::min<uint64_t>(quadTotal, 0xffffffffull);
-    quadTotal += (uint64_t)d->textures[t].width * d->textures[t].height;
-  }
-  const char* quadEnv = getenv("VKRT_TEX_QUADS");
-  const bool wantQuads = quadTotal * 16ull < (2ull << 30) && !(quadEnv && atoi(quadEnv) == 0);
-  std::vector<uint32_t> quads;
-  if(wantQuads)
-  {
-    quads.assign((size_t)quadTotal * 4, 0xffffffffu);
-    for(uint32_t t = 0; t < d->texture_count; t++)
-    {
-      const vkrt_texture& tx = d->textures[t];
-      const uint32_t* src = (const uint32_t*)tx.rgba8;
-      uint32_t* dst = &quads[(size_t)quadFirst[t] * 4];
-      for(uint32_t y = 0; y < tx.height; y++)
-      {
-        const uint32_t y1 = y + 1 == tx.height ? 0 : y + 1;
-        for(uint32_t x = 0; x < tx.width; x++)
-        {
-          const uint32_t x1 = x + 1 == tx.width ? 0 : x + 1;
-          uint32_t* q = dst + ((size_t)y * tx.width + x) * 4;
-          memcpy(&q[0], &src[(size_t)y * tx.width + x], 4); memcpy(&q[1], &src[(size_t)y * tx.width + x1], 4);
-          memcpy(&q[2], &src[(size_t)y1 * tx.width + x], 4); memcpy(&q[3], &src[(size_t)y1 * tx.width + x1], 4);
-        }
-      }
-    }
-  }
-  for(uint32_t t = 0; t < d->texture_count; t++)
-  {
-    const vkrt_texture& tx = d->textures[t];
-    const size_t n = (size_t)tx.width * tx.height;
-    size_t at = pool.size();
-    pool.resize(at + n);
-    memcpy(&pool[at], tx.rgba8, n * 4);
-    // the mip chain behind level 0 (sampled by the hybrid G-buffer's implicit-LOD texture(); the path tracer reads level 0)
-    uint32_t levels = 1, w = tx.width, h = tx.height;
-    mipTable[(size_t)t * VKRT_MAX_MIPS] = (uint32_t)at;
-    while((w > 1 || h > 1) && levels < VKRT_MAX_MIPS)
-    {
-      const uint32_t dw = std::max(1u, w / 2), dh = std::max(1u, h / 2);
-      const size_t to = pool.size();
-      pool.resize(to + (size_t)dw * dh);
-      downsampleLevel(&pool[at], w, h, &pool[to], dw, dh, tx.is_srgb != 0, lut);
-      mipTable[(size_t)t * VKRT_MAX_MIPS + levels] = (uint32_t)to;
-      at = to; w = dw; h = dh;
-      levels++;
-    }
-    table[t] = DevTexture{mipTable[(size_t)t * VKRT_MAX_MIPS], tx.width, tx.height, (tx.is_srgb ? 1u : 0u) | (levels << 8)};
-  }
-  if(pool.empty())
-    pool.push_back(0xffffffffu);  // shading always issues its texel loads (to texel 0 when a material has no texture)
-  // materials, with the descriptors of their textures folded in (DevMaterial)
-  std::vector<DevMaterial> mats(d->material_count);
-  std::vector<DevShadeMaterial> shadeMats(d->material_count);
-  for(uint32_t i = 0; i < d->material_count; i++)
-  {
-    memset(&mats[i], 0, sizeof(DevMaterial));
-    mats[i].m = d->materials[i];
-    mats[i].alphaMode = kDefaultAlpha.mode;
-    mats[i].alphaCutoff = kDefaultAlpha.cutoff;
-    DevShadeMaterial& sm = shadeMats[i];
-    memset(&sm, 0, sizeof(sm));
-    for(int k = 0; k < 3; k++)
-    {
-      sm.f[k] = d->materials[i].pbrBaseColorFactor[k];
-      sm.f[5 + k] = d->materials[i].emissiveFactor[k];
-    }
-    sm.f[3] = d->materials[i].metallicFactor;
-    sm.f[4] = d->materials[i].roughnessFactor;
-    s->materialAlpha.push_back(d->materials[i].pbrBaseColorFactor[3]);
-    const int idx[4] = {mats[i].m.pbrBaseColorTexture, mats[i].m.metallicRoughnessTexture, mats[i].m.normalTexture, mats[i].m.emissiveTexture};
-    for(int k = 0; k < 4; k++)
-    {
-      DevTexRef& r = mats[i].tex[k];
-      r = DevTexRef{0u, 1u | (1u << 16), 0u, 0u};
-      if(idx[k] >= 0 && (uint32_t)idx[k] < d->texture_count)
-      {
-        const DevTexture& t = table[(size_t)idx[k]];
-        if(t.width == 0u || t.height == 0u || t.width > 32768u || t.height > 32768u)
-          return bail(fail(VKRT_ERR_UNSUPPORTED, "texture %d is %ux%u (supported: 1..32768 per side)", idx[k], t.width, t.height));
-        r = DevTexRef{t.offset, t.width | (t.height << 16), 1u | ((t.srgb & 1u) ? 2u : 0u), wantQuads ? quadFirst[(size_t)idx[k]] : 0u};
-      }
-      // (the reference order of DevShadeMaterial is VKRT_TEXREF_*: BASE, MR, NORMAL, EMISSIVE = the order of idx[])
-      const uint32_t base = wantQuads ? r.quads : r.offset;
-      if(base >> 31)
-        return bail(fail(VKRT_ERR_UNSUPPORTED, "texture pool of 2^31 records and more is not supported"));
-      sm.ref[2 * k] = ((r.wh & 0xffffu) - 1u) | (idx[k] > -1 ? 1u << 15 : 0u) | (((r.wh >> 16) - 1u) << 16) | ((r.flags & 1u) << 31);
-      sm.ref[2 * k + 1] = base | ((r.flags & 2u) << 30);
-    }
-  }
-  if((rc = upload(s, mats.data(), mats.size(), &D.materials)) != VKRT_OK) return bail(rc);
-  if((rc = upload(s, shadeMats.data(), shadeMats.size(), &D.shadeMaterials)) != VKRT_OK) return bail(rc);
-  if((rc = upload(s, table.data(), table.size(), &D.textures)) != VKRT_OK) return bail(rc);
-  if((rc = upload(s, mipTable.data(), mipTable.size(), &D.texMips)) != VKRT_OK) return bail(rc);
-  if((rc = upload(s, pool.data(), pool.size(), &D.texels)) != VKRT_OK) return bail(rc);
-  D.texQuads = nullptr;
-  if(wantQuads)
-  {
-    const uint32_t* qd = nullptr;
-    if((rc = upload(s, quads.data(), quads.size(), &qd)) != VKRT_OK) return bail(rc);
-    D.texQuads = (const uint4*)qd;
-  }
-  // the hit shader addresses its tables with 32-bit byte offsets (shade.h BufView): refuse what does not fit
-  if((uint64_t)pool.size() * 4 >= (4ull << 30) || (uint64_t)d->vertex_count * VKRT_VERTEX_BYTES >= (4ull << 30) || (uint64_t)d->material_count * 128 >= (4ull << 30) ||
-     (uint64_t)d->node_count * 96 >= (4ull << 30))
-    return bail(fail(VKRT_ERR_UNSUPPORTED, "scene tables of 4 GiB and more are not supported (texel pool %zu texels, %u vertices)", pool.size(), d->vertex_count));
-  const float* lutDev = nullptr;
-  if((rc = upload(s, lut, 512, &lutDev)) != VKRT_OK) return bail(rc);
-  D.srgbLut = lutDev;
+  if((rc = upload(s, packed.primMeshes.data(), packed.primMeshes.size(), &pm)) != VKRT_OK) return bail(rc);
+  if((rc = upload(s, packed.instances.data(), packed.instances.size(), &D.instances)) != VKRT_OK) return bail(rc);
+  if((rc = upload(s, packed.materials.data(), packed.materials.size(), &D.materials)) != VKRT_OK) return bail(rc);
+  if((rc = upload(s, packed.shadeMaterials.data(), packed.shadeMaterials.size(), &D.shadeMaterials)) != VKRT_OK) return bail(rc);
+  if((rc = upload(s, packed.textures.data(), packed.textures.size(), &D.textures)) != VKRT_OK) return bail(rc);
+  if((rc = upload(s, packed.texMips.data(), packed.texMips.size(), &D.texMips)) != VKRT_OK) return bail(rc);
+  if((rc = upload(s, packed.texels.data(), packed.texels.size(), &D.texels)) != VKRT_OK) return bail(rc);
+  if(!packed.texQuads.empty() && (rc = upload(s, packed.texQuads.data(), packed.texQuads.size(), &quads)) != VKRT_OK) return bail(rc);
+  if((rc = upload(s, packed.srgbLut, 512, &lut)) != VKRT_OK) return bail(rc);
+  D.vertexPN = (const float4*)pn;
+  s->surfacePrimMeshes = (const uint4*)pm;
+  D.texQuads = (const uint4*)quads;
+  D.srgbLut = lut;
   D.textureCount = d->texture_count;
   D.rootRef = VKRT_TRAV_DONE;
   D.stackCap = 1;
@@ -834,16 +556,11 @@ int vkrt_scene_create(const vkrt_scene_desc* d, int device, vkrt_scene** out)
   D.shareFlags = 0;
   D.gbufferMips = 1;
 
-  void* p = nullptr;
-  if(hipMalloc(&p, 64) != hipSuccess) return bail(fail(VKRT_ERR_OUT_OF_MEMORY, "hipMalloc(work counter)"));
-  s->allocs.push_back(p);
-  s->workCounter = (unsigned int*)p;
-  if(hipMalloc(&p, sizeof(DevCounters)) != hipSuccess) return bail(fail(VKRT_ERR_OUT_OF_MEMORY, "hipMalloc(counters)"));
-  s->allocs.push_back(p);
-  s->counters = (DevCounters*)p;
+  if(s->tables.alloc(&s->workCounter, 16) != hipSuccess) return bail(fail(VKRT_ERR_OUT_OF_MEMORY, "hipMalloc(work counter)"));
+  if(s->tables.alloc(&s->counters, 1) != hipSuccess) return bail(fail(VKRT_ERR_OUT_OF_MEMORY, "hipMalloc(counters)"));
   D.faults = &s->counters->v[0][10];
   if(hipMemset(s->counters, 0, sizeof(DevCounters)) != hipSuccess) return bail(fail(VKRT_ERR_HIP, "hipMemset(counters)"));
-  if(hipEventCreate(&s->evStart) != hipSuccess || hipEventCreate(&s->evStop) != hipSuccess)
+  if(s->evStart.create() != hipSuccess || s->evStop.create() != hipSuccess)
     return bail(fail(VKRT_ERR_HIP, "hipEventCreate"));
   *out = s;
   return VKRT_OK;
@@ -854,23 +571,6 @@ void vkrt_scene_destroy(vkrt_scene* s)
   if(!s)
     return;
   (void)hipSetDevice(s->device);
-  freeAccel(s);
-  for(void* p : s->allocs)
-    (void)hipFree(p);
-  if(s->wfMem) (void)hipFree(s->wfMem);
-  if(s->wfAsync.count)
-  {
-    (void)hipEventDestroy(s->wfAsync.fork);
-    for(int j = 0; j < s->wfAsync.count; j++)
-    {
-      (void)hipStreamDestroy(s->wfAsync.streams[j]);
-      (void)hipEventDestroy(s->wfAsync.join[j]);
-    }
-  }
-  for(hipEvent_t e : s->wfEvents) (void)hipEventDestroy(e);
-  for(hipEvent_t e : s->wfPool) (void)hipEventDestroy(e);
-  if(s->evStart) (void)hipEventDestroy(s->evStart);
-  if(s->evStop) (void)hipEventDestroy(s->evStop);
   delete s;
 }
 
@@ -880,7 +580,7 @@ int vkrt_scene_set_option(vkrt_scene* s, int option, int value)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "scene is NULL");
   if(option < VKRT_OPT_MODE || option > VKRT_OPT_ALPHA_TEST)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "unknown option %d", option);
-  if(clampOption(option, value) != value)
+  if(vkrt::clamp_option(option, value) != value)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "option %d: value %d out of range", option, value);
   s->opt[option] = value;
   if(option == VKRT_OPT_WF_TRI_LEND && s->built && s->dev.layout == 1u)  // a launch-uniform word of the walk, not a property of the tree: no rebuild needed
@@ -984,68 +684,6 @@ int uploadHostTree(vkrt_scene* s, const std::vector<vkrt::FlatTri>& tris, const 
   std::string m;
   const int rc = vkrt::hip_status(e, "uploading the acceleration structure", m);
   return rc == VKRT_OK ? VKRT_OK : fail(rc, "%s", m.c_str());
-}
-
-// World-space bounds of the instanced geometry, conservatively from the corners of every node's local box, and whether the scene has
-// large triangles (the any-hit order heuristic asks whether a ray ends outside the bounds; nothing else reads them)
-void sceneBounds(vkrt_scene* s)
-{
-  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  std::vector<float> meshBox(s->primMeshes.size() * 6);
-  for(size_t m = 0; m < s->primMeshes.size(); m++)
-  {
-    const vkrt_prim_mesh& pm = s->primMeshes[m];
-    float* b = &meshBox[m * 6];
-    for(int k = 0; k < 3; k++) { b[k] = INFINITY; b[3 + k] = -INFINITY; }
-    for(uint32_t v = 0; v < pm.vertexCount; v++)
-      for(int k = 0; k < 3; k++)
-      {
-        const float x = s->positions[3 * (size_t)(pm.vertexOffset + v) + k];
-        b[k] = std::min(b[k], x); b[3 + k] = std::max(b[3 + k], x);
-      }
-  }
-  for(const vkrt_node& n : s->nodes)
-  {
-    const float* b = &meshBox[(size_t)n.primMesh * 6];
-    if(!(b[0] <= b[3]))
-      continue;
-    for(int c = 0; c < 8; c++)
-    {
-      const float p[3] = {(c & 1) ? b[3] : b[0], (c & 2) ? b[4] : b[1], (c & 4) ? b[5] : b[2]};
-      for(int k = 0; k < 3; k++)
-      {
-        const float w = n.worldMatrix[k] * p[0] + n.worldMatrix[4 + k] * p[1] + n.worldMatrix[8 + k] * p[2] + n.worldMatrix[12 + k];
-        lo[k] = std::min(lo[k], w); hi[k] = std::max(hi[k], w);
-      }
-    }
-  }
-  for(int k = 0; k < 3; k++)
-  {
-    const float pad = 1e-3f * std::max(1e-6f, hi[k] - lo[k]);
-    s->dev.sceneLo[k] = lo[k] - pad; s->dev.sceneHi[k] = hi[k] + pad;
-  }
-  // "large" = a triangle of more than 1 % of the largest face of the scene's box (world space, every instance)
-  const double ex = (double)hi[0] - lo[0], ey = (double)hi[1] - lo[1], ez = (double)hi[2] - lo[2];
-  const double face = std::max(ex * ey, std::max(ey * ez, ez * ex));
-  double maxArea = 0.0;
-  for(const vkrt_node& n : s->nodes)
-  {
-    const vkrt_prim_mesh& pm = s->primMeshes[(size_t)n.primMesh];
-    const float* M = n.worldMatrix;
-    for(uint32_t t = 0; t + 3 <= pm.indexCount; t += 3)
-    {
-      double w[3][3];
-      for(int v = 0; v < 3; v++)
-      {
-        const float* p = &s->positions[3 * (size_t)(s->indices[pm.firstIndex + t + v] + pm.vertexOffset)];
-        for(int k = 0; k < 3; k++) w[v][k] = (double)M[k] * p[0] + (double)M[4 + k] * p[1] + (double)M[8 + k] * p[2] + (double)M[12 + k];
-      }
-      const double a[3] = {w[1][0] - w[0][0], w[1][1] - w[0][1], w[1][2] - w[0][2]}, b[3] = {w[2][0] - w[0][0], w[2][1] - w[0][1], w[2][2] - w[0][2]};
-      const double cx = a[1] * b[2] - a[2] * b[1], cy = a[2] * b[0] - a[0] * b[2], cz = a[0] * b[1] - a[1] * b[0];
-      maxArea = std::max(maxArea, 0.5 * std::sqrt(cx * cx + cy * cy + cz * cz));
-    }
-  }
-  s->hasLargeTriangles = face > 0.0 && maxArea > 0.01 * face;
 }
 
 // The traversal settings of the installed tree: step bound, any-hit order, triangle postponing and work sharing (from the options),
@@ -1198,7 +836,7 @@ int accelBuildOnce(vkrt_scene* s, uint32_t flags, int splitBudget, hipStream_t s
       tree = std::move(r.tree);
   }
   installTree(s, tree);
-  sceneBounds(s);
+  vkrt::scene_bounds(s->positions, s->indices, s->primMeshes, s->nodes, s->dev.sceneLo, s->dev.sceneHi, s->hasLargeTriangles);
   if((rc = traversalSettings(s)) != VKRT_OK)
     return rc;
   if(s->dev.layout == 1u)
@@ -1225,7 +863,7 @@ int vkrt_accel_build(vkrt_scene* s, uint32_t flags, void* hip_stream)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "scene is NULL");
   hipStream_t stream = (hipStream_t)hip_stream;
   if(s->positionsOnDevice)
-  {  // vertices moved by a device-sourced vkrt_scene_update_vertices: the host builder and sceneBounds read the host copy
+  {  // vertices moved by a device-sourced vkrt_scene_update_vertices: the host builder and scene_bounds read the host copy
     int rc = setDevice(s);
     if(rc != VKRT_OK)
       return rc;
@@ -1289,8 +927,8 @@ int vkrt_scene_update_nodes(vkrt_scene* s, uint32_t first, uint32_t count, const
     if(nodes[i].primMesh != s->nodes[(size_t)first + i].primMesh)
       return fail(VKRT_ERR_INVALID_ARGUMENT, "node %u: primMesh %d != %d (an update moves instances, it does not change their geometry)", first + i,
                   nodes[i].primMesh, s->nodes[(size_t)first + i].primMesh);
-    if(checkTransform(nodes[i], first + i) != VKRT_OK)
-      return VKRT_ERR_INVALID_ARGUMENT;
+    if(std::string err; vkrt::check_transform(nodes[i], first + i, err) != VKRT_OK)
+      return failWith(VKRT_ERR_INVALID_ARGUMENT, err);
   }
   if(count == 0)
     return VKRT_OK;
@@ -1299,7 +937,7 @@ int vkrt_scene_update_nodes(vkrt_scene* s, uint32_t first, uint32_t count, const
     return rc;
   std::vector<DevInstance> inst(count);
   for(uint32_t i = 0; i < count; i++)
-    makeInstance(nodes[i], s->vis[(size_t)first + i], inst[i]);  // (the visibility word stays; the mirrored bit follows the new matrix)
+    vkrt::make_instance(nodes[i], s->vis[(size_t)first + i], inst[i]);  // (the visibility word stays; the mirrored bit follows the new matrix)
   // Stream-ordered: the records travel as kernel arguments of launches on hip_stream, after whatever the caller enqueued there before
   // (a trace that still reads the old transforms) and before whatever comes after (the refit, the next trace).  The trace entry points'
   // internal lane streams fork from and join to the caller's stream, so ordering on it is all that is needed.
@@ -1545,7 +1183,7 @@ int vkrt_scene_set_instance_visibility(vkrt_scene* s, uint32_t first, uint32_t c
   // kernel arguments on hip_stream like vkrt_scene_update_nodes does: stream-ordered, nothing staged, no synchronisation
   std::vector<DevInstance> inst(count);
   for(uint32_t i = 0; i < count; i++)
-    makeInstance(s->nodes[(size_t)first + i], vis[i], inst[i]);
+    vkrt::make_instance(s->nodes[(size_t)first + i], vis[i], inst[i]);
   hipStream_t stream = (hipStream_t)hip_stream;
   HIP_TRY(vkrt::upload_instances(const_cast<DevInstance*>(s->dev.instances), first, count, inst.data(), stream));
   std::copy(vis, vis + count, s->vis.begin() + first);
@@ -1680,20 +1318,15 @@ int vkrt_pathtrace_frames(vkrt_scene* s, const PushConstantRay* pc, const Global
     WfTiming* timing = nullptr;
     if(P.flags & VKRT_TRACE_TIME_KERNELS)
     {
-      const size_t wantEv = wfTimingEvents(pc->samples, pc->depth, n_frames);
-      while(s->wfEvents.size() < wantEv)
-      {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        s->wfEvents.push_back(e);
-      }
+      if((rc = growEvents(s->wfEventOwners, s->wfEvents, wfTimingEvents(pc->samples, pc->depth, n_frames), hipEventDefault)) != VKRT_OK)
+        return rc;
       s->wfTiming.events = s->wfEvents.data();
       s->wfTiming.capacity = (int)s->wfEvents.size();
       timing = &s->wfTiming;
     }
     s->wfTimed = timing != nullptr;
     s->wfTimingRounds = wfRounds(pc->samples, pc->depth);
-    HIP_TRY(hipEventRecord(s->evStart, stream));
+    HIP_TRY(hipEventRecord(s->evStart.get(), stream));
     const WfOptions wo{s->opt[VKRT_OPT_WF_SUBFRAMES], travBlock(s), s->opt[VKRT_OPT_WF_FRAMES_IN_FLIGHT]};
     if(timing)
       timing->used = 0;  // one timing record per call: the batches of a long call append to it
@@ -1702,7 +1335,7 @@ int vkrt_pathtrace_frames(vkrt_scene* s, const PushConstantRay* pc, const Global
       const TraceParams Pb = wfFrameParams(P, first, seedStep);
       HIP_TRY(vkrt_launch_wavefront(Pb, s->wf, wo, (int)std::min<uint32_t>(VKRT_FRAMES_PER_BATCH, n_frames - first), seedStep, count, stream, timing, &s->wfAsync));
     }
-    HIP_TRY(hipEventRecord(s->evStop, stream));
+    HIP_TRY(hipEventRecord(s->evStop.get(), stream));
     s->timed = true;
     return VKRT_OK;
   }
@@ -1714,14 +1347,14 @@ int vkrt_pathtrace_frames(vkrt_scene* s, const PushConstantRay* pc, const Global
   const uint64_t wantBlocks = ((uint64_t)P.tileCount * 64 + 255) / 256;
   const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(wantBlocks, (uint64_t)s->cuCount * perCU));
 
-  HIP_TRY(hipEventRecord(s->evStart, stream));
+  HIP_TRY(hipEventRecord(s->evStart.get(), stream));
   for(uint32_t k = 0; k < n_frames; k++)  // the megakernel renders the frames of a call one after another
   {
     const TraceParams Pk = wfFrameParams(P, k, seedStep);
     HIP_TRY(hipMemsetAsync(s->workCounter, 0, sizeof(unsigned int), stream));
     HIP_TRY(vkrt_launch_pathtrace(Pk, grid, count, stream));
   }
-  HIP_TRY(hipEventRecord(s->evStop, stream));
+  HIP_TRY(hipEventRecord(s->evStop.get(), stream));
   s->timed = true;
   s->wfTimed = false;
   return VKRT_OK;
@@ -1833,7 +1466,7 @@ int hybridImpl(vkrt_scene* s, const PushConstantRay* pc, const GlobalUniforms* c
   if((rc = frameAlphaStage(s, "vkrt_hybrid_trace", P)) != VKRT_OK)
     return rc;
   hipStream_t stream = (hipStream_t)hip_stream;
-  HIP_TRY(hipEventRecord(s->evStart, stream));
+  HIP_TRY(hipEventRecord(s->evStart.get(), stream));
   const HybridGi G{(float4*)g->color, (float4*)g->position, (float4*)g->normal, (float2*)g->roughMetal, (float4*)accum,
                    nrd ? (float4*)nrd->diffRadianceHitDist : nullptr, nrd ? nrd->viewZ : nullptr};
   // The GI paths (raytraceHybrid.rgen:172-282) run on the path tracer's wavefront streams when the scene was built for them:
@@ -1850,7 +1483,7 @@ int hybridImpl(vkrt_scene* s, const PushConstantRay* pc, const GlobalUniforms* c
   }
   else
     HIP_TRY(vkrt_launch_hybrid(P, G, nullptr, stream));
-  HIP_TRY(hipEventRecord(s->evStop, stream));
+  HIP_TRY(hipEventRecord(s->evStop.get(), stream));
   s->timed = true;
   s->wfTimed = false;
   return VKRT_OK;
@@ -1906,8 +1539,8 @@ int vkrt_last_trace_ms(vkrt_scene* s, float* ms)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "NULL argument");
   if(!s->timed)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "no trace has been launched on this scene");
-  HIP_TRY(hipEventSynchronize(s->evStop));
-  HIP_TRY(hipEventElapsedTime(ms, s->evStart, s->evStop));
+  HIP_TRY(hipEventSynchronize(s->evStop.get()));
+  HIP_TRY(hipEventElapsedTime(ms, s->evStart.get(), s->evStop.get()));
   return VKRT_OK;
 }
 
@@ -1918,8 +1551,8 @@ int vkrt_last_trace_timing(vkrt_scene* s, vkrt_trace_timing* out)
   if(!s->timed)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "no trace has been launched on this scene");
   memset(out, 0, sizeof *out);
-  HIP_TRY(hipEventSynchronize(s->evStop));
-  HIP_TRY(hipEventElapsedTime(&out->total_ms, s->evStart, s->evStop));
+  HIP_TRY(hipEventSynchronize(s->evStop.get()));
+  HIP_TRY(hipEventElapsedTime(&out->total_ms, s->evStart.get(), s->evStop.get()));
   out->mode = s->wavefront ? 1u : 0u;
   if(s->wfTimed)
   {
@@ -2087,191 +1720,14 @@ int vkrt_debug_check_accel(vkrt_scene* s, vkrt_accel_check* out)
   if(rc != VKRT_OK)
     return rc;
   HIP_TRY(hipDeviceSynchronize());
-  memset(out, 0, sizeof *out);
   const uint32_t T = s->dev.triCount, N = s->info.node_count;
-  out->layout = s->dev.layout;
   std::vector<float> tris((size_t)T * 12);
+  std::vector<uint32_t> nodes((size_t)N * (s->dev.layout == 1u ? 20 : 16));
   if(T)
     HIP_TRY(hipMemcpy(tris.data(), s->dev.tris, tris.size() * 4, hipMemcpyDeviceToHost));
-  std::vector<uint32_t> seen(T, 0u);
-  std::vector<uint8_t> reached(N, 0);
-  struct Bound { float lo[3], hi[3]; };
-  std::vector<Bound> chain;  // boxes of the slots on the path from the root
-  // slots per triangle id: a triangle with one slot must lie inside every box above that slot (its vertices do: convexity); the slots
-  // of a pre-split triangle (VKRT_OPT_SPLIT_BUDGET) are checked together at the end: `reach[slot]` = intersection of the chain
-  auto gidOf = [&](uint32_t slot) { uint32_t g; memcpy(&g, &tris[(size_t)slot * 12 + 9], 4); return g & 0x7fffffffu; };
-  auto decode = [&](uint32_t slot) { return vkrt::unpack_triangle(&tris[(size_t)slot * 12], s->dev.watertight != 0); };
-  const uint32_t gidCount = s->info.triangle_count;
-  std::vector<uint32_t> slotsOfGid(gidCount, 0u);
-  for(uint32_t k = 0; k < T; k++)
-  {
-    const uint32_t g = gidOf(k);
-    if(g < gidCount) slotsOfGid[g]++; else out->bad_references++;
-  }
-  std::vector<Bound> reach(T);
-  for(Bound& b : reach)
-    for(int k = 0; k < 3; k++) { b.lo[k] = -INFINITY; b.hi[k] = INFINITY; }
-  auto checkTriangle = [&](uint32_t slot) {
-    out->triangles_referenced++;
-    if(slot >= T) { out->bad_references++; return; }
-    if(seen[slot]++) { out->triangles_repeated++; return; }
-    const uint32_t g = gidOf(slot);
-    const bool single = g < gidCount && slotsOfGid[g] == 1u;
-    for(const Bound& b : chain)
-      for(int k = 0; k < 3; k++)
-      {
-        reach[slot].lo[k] = std::max(reach[slot].lo[k], b.lo[k]);
-        reach[slot].hi[k] = std::min(reach[slot].hi[k], b.hi[k]);
-      }
-    if(!single)
-      return;
-    const vkrt::FlatTri ft = decode(slot);
-    for(const float* p : {ft.v0, ft.p1, ft.p2})
-      for(const Bound& b : chain)
-        for(int k = 0; k < 3; k++)
-          if(!(p[k] >= b.lo[k] && p[k] <= b.hi[k])) { out->box_violations++; break; }
-  };
-  if(s->dev.layout == 1u)
-  {
-    std::vector<uint32_t> nodes((size_t)N * 20);
-    if(N)
-      HIP_TRY(hipMemcpy(nodes.data(), s->dev.nodes, nodes.size() * 4, hipMemcpyDeviceToHost));
-    struct Item { uint32_t node, depth; size_t chainLen; Bound b; bool hasBound; };
-    std::vector<Item> stack;
-    if(s->dev.rootRef != VKRT_TRAV_DONE && N)
-      stack.push_back(Item{0u, 1u, 0, Bound{}, false});
-    while(!stack.empty())
-    {
-      const Item it = stack.back();
-      stack.pop_back();
-      chain.resize(it.chainLen);
-      if(it.hasBound) chain.push_back(it.b);
-      if(it.node >= N || reached[it.node]++) { out->bad_references++; continue; }
-      out->nodes_reached++;
-      out->max_depth = std::max(out->max_depth, it.depth);
-      const uint32_t* n = &nodes[(size_t)it.node * 20];
-      float org[3];
-      memcpy(org, n, 12);
-      const uint32_t ew = n[3], imask = ew >> 24, childBase = n[4], triBase = n[5];
-      double cell[3];
-      for(int k = 0; k < 3; k++) cell[k] = std::ldexp(1.0, (int)((ew >> (8 * k)) & 255u) - 127);
-      for(int slot = 0; slot < 8; slot++)
-      {
-        const uint32_t meta = (n[6 + (slot >> 2)] >> (8 * (slot & 3))) & 255u;
-        if(meta == 0u)
-        {
-          if(imask & (1u << slot)) out->bad_references++;
-          continue;
-        }
-        Bound b;
-        for(int k = 0; k < 3; k++)
-        {
-          const uint32_t ql = (n[8 + 2 * k + (slot >> 2)] >> (8 * (slot & 3))) & 255u;
-          const uint32_t qh = (n[14 + 2 * k + (slot >> 2)] >> (8 * (slot & 3))) & 255u;
-          b.lo[k] = (float)((double)org[k] + ql * cell[k]);  // (exact in double; the kernel pads its own float arithmetic)
-          b.hi[k] = (float)((double)org[k] + qh * cell[k]);
-          if((double)b.lo[k] > (double)org[k] + ql * cell[k]) b.lo[k] = std::nextafter(b.lo[k], -INFINITY);
-          if((double)b.hi[k] < (double)org[k] + qh * cell[k]) b.hi[k] = std::nextafter(b.hi[k], INFINITY);
-        }
-        const bool internal = (imask >> slot) & 1u;
-        if(internal)
-        {
-          if(meta != (0x20u | (24u + (uint32_t)slot))) out->bad_references++;
-          const uint32_t rank = (uint32_t)__builtin_popcount(imask & ((1u << slot) - 1u));
-          stack.push_back(Item{childBase + rank, it.depth + 1u, chain.size(), b, true});
-        }
-        else
-        {
-          const uint32_t unary = meta >> 5, off = meta & 31u;
-          const uint32_t cnt = (uint32_t)__builtin_popcount(unary);
-          if(unary != (1u << cnt) - 1u || cnt == 0u || off + cnt > 24u) out->bad_references++;
-          chain.push_back(b);
-          for(uint32_t t = 0; t < cnt; t++) checkTriangle(triBase + off + t);
-          chain.pop_back();
-        }
-      }
-    }
-  }
-  else
-  {
-    std::vector<float> nodes((size_t)N * 16);
-    if(N)
-      HIP_TRY(hipMemcpy(nodes.data(), s->dev.nodes, nodes.size() * 4, hipMemcpyDeviceToHost));
-    struct Item { int32_t ref; uint32_t depth; size_t chainLen; Bound b; bool hasBound; };
-    std::vector<Item> stack;
-    if(s->dev.rootRef != VKRT_TRAV_DONE)
-      stack.push_back(Item{s->dev.rootRef, 1u, 0, Bound{}, false});
-    while(!stack.empty())
-    {
-      const Item it = stack.back();
-      stack.pop_back();
-      chain.resize(it.chainLen);
-      if(it.hasBound) chain.push_back(it.b);
-      if(it.ref < 0)
-      {  // leaf: ~(first slot << 3 | count - 1)
-        const uint32_t code = (uint32_t)~it.ref, first = code >> 3, cnt = (code & 7u) + 1u;
-        out->max_depth = std::max(out->max_depth, it.depth - 1u);
-        for(uint32_t t = 0; t < cnt; t++) checkTriangle(first + t);
-        continue;
-      }
-      if((uint32_t)it.ref >= N || reached[(uint32_t)it.ref]++) { out->bad_references++; continue; }
-      out->nodes_reached++;
-      out->max_depth = std::max(out->max_depth, it.depth);
-      const float* n = &nodes[(size_t)it.ref * 16];
-      for(int c = 0; c < 2; c++)
-      {
-        Bound b;
-        for(int k = 0; k < 3; k++) { b.lo[k] = n[6 * c + k]; b.hi[k] = n[6 * c + 3 + k]; }
-        int32_t ref;
-        memcpy(&ref, &n[12 + c], 4);
-        stack.push_back(Item{ref, it.depth + 1u, chain.size(), b, true});
-      }
-    }
-  }
-  for(uint32_t t = 0; t < T; t++)
-    if(!seen[t]) out->triangles_missing++;
-  // pre-split triangles: every lattice point of the triangle must be reachable through at least one of its slots
-  {
-    std::vector<uint32_t> first(gidCount + 1, 0u), fill(gidCount, 0u), bySlot(T);
-    for(uint32_t g = 0; g < gidCount; g++) first[g + 1] = first[g] + slotsOfGid[g];
-    for(uint32_t k = 0; k < T; k++)
-    {
-      const uint32_t g = gidOf(k);
-      if(g < gidCount) bySlot[first[g] + fill[g]++] = k;
-    }
-    for(uint32_t g = 0; g < gidCount; g++)
-    {
-      if(slotsOfGid[g] == 0u) { out->triangles_uncovered++; continue; }  // an instanced triangle the tree does not hold at all
-      if(slotsOfGid[g] == 1u) continue;
-      out->triangles_split++;
-      const vkrt::FlatTri ft = decode(bySlot[first[g]]);
-      const float* v[3] = {ft.v0, ft.p1, ft.p2};
-      bool covered = true;
-      const int n = 8;  // lattice: barycentric (i, j, n - i - j) / n
-      for(int i = 0; i <= n && covered; i++)
-        for(int j = 0; i + j <= n && covered; j++)
-        {
-          double p[3];
-          for(int k = 0; k < 3; k++) p[k] = ((double)v[0][k] * (n - i - j) + (double)v[1][k] * i + (double)v[2][k] * j) / n;
-          bool inSome = false;
-          for(uint32_t q = first[g]; q < first[g + 1] && !inSome; q++)
-          {
-            if(!seen[bySlot[q]]) continue;
-            const Bound& b = reach[bySlot[q]];
-            bool in = true;
-            // (the lattice point is rounded from double; a piece's box is padded by 8 ulp of the coordinates: allow as much)
-            for(int k = 0; k < 3; k++)
-            {
-              const double tol = 1e-6 * std::max(1.0, std::fabs(p[k]));
-              in = in && p[k] >= (double)b.lo[k] - tol && p[k] <= (double)b.hi[k] + tol;
-            }
-            inSome = in;
-          }
-          covered = inSome;
-        }
-      if(!covered) out->triangles_uncovered++;
-    }
-  }
+  if(N)
+    HIP_TRY(hipMemcpy(nodes.data(), s->dev.nodes, nodes.size() * 4, hipMemcpyDeviceToHost));
+  vkrt::check_tree(s->dev.layout, s->dev.rootRef, nodes.data(), N, tris.data(), T, s->info.triangle_count, s->dev.watertight != 0, *out);
   return VKRT_OK;
 }
 
@@ -2280,7 +1736,7 @@ struct vkrt_denoiser
 {
   int device = 0;
   uint32_t width = 0, height = 0;
-  void* mem = nullptr;          // one allocation: 8 planes of float4 per pixel
+  vkrt::DevBuf mem;             // one allocation: 8 planes of float4 per pixel
   float4* colour[3] = {};       // colour history / temporal result / ping-pong of the a-trous passes (roles rotate per call)
   float4* geom[2] = {};         // (position.xyz, oct normal) of the current and the previous call
   float4* mom[2] = {};          // (m1, m2, history length, 0)
@@ -2309,13 +1765,13 @@ int vkrt_denoiser_create(int device, uint32_t width, uint32_t height, vkrt_denoi
   dn->width = width;
   dn->height = height;
   const size_t plane = (size_t)width * height * sizeof(float4);
-  const hipError_t e = hipMalloc(&dn->mem, 8 * plane);
+  const hipError_t e = dn->mem.alloc(8 * plane);
   if(e != hipSuccess)
   {
     delete dn;
     return fail(e == hipErrorOutOfMemory ? VKRT_ERR_OUT_OF_MEMORY : VKRT_ERR_HIP, "vkrt_denoiser_create: hipMalloc: %s", hipGetErrorString(e));
   }
-  float4* base = (float4*)dn->mem;
+  float4* base = dn->mem.get<float4>();
   const size_t n = (size_t)width * height;
   for(int k = 0; k < 3; k++) dn->colour[k] = base + k * n;
   dn->geom[0] = base + 3 * n; dn->geom[1] = base + 4 * n;
@@ -2330,7 +1786,6 @@ void vkrt_denoiser_destroy(vkrt_denoiser* dn)
   if(!dn)
     return;
   (void)hipSetDevice(dn->device);
-  (void)hipFree(dn->mem);
   delete dn;
 }
 
