@@ -373,6 +373,56 @@ typedef struct vkrt_vertex_update {
 } vkrt_vertex_update;
 int vkrt_scene_update_vertices(vkrt_scene* scene, const vkrt_vertex_update* update, void* hip_stream);
 
+/* ---- skinned meshes (glTF skins: JOINTS_0 / WEIGHTS_0 per vertex, a palette of joint matrices per frame): linear-blend skinning inside
+ *      the library, straight into the scene's live vertex arrays.  These entry points came after ABI version 4 without changing it or
+ *      any existing struct: detect them by symbol. ------------------------------------------------------------------------------------
+ * vkrt_scene_add_skin binds four influences per vertex to the range [first, first+count) (absolute vertex indices, as in
+ * vkrt_vertex_update) and captures the range's bind pose: positions, normals and tangents as the scene holds them at this point of
+ * hip_stream.  joints and weights are host arrays, copied to the device before return; the call may allocate and synchronise, like the
+ * first refit and the first mark.  *out_skin is the skin's number: 0, 1, ... in creation order.  Skins live until vkrt_scene_destroy
+ * and survive builds, refits and node updates; their ranges do not overlap.  A later vkrt_scene_update_vertices on a skinned range is
+ * allowed: the next vkrt_scene_skin_vertices overwrites positions, normals and tangents from the captured bind pose (not from the
+ * update).  Texture coordinates are never touched by skinning, so an update of them stays.
+ * Refused with VKRT_ERR_INVALID_ARGUMENT, changing nothing, in this order: a NULL desc; struct_size < sizeof(vkrt_skin_desc);
+ * joint_count 0 or above 65536; NULL joints or weights with count > 0; a joint index >= joint_count; a non-finite weight; a NULL
+ * out_skin; a NULL scene; a range outside the scene's vertices; count == 0; a range that overlaps an existing skin's.  Then, without a
+ * device: VKRT_ERR_NO_DEVICE.
+ *
+ * vkrt_scene_skin_vertices poses skin `skin` from joint_matrices ([joint_count][16], column-major like vkrt_node.worldMatrix: glTF's
+ * jointMatrix = inverse(meshGlobal) * jointGlobal * inverseBind, in the space the scene's vertices live in): one kernel launch on
+ * hip_stream (ordering as vkrt_scene_update_vertices) that writes the positions, normals and tangents of the skin's range.
+ * VKRT_MEMORY_DEVICE: the matrices are device memory on the scene's device, 16-byte aligned, valid until the stream has passed the
+ *   call.  Nothing is allocated, nothing synchronises, the values are not inspected (as for a device vertex update).
+ * VKRT_MEMORY_HOST: every element is checked finite before anything changes; the matrices are staged through the scene's staging
+ *   buffer (the one of host vertex updates) and the call waits for hip_stream before it returns.
+ * In both cases the library's host copy of the positions falls behind the device's: the next vkrt_accel_build downloads them first.
+ * Stale tree: with a built tree, the tree is stale exactly as after a vertex update with positions; one vkrt_accel_refit serves any
+ *   number of skin, vertex and node updates before it.  vkrt_hit_surface and vkrt_hit_motion see the new pose without a refit.  The
+ *   motion snapshot is untouched: mark -> skin -> vkrt_hit_motion gives the pose before the skin call as `previous`.
+ * Refused with VKRT_ERR_INVALID_ARGUMENT, changing nothing, in this order: a memory value that is neither of the two; a NULL scene; a
+ * skin index out of range; NULL or (device memory) misaligned joint_matrices; (host memory) a non-finite element.  Then, without a
+ * device: VKRT_ERR_NO_DEVICE.
+ *
+ * Arithmetic: binary32, in source order, no contraction.  Element (r, c) of joint k is m[16k + 4c + r]; only rows 0 to 2 are read.  For
+ * a vertex with joints j0..j3, weights w0..w3 (used as given: not renormalised, all four always multiply -- glTF pads unused
+ * influences with weight 0), bind position p, normal n and tangent (t, tw):
+ *     M[r][c] = ((w0*J[j0][r][c] + w1*J[j1][r][c]) + w2*J[j2][r][c]) + w3*J[j3][r][c]        r = 0..2, c = 0..3
+ *     p'[r]   = ((M[r][0]*p.x + M[r][1]*p.y) + M[r][2]*p.z) + M[r][3]
+ *     N[r]    = (M[r][0]*n.x + M[r][1]*n.y) + M[r][2]*n.z ;  d = (N.x*N.x + N.y*N.y) + N.z*N.z
+ *     n'      = (d > 0 && d < inf) ? N * (1.0f / sqrtf(d)) : N
+ *     t'.xyz  = the same from t ;  t'.w = tw
+ * Normals go through the blended 3x3 as glTF viewers do, not through its inverse transpose: exact for rigid joints and uniform scale,
+ * tilted towards the stretched axis under non-uniform scale. */
+typedef struct vkrt_skin_desc {
+  uint32_t struct_size;      /* sizeof(vkrt_skin_desc) */
+  uint32_t first, count;     /* vertices [first, first+count), absolute indices as in vkrt_vertex_update */
+  uint32_t joint_count;      /* 1..65536 */
+  const uint16_t* joints;    /* host, u16[count][4]: glTF JOINTS_0 */
+  const float*    weights;   /* host, f32[count][4]: glTF WEIGHTS_0, used as given (not renormalised) */
+} vkrt_skin_desc;
+int vkrt_scene_add_skin(vkrt_scene* scene, const vkrt_skin_desc* desc, void* hip_stream, uint32_t* out_skin);
+int vkrt_scene_skin_vertices(vkrt_scene* scene, uint32_t skin, const float* joint_matrices, uint32_t memory /* vkrt_memory */, void* hip_stream);
+
 /* ---- ray queries (replaces traceRayEXT on rays of the caller's own, raytrace.rgen:64-97 / VK_KHR_ray_query: a closest-hit and an
  *      occlusion query per ray of a device array).  These entry points came after ABI version 4 without changing it or any
  *      existing struct: detect them by symbol. ---------------------------------------------------------------------------------------
@@ -863,6 +913,12 @@ int vkrt_debug_read_node_masks(vkrt_scene* scene, void* out, uint64_t bytes);
  * references (VKRT_OPT_SPLIT_BUDGET) appears once per slot it owns.  Other byte counts or a NULL pointer:
  * VKRT_ERR_INVALID_ARGUMENT; no tree, or a stale one: VKRT_ERR_NOT_BUILT. */
 int vkrt_debug_read_triangle_ids(vkrt_scene* scene, uint32_t* out, uint64_t bytes);
+/* The live attributes of vertices [first, first+count) as the kernels read them (synchronises the device; a test hook like the other
+ * vkrt_debug_* calls, no kernel of its own), into host arrays laid out as at vkrt_scene_create: positions vec3 (from the position
+ * array the builders and the refit read), normals vec3, tangents vec4 and texcoords0 vec2 (unpacked from the 48-B shading records).
+ * A NULL array is skipped.  Needs no tree.  A NULL scene, a range outside the scene's vertices or all four arrays NULL:
+ * VKRT_ERR_INVALID_ARGUMENT. */
+int vkrt_debug_read_vertices(vkrt_scene* scene, uint32_t first, uint32_t count, float* positions, float* normals, float* tangents, float* texcoords0);
 /* The work of vkrt_closest_point on n queries of a HOST array (synchronises the device; a test hook like the other vkrt_debug_* calls):
  * out[0] = nodes visited, out[1] = triangle records tested, summed over the queries, by an instrumented instantiation of the same
  * walk.  opts and the order of errors as vkrt_closest_point; a NULL out: VKRT_ERR_INVALID_ARGUMENT. */

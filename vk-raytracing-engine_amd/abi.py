@@ -213,7 +213,13 @@ class VertexUpdate(C.Structure):
                 ("tangents", C.c_void_p), ("texcoords0", C.c_void_p)]
 
 
+# skinned meshes (vkrt_scene_add_skin): joints (u16 x 4 per vertex) and weights (f32 x 4 per vertex) are host pointers
+class SkinDesc(C.Structure):
+    _fields_ = [("struct_size", c_u), ("first", c_u), ("count", c_u), ("joint_count", c_u), ("joints", C.c_void_p), ("weights", C.c_void_p)]
+
+
 assert C.sizeof(VertexUpdate) == 48
+assert C.sizeof(SkinDesc) == 32
 assert C.sizeof(Ray) == 32
 assert C.sizeof(Hit) == 32
 assert C.sizeof(Surface) == 128
@@ -275,6 +281,8 @@ VKRT_SYMBOLS = [
     "vkrt_scene_update_nodes",
     "vkrt_accel_refit",
     "vkrt_scene_update_vertices",
+    "vkrt_scene_add_skin",
+    "vkrt_scene_skin_vertices",
     "vkrt_intersect",
     "vkrt_occluded",
     "vkrt_scene_set_instance_visibility",
@@ -310,6 +318,7 @@ VKRT_SYMBOLS = [
     "vkrt_debug_read_accel",
     "vkrt_debug_read_node_masks",
     "vkrt_debug_read_triangle_ids",
+    "vkrt_debug_read_vertices",
     "vkrt_debug_closest_point_work",
     "vkrt_debug_trace_rays",
     "vkrt_debug_eval_math",
@@ -345,6 +354,14 @@ def declare_vkrt(lib):
     lib.vkrt_accel_refit.restype = C.c_int
     lib.vkrt_scene_update_vertices.argtypes = [C.c_void_p, P(VertexUpdate), C.c_void_p]
     lib.vkrt_scene_update_vertices.restype = C.c_int
+    # (scene, desc, stream, out_skin) / (scene, skin, joint matrices: host or device pointer by `memory`, memory, stream)
+    lib.vkrt_scene_add_skin.argtypes = [C.c_void_p, P(SkinDesc), C.c_void_p, P(c_u)]
+    lib.vkrt_scene_add_skin.restype = C.c_int
+    lib.vkrt_scene_skin_vertices.argtypes = [C.c_void_p, c_u, C.c_void_p, c_u, C.c_void_p]
+    lib.vkrt_scene_skin_vertices.restype = C.c_int
+    # (scene, first, count, positions, normals, tangents, texcoords0: host pointers, any may be NULL)
+    lib.vkrt_debug_read_vertices.argtypes = [C.c_void_p, c_u, c_u, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vkrt_debug_read_vertices.restype = C.c_int
     # (rays, hits, occluded: device pointers)
     lib.vkrt_intersect.argtypes = [C.c_void_p, C.c_void_p, c_u, c_u, C.c_void_p, C.c_void_p]
     lib.vkrt_intersect.restype = C.c_int

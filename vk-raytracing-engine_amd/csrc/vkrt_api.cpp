@@ -28,6 +28,7 @@
 
 #include "lbvh.h"
 #include "refit.h"
+#include "skin.h"
 #include "vertex_update.h"
 
 namespace {
@@ -101,6 +102,15 @@ struct vkrt_scene
   bool positionsOnDevice = false;  // a device-sourced update moved vertices the host copy has not seen: the next build downloads them first
   vkrt::DevBuf vertexStage;        // staging of host-sourced updates (grown by an update larger than every earlier one)
   size_t vertexStageBytes = 0;
+  // skinned meshes (vkrt_scene_add_skin): per skin one allocation holding the captured bind pose and the influences of its vertex range;
+  // the ranges are disjoint, the index in the list is the skin's number
+  struct Skin
+  {
+    vkrt::DevBuf mem;
+    vkrt::SkinArrays arrays;
+    uint32_t jointCount = 0;
+  };
+  std::vector<Skin> skins;
   // ray-query visibility (vkrt_scene_set_instance_visibility): host copy per node, and which masks occur (bit m of masksPresent[m >> 6])
   std::vector<vkrt_instance_visibility> vis;
   uint64_t masksPresent[4] = {0, 0, 0, 0};
@@ -1048,6 +1058,144 @@ int vkrt_scene_update_vertices(vkrt_scene* s, const vkrt_vertex_update* u, void*
     s->positionsOnDevice = true;
   if(u->positions && s->built)
     s->stale = true;
+  return VKRT_OK;
+}
+
+int vkrt_scene_add_skin(vkrt_scene* s, const vkrt_skin_desc* k, void* hip_stream, uint32_t* out_skin)
+{
+  const char* who = "vkrt_scene_add_skin";
+  if(!k)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: desc is NULL", who);
+  if(k->struct_size < sizeof(vkrt_skin_desc))
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vkrt_skin_desc.struct_size %u < %zu (ABI mismatch)", who, k->struct_size, sizeof(vkrt_skin_desc));
+  if(k->joint_count == 0 || k->joint_count > 65536u)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: joint_count %u outside 1..65536", who, k->joint_count);
+  const size_t n = k->count;
+  if(n && !k->joints)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: joints is NULL", who);
+  if(n && !k->weights)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: weights is NULL", who);
+  // the gather of k_skin is bounded here: no later call looks at an index again
+  for(size_t i = 0; i < 4 * n; i++)
+    if(k->joints[i] >= k->joint_count)
+      return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: joints[%zu] (vertex %zu) is %u, joint_count is %u", who, i, (size_t)k->first + i / 4,
+                  (unsigned)k->joints[i], k->joint_count);
+  for(size_t i = 0; i < 4 * n; i++)
+    if(!std::isfinite(k->weights[i]))
+      return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: weights[%zu] (vertex %zu) is not finite", who, i, (size_t)k->first + i / 4);
+  if(!out_skin)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: out_skin is NULL", who);
+  if(!s)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
+  const size_t vertexCount = s->positions.size() / 3;
+  if((uint64_t)k->first + k->count > vertexCount)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vertices [%u, %llu) outside the scene's %zu vertices", who, k->first,
+                (unsigned long long)k->first + k->count, vertexCount);
+  if(n == 0)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: count is 0", who);
+  for(size_t j = 0; j < s->skins.size(); j++)
+  {
+    const vkrt::SkinArrays& a = s->skins[j].arrays;
+    if(k->first < a.first + a.count && a.first < k->first + k->count)
+      return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vertices [%u, %u) overlap skin %zu's [%u, %u)", who, k->first, k->first + k->count, j, a.first,
+                  a.first + a.count);
+  }
+  int rc = setDevice(s);
+  if(rc != VKRT_OK)
+    return rc;
+  vkrt_scene::Skin skin;
+  skin.jointCount = k->joint_count;
+  HIP_TRY(skin.mem.alloc(vkrt::skin_bytes(k->count)));
+  vkrt::skin_carve(skin.mem.get(), k->first, k->count, skin.arrays);
+  HIP_TRY(hipMemcpy(skin.arrays.joints, k->joints, n * 4 * sizeof(uint16_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(skin.arrays.weights, k->weights, n * 4 * sizeof(float), hipMemcpyHostToDevice));
+  // stream-ordered like the update calls: the bind pose is what the updates enqueued before this call on hip_stream left
+  HIP_TRY(vkrt::launch_skin_capture(s->dev.positions, s->dev.vertexPN, skin.arrays, (hipStream_t)hip_stream));
+  *out_skin = (uint32_t)s->skins.size();
+  s->skins.push_back(std::move(skin));
+  return VKRT_OK;
+}
+
+int vkrt_scene_skin_vertices(vkrt_scene* s, uint32_t skin, const float* joint_matrices, uint32_t memory, void* hip_stream)
+{
+  const char* who = "vkrt_scene_skin_vertices";
+  if(memory != VKRT_MEMORY_HOST && memory != VKRT_MEMORY_DEVICE)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: memory %u is neither VKRT_MEMORY_HOST nor VKRT_MEMORY_DEVICE", who, memory);
+  if(!s)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
+  if(skin >= s->skins.size())
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: skin %u outside the scene's %zu skins", who, skin, s->skins.size());
+  const bool host = memory == VKRT_MEMORY_HOST;
+  if(!joint_matrices)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: joint_matrices is NULL", who);
+  if(!host && ((uintptr_t)joint_matrices & 15u) != 0)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: joint_matrices %p is not 16-byte aligned", who, (const void*)joint_matrices);
+  const vkrt_scene::Skin& k = s->skins[skin];
+  const size_t floats = (size_t)k.jointCount * 16, bytes = floats * sizeof(float);
+  if(host)
+    for(size_t i = 0; i < floats; i++)
+      if(!std::isfinite(joint_matrices[i]))
+        return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: joint_matrices[%zu] (joint %zu) is not finite", who, i, i / 16);
+  int rc = setDevice(s);
+  if(rc != VKRT_OK)
+    return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const float4* palette = (const float4*)joint_matrices;
+  if(host)
+  {  // through the staging buffer of host vertex updates (every earlier host call has waited for its stream: nothing reads it)
+    if(bytes > s->vertexStageBytes)
+    {
+      s->vertexStageBytes = 0;
+      HIP_TRY(s->vertexStage.alloc(bytes));
+      s->vertexStageBytes = bytes;
+    }
+    HIP_TRY(hipMemcpyAsync(s->vertexStage.get(), joint_matrices, bytes, hipMemcpyHostToDevice, stream));
+    palette = s->vertexStage.get<const float4>();
+  }
+  HIP_TRY(vkrt::launch_skin(const_cast<float*>(s->dev.positions), const_cast<float4*>(s->dev.vertexPN), k.arrays, palette, stream));
+  if(host)
+    HIP_TRY(hipStreamSynchronize(stream));  // the caller's matrices and the staging buffer are free again
+  s->positionsOnDevice = true;  // (host matrices too: the posed positions exist on the device only)
+  if(s->built)
+    s->stale = true;
+  return VKRT_OK;
+}
+
+int vkrt_debug_read_vertices(vkrt_scene* s, uint32_t first, uint32_t count, float* positions, float* normals, float* tangents, float* texcoords0)
+{
+  const char* who = "vkrt_debug_read_vertices";
+  if(!s)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
+  const size_t vertexCount = s->positions.size() / 3;
+  if((uint64_t)first + count > vertexCount)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vertices [%u, %llu) outside the scene's %zu vertices", who, first, (unsigned long long)first + count,
+                vertexCount);
+  if(!positions && !normals && !tangents && !texcoords0)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: positions, normals, tangents and texcoords0 are all NULL", who);
+  const int rc = setDevice(s);
+  if(rc != VKRT_OK)
+    return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  if(count == 0)
+    return VKRT_OK;
+  const size_t n = count;
+  if(positions)
+    HIP_TRY(hipMemcpy(positions, s->dev.positions + 3 * (size_t)first, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if(normals || tangents || texcoords0)
+  {  // quad 0 = position.xyz, normal.x; quad 1 = normal.yz, uv; quad 2 = tangent
+    std::vector<float> rec(n * 4 * VKRT_VERTEX_QUADS);
+    HIP_TRY(hipMemcpy(rec.data(), s->dev.vertexPN + VKRT_VERTEX_QUADS * (size_t)first, rec.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for(size_t i = 0; i < n; i++)
+    {
+      const float* r = &rec[i * 4 * VKRT_VERTEX_QUADS];
+      if(normals)
+        normals[3 * i] = r[3], normals[3 * i + 1] = r[4], normals[3 * i + 2] = r[5];
+      if(texcoords0)
+        texcoords0[2 * i] = r[6], texcoords0[2 * i + 1] = r[7];
+      if(tangents)
+        std::copy(r + 8, r + 12, tangents + 4 * i);
+    }
+  }
   return VKRT_OK;
 }
 

@@ -51,6 +51,45 @@ void vkrt_host_scene_material_alpha(const void* s_, vkrt_material_alpha* out)
   const GltfScene* s = (const GltfScene*)s_;
   memcpy(out, s->m_materialAlpha.data(), s->m_materialAlpha.size() * sizeof(vkrt_material_alpha));
 }
+// what the loader had to say about the file (GltfScene::warnings; "" when nothing); valid until the scene is freed
+const char* vkrt_host_scene_warnings(const void* s_) { return ((const GltfScene*)s_)->warnings.c_str(); }
+// skins: counts[0] = skins, counts[1] = vertices that carry JOINTS_0 / WEIGHTS_0 (0 or the scene's vertex count); then per skin
+// counts[2 + 2 s] = joints, counts[3 + 2 s] = vertex ranges.  `cap` = entries of counts; returns the entries the scene needs.
+uint32_t vkrt_host_scene_skin_counts(const void* s_, uint32_t* counts, uint32_t cap)
+{
+  const GltfScene* s = (const GltfScene*)s_;
+  const uint32_t need = 2 + 2 * (uint32_t)s->m_skins.size();
+  if(cap >= 2)
+  {
+    counts[0] = (uint32_t)s->m_skins.size();
+    counts[1] = (uint32_t)(s->m_joints0.size() / 4);
+  }
+  for(uint32_t k = 0; k < s->m_skins.size() && 3 + 2 * k < cap; k++)
+  {
+    counts[2 + 2 * k] = (uint32_t)s->m_skins[k].jointNodes.size();
+    counts[3 + 2 * k] = (uint32_t)(s->m_skins[k].vertexRanges.size() / 2);
+  }
+  return need;
+}
+// skin == UINT32_MAX: joints0 (u16 x 4 per vertex) and weights0 (f32 x 4 per vertex) of the whole scene, the other pointers unused;
+// else skin `skin`: its joint nodes (i32 per joint), inverse bind and rest joint matrices (16 floats per joint each) and vertex
+// ranges (first, count pairs).  A NULL pointer is skipped.
+void vkrt_host_scene_skin_copy(const void* s_, uint32_t skin, uint16_t* joints0, float* weights0, int32_t* jointNodes, float* inverseBind,
+                               float* restJointMatrices, uint32_t* vertexRanges)
+{
+  const GltfScene* s = (const GltfScene*)s_;
+  if(skin == UINT32_MAX)
+  {
+    if(joints0) memcpy(joints0, s->m_joints0.data(), s->m_joints0.size() * sizeof(uint16_t));
+    if(weights0) memcpy(weights0, s->m_weights0.data(), s->m_weights0.size() * sizeof(float));
+    return;
+  }
+  const GltfSkin& k = s->m_skins.at(skin);
+  if(jointNodes) memcpy(jointNodes, k.jointNodes.data(), k.jointNodes.size() * sizeof(int32_t));
+  if(inverseBind) memcpy(inverseBind, k.inverseBind.data(), k.inverseBind.size() * sizeof(float));
+  if(restJointMatrices) memcpy(restJointMatrices, k.restJointMatrices.data(), k.restJointMatrices.size() * sizeof(float));
+  if(vertexRanges) memcpy(vertexRanges, k.vertexRanges.data(), k.vertexRanges.size() * sizeof(uint32_t));
+}
 void vkrt_host_texture_info(const void* s_, uint32_t i, uint32_t* whs)
 {
   const GltfScene* s = (const GltfScene*)s_;
@@ -201,6 +240,49 @@ int vkrt_host_render_gltf_deformed(const char* path, int device, int width, int 
     for(uint32_t k = 0; k < steps; k++)
     {
       vk.updateVertices(first, step(positions, k, 3), step(normals, k, 3), step(tangents, k, 4), step(texcoords0, k, 2));
+      vk.refitAccel();
+    }
+    vk.m_pcRay.samples = samples;
+    vk.m_pcRay.depth = depth;
+    const float clear[4] = {1, 1, 1, 1};
+    for(int f = 0; f < frames; f++)
+    {
+      vk.updateUniformBuffer();
+      vk.updateFrame();
+      vk.m_seed = seed0 + (uint32_t)f;
+      vk.pathtrace(clear);
+    }
+    std::vector<float> img;
+    vk.downloadImage(img);
+    memcpy(rgbaOut, img.data(), img.size() * sizeof(float));
+    return 0;
+  }
+  catch(const std::exception& e) { g_err = e.what(); return 1; }
+}
+
+// vkrt_host_render_gltf with a skinned mesh: build, then `steps` times HelloVkrt::skinVertices(skin, jointMatrices[step]) + refitAccel
+// (jointMatrices: steps x joints x 16 floats, column-major), then the frames.  skinCountOut (may be NULL) receives HelloVkrt::skinCount().
+int vkrt_host_render_gltf_skinned(const char* path, int device, int width, int height, int samples, int depth, int frames, uint32_t seed0,
+                                  const float* eye, const float* center, const float* up, float fov, uint32_t buildFlags, uint32_t skin,
+                                  uint32_t joints, uint32_t steps, const float* jointMatrices, uint32_t* skinCountOut, float* rgbaOut)
+{
+  try
+  {
+    HelloVkrt vk(device);
+    vk.setup(width, height);
+    vk.CameraManip.setLookat(Vec3{eye[0], eye[1], eye[2]}, Vec3{center[0], center[1], center[2]}, Vec3{up[0], up[1], up[2]});
+    vk.CameraManip.setFov(fov);
+    vk.loadGltfScene(path);
+    vk.createOffscreenRender();
+    vk.initRayTracing();
+    vk.m_buildFlags = buildFlags;
+    vk.createBottomLevelASGltf();
+    vk.createTopLevelAsGltf();
+    if(skinCountOut)
+      *skinCountOut = vk.skinCount();
+    for(uint32_t k = 0; k < steps; k++)
+    {
+      vk.skinVertices(skin, std::vector<float>(jointMatrices + (size_t)k * joints * 16, jointMatrices + (size_t)(k + 1) * joints * 16));
       vk.refitAccel();
     }
     vk.m_pcRay.samples = samples;

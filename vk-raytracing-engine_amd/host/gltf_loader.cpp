@@ -216,6 +216,35 @@ void readIndices(const Doc& d, int idx, std::vector<uint32_t>& out)
   }
 }
 
+// JOINTS_0: VEC4 of unsigned bytes or shorts, not normalised -> u16 x 4 per vertex
+void readJoints(const Doc& d, int idx, std::vector<uint16_t>& out, size_t& count)
+{
+  const Json& a = d.g["accessors"][(size_t)idx];
+  const int ct = a["componentType"].integer();
+  if(a["type"].string() != "VEC4" || (ct != 5121 && ct != 5123))
+    throw std::runtime_error("gltf: JOINTS_0 accessor " + std::to_string(idx) + " is not a VEC4 of unsigned bytes or unsigned shorts");
+  std::vector<float> f;
+  readAccessorFloat(d, idx, 4, f, count);  // (integers up to 65535 are exact in a float; a normalised flag on joints would not be)
+  if(a["normalized"].boolean(false))
+    throw std::runtime_error("gltf: JOINTS_0 accessor " + std::to_string(idx) + " is normalised");
+  out.resize(f.size());
+  for(size_t i = 0; i < f.size(); i++) out[i] = (uint16_t)f[i];
+}
+
+// WEIGHTS_0: VEC4 of floats, or of normalised unsigned bytes or shorts
+void readWeights(const Doc& d, int idx, std::vector<float>& out, size_t& count)
+{
+  const Json& a = d.g["accessors"][(size_t)idx];
+  const int ct = a["componentType"].integer();
+  const bool norm = a["normalized"].boolean(false);
+  if(a["type"].string() != "VEC4" || !(ct == 5126 || ((ct == 5121 || ct == 5123) && norm)))
+    throw std::runtime_error("gltf: WEIGHTS_0 accessor " + std::to_string(idx) + " is not a VEC4 of floats or of normalised unsigned bytes or shorts");
+  readAccessorFloat(d, idx, 4, out, count);
+  for(float w : out)
+    if(!std::isfinite(w))
+      throw std::runtime_error("gltf: WEIGHTS_0 accessor " + std::to_string(idx) + " holds a non-finite weight");
+}
+
 int textureIndex(const Json& obj, const char* key)
 {
   const Json& t = obj[key];
@@ -524,6 +553,8 @@ GltfScene loadGltf(const std::string& filename)
   // ---- primitive meshes (processMesh, in mesh order; shared attribute sets are cached) -------------------
   std::vector<std::vector<uint32_t>> meshToPrims(g["meshes"].size());
   std::map<std::string, std::pair<uint32_t, uint32_t>> cache;  // attribute key -> (vertexOffset, vertexCount)
+  const bool hasSkins = g["skins"].size() > 0;  // then every vertex carries four influences (zeros where a primitive has none)
+  std::vector<bool> primSkinned;                // per primitive-mesh: it has JOINTS_0 / WEIGHTS_0
   for(size_t mi = 0; mi < g["meshes"].size(); mi++)
   {
     const Json& prims = g["meshes"][mi]["primitives"];
@@ -541,6 +572,11 @@ GltfScene loadGltf(const std::string& filename)
       std::ostringstream key;
       for(const auto& kv : keyv) key << kv.first << kv.second << ";";
 
+      if(hasSkins && attr.has("JOINTS_0") != attr.has("WEIGHTS_0"))
+        throw std::runtime_error(std::string("gltf: primitive with ") + (attr.has("JOINTS_0") ? "JOINTS_0 but no WEIGHTS_0" : "WEIGHTS_0 but no JOINTS_0"));
+      const bool skinned = hasSkins && attr.has("JOINTS_0");
+      if(skinned && (attr.has("JOINTS_1") || attr.has("WEIGHTS_1")))
+        sc.warnings += "mesh " + std::to_string(mi) + " primitive " + std::to_string(pi) + ": more than four influences (JOINTS_1 / WEIGHTS_1), the first four are used; ";
       std::vector<float> pos;
       size_t vcount = 0;
       readAccessorFloat(doc, attr["POSITION"].integer(), 3, pos, vcount);
@@ -611,12 +647,63 @@ GltfScene loadGltf(const std::string& filename)
         sc.m_normals.insert(sc.m_normals.end(), nrm.begin(), nrm.end());
         sc.m_texcoords0.insert(sc.m_texcoords0.end(), uv.begin(), uv.end());
         sc.m_tangents.insert(sc.m_tangents.end(), tan.begin(), tan.end());
+        if(hasSkins)
+        {
+          std::vector<uint16_t> jnt(vcount * 4, 0);
+          std::vector<float> wgt(vcount * 4, 0.f);
+          if(skinned)
+          {
+            readJoints(doc, attr["JOINTS_0"].integer(), jnt, n2);
+            if(n2 != vcount) throw std::runtime_error("gltf: JOINTS_0 count mismatch");
+            readWeights(doc, attr["WEIGHTS_0"].integer(), wgt, n2);
+            if(n2 != vcount) throw std::runtime_error("gltf: WEIGHTS_0 count mismatch");
+          }
+          sc.m_joints0.insert(sc.m_joints0.end(), jnt.begin(), jnt.end());
+          sc.m_weights0.insert(sc.m_weights0.end(), wgt.begin(), wgt.end());
+        }
       }
+      primSkinned.push_back(skinned);
       sc.m_indices.insert(sc.m_indices.end(), idx.begin(), idx.end());
       meshToPrims[mi].push_back((uint32_t)sc.m_primMeshes.size());
       sc.m_primMeshes.push_back(pm);
     }
   }
+
+  // ---- skins: joint node lists and inverse bind matrices (`skeleton` is ignored: it does not enter the joint matrices) ------------
+  for(size_t si = 0; si < g["skins"].size(); si++)
+  {
+    const Json& sj = g["skins"][si];
+    GltfSkin sk;
+    const Json& joints = sj["joints"];
+    if(joints.size() == 0 || joints.size() > 65536)
+      throw std::runtime_error("gltf: skin " + std::to_string(si) + " has " + std::to_string(joints.size()) + " joints (1..65536)");
+    for(size_t k = 0; k < joints.size(); k++)
+    {
+      const int ni = joints[k].integer(-1);
+      if(ni < 0 || (size_t)ni >= g["nodes"].size())
+        throw std::runtime_error("gltf: skin " + std::to_string(si) + ": joint " + std::to_string(k) + " is not a node");
+      sk.jointNodes.push_back(ni);
+    }
+    if(sj.has("inverseBindMatrices"))
+    {
+      const int ai = sj["inverseBindMatrices"].integer();
+      const Json& a = g["accessors"][(size_t)ai];
+      if(a["type"].string() != "MAT4" || a["componentType"].integer() != 5126)
+        throw std::runtime_error("gltf: skin " + std::to_string(si) + ": inverseBindMatrices is not a MAT4 accessor of floats");
+      size_t n = 0;
+      readAccessorFloat(doc, ai, 16, sk.inverseBind, n);
+      if(n != joints.size())
+        throw std::runtime_error("gltf: skin " + std::to_string(si) + ": " + std::to_string(n) + " inverseBindMatrices for " + std::to_string(joints.size()) + " joints");
+    }
+    else
+      for(size_t k = 0; k < joints.size(); k++)
+      {
+        const M4 one = ident();
+        sk.inverseBind.insert(sk.inverseBind.end(), one.m, one.m + 16);
+      }
+    sc.m_skins.push_back(sk);
+  }
+  std::map<uint32_t, int> rangeSkin;  // vertexOffset of a skinned primitive-mesh -> the skin that poses its vertices
 
   // ---- node hierarchy (processNode) -------------------------------------------------------------------
   struct LightRef { M4 world; int light; };
@@ -643,10 +730,35 @@ GltfScene loadGltf(const std::string& filename)
     {
       const size_t mi = (size_t)node["mesh"].integer();
       if(mi >= meshToPrims.size()) throw std::runtime_error("gltf: bad mesh index");
+      const int skin = node.has("skin") ? node["skin"].integer(-1) : -1;
+      if(node.has("skin") && (skin < 0 || (size_t)skin >= sc.m_skins.size()))
+        throw std::runtime_error("gltf: node " + std::to_string(ni) + ": bad skin index");
       for(uint32_t pmi : meshToPrims[mi])
       {
         vkrt_node n;
-        memcpy(n.worldMatrix, world.m, sizeof n.worldMatrix);
+        // a skinned primitive is placed by its joints alone: the node's own transform is ignored (its instance matrix is identity)
+        const bool posed = skin >= 0 && primSkinned[pmi];
+        const M4 place = posed ? ident() : world;
+        if(posed)
+        {
+          const vkrt_prim_mesh& pm = sc.m_primMeshes[pmi];
+          const size_t jointCount = sc.m_skins[(size_t)skin].jointNodes.size();
+          for(size_t k = 4 * (size_t)pm.vertexOffset; k < 4 * ((size_t)pm.vertexOffset + pm.vertexCount); k++)
+            if(sc.m_joints0[k] >= jointCount)
+              throw std::runtime_error("gltf: node " + std::to_string(ni) + ": joint index " + std::to_string(sc.m_joints0[k]) + " outside skin " +
+                                       std::to_string(skin) + "'s " + std::to_string(jointCount) + " joints");
+          // (primitives that share one attribute set share vertices: their range is listed once, and one skin poses it)
+          const auto used = rangeSkin.find(pm.vertexOffset);
+          if(used != rangeSkin.end() && used->second != skin)
+            throw std::runtime_error("gltf: the vertices of one primitive posed by two skins are not supported");
+          if(used == rangeSkin.end())
+          {
+            rangeSkin[pm.vertexOffset] = skin;
+            sc.m_skins[(size_t)skin].vertexRanges.push_back(pm.vertexOffset);
+            sc.m_skins[(size_t)skin].vertexRanges.push_back(pm.vertexCount);
+          }
+        }
+        memcpy(n.worldMatrix, place.m, sizeof n.worldMatrix);
         n.primMesh = (int32_t)pmi;
         sc.m_nodes.push_back(n);
       }
@@ -657,6 +769,40 @@ GltfScene loadGltf(const std::string& filename)
     const Json& ch = node["children"];
     for(size_t k = ch.size(); k-- > 0;)
       stack.emplace_back(ch[k].integer(), world);
+  }
+
+  // ---- rest pose of the skins: jointGlobal x inverseBind, the joint's global transform through its chain of parents ----------------
+  if(!sc.m_skins.empty())
+  {
+    const size_t nodeCount = g["nodes"].size();
+    std::vector<int> parent(nodeCount, -1);
+    for(size_t p = 0; p < nodeCount; p++)
+    {
+      const Json& ch = g["nodes"][p]["children"];
+      for(size_t k = 0; k < ch.size(); k++)
+      {
+        const int c = ch[k].integer(-1);
+        if(c < 0 || (size_t)c >= nodeCount) throw std::runtime_error("gltf: bad node index");
+        parent[(size_t)c] = (int)p;
+      }
+    }
+    for(GltfSkin& sk : sc.m_skins)
+      for(size_t j = 0; j < sk.jointNodes.size(); j++)
+      {
+        std::vector<int> chain;  // the joint, its parent, ... up to a root
+        for(int n = sk.jointNodes[j]; n >= 0; n = parent[(size_t)n])
+        {
+          if(chain.size() > nodeCount) throw std::runtime_error("gltf: node graph too large or cyclic");
+          chain.push_back(n);
+        }
+        M4 global = ident();  // root first, in the order the node walk above multiplies
+        for(size_t k = chain.size(); k-- > 0;)
+          global = mul(global, localMatrix(g["nodes"][(size_t)chain[k]]));
+        M4 ib;
+        memcpy(ib.m, &sk.inverseBind[16 * j], sizeof ib.m);
+        const M4 rest = mul(global, ib);
+        sk.restJointMatrices.insert(sk.restJointMatrices.end(), rest.m, rest.m + 16);
+      }
   }
 
   // ---- lights (loadGltfLights, hello_vulkan.cpp:226-325) ---------------------------------------------------

@@ -19,12 +19,25 @@ struct TextureImage
   bool srgb = false;
 };
 
+// One glTF skin: its joints, and where its vertices are.  A joint matrix (vkrt_scene_skin_vertices) is jointGlobal x inverseBind; a
+// skinned mesh node's own transform does not count (glTF 2.0, section 3.7.3.3), so its instance matrix in m_nodes is identity.
+struct GltfSkin
+{
+  std::vector<int32_t> jointNodes;       // glTF node index per joint
+  std::vector<float> inverseBind;        // 16 floats per joint, column-major (identity when the file has no inverseBindMatrices)
+  std::vector<float> restJointMatrices;  // 16 floats per joint: jointGlobal x inverseBind from the file's node hierarchy at rest
+  std::vector<uint32_t> vertexRanges;    // (first, count) pairs: the vertex ranges of the primitive-meshes that use the skin
+};
+
 struct GltfScene
 {
   std::vector<float> m_positions;   // vec3
   std::vector<float> m_normals;     // vec3
   std::vector<float> m_tangents;    // vec4
   std::vector<float> m_texcoords0;  // vec2
+  std::vector<uint16_t> m_joints0;  // u16 x 4 per vertex (JOINTS_0; zeros where a primitive has none); empty when the file has no skin
+  std::vector<float> m_weights0;    // f32 x 4 per vertex (WEIGHTS_0), like m_joints0
+  std::vector<GltfSkin> m_skins;
   std::vector<uint32_t> m_indices;
   std::vector<vkrt_prim_mesh> m_primMeshes;
   std::vector<vkrt_node> m_nodes;

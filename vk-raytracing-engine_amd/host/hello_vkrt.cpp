@@ -47,6 +47,26 @@ void HelloVkrt::loadScene(const GltfScene& scene)
   if(m_gltfScene.hasAlphaMask())
     check(vkrt_scene_set_material_alpha(m_scene, 0, (uint32_t)m_gltfScene.m_materialAlpha.size(), m_gltfScene.m_materialAlpha.data(), nullptr),
           "vkrt_scene_set_material_alpha");
+  // glTF's skins: one library skin per vertex range, bound to the file's JOINTS_0 / WEIGHTS_0; the bind pose is what was just uploaded
+  m_skinIds.clear();
+  for(const GltfSkin& sk : m_gltfScene.m_skins)
+  {
+    std::vector<uint32_t> ids;
+    for(size_t k = 0; k + 1 < sk.vertexRanges.size(); k += 2)
+    {
+      vkrt_skin_desc sd{};
+      sd.struct_size = sizeof(sd);
+      sd.first = sk.vertexRanges[k];
+      sd.count = sk.vertexRanges[k + 1];
+      sd.joint_count = (uint32_t)sk.jointNodes.size();
+      sd.joints = &m_gltfScene.m_joints0[4 * (size_t)sd.first];
+      sd.weights = &m_gltfScene.m_weights0[4 * (size_t)sd.first];
+      uint32_t id = 0;
+      check(vkrt_scene_add_skin(m_scene, &sd, nullptr, &id), "vkrt_scene_add_skin");
+      ids.push_back(id);
+    }
+    m_skinIds.push_back(ids);
+  }
   m_pcRay.lightsCount = (int32_t)m_gltfScene.m_lights.size();  // hello_vulkan.cpp:323-324
 }
 
@@ -133,6 +153,19 @@ void HelloVkrt::updateVertices(uint32_t first, const std::vector<float>& positio
   check(vkrt_scene_update_vertices(m_scene, &u, nullptr), "vkrt_scene_update_vertices");
   for(int k = 0; k < 4; k++)  // the host copy follows, like m_gltfScene's node matrices
     std::copy(src[k]->begin(), src[k]->end(), mirror[k]->begin() + (size_t)first * width[k]);
+}
+
+void HelloVkrt::skinVertices(uint32_t skin, const std::vector<float>& jointMatrices)
+{
+  if(!m_scene)
+    throw std::runtime_error("skinVertices before loadGltfScene");
+  if(skin >= m_skinIds.size())
+    throw std::runtime_error("skinVertices: skin " + std::to_string(skin) + " outside the scene's " + std::to_string(m_skinIds.size()) + " skins");
+  if(jointMatrices.size() != 16 * m_gltfScene.m_skins[skin].jointNodes.size())
+    throw std::runtime_error("skinVertices: jointMatrices must hold 16 floats for each of the skin's " +
+                             std::to_string(m_gltfScene.m_skins[skin].jointNodes.size()) + " joints");
+  for(uint32_t id : m_skinIds[skin])
+    check(vkrt_scene_skin_vertices(m_scene, id, jointMatrices.data(), VKRT_MEMORY_HOST, nullptr), "vkrt_scene_skin_vertices");
 }
 
 void HelloVkrt::refitAccel()

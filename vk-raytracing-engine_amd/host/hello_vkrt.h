@@ -48,6 +48,12 @@ public:
   void updateVertices(uint32_t first, const std::vector<float>& positions, const std::vector<float>& normals = {},
                       const std::vector<float>& tangents = {}, const std::vector<float>& texcoords0 = {});
   void refitAccel();                                                             // vkrt_accel_refit
+  // skinned meshes: loadScene adds the file's skins to the library (vkrt_scene_add_skin per vertex range of a GltfSkin; the bind pose
+  // is the file's).  skinVertices poses skin `skin` of m_gltfScene.m_skins from 16 floats per joint, column-major (glTF's
+  // jointMatrix = jointGlobal x inverseBind: GltfSkin::restJointMatrices gives the file's rest pose) -- vkrt_scene_skin_vertices from
+  // host memory for every range of the skin; refitAccel() follows.  m_gltfScene's vertex arrays keep the bind pose.
+  void skinVertices(uint32_t skin, const std::vector<float>& jointMatrices);
+  uint32_t skinCount() const { return (uint32_t)m_skinIds.size(); }
   // vkrt_scene_motion_mark: the transforms and vertices as they are now become the scene's previous state -- call it at the top of an
   // animated frame, before updateNodeTransforms / updateVertices.  From the first call on the hybrid sequence carries motion: rasterizeGltf
   // also writes a hit record per pixel and where each pixel's surface point was at the mark (vkrt_gbuffer_raycast_hits, vkrt_hit_motion)
@@ -114,6 +120,7 @@ private:
   vkrt_shard launchShard() const;
   int m_device;
   vkrt_scene* m_scene = nullptr;
+  std::vector<std::vector<uint32_t>> m_skinIds;  // per GltfSkin: the library's skin number of each of its vertex ranges
   float* m_offscreenColor = nullptr;  // device rgba32f
   // hybrid planes (createOffscreenRender :637-826): position, normal, rough/metal, accumulation, display
   float* m_positionTexture = nullptr;

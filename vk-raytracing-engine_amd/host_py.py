@@ -25,6 +25,11 @@ def lib():
         L.vkrt_host_scene_counts.argtypes = [C.c_void_p, C.c_void_p]
         L.vkrt_host_scene_copy.argtypes = [C.c_void_p] + [C.c_void_p] * 9
         L.vkrt_host_scene_material_alpha.argtypes = [C.c_void_p, C.c_void_p]
+        L.vkrt_host_scene_warnings.argtypes = [C.c_void_p]
+        L.vkrt_host_scene_warnings.restype = C.c_char_p
+        L.vkrt_host_scene_skin_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.vkrt_host_scene_skin_counts.restype = C.c_uint32
+        L.vkrt_host_scene_skin_copy.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 6
         L.vkrt_host_texture_info.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.vkrt_host_texture_copy.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.vkrt_host_global_uniforms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.POINTER(abi.GlobalUniforms)]
@@ -43,6 +48,10 @@ def lib():
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vkrt_host_render_gltf_deformed.restype = C.c_int
+        L.vkrt_host_render_gltf_skinned.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                    C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
+        L.vkrt_host_render_gltf_skinned.restype = C.c_int
         L.vkrt_host_render_gltf_hybrid.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_float, C.c_uint32, C.c_uint32, C.c_void_p]
         L.vkrt_host_render_gltf_hybrid.restype = C.c_int
@@ -110,6 +119,33 @@ def load_gltf(path):
         alpha = np.zeros(M, ALPHA_DTYPE)
         L.vkrt_host_scene_material_alpha(h, alpha.ctypes.data)
         return FlatScene(pos, nrm, tan, uv, idx, pm, mats, lights, nd, tex, alpha if np.any(alpha["mode"] != 0) else None)
+    finally:
+        L.vkrt_host_free_scene(h)
+
+
+def load_gltf_skins(path):
+    """C++ loader -> the skinning data of a glTF file: dict(joints0 uint16 (V, 4), weights0 float32 (V, 4) -- both (0, 4) when the file
+    has no skin --, skins = [dict(joint_nodes int32 (J,), inverse_bind (J, 16), rest_joint_matrices (J, 16) float32
+    column-major, vertex_ranges uint32 (R, 2) of (first, count))], warnings = the loader's GltfScene::warnings)."""
+    L = lib()
+    h = L.vkrt_host_load_gltf(os.fsencode(path))
+    if not h:
+        raise RuntimeError("vkrt_host_load_gltf: " + L.vkrt_host_last_error().decode())
+    try:
+        need = int(L.vkrt_host_scene_skin_counts(h, None, 0))
+        cnt = np.zeros(need, np.uint32)
+        L.vkrt_host_scene_skin_counts(h, cnt.ctypes.data, need)
+        S, V = int(cnt[0]), int(cnt[1])
+        joints0, weights0 = np.zeros((V, 4), np.uint16), np.zeros((V, 4), np.float32)
+        L.vkrt_host_scene_skin_copy(h, 0xFFFFFFFF, joints0.ctypes.data, weights0.ctypes.data, None, None, None, None)
+        skins = []
+        for k in range(S):
+            J, R = int(cnt[2 + 2 * k]), int(cnt[3 + 2 * k])
+            nodes, ranges = np.zeros(J, np.int32), np.zeros((R, 2), np.uint32)
+            ib, rest = np.zeros((J, 16), np.float32), np.zeros((J, 16), np.float32)
+            L.vkrt_host_scene_skin_copy(h, k, None, None, nodes.ctypes.data, ib.ctypes.data, rest.ctypes.data, ranges.ctypes.data)
+            skins.append({"joint_nodes": nodes, "inverse_bind": ib, "rest_joint_matrices": rest, "vertex_ranges": ranges})
+        return {"joints0": joints0, "weights0": weights0, "skins": skins, "warnings": L.vkrt_host_scene_warnings(h).decode()}
     finally:
         L.vkrt_host_free_scene(h)
 
@@ -192,6 +228,25 @@ def render_gltf_deformed(path, width, height, first, positions, normals=None, ta
     if rc != 0:
         raise RuntimeError("vkrt_host_render_gltf_deformed: " + lib().vkrt_host_last_error().decode())
     return img
+
+
+def render_gltf_skinned(path, width, height, skin, joint_matrices, samples=1, depth=3, frames=1, seed0=0, eye=(0, 0, 15), center=(0, 0, 0),
+                        up=(0, 1, 0), fov=60.0, build=abi.VKRT_BUILD_PLOC_GPU, device=0):
+    """render_gltf after posing skin `skin` of the file through the C++ HelloVkrt: joint_matrices (steps, joints, 16) column-major; each
+    step is skinVertices(skin, joint_matrices[step]) + refitAccel().  Returns (image, HelloVkrt::skinCount())."""
+    m = np.ascontiguousarray(joint_matrices, np.float32)
+    if m.ndim == 2:
+        m = m[None]
+    if m.ndim != 3 or m.shape[2] != 16:
+        raise ValueError(f"render_gltf_skinned: joint_matrices of shape {m.shape}, expected (steps, joints, 16)")
+    img = np.zeros((height, width, 4), np.float32)
+    e, c, p = (np.asarray(v, np.float32) for v in (eye, center, up))
+    count = C.c_uint32(0)
+    rc = lib().vkrt_host_render_gltf_skinned(os.fsencode(path), device, width, height, samples, depth, frames, seed0, e.ctypes.data, c.ctypes.data,
+                                             p.ctypes.data, fov, build, int(skin), m.shape[1], m.shape[0], m.ctypes.data, C.byref(count), img.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("vkrt_host_render_gltf_skinned: " + lib().vkrt_host_last_error().decode())
+    return img, int(count.value)
 
 
 def render_gltf_hybrid(path, width, height, depth=3, frames=1, seed0=0, eye=(0, 0, 15), center=(0, 0, 0), up=(0, 1, 0), fov=60.0, rank=0, world=1, device=0):

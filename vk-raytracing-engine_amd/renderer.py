@@ -139,6 +139,7 @@ class Renderer:
         self._prim_mesh = np.array(flat.nodes["primMesh"], np.int32)  # update_nodes keeps every node's primMesh
         self._vertex_count = int(flat.positions.shape[0])
         self._material_count = int(flat.materials.shape[0])
+        self._skins = []  # (first, count, joint_count) of every add_skin, in the library's numbering
         for k, v in (options or {}).items():
             self.set_option(k, v)
         if getattr(flat, "material_alpha", None) is not None:
@@ -231,6 +232,99 @@ class Renderer:
                              ptr.get("positions"), ptr.get("normals"), ptr.get("tangents"), ptr.get("texcoords0"))
         st = C.c_void_p(stream.cuda_stream) if stream is not None else None
         _check(self.lib.vkrt_scene_update_vertices(self._h, C.byref(u), st), "vkrt_scene_update_vertices")
+
+    def add_skin(self, first, joints, weights, joint_count=None, stream=None):
+        """vkrt_scene_add_skin: bind four influences per vertex to vertices [first, first + n) (absolute indices) and capture their
+        positions, normals and tangents, as they are at this point of `stream`, as the bind pose.  joints: integer (n, 4) numpy array
+        (glTF JOINTS_0); weights: float32 (n, 4) numpy array (WEIGHTS_0, used as given); joint_count: how many joint matrices skin()
+        takes (default joints.max() + 1).  Returns the skin's number.  Refused here, before the call: a wrong dtype or shape, a
+        non-contiguous array, lengths that differ, an empty range or one outside the scene or overlapping an earlier skin's, a joint
+        index outside [0, joint_count), a non-finite weight."""
+        for k, a, kinds, want in (("joints", joints, "iu", "an integer"), ("weights", weights, "f", "float32")):
+            if not isinstance(a, np.ndarray):
+                raise VkrtError(f"add_skin: {k} must be a numpy array, got {type(a).__name__}")
+            if a.dtype.kind not in kinds or (k == "weights" and a.dtype != np.float32):
+                raise VkrtError(f"add_skin: {k} is {a.dtype}, expected {want} dtype")
+            if a.ndim != 2 or a.shape[1] != 4:
+                raise VkrtError(f"add_skin: {k} has shape {tuple(a.shape)}, expected (n, 4)")
+            if not a.flags["C_CONTIGUOUS"]:
+                raise VkrtError(f"add_skin: {k} must be contiguous")
+        n = int(joints.shape[0])
+        if weights.shape[0] != n:
+            raise VkrtError(f"add_skin: weights has {weights.shape[0]} vertices, joints {n}")
+        if isinstance(first, bool) or not isinstance(first, (int, np.integer)) or first < 0 or n == 0 or int(first) + n > self._vertex_count:
+            raise VkrtError(f"add_skin: first: vertices [{first}, {first} + {n}) empty or outside the scene's {self._vertex_count} vertices")
+        first = int(first)
+        for k, (f0, c0, _) in enumerate(self._skins):
+            if first < f0 + c0 and f0 < first + n:
+                raise VkrtError(f"add_skin: first: vertices [{first}, {first + n}) overlap skin {k}'s [{f0}, {f0 + c0})")
+        if joint_count is None:
+            joint_count = int(joints.max()) + 1
+        if isinstance(joint_count, bool) or not isinstance(joint_count, (int, np.integer)) or not 1 <= joint_count <= 65536:
+            raise VkrtError(f"add_skin: joint_count {joint_count!r} outside 1..65536")
+        if int(joints.min()) < 0 or int(joints.max()) >= joint_count:
+            raise VkrtError(f"add_skin: joints holds indices in [{int(joints.min())}, {int(joints.max())}], joint_count is {joint_count}")
+        if not np.all(np.isfinite(weights)):
+            raise VkrtError("add_skin: weights holds a non-finite value")
+        j16 = np.ascontiguousarray(joints, np.uint16)
+        d = abi.SkinDesc(C.sizeof(abi.SkinDesc), first, n, int(joint_count), j16.ctypes.data, weights.ctypes.data)
+        out = abi.c_u()
+        st = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        _check(self.lib.vkrt_scene_add_skin(self._h, C.byref(d), st, C.byref(out)), "vkrt_scene_add_skin")
+        self._skins.append((first, n, int(joint_count)))
+        return int(out.value)
+
+    def skin(self, skin, joint_matrices, stream=None):
+        """vkrt_scene_skin_vertices: pose skin `skin` from joint_matrices, (joint_count, 16) float32, column-major like
+        vkrt_node.worldMatrix.  A numpy array takes the host path (checked finite, copied before return, the call waits for `stream`);
+        a torch tensor on the scene's device takes the device path: no copy, no synchronisation, the tensor must live until `stream`
+        has passed the call.  One kernel launch on `stream` (a torch stream; None = the default stream) writes positions, normals and
+        tangents of the skin's vertices from the captured bind pose; the tree is stale until refit() or build().  Refused here, before
+        the call: a skin index out of range, a wrong dtype or shape, a non-contiguous or misaligned tensor, a tensor on another
+        device, a non-finite host matrix."""
+        import torch
+
+        if isinstance(skin, bool) or not isinstance(skin, (int, np.integer)) or not 0 <= skin < len(self._skins):
+            raise VkrtError(f"skin: skin {skin!r} outside the scene's {len(self._skins)} skins")
+        jc = self._skins[int(skin)][2]
+        m = joint_matrices
+        if isinstance(m, torch.Tensor):
+            memory = abi.VKRT_MEMORY_DEVICE
+            if not m.is_cuda or m.device.index != self.device:
+                raise VkrtError(f"skin: joint_matrices is on {m.device}, the scene is on cuda:{self.device}")
+            if m.dtype != torch.float32:
+                raise VkrtError(f"skin: joint_matrices is {m.dtype}, expected torch.float32")
+            if not m.is_contiguous():
+                raise VkrtError("skin: joint_matrices must be contiguous")
+            ptr = m.data_ptr()
+            if ptr % 16:
+                raise VkrtError("skin: joint_matrices must be 16-byte aligned")
+        elif isinstance(m, np.ndarray):
+            memory = abi.VKRT_MEMORY_HOST
+            if m.dtype != np.float32:
+                raise VkrtError(f"skin: joint_matrices is {m.dtype}, expected float32")
+            if not m.flags["C_CONTIGUOUS"]:
+                raise VkrtError("skin: joint_matrices must be contiguous")
+            ptr = m.ctypes.data
+        else:
+            raise VkrtError(f"skin: joint_matrices must be a numpy array or a torch tensor, got {type(m).__name__}")
+        if m.ndim != 2 or tuple(m.shape) != (jc, 16):
+            raise VkrtError(f"skin: joint_matrices has shape {tuple(m.shape)}, expected ({jc}, 16)")
+        if memory == abi.VKRT_MEMORY_HOST and not np.all(np.isfinite(m)):
+            raise VkrtError("skin: joint_matrices holds a non-finite value")
+        st = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        _check(self.lib.vkrt_scene_skin_vertices(self._h, int(skin), ptr, memory, st), "vkrt_scene_skin_vertices")
+
+    def read_vertices(self, first, count):
+        """The live attributes of vertices [first, first + count) (vkrt_debug_read_vertices, synchronises): a dict of float32 arrays,
+        positions (count, 3), normals (count, 3), tangents (count, 4), texcoords0 (count, 2)."""
+        ok = all(not isinstance(x, bool) and isinstance(x, (int, np.integer)) for x in (first, count))
+        if not ok or first < 0 or count < 0 or int(first) + int(count) > self._vertex_count:
+            raise VkrtError(f"read_vertices: first: vertices [{first}, {first} + {count}) outside the scene's {self._vertex_count} vertices")
+        out = {k: np.zeros((int(count), w), np.float32) for k, w in (("positions", 3), ("normals", 3), ("tangents", 4), ("texcoords0", 2))}
+        _check(self.lib.vkrt_debug_read_vertices(self._h, int(first), int(count), *(out[k].ctypes.data for k in ("positions", "normals", "tangents",
+                                                                                                         "texcoords0"))), "vkrt_debug_read_vertices")
+        return out
 
     def set_instance_visibility(self, first, masks, flags=None, stream=None):
         """vkrt_scene_set_instance_visibility for nodes [first, first + n): masks = n ints in 1..255 (the instance masks of the
