@@ -913,6 +913,21 @@ int vkrt_debug_read_node_masks(vkrt_scene* scene, void* out, uint64_t bytes);
  * references (VKRT_OPT_SPLIT_BUDGET) appears once per slot it owns.  Other byte counts or a NULL pointer:
  * VKRT_ERR_INVALID_ARGUMENT; no tree, or a stale one: VKRT_ERR_NOT_BUILT. */
 int vkrt_debug_read_triangle_ids(vkrt_scene* scene, uint32_t* out, uint64_t bytes);
+/* The references triangle pre-splitting (VKRT_OPT_SPLIT_BUDGET) makes of the scene for a budget of split_percent % (1..100) extra
+ * references (synchronises the device; a test hook like the other vkrt_debug_* calls, no kernel of its own, no struct change, so
+ * VKRT_ABI_VERSION stays 4): the flattening and the pre-split stage of the device builders, the very functions a PLOC or LBVH build runs,
+ * on the scene's current arrays with its current VKRT_OPT_WATERTIGHT, and nothing after them.  With T = instanced triangles:
+ * prio[T] (or NULL) = the split priority of every flattened triangle, scale[1] (or NULL) = D, the splits per unit of priority -- triangle g
+ * is cut min((unsigned)(D * prio[g]), 255) times; both are zeros when T * split_percent / 100 is 0 or T < 2 --, *ref_count = the
+ * references, ref_tri[r] = the flattened triangle of reference r and ref_box[6 r .. 6 r + 5] = its box (lo3, hi3), in emission order: the
+ * pieces of a triangle are contiguous and the triangles appear in id order.  When nothing was split: the identity list with the
+ * whole-triangle boxes.  Needs no tree and does not touch the installed one.  capacity (in references) < T + T * split_percent / 100, a
+ * percent outside 1..100, or a NULL scene, ref_tri, ref_box or ref_count: VKRT_ERR_INVALID_ARGUMENT; without a device:
+ * VKRT_ERR_NO_DEVICE. */
+int vkrt_debug_split_references(vkrt_scene* scene, uint32_t split_percent /* 1..100 */,
+                                float* prio /* [T] or NULL */, float* scale /* [1] = D, or NULL */,
+                                uint32_t* ref_tri, float* ref_box /* 6 per reference */, uint64_t capacity,
+                                uint32_t* ref_count);
 /* The live attributes of vertices [first, first+count) as the kernels read them (synchronises the device; a test hook like the other
  * vkrt_debug_* calls, no kernel of its own), into host arrays laid out as at vkrt_scene_create: positions vec3 (from the position
  * array the builders and the refit read), normals vec3, tangents vec4 and texcoords0 vec2 (unpacked from the 48-B shading records).

@@ -343,3 +343,66 @@ def sah_bvh2(nodes, root_ref, box=None, levels=None):
         total += (area64(bx[:, c, 0:3], bx[:, c, 3:6]) * np.where(r < 0, cnt, 0)).sum()
     ra = area64(lo[0], hi[0])
     return float(total / ra) if ra > 0 else 0.0
+
+
+# ---- which reference sits in which slot (pre-split trees) -----------------------------------------------------------------------------
+
+def slot_references(a, ids, ref_tri, ref_lo, ref_hi, scene_lo, scene_hi):
+    """The reference (row of vkrt_debug_split_references) in every slot of a device-built tree `a` (read_accel) whose slots hold the
+    triangles `ids` (read_triangle_ids).  BVH2: the slots are the leaves in order, the stable sort of the references' Morton keys inside
+    the scene bounds of the whole triangles -- restated and held to ids.  wide8: the collapse renumbers the slots, and the slots of one
+    triangle carry the same record; a piece goes to a slot of its triangle whose leaf child's decoded box contains the piece's box (a
+    perfect matching per triangle, tightest leaf boxes first).  The assignment is a witness only: the caller proves the tree's words
+    exact under it."""
+    import np_bvh_build as nb
+
+    ids = np.asarray(ids, np.int64)
+    ref_tri = np.asarray(ref_tri, np.int64)
+    R = ref_tri.size
+    assert ids.size == R, f"{ids.size} slots for {R} references"
+    assert np.array_equal(np.sort(ids), np.sort(ref_tri)), "the slots do not hold the references' triangles (as multisets)"
+    if a["layout"] != 1:
+        order = nb.sorted_order(nb.morton_keys(ref_lo, ref_hi, scene_lo, scene_hi))
+        bad = np.flatnonzero(ref_tri[order] != ids)
+        assert bad.size == 0, f"{bad.size} of {R} slots differ from the stable Morton sort of the references, first slot {int(bad[0]) if bad.size else -1}"
+        return order
+    d = decode_wide8(a["nodes"])
+    dlo, dhi = decoded_wide8_boxes(d)
+    N = d["imask"].shape[0]
+    leaf, cnt, first = _leaf_slots(d, np.arange(N))
+    slot_lo = np.full((R, 3), np.inf)
+    slot_hi = np.full((R, 3), -np.inf)
+    for s in range(8):
+        for k in range(3):
+            use = leaf[:, s] & (cnt[:, s] > k)
+            slot_lo[first[use, s] + k] = dlo[use, s]
+            slot_hi[first[use, s] + k] = dhi[use, s]
+    out = np.full(R, -1, np.int64)
+    refs_of = np.argsort(ref_tri, kind="stable")   # references grouped by triangle
+    slots_of = np.argsort(ids, kind="stable")      # slots grouped by triangle: the same group sizes
+    count = np.bincount(ref_tri)
+    start = np.concatenate([[0], np.cumsum(count)])
+    single = np.flatnonzero(count == 1)
+    out[slots_of[start[single]]] = refs_of[start[single]]
+    rl, rh = np.asarray(ref_lo, np.float64), np.asarray(ref_hi, np.float64)
+    for g in np.flatnonzero(count > 1):
+        rr, ss = refs_of[start[g]:start[g + 1]], slots_of[start[g]:start[g + 1]]
+        fits = np.all(rl[rr][:, None] >= slot_lo[ss][None], axis=2) & np.all(rh[rr][:, None] <= slot_hi[ss][None], axis=2)  # [ref, slot]
+        tight = np.argsort(np.prod(slot_hi[ss] - slot_lo[ss] + 1e-300, axis=1), kind="stable")
+        owner = {}  # slot -> ref (Kuhn's augmenting paths)
+
+        def place(i, seen):
+            for j in tight:
+                if fits[i, j] and j not in seen:
+                    seen.add(j)
+                    if j not in owner or place(owner[j], seen):
+                        owner[j] = i
+                        return True
+            return False
+
+        for i in np.argsort(fits.sum(axis=1), kind="stable"):  # the pieces with the fewest candidates first
+            assert place(int(i), set()), f"triangle {int(g)}: no slot's leaf box contains piece {int(i)} of {rr.size}"
+        for j, i in owner.items():
+            out[ss[j]] = rr[i]
+    assert np.array_equal(np.sort(out), np.arange(R))
+    return out

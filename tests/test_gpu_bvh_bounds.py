@@ -94,12 +94,13 @@ def _assert_sah(got, want, what):
     assert abs(float(got) - want) <= SAH_REL * abs(want), (what, float(got), want)
 
 
-def check_exact(r, wt, what):
-    """The installed tree is the exact restatement of its topology: leaf boxes = unions of their records' whole-triangle boxes, nodes
-    quantised by the header's rule (wide8) or stored as floats (BVH2), and sah_cost the float64 cost of those boxes.  Returns the tree."""
+def check_exact(r, wt, what, slot_boxes=None):
+    """The installed tree is the exact restatement of its topology: leaf boxes = unions of their records' whole-triangle boxes (or of
+    slot_boxes = (lo, hi) per slot: the boxes of a pre-split tree's references), nodes quantised by the header's rule (wide8) or stored
+    as floats (BVH2), and sah_cost the float64 cost of those boxes.  Returns the tree."""
     a = r.read_accel()
     info = r.accel_info()
-    rlo, rhi = np_bvh.record_bounds(a["tris"], wt)
+    rlo, rhi = np_bvh.record_bounds(a["tris"], wt) if slot_boxes is None else slot_boxes
     if a["layout"] == 1:
         exp, _, _, slo, shi, d = np_bvh.exact_wide8(a["nodes"], rlo, rhi)
         levels = np_bvh.wide8_levels(d)
@@ -241,10 +242,11 @@ def rotated_building():
 
 @pytest.mark.parametrize("budget", [30, 100])
 def test_split_tree_boxes_are_bounded(rotated_building, budget):
-    """Pre-split trees before any refit: a reference's clipped box is not observable, so the words are held to upper bounds -- a leaf
-    child inside the tightest quantisation of its records' whole-triangle boxes, an internal child inside the tightest quantisation (on
-    the parent's grid) of its own children's decoded boxes -- and sah_cost to at most the cost those decoded boxes give (wide8) or to
-    the cost of the stored boxes (BVH2, float boxes: exact)."""
+    """Pre-split trees before any refit, from the installed words alone: upper bounds -- a leaf child inside the tightest quantisation
+    of its records' whole-triangle boxes, an internal child inside the tightest quantisation (on the parent's grid) of its own
+    children's decoded boxes -- and sah_cost at most the cost those decoded boxes give (wide8) or the cost of the stored boxes (BVH2,
+    float boxes: exact).  The references' clipped boxes themselves are shown by vkrt_debug_split_references: held exactly in
+    test_split_tree_boxes_are_exact below, and to the restated splitter in tests/test_gpu_split_refs.py."""
     from vkrt_amd.renderer import Renderer
 
     for layout in ("wide8", "bvh2"):
@@ -259,6 +261,31 @@ def test_split_tree_boxes_are_bounded(rotated_building, budget):
                 _split_wide8(a["nodes"], rlo, rhi, info["sah_cost"], what)
             else:
                 _split_bvh2(a, rlo, rhi, info["sah_cost"], what)
+            r.close()
+
+
+@pytest.mark.parametrize("name", ["grid8", "rotated_small"])
+def test_split_tree_boxes_are_exact(name):
+    """Budget 30, {ploc, lbvh} x {wide8, BVH2}: with the box of every reference in its slot (vkrt_debug_split_references; which reference
+    sits in which slot: np_bvh.slot_references) the installed words are those of exact_wide8 / exact_bvh2, word for word, and sah_cost is
+    within 2e-6 of the float64 cost of those boxes -- what test_built_boxes_and_cost_are_exact_and_reproducible holds unsplit trees to."""
+    from test_gpu_split_refs import flat_scene
+    from vkrt_amd.renderer import Renderer
+
+    flat = flat_scene(name)
+    for layout in ("wide8", "bvh2"):
+        for kind in ("ploc", "lbvh"):
+            what = f"{name} {kind} {layout} budget=30"
+            r = Renderer(flat, device=0, build=kind, options=_options(layout, 0, 30))
+            a = r.read_accel()
+            d = r.split_references(30)
+            assert r.accel_info()["reference_count"] == d["ref_count"] > r.accel_info()["triangle_count"], what
+            wlo, whi = np_bvh.record_bounds(a["tris"], 0)  # every triangle owns a slot: the scene bounds of the whole triangles
+            ref = np_bvh.slot_references(a, r.read_triangle_ids(), d["ref_tri"], d["ref_box"][:, 0:3], d["ref_box"][:, 3:6], wlo.min(axis=0),
+                                         whi.max(axis=0))
+            box = d["ref_box"][ref]
+            assert np.all(box[:, 0:3] >= wlo) and np.all(box[:, 3:6] <= whi), f"{what}: a reference's box outside its triangle's"
+            check_exact(r, 0, what, (np.ascontiguousarray(box[:, 0:3]), np.ascontiguousarray(box[:, 3:6])))
             r.close()
 
 

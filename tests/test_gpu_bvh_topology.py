@@ -4,8 +4,9 @@ whatever topology was installed; the images do not depend on the tree.  So a bui
 searches a shorter window or collapses short of its optimum passes all of that and only loses a few percent of ray rate.  Here the order of
 the leaves, every node of the binary trees and the structure and cost of the wide trees must be what the algorithms give.
 
-All builds use VKRT_OPT_SPLIT_BUDGET = 0 (split references: test_split_tree_boxes_are_bounded).  The host `sah` builder is not part of
-the wide checks: the BVH2 it installs has leaves of up to 4 triangles, the tree its collapse consumes is a second build with one triangle
+The scenes are built with VKRT_OPT_SPLIT_BUDGET = 0; `grid8` and `rotated_small` run with a budget of 30 as well: the leaves are then the
+references vkrt_debug_split_references shows, with their clipped boxes (held to the restated splitter in tests/test_gpu_split_refs.py),
+their keys taken inside the scene bounds of the whole triangles.  The host `sah` builder is not part of the wide checks: the BVH2 it installs has leaves of up to 4 triangles, the tree its collapse consumes is a second build with one triangle
 per leaf, which no entry point shows."""
 import os
 import sys
@@ -28,6 +29,9 @@ SMALL = tuple(f"soup{n}" for n in SOUP_SIZES) + ("pile", "line", "soup_far", "co
 BVH2_STACK_WORDS = 64  # per lane: a BVH2 deeper than 62 is refused at install (VKRT_ERR_UNSUPPORTED)
 LARGE = ("soup4200", "atrium_small")  # above 4096 triangles: the upper-level pass, on its full-sweep path and on its binned path
 SCENES = SMALL + LARGE
+SPLIT = ("grid8", "rotated_small")  # the scenes that also run pre-split, budget 30
+CASES = [(n, 0) for n in SCENES] + [(n, 30) for n in SPLIT]
+IDS = list(SCENES) + [f"{n}-split30" for n in SPLIT]
 
 
 @pytest.fixture(scope="module")
@@ -45,16 +49,22 @@ def scenes():
     out["soup_far"] = _triangle_scene(_soup(1000), _col_major(far))
     out["cornell"] = FlatScene.load_npz(os.path.join(ROOT, "tests", "golden", "cornell_flat.npz"))
     out["atrium_small"], _ = atrium.build_atrium(20000, seed=4, with_textures=False)
+    from test_gpu_split_refs import flat_scene
+
+    for n in SPLIT:
+        out[n] = flat_scene(n)
     return out
 
 
-def _build(flat, kind, layout):
+def _build(flat, kind, layout, budget=0):
     from vkrt_amd.renderer import Renderer
 
-    r = Renderer(flat, device=0, build=kind, options=_options(layout, 0))
+    r = Renderer(flat, device=0, build=kind, options=_options(layout, 0, budget))
     a = r.read_accel()
     a["ids"] = r.read_triangle_ids()
     a["info"] = r.accel_info()
+    if budget:
+        a["refs"] = r.split_references(budget)
     r.close()
     assert a["layout"] == (1 if layout == "wide8" else 0)
     return a
@@ -63,19 +73,31 @@ def _build(flat, kind, layout):
 class Restated:
     """One scene: the device's BVH2 builds (read once) and everything the restatement derives from the installed records."""
 
-    def __init__(self, name, flat):
-        self.name, self.flat = name, flat
+    def __init__(self, name, flat, budget=0):
+        self.name, self.flat, self.budget = name, flat, budget
         self.device = {}
         self.trees = {}
         a = self.built("lbvh", "bvh2")
         ids = a["ids"].astype(np.int64)
-        self.T = T = ids.size
-        assert T == flat.instanced_triangle_count and np.array_equal(np.sort(ids), np.arange(T)), f"{name}: slot ids are not a permutation"
-        rlo, rhi = np_bvh.record_bounds(a["tris"], 0)  # per slot; back to the order of the flattened ids
-        self.lo, self.hi = np.zeros((T, 3), np.float32), np.zeros((T, 3), np.float32)
-        self.lo[ids], self.hi[ids] = rlo, rhi
-        self.keys = nb.morton_keys(self.lo, self.hi)
+        rlo, rhi = np_bvh.record_bounds(a["tris"], 0)  # per slot
+        if budget == 0:
+            self.T = T = ids.size
+            assert T == flat.instanced_triangle_count and np.array_equal(np.sort(ids), np.arange(T)), f"{name}: slot ids are not a permutation"
+            self.lo, self.hi = np.zeros((T, 3), np.float32), np.zeros((T, 3), np.float32)
+            self.lo[ids], self.hi[ids] = rlo, rhi  # back to the order of the flattened ids
+            self.tri_of = np.arange(T)
+            self.bounds = nb.scene_bounds(self.lo, self.hi)
+            self.keys = nb.morton_keys(self.lo, self.hi)
+        else:  # the leaves are the references of the pre-split stage, in emission order, with their clipped boxes
+            d = a["refs"]
+            self.T = T = d["ref_count"]
+            assert T == ids.size == a["info"]["reference_count"] > flat.instanced_triangle_count, f"{name}: {T} references, {ids.size} slots"
+            self.lo, self.hi = np.ascontiguousarray(d["ref_box"][:, 0:3]), np.ascontiguousarray(d["ref_box"][:, 3:6])
+            self.tri_of = d["ref_tri"].astype(np.int64)
+            self.bounds = nb.scene_bounds(rlo, rhi)  # of the whole triangles: every triangle owns a slot
+            self.keys = nb.morton_keys(self.lo, self.hi, *self.bounds)
         self.order = nb.sorted_order(self.keys)
+        self.slot_ids = self.tri_of[self.order]  # the triangle every leaf position holds
         self.slo, self.shi = self.lo[self.order], self.hi[self.order]  # leaf boxes by position
 
     def built(self, kind, layout, metric=None, monkeypatch=None):
@@ -86,7 +108,7 @@ class Restated:
             if metric is not None:
                 monkeypatch.setenv("VKRT_PLOC_METRIC", str(metric))
             try:
-                self.device[key] = _build(self.flat, kind, layout)
+                self.device[key] = _build(self.flat, kind, layout, self.budget)
             finally:
                 if metric is not None:
                     monkeypatch.delenv("VKRT_PLOC_METRIC")
@@ -114,10 +136,10 @@ class Restated:
 def restated(scenes):
     cache = {}
 
-    def get(name):
-        if name not in cache:
-            cache[name] = Restated(name, scenes[name])
-        return cache[name]
+    def get(name, budget=0):
+        if (name, budget) not in cache:
+            cache[name, budget] = Restated(name, scenes[name], budget)
+        return cache[name, budget]
 
     return get
 
@@ -138,39 +160,41 @@ def _assert_same_bvh2(a, root, refs, what):
                            f"{dev[want[bad[0]]].tolist()}, restated {exp[bad[0]].tolist()}")
 
 
-@pytest.mark.parametrize("name", SCENES)
-def test_leaf_order_is_the_stable_morton_sort(restated, name):
-    """lbvh and ploc, BVH2: slot k holds the k-th triangle of the stable sort of (63-bit key, flattened id)."""
-    s = restated(name)
+@pytest.mark.parametrize("name,budget", CASES, ids=IDS)
+def test_leaf_order_is_the_stable_morton_sort(restated, name, budget):
+    """lbvh and ploc, BVH2: slot k holds the k-th triangle of the stable sort of (63-bit key, flattened id) -- pre-split: the triangle of
+    the k-th reference of the stable sort of (key, reference number)."""
+    s = restated(name, budget)
     k = s.keys[s.order]
     assert np.all(k[1:] >= k[:-1]) and np.all((k[1:] > k[:-1]) | (s.order[1:] > s.order[:-1]))
     for kind in ("lbvh", "ploc"):
         ids = s.built(kind, "bvh2")["ids"].astype(np.int64)
-        bad = np.flatnonzero(ids != s.order)
-        assert bad.size == 0, (f"{name} {kind}: {bad.size} of {s.T} slots differ, first slot {int(bad[0])}: device id {int(ids[bad[0]])} (key "
-                               f"{int(s.keys[ids[bad[0]]]):#x}), restated id {int(s.order[bad[0]])} (key {int(s.keys[s.order[bad[0]]]):#x})")
+        bad = np.flatnonzero(ids != s.slot_ids)
+        assert bad.size == 0, (f"{name} {kind}: {bad.size} of {s.T} slots differ, first slot {int(bad[0])}: device id {int(ids[bad[0]])}" +
+                               (f" (key {int(s.keys[ids[bad[0]]]):#x})" if budget == 0 else "") +
+                               f", restated id {int(s.slot_ids[bad[0]])} (key {int(s.keys[s.order[bad[0]]]):#x})")
     if name in ("pile", "soup_far"):
         assert np.unique(s.keys).size < s.T // 2, f"{name}: the scene is here for its tied keys"
     if name == "pile":
         assert np.array_equal(s.order, np.arange(s.T))
 
 
-@pytest.mark.parametrize("name", SCENES)
-def test_lbvh_is_the_karras_tree(restated, name):
+@pytest.mark.parametrize("name,budget", CASES, ids=IDS)
+def test_lbvh_is_the_karras_tree(restated, name, budget):
     """BVH2 layout: the radix tree with position tie-breaks, subtrees of <= 4 triangles as leaves ~((first << 3) | (count - 1))."""
-    s = restated(name)
+    s = restated(name, budget)
     root, refs = nb.emit(s.tree("lbvh"), s.T, 4)
     _assert_same_bvh2(s.built("lbvh", "bvh2"), root, refs, f"{name} lbvh")
 
 
-@pytest.mark.parametrize("name", SCENES)
-def test_ploc_is_the_restated_clustering(restated, name, monkeypatch):
+@pytest.mark.parametrize("name,budget", CASES, ids=IDS)
+def test_ploc_is_the_restated_clustering(restated, name, budget, monkeypatch):
     """BVH2 layout, one triangle per leaf.  Up to 1000 triangles: the pure clustering under all three merge costs (T = 257 also with
     the hook that makes every search pass barren).  Above 4096: the default cost with the SAH pass over the upper levels."""
     from vkrt_amd.renderer import VkrtError
 
-    s = restated(name)
-    metrics = (2,) if name in LARGE else (0, 1, 2) + ((98,) if name == "soup257" else ())
+    s = restated(name, budget)
+    metrics = (2,) if s.T > nb.TOP_MIN_TRIANGLES else (0, 1, 2) + ((98,) if name == "soup257" else ())
     for metric in metrics:
         what = f"{name} ploc metric {metric}"
         hook = None if metric == 2 else metric
@@ -188,8 +212,8 @@ def test_ploc_is_the_restated_clustering(restated, name, monkeypatch):
         a = s.built("ploc", "bvh2", hook, monkeypatch)
         _assert_same_bvh2(a, root, refs, what)
         assert a["info"]["max_depth"] == depth, (what, a["info"]["max_depth"], depth)
-        assert np.array_equal(a["ids"], s.order), f"{name} ploc metric {metric}: leaf order"
-    if name in LARGE:  # (also asserted on the CPU, on boxes without slop: tests/test_np_bvh_build.py)
+        assert np.array_equal(a["ids"], s.slot_ids), f"{name} ploc metric {metric}: leaf order"
+    if name in LARGE and budget == 0:  # (also asserted on the CPU, on boxes without slop: tests/test_np_bvh_build.py)
         F = s.tree("ploc")["frontier"]
         assert (F > nb.TOP_SWEEP_MAX) == (name == "atrium_small") and F >= 2, (name, F)
 
@@ -202,7 +226,10 @@ def _wide_against_binary(a, s, h, what):
     levels = np_bvh.wide8_levels(d)
     assert sum(l.size for l in levels) == a["nodes"].shape[0] == a["info"]["node_count"], what
     ids = a["ids"].astype(np.int64)
-    assert ids.size == T and np.array_equal(np.sort(ids), np.arange(T)), f"{what}: a triangle is missing or repeated among the slots"
+    if s.budget == 0:
+        assert ids.size == T and np.array_equal(np.sort(ids), np.arange(T)), f"{what}: a triangle is missing or repeated among the slots"
+    else:  # the slots of a triangle hold the same record: which of its references each one is, from the leaf boxes (np_bvh.slot_references)
+        ids = np_bvh.slot_references(a, ids, s.tri_of, s.lo, s.hi, *s.bounds)
     pos_of = np.empty(T, np.int64)
     pos_of[s.order] = np.arange(T)
     pos = pos_of[ids]  # leaf position of every wide-tree slot
@@ -273,8 +300,8 @@ def _wide_against_binary(a, s, h, what):
 
 
 @pytest.mark.parametrize("kind", ["lbvh", "ploc"])
-@pytest.mark.parametrize("name", SCENES)
-def test_wide_collapse_cuts_the_binary_tree_at_its_optimum(restated, name, kind):
+@pytest.mark.parametrize("name,budget", CASES, ids=IDS)
+def test_wide_collapse_cuts_the_binary_tree_at_its_optimum(restated, name, budget, kind):
     """wide8 layout.  Structure: every child of every wide node holds the leaf set of one node of the restated binary tree, the
     children of a node partition the node they came from, no leaf child holds more than 3 triangles, each triangle appears once.
     Optimum: the float64 SAH sum of the wide tree on the binary tree's float32 boxes equals the optimum of the recurrences in the header
@@ -282,7 +309,7 @@ def test_wide_collapse_cuts_the_binary_tree_at_its_optimum(restated, name, kind)
     programme (a sum of two child costs, the area term, the leaf product) and nothing else.
     Choice: among cuts of equal cost the tree is the one the same recurrences give in float32 with the lowest k on equal sums, the leaf
     form when it costs no more, and no extra slot unless strictly cheaper -- wide node for wide node, child for child."""
-    s = restated(name)
+    s = restated(name, budget)
     _assert_wide_is_optimal_cut(s, s.tree(kind), s.built(kind, "wide8"), f"{name} {kind} wide8")
 
 

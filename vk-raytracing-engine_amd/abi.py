@@ -318,6 +318,7 @@ VKRT_SYMBOLS = [
     "vkrt_debug_read_accel",
     "vkrt_debug_read_node_masks",
     "vkrt_debug_read_triangle_ids",
+    "vkrt_debug_split_references",
     "vkrt_debug_read_vertices",
     "vkrt_debug_closest_point_work",
     "vkrt_debug_trace_rays",
@@ -400,6 +401,9 @@ def declare_vkrt(lib):
     lib.vkrt_debug_read_node_masks.restype = C.c_int
     lib.vkrt_debug_read_triangle_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     lib.vkrt_debug_read_triangle_ids.restype = C.c_int
+    # (scene, percent, prio, scale, ref_tri, ref_box: host pointers, the first two may be NULL; capacity in references; ref_count)
+    lib.vkrt_debug_split_references.argtypes = [C.c_void_p, c_u, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, P(c_u)]
+    lib.vkrt_debug_split_references.restype = C.c_int
     lib.vkrt_debug_check_accel.argtypes = [C.c_void_p, P(AccelCheck)]
     lib.vkrt_debug_check_accel.restype = C.c_int
     lib.vkrt_debug_read_accel.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, P(C.c_int32)]

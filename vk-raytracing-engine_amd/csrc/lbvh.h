@@ -43,4 +43,13 @@ int ploc_cluster_device(uint32_t T, const unsigned* order, const float* triBox, 
 int build_lbvh_device(const DevScene& sc, uint32_t instCount, const std::vector<vkrt_prim_mesh>& pm, const std::vector<vkrt_node>& nodes,
                       const LbvhParams& p, hipStream_t stream, LbvhResult& out);
 
+// What triangle pre-splitting makes of the scene for a budget of splitPercent % (vkrt_debug_split_references): the flattening and the
+// pre-split stage of build_lbvh_device and nothing after them, downloaded into host arrays -- the priorities [triangles] and the scale D
+// (either may be null; zeros when the budget rounds to 0 splits), and the references in emission order, refTri [refCount] and
+// refBox [6 x refCount]; the identity list with the whole-triangle boxes when nothing was split.  A capacity below triangles + budget
+// is VKRT_ERR_INVALID_ARGUMENT and writes nothing.  No tree is built or touched.
+int split_references_device(const DevScene& sc, uint32_t instCount, const std::vector<vkrt_prim_mesh>& pm, const std::vector<vkrt_node>& nodes,
+                            unsigned splitPercent, hipStream_t stream, float* prio, float* scale, uint32_t* refTri, float* refBox, uint64_t capacity,
+                            uint32_t* refCount, std::string& err);
+
 }  // namespace vkrt

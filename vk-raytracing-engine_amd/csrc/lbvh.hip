@@ -446,13 +446,30 @@ VKRT_DEV int splitPlane(const SplitGrid& G, const float* b, float& pos, int& mOu
 #pragma unroll
   for(int k = 0; k < 3; k++)
   {
-    const unsigned qa = splitCell(G, k, b[k]), qb = splitCell(G, k, b[3 + k]);
-    if(qa == qb)
+    unsigned qa = splitCell(G, k, b[k]), qb = splitCell(G, k, b[3 + k]);
+    // The most important plane between the two cells that lies strictly inside the box.  A face that lies ON a plane -- the upper face of
+    // every left half: it was cut there -- has that very plane as the most important one between its cells; the search then goes on among
+    // the planes on the box's side of it (each step lowers the bit index, so it ends).  Giving the axis up instead left every left half
+    // uncuttable on the axis it came from: a room-sized triangle with 255 splits came out in 83 pieces, the other splits unspent.
+    int m = -1;
+    float c = 0.0f;
+    while(qa != qb)
+    {
+      const int mq = 31 - __clz((int)(qa ^ qb));
+      const unsigned q = (qb >> mq) << mq;
+      c = G.lo[k] + (float)q * (G.ext[k] / (float)(1u << VKRT_SPLIT_GRID_BITS));
+      if(c > b[k] && c < b[3 + k])
+      {
+        m = mq;
+        break;
+      }
+      if(c >= b[3 + k])
+        qb = q - 1u;  // on (or, by rounding, beyond) the upper face
+      else
+        qa = q;       // on or below the lower face
+    }
+    if(m < 0)
       continue;
-    const int m = 31 - __clz((int)(qa ^ qb));
-    const float c = G.lo[k] + (float)((qb >> m) << m) * (G.ext[k] / (float)(1u << VKRT_SPLIT_GRID_BITS));
-    if(!(c > b[k] && c < b[3 + k]))
-      continue;  // (rounding put the plane on the box's face: nothing to cut on this axis)
     const float ext = b[3 + k] - b[k];
     if(m > mBest || (m == mBest && ext > extBest))
     {
@@ -998,6 +1015,8 @@ struct Leaves
   float* box = nullptr;
   unsigned long long* keys = nullptr;
   unsigned* order = nullptr;
+  const float* prio = nullptr;   // pre-splitting ran: the priority of every triangle and the scale D (what split_references_device shows)
+  const float* scale = nullptr;
 };
 
 // The binary hierarchy over the sorted leaves (node 0 is the root).
@@ -1075,6 +1094,8 @@ int preSplit(Ctx& c, const DevScene& sc, const Flat& f, unsigned splitPercent, L
   hipLaunchKernelGGL((k_split_refs<false>), dim3(G3), dim3(B), 0, c.stream, triangles, (const float4*)f.triU, (const float*)f.triBox, (const unsigned*)f.bounds,
                      watertight, (const float*)prio, (const float*)dD, counts, (unsigned*)nullptr, (float*)nullptr);
   VKRT_TRY(c.err, hipGetLastError());
+  l.prio = prio;
+  l.scale = dD;
   size_t scanBytes = 0;
   VKRT_TRY(c.err, rocprim::exclusive_scan(nullptr, scanBytes, counts, offsets, 0u, (size_t)triangles + 1, rocprim::plus<unsigned>(), c.stream));
   char* scanTmp;
@@ -1278,6 +1299,55 @@ int build_lbvh_device(const DevScene& sc, uint32_t instCount, const std::vector<
   if(p.wide && (rc = collapse_wide8_device(T, t.buf, h.parentInternal, h.parentLeaf, stream, out.wide, c.err)) != VKRT_OK)
     return rc;
   return readBack(c, h, t);
+}
+
+int split_references_device(const DevScene& sc, uint32_t instCount, const std::vector<vkrt_prim_mesh>& pm, const std::vector<vkrt_node>& nodes,
+                            unsigned splitPercent, hipStream_t stream, float* prio, float* scale, uint32_t* refTri, float* refBox, uint64_t capacity,
+                            uint32_t* refCount, std::string& err)
+{
+  uint64_t triangles = 0;  // (what flattenInstances will count: checked before anything is launched)
+  for(uint32_t n = 0; n < instCount; n++) triangles += pm[nodes[n].primMesh].indexCount / 3;
+  if(capacity < triangles + triangles * splitPercent / 100u)
+  {
+    err = "a capacity of " + std::to_string(capacity) + " references for " + std::to_string(triangles) + " triangles and a budget of " +
+          std::to_string(triangles * splitPercent / 100u);
+    return VKRT_ERR_INVALID_ARGUMENT;
+  }
+  Ctx c{stream, err, {}};
+  Flat f;
+  int rc = flattenInstances(c, sc, instCount, pm, nodes, f);
+  if(rc != VKRT_OK)
+    return rc;
+  Leaves l;
+  if((rc = preSplit(c, sc, f, splitPercent, l)) != VKRT_OK)
+    return rc;
+  VKRT_TRY(c.err, hipStreamSynchronize(stream));
+  if(l.T > capacity)
+  {
+    err = "triangle pre-splitting: more references than the budget allows (internal error)";
+    return VKRT_ERR_HIP;
+  }
+  if(prio && triangles)
+  {
+    if(l.prio)
+      VKRT_TRY(c.err, hipMemcpy(prio, l.prio, (size_t)triangles * 4, hipMemcpyDeviceToHost));
+    else
+      std::fill(prio, prio + triangles, 0.0f);
+  }
+  if(scale)
+  {
+    *scale = 0.0f;
+    if(l.scale)
+      VKRT_TRY(c.err, hipMemcpy(scale, l.scale, 4, hipMemcpyDeviceToHost));
+  }
+  if(l.T)
+    VKRT_TRY(c.err, hipMemcpy(refBox, l.box, (size_t)l.T * 24, hipMemcpyDeviceToHost));
+  if(l.tri)
+    VKRT_TRY(c.err, hipMemcpy(refTri, l.tri, (size_t)l.T * 4, hipMemcpyDeviceToHost));
+  else
+    for(uint32_t g = 0; g < l.T; g++) refTri[g] = g;
+  *refCount = l.T;
+  return VKRT_OK;
 }
 
 }  // namespace vkrt

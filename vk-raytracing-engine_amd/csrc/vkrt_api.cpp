@@ -1858,6 +1858,30 @@ int vkrt_debug_read_triangle_ids(vkrt_scene* s, uint32_t* out, uint64_t bytes)
   return VKRT_OK;
 }
 
+int vkrt_debug_split_references(vkrt_scene* s, uint32_t split_percent, float* prio, float* scale, uint32_t* ref_tri, float* ref_box, uint64_t capacity,
+                                uint32_t* ref_count)
+{
+  if(!s || !ref_tri || !ref_box || !ref_count)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "NULL argument");
+  if(split_percent < 1u || split_percent > 100u)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_debug_split_references: a budget of %u %% (1..100)", split_percent);
+  if(vkrt_device_count() <= 0)
+    return fail(VKRT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
+  int rc = setDevice(s);
+  if(rc != VKRT_OK)
+    return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  // the builders' view of the scene with the option as it stands now; the installed tree keeps the setting it was built with
+  DevScene sc = s->dev;
+  sc.watertight = s->opt[VKRT_OPT_WATERTIGHT] != 0 ? 1u : 0u;
+  std::string err;
+  rc = vkrt::split_references_device(sc, (uint32_t)s->nodes.size(), s->primMeshes, s->nodes, split_percent, nullptr, prio, scale, ref_tri, ref_box,
+                                     capacity, ref_count, err);
+  if(rc != VKRT_OK)
+    return fail(rc, "vkrt_debug_split_references: %s", err.c_str());
+  return VKRT_OK;
+}
+
 int vkrt_debug_check_accel(vkrt_scene* s, vkrt_accel_check* out)
 {
   if(!s || !out)

@@ -139,6 +139,7 @@ class Renderer:
         self._prim_mesh = np.array(flat.nodes["primMesh"], np.int32)  # update_nodes keeps every node's primMesh
         self._vertex_count = int(flat.positions.shape[0])
         self._material_count = int(flat.materials.shape[0])
+        self._triangle_count = int((np.asarray(flat.prim_meshes["indexCount"], np.int64)[self._prim_mesh] // 3).sum())  # instanced
         self._skins = []  # (first, count, joint_count) of every add_skin, in the library's numbering
         for k, v in (options or {}).items():
             self.set_option(k, v)
@@ -409,6 +410,22 @@ class Renderer:
         out = np.zeros(max(nb, 4) // 4, np.uint32)
         _check(self.lib.vkrt_debug_read_triangle_ids(self._h, out.ctypes.data, nb), "vkrt_debug_read_triangle_ids")
         return out[: nb // 4]
+
+    def split_references(self, percent):
+        """What triangle pre-splitting makes of the scene for a budget of `percent` % (vkrt_debug_split_references, synchronises; needs no
+        tree): a dict of numpy arrays -- "prio" float32 [T], "scale" float32 (D), "ref_tri" uint32 [R] and "ref_box" float32 [R, 6] (lo3,
+        hi3) in emission order, and "ref_count" = R."""
+        T = self._triangle_count
+        cap = T + T * int(percent) // 100
+        prio = np.zeros(max(T, 1), np.float32)
+        scale = np.zeros(1, np.float32)
+        tri = np.zeros(max(cap, 1), np.uint32)
+        box = np.zeros((max(cap, 1), 6), np.float32)
+        n = C.c_uint32(0)
+        _check(self.lib.vkrt_debug_split_references(self._h, int(percent), prio.ctypes.data, scale.ctypes.data, tri.ctypes.data, box.ctypes.data, cap,
+                                                    C.byref(n)), "vkrt_debug_split_references")
+        R = int(n.value)
+        return {"prio": prio[:T], "scale": scale[0], "ref_tri": tri[:R].copy(), "ref_box": box[:R].copy(), "ref_count": R}
 
     def refit(self, stream=None):
         """vkrt_accel_refit: the built tree follows the current node transforms and vertices (same topology, new boxes), enqueued on
