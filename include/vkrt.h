@@ -385,8 +385,9 @@ int vkrt_scene_update_vertices(vkrt_scene* scene, const vkrt_vertex_update* upda
  * update).  Texture coordinates are never touched by skinning, so an update of them stays.
  * Refused with VKRT_ERR_INVALID_ARGUMENT, changing nothing, in this order: a NULL desc; struct_size < sizeof(vkrt_skin_desc);
  * joint_count 0 or above 65536; NULL joints or weights with count > 0; a joint index >= joint_count; a non-finite weight; a NULL
- * out_skin; a NULL scene; a range outside the scene's vertices; count == 0; a range that overlaps an existing skin's.  Then, without a
- * device: VKRT_ERR_NO_DEVICE.
+ * out_skin; a NULL scene; a range outside the scene's vertices; count == 0; a range that overlaps an existing skin's; a range that
+ * overlaps an existing morph's (vkrt_scene_add_morph: skins are added before the morphs inside them).  Then, without a device:
+ * VKRT_ERR_NO_DEVICE.
  *
  * vkrt_scene_skin_vertices poses skin `skin` from joint_matrices ([joint_count][16], column-major like vkrt_node.worldMatrix: glTF's
  * jointMatrix = inverse(meshGlobal) * jointGlobal * inverseBind, in the space the scene's vertices live in): one kernel launch on
@@ -422,6 +423,66 @@ typedef struct vkrt_skin_desc {
 } vkrt_skin_desc;
 int vkrt_scene_add_skin(vkrt_scene* scene, const vkrt_skin_desc* desc, void* hip_stream, uint32_t* out_skin);
 int vkrt_scene_skin_vertices(vkrt_scene* scene, uint32_t skin, const float* joint_matrices, uint32_t memory /* vkrt_memory */, void* hip_stream);
+
+/* ---- morph targets (glTF primitives[].targets, blend shapes: a displacement of POSITION, NORMAL and TANGENT per target and vertex, a
+ *      vector of weights per frame): base + sum(w * delta) inside the library.  These entry points came after ABI version 4 without
+ *      changing it or any existing struct: detect them by symbol. ---------------------------------------------------------------------
+ * vkrt_scene_add_morph binds target_count targets to the range [first, first+count) (absolute vertex indices, as in
+ * vkrt_vertex_update) and captures the range's base shape: positions, normals and tangents as they stand at this point of hip_stream.
+ * The delta arrays are host arrays, vec3[target_count][count] (target-major: all vertices of target 0, then of target 1, ...), copied
+ * to the device before return; an attribute whose array is NULL is not morphed.  Tangent deltas are xyz only, as in glTF: the
+ * handedness w is kept.  The call may allocate and synchronise.  *out_morph is the morph's number: 0, 1, ... in creation order.
+ * Morphs live until vkrt_scene_destroy and survive builds, refits and node updates; their ranges do not overlap each other.
+ * Where a morph writes (glTF 3.7.2.2: morph, then skin):
+ *   a range that overlaps no skin: the live arrays, like a skin: positions, normals and tangents; texture coordinates are never
+ *     touched.  A later vkrt_scene_update_vertices on the range is allowed: the next vkrt_scene_morph_vertices overwrites positions,
+ *     normals and tangents from the captured base (not from the update).
+ *   a range that lies wholly inside one skin's range: the base is captured from that skin's bind pose, and vkrt_scene_morph_vertices
+ *     writes that bind pose and nothing else -- the live arrays and the tree stay as they are.  The next vkrt_scene_skin_vertices of
+ *     that skin, later on the same stream, carries the morphed shape into the scene.  Add skins before morphs.
+ * Refused with VKRT_ERR_INVALID_ARGUMENT, changing nothing, in this order: a NULL desc; struct_size < sizeof(vkrt_morph_desc);
+ * target_count 0 or above VKRT_MORPH_TARGETS_MAX; all three delta arrays NULL; a non-finite delta (positions, then normals, then
+ * tangents); a NULL out_morph; a NULL scene; a range outside the scene's vertices; count == 0; a range that overlaps an existing
+ * morph's; a range that straddles a skin's boundary or touches two skins.  Then, without a device: VKRT_ERR_NO_DEVICE; if the device
+ * has no memory for the deltas: VKRT_ERR_OUT_OF_MEMORY, and nothing has been added.
+ *
+ * vkrt_scene_morph_vertices poses morph `morph` from weights[target_count]: one kernel launch on hip_stream (ordering as
+ * vkrt_scene_update_vertices).
+ * VKRT_MEMORY_DEVICE: the weights are device memory on the scene's device, 4-byte aligned, valid until the stream has passed the
+ *   call.  Nothing is allocated, nothing synchronises, the values are not inspected.
+ * VKRT_MEMORY_HOST: every weight is checked finite before anything changes; the weights are staged through the scene's staging buffer
+ *   (the one of host vertex updates) and the call waits for hip_stream before it returns.
+ * A morph outside every skin leaves the library's host copy of the positions behind the device's (the next vkrt_accel_build downloads
+ * them first) and, with a built tree, the tree stale exactly as after vkrt_scene_skin_vertices; one vkrt_accel_refit serves any number
+ * of morph, skin, vertex and node updates before it.  vkrt_hit_surface and vkrt_hit_motion see the new shape without a refit.  The
+ * motion snapshot is untouched: mark -> morph -> vkrt_hit_motion gives the shape before the morph call as `previous`.
+ * Refused with VKRT_ERR_INVALID_ARGUMENT, changing nothing, in this order: a memory value that is neither of the two; a NULL scene; a
+ * morph index out of range; NULL or (device memory) misaligned weights; (host memory) a non-finite weight.  Then, without a device:
+ * VKRT_ERR_NO_DEVICE.
+ *
+ * Arithmetic: binary32, in source order, no contraction.  For a vertex with captured base position p, normal n and tangent (t, tw),
+ * deltas dP[k], dN[k], dT[k] of target k and weights w[0..T-1], per component:
+ *     P = p;  for k = 0..T-1 in index order:  if (w[k] != 0)  P = P + w[k] * dP[k]         (the product rounded, then the sum)
+ *     N, Tn likewise from n, t with dN, dT -- only if the morph has that delta array
+ *     p'      = P
+ *     n'      = (the morph has normal deltas and some w[k] != 0) ? normalizeGuarded(N) : n
+ *     t'.xyz  = (the morph has tangent deltas and some w[k] != 0) ? normalizeGuarded(Tn) : t ;  t'.w = tw
+ *     normalizeGuarded(a): d = (a.x*a.x + a.y*a.y) + a.z*a.z ;  (d > 0 && d < inf) ? a * (1.0f / sqrtf(d)) : a     (the skin's rule)
+ * A weight of exactly zero, of either sign, skips its target: all-zero weights give back the captured base in every bit (a component
+ * that is -0 stays -0, which -0 + 0 * d would not), and the kernel reads only the targets that are in use.  An attribute without deltas
+ * is written from the captured base. */
+#define VKRT_MORPH_TARGETS_MAX 256
+typedef struct vkrt_morph_desc {
+  uint32_t struct_size;            /* sizeof(vkrt_morph_desc) */
+  uint32_t first, count;           /* vertices [first, first+count), absolute indices as in vkrt_vertex_update */
+  uint32_t target_count;           /* 1..VKRT_MORPH_TARGETS_MAX */
+  const float* position_deltas;    /* host, vec3[target_count][count] (target-major) or NULL */
+  const float* normal_deltas;      /* host, vec3[target_count][count] or NULL */
+  const float* tangent_deltas;     /* host, vec3[target_count][count] or NULL (glTF: xyz only, w is kept) */
+} vkrt_morph_desc;
+int vkrt_scene_add_morph(vkrt_scene* scene, const vkrt_morph_desc* desc, void* hip_stream, uint32_t* out_morph);
+int vkrt_scene_morph_vertices(vkrt_scene* scene, uint32_t morph, const float* weights /* [target_count] */, uint32_t memory /* vkrt_memory */,
+                              void* hip_stream);
 
 /* ---- ray queries (replaces traceRayEXT on rays of the caller's own, raytrace.rgen:64-97 / VK_KHR_ray_query: a closest-hit and an
  *      occlusion query per ray of a device array).  These entry points came after ABI version 4 without changing it or any

@@ -218,8 +218,18 @@ class SkinDesc(C.Structure):
     _fields_ = [("struct_size", c_u), ("first", c_u), ("count", c_u), ("joint_count", c_u), ("joints", C.c_void_p), ("weights", C.c_void_p)]
 
 
+# morph targets (vkrt_scene_add_morph): host pointers to float32 [target_count][count][3], NULL for an attribute that is not morphed
+VKRT_MORPH_TARGETS_MAX = 256
+
+
+class MorphDesc(C.Structure):
+    _fields_ = [("struct_size", c_u), ("first", c_u), ("count", c_u), ("target_count", c_u), ("position_deltas", C.c_void_p),
+                ("normal_deltas", C.c_void_p), ("tangent_deltas", C.c_void_p)]
+
+
 assert C.sizeof(VertexUpdate) == 48
 assert C.sizeof(SkinDesc) == 32
+assert C.sizeof(MorphDesc) == 40
 assert C.sizeof(Ray) == 32
 assert C.sizeof(Hit) == 32
 assert C.sizeof(Surface) == 128
@@ -283,6 +293,8 @@ VKRT_SYMBOLS = [
     "vkrt_scene_update_vertices",
     "vkrt_scene_add_skin",
     "vkrt_scene_skin_vertices",
+    "vkrt_scene_add_morph",
+    "vkrt_scene_morph_vertices",
     "vkrt_intersect",
     "vkrt_occluded",
     "vkrt_scene_set_instance_visibility",
@@ -360,6 +372,11 @@ def declare_vkrt(lib):
     lib.vkrt_scene_add_skin.restype = C.c_int
     lib.vkrt_scene_skin_vertices.argtypes = [C.c_void_p, c_u, C.c_void_p, c_u, C.c_void_p]
     lib.vkrt_scene_skin_vertices.restype = C.c_int
+    # (scene, desc, stream, out_morph) / (scene, morph, weights: host or device pointer by `memory`, memory, stream)
+    lib.vkrt_scene_add_morph.argtypes = [C.c_void_p, P(MorphDesc), C.c_void_p, P(c_u)]
+    lib.vkrt_scene_add_morph.restype = C.c_int
+    lib.vkrt_scene_morph_vertices.argtypes = [C.c_void_p, c_u, C.c_void_p, c_u, C.c_void_p]
+    lib.vkrt_scene_morph_vertices.restype = C.c_int
     # (scene, first, count, positions, normals, tangents, texcoords0: host pointers, any may be NULL)
     lib.vkrt_debug_read_vertices.argtypes = [C.c_void_p, c_u, c_u, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.vkrt_debug_read_vertices.restype = C.c_int

@@ -27,6 +27,7 @@
 #include "wide_node.h"
 
 #include "lbvh.h"
+#include "morph.h"
 #include "refit.h"
 #include "skin.h"
 #include "vertex_update.h"
@@ -111,6 +112,16 @@ struct vkrt_scene
     uint32_t jointCount = 0;
   };
   std::vector<Skin> skins;
+  // morph targets (vkrt_scene_add_morph): per morph one allocation holding the captured base shape and the deltas of its vertex range;
+  // the ranges are disjoint, the index in the list is the morph's number.  skin >= 0: the range lies inside that skin's, and the morph
+  // writes the skin's bind pose instead of the live arrays
+  struct Morph
+  {
+    vkrt::DevBuf mem;
+    vkrt::MorphArrays arrays;
+    int skin = -1;
+  };
+  std::vector<Morph> morphs;
   // ray-query visibility (vkrt_scene_set_instance_visibility): host copy per node, and which masks occur (bit m of masksPresent[m >> 6])
   std::vector<vkrt_instance_visibility> vis;
   uint64_t masksPresent[4] = {0, 0, 0, 0};
@@ -1100,6 +1111,13 @@ int vkrt_scene_add_skin(vkrt_scene* s, const vkrt_skin_desc* k, void* hip_stream
       return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vertices [%u, %u) overlap skin %zu's [%u, %u)", who, k->first, k->first + k->count, j, a.first,
                   a.first + a.count);
   }
+  for(size_t j = 0; j < s->morphs.size(); j++)
+  {  // (skins come first: a morph inside a skin's range captured its base from that skin's bind pose)
+    const vkrt::MorphArrays& a = s->morphs[j].arrays;
+    if(k->first < a.first + a.count && a.first < k->first + k->count)
+      return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vertices [%u, %u) overlap morph %zu's [%u, %u): add skins before morphs", who, k->first,
+                  k->first + k->count, j, a.first, a.first + a.count);
+  }
   int rc = setDevice(s);
   if(rc != VKRT_OK)
     return rc;
@@ -1158,6 +1176,147 @@ int vkrt_scene_skin_vertices(vkrt_scene* s, uint32_t skin, const float* joint_ma
   s->positionsOnDevice = true;  // (host matrices too: the posed positions exist on the device only)
   if(s->built)
     s->stale = true;
+  return VKRT_OK;
+}
+
+int vkrt_scene_add_morph(vkrt_scene* s, const vkrt_morph_desc* m, void* hip_stream, uint32_t* out_morph)
+{
+  const char* who = "vkrt_scene_add_morph";
+  if(!m)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: desc is NULL", who);
+  if(m->struct_size < sizeof(vkrt_morph_desc))
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vkrt_morph_desc.struct_size %u < %zu (ABI mismatch)", who, m->struct_size, sizeof(vkrt_morph_desc));
+  if(m->target_count == 0 || m->target_count > VKRT_MORPH_TARGETS_MAX)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: target_count %u outside 1..%u", who, m->target_count, (unsigned)VKRT_MORPH_TARGETS_MAX);
+  if(!m->position_deltas && !m->normal_deltas && !m->tangent_deltas)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: position_deltas, normal_deltas and tangent_deltas are all NULL", who);
+  const size_t n = m->count, floats = (size_t)m->target_count * n * 3;
+  const float* const deltas[3] = {m->position_deltas, m->normal_deltas, m->tangent_deltas};
+  const char* const names[3] = {"position_deltas", "normal_deltas", "tangent_deltas"};
+  for(int a = 0; a < 3; a++)
+    if(deltas[a])
+      for(size_t i = 0; i < floats; i++)
+        if(!std::isfinite(deltas[a][i]))
+          return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: %s[%zu] (target %zu, vertex %zu) is not finite", who, names[a], i, i / (3 * n),
+                      (size_t)m->first + i / 3 % n);
+  if(!out_morph)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: out_morph is NULL", who);
+  if(!s)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
+  const size_t vertexCount = s->positions.size() / 3;
+  if((uint64_t)m->first + m->count > vertexCount)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vertices [%u, %llu) outside the scene's %zu vertices", who, m->first,
+                (unsigned long long)m->first + m->count, vertexCount);
+  if(n == 0)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: count is 0", who);
+  const uint32_t end = m->first + m->count;
+  for(size_t j = 0; j < s->morphs.size(); j++)
+  {
+    const vkrt::MorphArrays& a = s->morphs[j].arrays;
+    if(m->first < a.first + a.count && a.first < end)
+      return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vertices [%u, %u) overlap morph %zu's [%u, %u)", who, m->first, end, j, a.first, a.first + a.count);
+  }
+  int inSkin = -1;
+  for(size_t j = 0; j < s->skins.size(); j++)
+  {  // inside one skin or clear of all of them (the skins are disjoint: a range inside one touches no other)
+    const vkrt::SkinArrays& a = s->skins[j].arrays;
+    if(!(m->first < a.first + a.count && a.first < end))
+      continue;
+    if(m->first < a.first || end > a.first + a.count)
+      return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vertices [%u, %u) straddle the boundary of skin %zu's [%u, %u): a morph lies inside one skin or outside all",
+                  who, m->first, end, j, a.first, a.first + a.count);
+    inSkin = (int)j;
+  }
+  int rc = setDevice(s);
+  if(rc != VKRT_OK)
+    return rc;
+  vkrt_scene::Morph morph;
+  morph.skin = inSkin;
+  const bool has[3] = {deltas[0] != nullptr, deltas[1] != nullptr, deltas[2] != nullptr};
+  if(morph.mem.alloc(vkrt::morph_bytes(m->count, m->target_count, has[0], has[1], has[2])) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return fail(VKRT_ERR_OUT_OF_MEMORY, "%s: no device memory for %u targets of %u vertices", who, m->target_count, m->count);
+  }
+  vkrt::MorphArrays& a = morph.arrays;
+  vkrt::morph_carve(morph.mem.get(), m->first, m->count, m->target_count, has[0], has[1], has[2], a);
+  float* const dst[3] = {a.dPos, a.dNrm, a.dTan};
+  for(int i = 0; i < 3; i++)
+    if(deltas[i])
+      HIP_TRY(hipMemcpy(dst[i], deltas[i], floats * sizeof(float), hipMemcpyHostToDevice));
+  // stream-ordered like the update calls: the base is what the calls enqueued before this one on hip_stream left
+  hipStream_t stream = (hipStream_t)hip_stream;
+  if(inSkin < 0)
+  {  // (skin.hip's capture: a morph's base arrays are laid out like a skin's bind pose)
+    vkrt::SkinArrays cap;
+    cap.first = a.first, cap.count = a.count, cap.bindPN = a.basePN, cap.bindNyz = a.baseNyz, cap.bindTan = a.baseTan;
+    HIP_TRY(vkrt::launch_skin_capture(s->dev.positions, s->dev.vertexPN, cap, stream));
+  }
+  else
+  {
+    const vkrt::SkinArrays& k = s->skins[inSkin].arrays;
+    const size_t off = m->first - k.first;
+    HIP_TRY(hipMemcpyAsync(a.basePN, k.bindPN + off, n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(a.baseNyz, k.bindNyz + off, n * sizeof(float2), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(a.baseTan, k.bindTan + off, n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+  }
+  *out_morph = (uint32_t)s->morphs.size();
+  s->morphs.push_back(std::move(morph));
+  return VKRT_OK;
+}
+
+int vkrt_scene_morph_vertices(vkrt_scene* s, uint32_t morph, const float* weights, uint32_t memory, void* hip_stream)
+{
+  const char* who = "vkrt_scene_morph_vertices";
+  if(memory != VKRT_MEMORY_HOST && memory != VKRT_MEMORY_DEVICE)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: memory %u is neither VKRT_MEMORY_HOST nor VKRT_MEMORY_DEVICE", who, memory);
+  if(!s)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
+  if(morph >= s->morphs.size())
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: morph %u outside the scene's %zu morphs", who, morph, s->morphs.size());
+  const bool host = memory == VKRT_MEMORY_HOST;
+  if(!weights)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: weights is NULL", who);
+  if(!host && ((uintptr_t)weights & 3u) != 0)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: weights %p is not 4-byte aligned", who, (const void*)weights);
+  const vkrt_scene::Morph& m = s->morphs[morph];
+  const size_t bytes = (size_t)m.arrays.targetCount * sizeof(float);
+  if(host)
+    for(uint32_t i = 0; i < m.arrays.targetCount; i++)
+      if(!std::isfinite(weights[i]))
+        return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: weights[%u] is not finite", who, i);
+  int rc = setDevice(s);
+  if(rc != VKRT_OK)
+    return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const float* w = weights;
+  if(host)
+  {  // through the staging buffer of host vertex updates (every earlier host call has waited for its stream: nothing reads it)
+    if(bytes > s->vertexStageBytes)
+    {
+      s->vertexStageBytes = 0;
+      HIP_TRY(s->vertexStage.alloc(bytes));
+      s->vertexStageBytes = bytes;
+    }
+    HIP_TRY(hipMemcpyAsync(s->vertexStage.get(), weights, bytes, hipMemcpyHostToDevice, stream));
+    w = s->vertexStage.get<const float>();
+  }
+  if(m.skin >= 0)
+  {  // morph, then skin: the skin's next pose reads the morphed bind pose; the live arrays and the tree are as they were
+    const vkrt::SkinArrays& k = s->skins[m.skin].arrays;
+    const size_t off = m.arrays.first - k.first;
+    HIP_TRY(vkrt::launch_morph_bind(k.bindPN + off, k.bindNyz + off, k.bindTan + off, m.arrays, w, stream));
+  }
+  else
+    HIP_TRY(vkrt::launch_morph_live(const_cast<float*>(s->dev.positions), const_cast<float4*>(s->dev.vertexPN), m.arrays, w, stream));
+  if(host)
+    HIP_TRY(hipStreamSynchronize(stream));  // the caller's weights and the staging buffer are free again
+  if(m.skin < 0)
+  {
+    s->positionsOnDevice = true;  // (host weights too: the morphed positions exist on the device only)
+    if(s->built)
+      s->stale = true;
+  }
   return VKRT_OK;
 }
 

@@ -90,6 +90,32 @@ void vkrt_host_scene_skin_copy(const void* s_, uint32_t skin, uint16_t* joints0,
   if(restJointMatrices) memcpy(restJointMatrices, k.restJointMatrices.data(), k.restJointMatrices.size() * sizeof(float));
   if(vertexRanges) memcpy(vertexRanges, k.vertexRanges.data(), k.vertexRanges.size() * sizeof(uint32_t));
 }
+// morphs: counts[0] = morphs; then per morph counts[1 + 6 m ..] = first, count, targets, and whether it has position, normal and tangent
+// deltas (0 or 1 each).  `cap` = entries of counts; returns the entries the scene needs.
+uint32_t vkrt_host_scene_morph_counts(const void* s_, uint32_t* counts, uint32_t cap)
+{
+  const GltfScene* s = (const GltfScene*)s_;
+  const uint32_t need = 1 + 6 * (uint32_t)s->m_morphs.size();
+  if(cap >= 1)
+    counts[0] = (uint32_t)s->m_morphs.size();
+  for(uint32_t m = 0; m < s->m_morphs.size() && 1 + 6 * (m + 1) <= cap; m++)
+  {
+    const GltfMorph& mo = s->m_morphs[m];
+    const uint32_t v[6] = {mo.first, mo.count, mo.targetCount, !mo.positionDeltas.empty(), !mo.normalDeltas.empty(), !mo.tangentDeltas.empty()};
+    memcpy(counts + 1 + 6 * m, v, sizeof v);
+  }
+  return need;
+}
+// morph `morph`: its deltas (f32 [targets][count][3] each) and default weights (f32 per target).  A NULL pointer, or an array the morph
+// does not have, is skipped.
+void vkrt_host_scene_morph_copy(const void* s_, uint32_t morph, float* positionDeltas, float* normalDeltas, float* tangentDeltas, float* weights)
+{
+  const GltfMorph& mo = ((const GltfScene*)s_)->m_morphs.at(morph);
+  if(positionDeltas) memcpy(positionDeltas, mo.positionDeltas.data(), mo.positionDeltas.size() * sizeof(float));
+  if(normalDeltas) memcpy(normalDeltas, mo.normalDeltas.data(), mo.normalDeltas.size() * sizeof(float));
+  if(tangentDeltas) memcpy(tangentDeltas, mo.tangentDeltas.data(), mo.tangentDeltas.size() * sizeof(float));
+  if(weights) memcpy(weights, mo.weights.data(), mo.weights.size() * sizeof(float));
+}
 void vkrt_host_texture_info(const void* s_, uint32_t i, uint32_t* whs)
 {
   const GltfScene* s = (const GltfScene*)s_;
@@ -283,6 +309,50 @@ int vkrt_host_render_gltf_skinned(const char* path, int device, int width, int h
     for(uint32_t k = 0; k < steps; k++)
     {
       vk.skinVertices(skin, std::vector<float>(jointMatrices + (size_t)k * joints * 16, jointMatrices + (size_t)(k + 1) * joints * 16));
+      vk.refitAccel();
+    }
+    vk.m_pcRay.samples = samples;
+    vk.m_pcRay.depth = depth;
+    const float clear[4] = {1, 1, 1, 1};
+    for(int f = 0; f < frames; f++)
+    {
+      vk.updateUniformBuffer();
+      vk.updateFrame();
+      vk.m_seed = seed0 + (uint32_t)f;
+      vk.pathtrace(clear);
+    }
+    std::vector<float> img;
+    vk.downloadImage(img);
+    memcpy(rgbaOut, img.data(), img.size() * sizeof(float));
+    return 0;
+  }
+  catch(const std::exception& e) { g_err = e.what(); return 1; }
+}
+
+// vkrt_host_render_gltf with morph targets: build (the file's default weights are in), then `steps` times
+// HelloVkrt::morphVertices(morph, weights[step]) + refitAccel (weights: steps x targets floats; steps = 0: the file as authored), then
+// the frames.  morphCountOut (may be NULL) receives HelloVkrt::morphCount().
+int vkrt_host_render_gltf_morphed(const char* path, int device, int width, int height, int samples, int depth, int frames, uint32_t seed0,
+                                  const float* eye, const float* center, const float* up, float fov, uint32_t buildFlags, uint32_t morph,
+                                  uint32_t targets, uint32_t steps, const float* weights, uint32_t* morphCountOut, float* rgbaOut)
+{
+  try
+  {
+    HelloVkrt vk(device);
+    vk.setup(width, height);
+    vk.CameraManip.setLookat(Vec3{eye[0], eye[1], eye[2]}, Vec3{center[0], center[1], center[2]}, Vec3{up[0], up[1], up[2]});
+    vk.CameraManip.setFov(fov);
+    vk.loadGltfScene(path);
+    vk.createOffscreenRender();
+    vk.initRayTracing();
+    vk.m_buildFlags = buildFlags;
+    vk.createBottomLevelASGltf();
+    vk.createTopLevelAsGltf();
+    if(morphCountOut)
+      *morphCountOut = vk.morphCount();
+    for(uint32_t k = 0; k < steps; k++)
+    {
+      vk.morphVertices(morph, std::vector<float>(weights + (size_t)k * targets, weights + (size_t)(k + 1) * targets));
       vk.refitAccel();
     }
     vk.m_pcRay.samples = samples;

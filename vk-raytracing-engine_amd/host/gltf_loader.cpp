@@ -245,6 +245,57 @@ void readWeights(const Doc& d, int idx, std::vector<float>& out, size_t& count)
       throw std::runtime_error("gltf: WEIGHTS_0 accessor " + std::to_string(idx) + " holds a non-finite weight");
 }
 
+// One attribute of one morph target: a VEC3 accessor of floats with one element per vertex, dense or sparse.  A sparse accessor starts
+// from its bufferView, or from zeros without one, and has `sparse.count` elements replaced: element sparse.indices[i] (unsigned bytes,
+// shorts or ints, increasing) becomes sparse.values[i] -- the way exporters store targets that move a few vertices.
+void readTargetAccessor(const Doc& d, int idx, const char* semantic, size_t vcount, std::vector<float>& out)
+{
+  const std::string name = std::string("gltf: morph target ") + semantic + " accessor " + std::to_string(idx);
+  if(idx < 0 || (size_t)idx >= d.g["accessors"].size())
+    throw std::runtime_error(name + " does not exist");
+  const Json& a = d.g["accessors"][(size_t)idx];
+  if(a["type"].string() != "VEC3" || a["componentType"].integer() != 5126)
+    throw std::runtime_error(name + " is not a VEC3 of floats");
+  size_t count = 0;
+  readAccessorFloat(d, idx, 3, out, count);
+  if(count != vcount)
+    throw std::runtime_error(name + " has " + std::to_string(count) + " elements, the primitive has " + std::to_string(vcount) + " vertices");
+  if(a.has("sparse"))
+  {
+    const Json& sp = a["sparse"];
+    const size_t n = (size_t)sp["count"].integer(0);
+    if(n > count)
+      throw std::runtime_error(name + ": sparse.count " + std::to_string(n) + " above the accessor's count");
+    const Json &si = sp["indices"], &sv = sp["values"];
+    const int ict = si["componentType"].integer(0);
+    if(ict != 5121 && ict != 5123 && ict != 5125)
+      throw std::runtime_error(name + ": sparse.indices.componentType " + std::to_string(ict) + " is not an unsigned byte, short or int");
+    if(!si.has("bufferView") || !sv.has("bufferView"))
+      throw std::runtime_error(name + ": sparse.indices or sparse.values without a bufferView");
+    const Json &ibv = d.g["bufferViews"][(size_t)si["bufferView"].integer()], &vbv = d.g["bufferViews"][(size_t)sv["bufferView"].integer()];
+    const std::vector<uint8_t>&ibuf = d.buffers.at((size_t)ibv["buffer"].integer()), &vbuf = d.buffers.at((size_t)vbv["buffer"].integer());
+    const size_t ioff = (size_t)ibv["byteOffset"].integer(0) + (size_t)si["byteOffset"].integer(0);
+    const size_t voff = (size_t)vbv["byteOffset"].integer(0) + (size_t)sv["byteOffset"].integer(0);
+    const size_t is = (size_t)compSize(ict);
+    if(ioff + n * is > ibuf.size() || voff + n * 12 > vbuf.size())
+      throw std::runtime_error(name + ": sparse data overruns its buffer");
+    for(size_t i = 0; i < n; i++)
+    {
+      uint32_t at = 0;
+      const uint8_t* p = ibuf.data() + ioff + i * is;
+      if(is == 1) at = p[0];
+      else if(is == 2) { uint16_t x; memcpy(&x, p, 2); at = x; }
+      else memcpy(&at, p, 4);
+      if(at >= count)
+        throw std::runtime_error(name + ": sparse index " + std::to_string(at) + " outside its " + std::to_string(count) + " elements");
+      memcpy(&out[3 * (size_t)at], vbuf.data() + voff + i * 12, 12);
+    }
+  }
+  for(float v : out)
+    if(!std::isfinite(v))
+      throw std::runtime_error(name + " holds a non-finite value");
+}
+
 int textureIndex(const Json& obj, const char* key)
 {
   const Json& t = obj[key];
@@ -555,6 +606,7 @@ GltfScene loadGltf(const std::string& filename)
   std::map<std::string, std::pair<uint32_t, uint32_t>> cache;  // attribute key -> (vertexOffset, vertexCount)
   const bool hasSkins = g["skins"].size() > 0;  // then every vertex carries four influences (zeros where a primitive has none)
   std::vector<bool> primSkinned;                // per primitive-mesh: it has JOINTS_0 / WEIGHTS_0
+  std::vector<int> meshTargets(g["meshes"].size(), -1);  // per glTF mesh: the morph target count of its primitives (they must agree)
   for(size_t mi = 0; mi < g["meshes"].size(); mi++)
   {
     const Json& prims = g["meshes"][mi]["primitives"];
@@ -571,6 +623,27 @@ GltfScene loadGltf(const std::string& filename)
       std::sort(keyv.begin(), keyv.end());
       std::ostringstream key;
       for(const auto& kv : keyv) key << kv.first << kv.second << ";";
+      // (primitives share vertices only where they share their morph targets too)
+      const Json& targets = prim["targets"];
+      for(size_t t = 0; t < targets.size(); t++)
+      {
+        key << "|";
+        for(const char* sem : {"POSITION", "NORMAL", "TANGENT"})
+          if(targets[t].has(sem)) key << sem << targets[t][sem].integer() << ";";
+      }
+      if(targets.size() > VKRT_MORPH_TARGETS_MAX)
+        throw std::runtime_error("gltf: mesh " + std::to_string(mi) + " primitive " + std::to_string(pi) + " has " + std::to_string(targets.size()) +
+                                 " morph targets (at most " + std::to_string(VKRT_MORPH_TARGETS_MAX) + ")");
+      for(size_t t = 0; t < targets.size(); t++)
+        for(const auto& kv : targets[t].obj)
+          if(kv.first != "POSITION" && kv.first != "NORMAL" && kv.first != "TANGENT")
+            throw std::runtime_error("gltf: mesh " + std::to_string(mi) + " primitive " + std::to_string(pi) + ": morph target attribute " + kv.first +
+                                     " (accessor " + std::to_string(kv.second.integer()) + ") is not POSITION, NORMAL or TANGENT");
+      if(meshTargets[mi] < 0)
+        meshTargets[mi] = (int)targets.size();
+      else if((size_t)meshTargets[mi] != targets.size())
+        throw std::runtime_error("gltf: mesh " + std::to_string(mi) + " primitive " + std::to_string(pi) + " has " + std::to_string(targets.size()) +
+                                 " morph targets, an earlier primitive of the mesh has " + std::to_string(meshTargets[mi]));
 
       if(hasSkins && attr.has("JOINTS_0") != attr.has("WEIGHTS_0"))
         throw std::runtime_error(std::string("gltf: primitive with ") + (attr.has("JOINTS_0") ? "JOINTS_0 but no WEIGHTS_0" : "WEIGHTS_0 but no JOINTS_0"));
@@ -661,6 +734,43 @@ GltfScene loadGltf(const std::string& filename)
           sc.m_joints0.insert(sc.m_joints0.end(), jnt.begin(), jnt.end());
           sc.m_weights0.insert(sc.m_weights0.end(), wgt.begin(), wgt.end());
         }
+        if(targets.size() > 0)
+        {  // target-major: all vertices of target 0, then of target 1, ...; a target without an attribute that another has moves nothing
+          GltfMorph mo;
+          mo.first = pm.vertexOffset;
+          mo.count = pm.vertexCount;
+          mo.targetCount = (uint32_t)targets.size();
+          mo.mesh = (int32_t)mi;
+          const char* sems[3] = {"POSITION", "NORMAL", "TANGENT"};
+          std::vector<float>* dst[3] = {&mo.positionDeltas, &mo.normalDeltas, &mo.tangentDeltas};
+          for(int k = 0; k < 3; k++)
+          {
+            bool any = false;
+            for(size_t t = 0; t < targets.size(); t++) any = any || targets[t].has(sems[k]);
+            if(!any)
+              continue;
+            dst[k]->assign(targets.size() * vcount * 3, 0.f);
+            for(size_t t = 0; t < targets.size(); t++)
+              if(targets[t].has(sems[k]))
+              {
+                std::vector<float> one;
+                readTargetAccessor(doc, targets[t][sems[k]].integer(-1), sems[k], vcount, one);
+                std::copy(one.begin(), one.end(), dst[k]->begin() + t * vcount * 3);
+              }
+          }
+          if(mo.positionDeltas.empty() && mo.normalDeltas.empty() && mo.tangentDeltas.empty())
+            throw std::runtime_error("gltf: mesh " + std::to_string(mi) + " primitive " + std::to_string(pi) + ": morph targets without POSITION, NORMAL or TANGENT");
+          mo.weights.assign(targets.size(), 0.f);
+          const Json& mw = g["meshes"][mi]["weights"];
+          if(g["meshes"][mi].has("weights"))
+          {
+            if(mw.size() != targets.size())
+              throw std::runtime_error("gltf: mesh " + std::to_string(mi) + ": " + std::to_string(mw.size()) + " weights for " + std::to_string(targets.size()) +
+                                       " morph targets");
+            for(size_t t = 0; t < targets.size(); t++) mo.weights[t] = (float)mw[t].number();
+          }
+          sc.m_morphs.push_back(std::move(mo));
+        }
       }
       primSkinned.push_back(skinned);
       sc.m_indices.insert(sc.m_indices.end(), idx.begin(), idx.end());
@@ -704,6 +814,7 @@ GltfScene loadGltf(const std::string& filename)
     sc.m_skins.push_back(sk);
   }
   std::map<uint32_t, int> rangeSkin;  // vertexOffset of a skinned primitive-mesh -> the skin that poses its vertices
+  std::vector<bool> meshWeightsFromNode(g["meshes"].size(), false);  // the mesh has met its first node: the default morph weights are settled
 
   // ---- node hierarchy (processNode) -------------------------------------------------------------------
   struct LightRef { M4 world; int light; };
@@ -730,6 +841,20 @@ GltfScene loadGltf(const std::string& filename)
     {
       const size_t mi = (size_t)node["mesh"].integer();
       if(mi >= meshToPrims.size()) throw std::runtime_error("gltf: bad mesh index");
+      // morph weights of the node override the mesh's -- for the first node that instances the mesh: its vertices exist once, so a mesh
+      // that several nodes instance morphs in all of them, as a vertex update does
+      if(node.has("weights") && meshTargets[mi] > 0)
+      {
+        const Json& nw = node["weights"];
+        if(nw.size() != (size_t)meshTargets[mi])
+          throw std::runtime_error("gltf: node " + std::to_string(ni) + ": " + std::to_string(nw.size()) + " weights for mesh " + std::to_string(mi) + "'s " +
+                                   std::to_string(meshTargets[mi]) + " morph targets");
+        if(!meshWeightsFromNode[mi])
+          for(GltfMorph& mo : sc.m_morphs)
+            if(mo.mesh == (int32_t)mi)
+              for(size_t t = 0; t < nw.size(); t++) mo.weights[t] = (float)nw[t].number();
+      }
+      meshWeightsFromNode[mi] = true;  // (a first node without weights keeps the mesh's)
       const int skin = node.has("skin") ? node["skin"].integer(-1) : -1;
       if(node.has("skin") && (skin < 0 || (size_t)skin >= sc.m_skins.size()))
         throw std::runtime_error("gltf: node " + std::to_string(ni) + ": bad skin index");

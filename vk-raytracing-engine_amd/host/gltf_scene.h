@@ -29,6 +29,21 @@ struct GltfSkin
   std::vector<uint32_t> vertexRanges;    // (first, count) pairs: the vertex ranges of the primitive-meshes that use the skin
 };
 
+// The morph targets of one primitive-mesh's vertex range (glTF primitives[].targets): a vkrt_morph_desc's arrays and the weights the file
+// authored.  A range inside a skinned primitive is morphed first and skinned after (glTF 2.0, section 3.7.2.2).
+struct GltfMorph
+{
+  uint32_t first = 0, count = 0;      // the vertex range
+  uint32_t targetCount = 0;
+  int32_t mesh = -1;                  // glTF mesh index
+  std::vector<float> positionDeltas;  // vec3[targetCount][count], target-major; empty when no target has POSITION
+  std::vector<float> normalDeltas;    // likewise for NORMAL
+  std::vector<float> tangentDeltas;   // likewise for TANGENT (xyz)
+  // mesh.weights (zeros without), overridden by `weights` of the first node, in traversal order, that instances the mesh.  The
+  // vertices belong to the mesh, not to a node: a mesh that several nodes instance morphs in all of them, as a vertex update does.
+  std::vector<float> weights;
+};
+
 struct GltfScene
 {
   std::vector<float> m_positions;   // vec3
@@ -38,6 +53,7 @@ struct GltfScene
   std::vector<uint16_t> m_joints0;  // u16 x 4 per vertex (JOINTS_0; zeros where a primitive has none); empty when the file has no skin
   std::vector<float> m_weights0;    // f32 x 4 per vertex (WEIGHTS_0), like m_joints0
   std::vector<GltfSkin> m_skins;
+  std::vector<GltfMorph> m_morphs;  // one per vertex range that has morph targets, in vertex order
   std::vector<uint32_t> m_indices;
   std::vector<vkrt_prim_mesh> m_primMeshes;
   std::vector<vkrt_node> m_nodes;

@@ -67,6 +67,26 @@ void HelloVkrt::loadScene(const GltfScene& scene)
     }
     m_skinIds.push_back(ids);
   }
+  // glTF's morph targets, after the skins: a morph inside a skinned range captures that skin's bind pose and writes it (morph, then
+  // skin).  Default weights that are not all zero are applied once, so an unskinned file renders as authored; a skinned range shows
+  // them with its next skinVertices.
+  m_morphIds.clear();
+  for(const GltfMorph& mo : m_gltfScene.m_morphs)
+  {
+    vkrt_morph_desc md{};
+    md.struct_size = sizeof(md);
+    md.first = mo.first;
+    md.count = mo.count;
+    md.target_count = mo.targetCount;
+    md.position_deltas = mo.positionDeltas.empty() ? nullptr : mo.positionDeltas.data();
+    md.normal_deltas = mo.normalDeltas.empty() ? nullptr : mo.normalDeltas.data();
+    md.tangent_deltas = mo.tangentDeltas.empty() ? nullptr : mo.tangentDeltas.data();
+    uint32_t id = 0;
+    check(vkrt_scene_add_morph(m_scene, &md, nullptr, &id), "vkrt_scene_add_morph");
+    m_morphIds.push_back(id);
+    if(std::any_of(mo.weights.begin(), mo.weights.end(), [](float w) { return w != 0.f; }))
+      check(vkrt_scene_morph_vertices(m_scene, id, mo.weights.data(), VKRT_MEMORY_HOST, nullptr), "vkrt_scene_morph_vertices");
+  }
   m_pcRay.lightsCount = (int32_t)m_gltfScene.m_lights.size();  // hello_vulkan.cpp:323-324
 }
 
@@ -166,6 +186,18 @@ void HelloVkrt::skinVertices(uint32_t skin, const std::vector<float>& jointMatri
                              std::to_string(m_gltfScene.m_skins[skin].jointNodes.size()) + " joints");
   for(uint32_t id : m_skinIds[skin])
     check(vkrt_scene_skin_vertices(m_scene, id, jointMatrices.data(), VKRT_MEMORY_HOST, nullptr), "vkrt_scene_skin_vertices");
+}
+
+void HelloVkrt::morphVertices(uint32_t morph, const std::vector<float>& weights)
+{
+  if(!m_scene)
+    throw std::runtime_error("morphVertices before loadGltfScene");
+  if(morph >= m_morphIds.size())
+    throw std::runtime_error("morphVertices: morph " + std::to_string(morph) + " outside the scene's " + std::to_string(m_morphIds.size()) + " morphs");
+  if(weights.size() != m_gltfScene.m_morphs[morph].targetCount)
+    throw std::runtime_error("morphVertices: weights must hold one float for each of the morph's " +
+                             std::to_string(m_gltfScene.m_morphs[morph].targetCount) + " targets");
+  check(vkrt_scene_morph_vertices(m_scene, m_morphIds[morph], weights.data(), VKRT_MEMORY_HOST, nullptr), "vkrt_scene_morph_vertices");
 }
 
 void HelloVkrt::refitAccel()

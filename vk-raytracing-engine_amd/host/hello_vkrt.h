@@ -54,6 +54,12 @@ public:
   // host memory for every range of the skin; refitAccel() follows.  m_gltfScene's vertex arrays keep the bind pose.
   void skinVertices(uint32_t skin, const std::vector<float>& jointMatrices);
   uint32_t skinCount() const { return (uint32_t)m_skinIds.size(); }
+  // morph targets: loadScene adds the file's morphs to the library after its skins (vkrt_scene_add_morph per GltfMorph; the base shape
+  // is the file's, or the bind pose of the skin the range lies in) and applies default weights that are not all zero.  morphVertices
+  // poses morph `morph` of m_gltfScene.m_morphs from one weight per target -- vkrt_scene_morph_vertices from host memory; refitAccel()
+  // follows for an unskinned range, skinVertices + refitAccel() for a skinned one.  m_gltfScene's vertex arrays keep the base shape.
+  void morphVertices(uint32_t morph, const std::vector<float>& weights);
+  uint32_t morphCount() const { return (uint32_t)m_morphIds.size(); }
   // vkrt_scene_motion_mark: the transforms and vertices as they are now become the scene's previous state -- call it at the top of an
   // animated frame, before updateNodeTransforms / updateVertices.  From the first call on the hybrid sequence carries motion: rasterizeGltf
   // also writes a hit record per pixel and where each pixel's surface point was at the mark (vkrt_gbuffer_raycast_hits, vkrt_hit_motion)
@@ -121,6 +127,7 @@ private:
   int m_device;
   vkrt_scene* m_scene = nullptr;
   std::vector<std::vector<uint32_t>> m_skinIds;  // per GltfSkin: the library's skin number of each of its vertex ranges
+  std::vector<uint32_t> m_morphIds;              // per GltfMorph: the library's morph number
   float* m_offscreenColor = nullptr;  // device rgba32f
   // hybrid planes (createOffscreenRender :637-826): position, normal, rough/metal, accumulation, display
   float* m_positionTexture = nullptr;

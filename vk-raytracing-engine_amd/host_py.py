@@ -30,6 +30,9 @@ def lib():
         L.vkrt_host_scene_skin_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.vkrt_host_scene_skin_counts.restype = C.c_uint32
         L.vkrt_host_scene_skin_copy.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 6
+        L.vkrt_host_scene_morph_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.vkrt_host_scene_morph_counts.restype = C.c_uint32
+        L.vkrt_host_scene_morph_copy.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 4
         L.vkrt_host_texture_info.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.vkrt_host_texture_copy.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.vkrt_host_global_uniforms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.POINTER(abi.GlobalUniforms)]
@@ -52,6 +55,10 @@ def lib():
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                     C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
         L.vkrt_host_render_gltf_skinned.restype = C.c_int
+        L.vkrt_host_render_gltf_morphed.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                    C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
+        L.vkrt_host_render_gltf_morphed.restype = C.c_int
         L.vkrt_host_render_gltf_hybrid.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_float, C.c_uint32, C.c_uint32, C.c_void_p]
         L.vkrt_host_render_gltf_hybrid.restype = C.c_int
@@ -146,6 +153,31 @@ def load_gltf_skins(path):
             L.vkrt_host_scene_skin_copy(h, k, None, None, nodes.ctypes.data, ib.ctypes.data, rest.ctypes.data, ranges.ctypes.data)
             skins.append({"joint_nodes": nodes, "inverse_bind": ib, "rest_joint_matrices": rest, "vertex_ranges": ranges})
         return {"joints0": joints0, "weights0": weights0, "skins": skins, "warnings": L.vkrt_host_scene_warnings(h).decode()}
+    finally:
+        L.vkrt_host_free_scene(h)
+
+
+def load_gltf_morphs(path):
+    """C++ loader -> the morph targets of a glTF file: a list, in vertex order, of dict(first, count, target_count, position_deltas,
+    normal_deltas, tangent_deltas float32 (T, count, 3) or None, weights float32 (T,): mesh.weights, overridden by the weights of the
+    first node that instances the mesh)."""
+    L = lib()
+    h = L.vkrt_host_load_gltf(os.fsencode(path))
+    if not h:
+        raise RuntimeError("vkrt_host_load_gltf: " + L.vkrt_host_last_error().decode())
+    try:
+        need = int(L.vkrt_host_scene_morph_counts(h, None, 0))
+        cnt = np.zeros(need, np.uint32)
+        L.vkrt_host_scene_morph_counts(h, cnt.ctypes.data, need)
+        out = []
+        for m in range(int(cnt[0])):
+            first, count, T, hp, hn, ht = (int(x) for x in cnt[1 + 6 * m:7 + 6 * m])
+            d = [np.zeros((T, count, 3), np.float32) if has else None for has in (hp, hn, ht)]
+            w = np.zeros(T, np.float32)
+            L.vkrt_host_scene_morph_copy(h, m, *(None if a is None else a.ctypes.data for a in d), w.ctypes.data)
+            out.append({"first": first, "count": count, "target_count": T, "position_deltas": d[0], "normal_deltas": d[1], "tangent_deltas": d[2],
+                        "weights": w})
+        return out
     finally:
         L.vkrt_host_free_scene(h)
 
@@ -246,6 +278,26 @@ def render_gltf_skinned(path, width, height, skin, joint_matrices, samples=1, de
                                              p.ctypes.data, fov, build, int(skin), m.shape[1], m.shape[0], m.ctypes.data, C.byref(count), img.ctypes.data)
     if rc != 0:
         raise RuntimeError("vkrt_host_render_gltf_skinned: " + lib().vkrt_host_last_error().decode())
+    return img, int(count.value)
+
+
+def render_gltf_morphed(path, width, height, morph=0, weights=None, samples=1, depth=3, frames=1, seed0=0, eye=(0, 0, 15), center=(0, 0, 0),
+                        up=(0, 1, 0), fov=60.0, build=abi.VKRT_BUILD_PLOC_GPU, device=0):
+    """render_gltf of a file with morph targets through the C++ HelloVkrt: the file's default weights are applied at load; weights
+    (steps, targets), if given, are then posed one after the other on morph `morph`, each step morphVertices(morph, weights[step]) +
+    refitAccel().  Returns (image, HelloVkrt::morphCount())."""
+    w = np.zeros((0, 1), np.float32) if weights is None else np.ascontiguousarray(weights, np.float32)
+    if w.ndim == 1:
+        w = w[None]
+    if w.ndim != 2:
+        raise ValueError(f"render_gltf_morphed: weights of shape {w.shape}, expected (steps, targets)")
+    img = np.zeros((height, width, 4), np.float32)
+    e, c, p = (np.asarray(v, np.float32) for v in (eye, center, up))
+    count = C.c_uint32(0)
+    rc = lib().vkrt_host_render_gltf_morphed(os.fsencode(path), device, width, height, samples, depth, frames, seed0, e.ctypes.data, c.ctypes.data,
+                                             p.ctypes.data, fov, build, int(morph), w.shape[1], w.shape[0], w.ctypes.data, C.byref(count), img.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("vkrt_host_render_gltf_morphed: " + lib().vkrt_host_last_error().decode())
     return img, int(count.value)
 
 

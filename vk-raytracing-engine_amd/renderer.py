@@ -141,6 +141,7 @@ class Renderer:
         self._material_count = int(flat.materials.shape[0])
         self._triangle_count = int((np.asarray(flat.prim_meshes["indexCount"], np.int64)[self._prim_mesh] // 3).sum())  # instanced
         self._skins = []  # (first, count, joint_count) of every add_skin, in the library's numbering
+        self._morphs = []  # (first, count, target_count) of every add_morph, in the library's numbering
         for k, v in (options or {}).items():
             self.set_option(k, v)
         if getattr(flat, "material_alpha", None) is not None:
@@ -259,6 +260,9 @@ class Renderer:
         for k, (f0, c0, _) in enumerate(self._skins):
             if first < f0 + c0 and f0 < first + n:
                 raise VkrtError(f"add_skin: first: vertices [{first}, {first + n}) overlap skin {k}'s [{f0}, {f0 + c0})")
+        for k, (f0, c0, _) in enumerate(getattr(self, "_morphs", ())):  # skins come first: a morph inside one captured its bind pose
+            if first < f0 + c0 and f0 < first + n:
+                raise VkrtError(f"add_skin: first: vertices [{first}, {first + n}) overlap morph {k}'s [{f0}, {f0 + c0}): add skins before morphs")
         if joint_count is None:
             joint_count = int(joints.max()) + 1
         if isinstance(joint_count, bool) or not isinstance(joint_count, (int, np.integer)) or not 1 <= joint_count <= 65536:
@@ -315,6 +319,94 @@ class Renderer:
             raise VkrtError("skin: joint_matrices holds a non-finite value")
         st = C.c_void_p(stream.cuda_stream) if stream is not None else None
         _check(self.lib.vkrt_scene_skin_vertices(self._h, int(skin), ptr, memory, st), "vkrt_scene_skin_vertices")
+
+    def add_morph(self, first, position_deltas=None, normal_deltas=None, tangent_deltas=None, stream=None):
+        """vkrt_scene_add_morph: bind T morph targets to vertices [first, first + n) (absolute indices) and capture their positions,
+        normals and tangents, as they are at this point of `stream`, as the base shape.  Each deltas array is a float32 (T, n, 3) numpy
+        array (target-major, glTF's POSITION / NORMAL / TANGENT of primitives[].targets) or None for an attribute that is not morphed.
+        A range inside a skin's range morphs that skin's bind pose (morph, then skin); add skins first.  Returns the morph's number.
+        Refused here, before the call: no array at all, a wrong dtype or shape, a non-contiguous array, shapes that differ, more than
+        VKRT_MORPH_TARGETS_MAX targets, an empty range or one outside the scene, overlapping an earlier morph's or straddling a skin's
+        boundary, a non-finite delta."""
+        given = [(k, a) for k, a in (("position_deltas", position_deltas), ("normal_deltas", normal_deltas), ("tangent_deltas", tangent_deltas))
+                 if a is not None]
+        if not given:
+            raise VkrtError("add_morph: position_deltas, normal_deltas and tangent_deltas are all None")
+        for k, a in given:
+            if not isinstance(a, np.ndarray):
+                raise VkrtError(f"add_morph: {k} must be a numpy array, got {type(a).__name__}")
+            if a.dtype != np.float32:
+                raise VkrtError(f"add_morph: {k} is {a.dtype}, expected float32 dtype")
+            if a.ndim != 3 or a.shape[2] != 3:
+                raise VkrtError(f"add_morph: {k} has shape {tuple(a.shape)}, expected (T, n, 3)")
+            if not a.flags["C_CONTIGUOUS"]:
+                raise VkrtError(f"add_morph: {k} must be contiguous")
+            if a.shape != given[0][1].shape:
+                raise VkrtError(f"add_morph: {k} has shape {tuple(a.shape)}, {given[0][0]} {tuple(given[0][1].shape)}")
+        T, n = int(given[0][1].shape[0]), int(given[0][1].shape[1])
+        if not 1 <= T <= abi.VKRT_MORPH_TARGETS_MAX:
+            raise VkrtError(f"add_morph: {given[0][0]} has {T} targets, outside 1..{abi.VKRT_MORPH_TARGETS_MAX}")
+        if isinstance(first, bool) or not isinstance(first, (int, np.integer)) or first < 0 or n == 0 or int(first) + n > self._vertex_count:
+            raise VkrtError(f"add_morph: first: vertices [{first}, {first} + {n}) empty or outside the scene's {self._vertex_count} vertices")
+        first = int(first)
+        for k, (f0, c0, _) in enumerate(self._morphs):
+            if first < f0 + c0 and f0 < first + n:
+                raise VkrtError(f"add_morph: first: vertices [{first}, {first + n}) overlap morph {k}'s [{f0}, {f0 + c0})")
+        for k, (f0, c0, _) in enumerate(self._skins):
+            if first < f0 + c0 and f0 < first + n and (first < f0 or first + n > f0 + c0):
+                raise VkrtError(f"add_morph: first: vertices [{first}, {first + n}) straddle the boundary of skin {k}'s [{f0}, {f0 + c0})")
+        for k, a in given:
+            if not np.all(np.isfinite(a)):
+                raise VkrtError(f"add_morph: {k} holds a non-finite value")
+        ptr = [None if a is None else a.ctypes.data for a in (position_deltas, normal_deltas, tangent_deltas)]
+        d = abi.MorphDesc(C.sizeof(abi.MorphDesc), first, n, T, *ptr)
+        out = abi.c_u()
+        st = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        _check(self.lib.vkrt_scene_add_morph(self._h, C.byref(d), st, C.byref(out)), "vkrt_scene_add_morph")
+        self._morphs.append((first, n, T))
+        return int(out.value)
+
+    def morph(self, morph, weights, stream=None):
+        """vkrt_scene_morph_vertices: pose morph `morph` from weights, (T,) float32.  A numpy array takes the host path (checked
+        finite, copied before return, the call waits for `stream`); a torch tensor on the scene's device takes the device path: no
+        copy, no synchronisation, the tensor must live until `stream` has passed the call.  One kernel launch on `stream` (a torch
+        stream; None = the default stream) writes base + sum(w * delta); a weight of exactly zero skips its target.  A morph outside
+        every skin writes the scene's positions, normals and tangents, and the tree is stale until refit() or build(); a morph inside
+        a skin writes that skin's bind pose, which the skin's next skin() carries into the scene.  Refused here, before the call: a
+        morph index out of range, a wrong dtype or shape, a non-contiguous or misaligned tensor, a tensor on another device, a
+        non-finite host weight."""
+        import torch
+
+        if isinstance(morph, bool) or not isinstance(morph, (int, np.integer)) or not 0 <= morph < len(self._morphs):
+            raise VkrtError(f"morph: morph {morph!r} outside the scene's {len(self._morphs)} morphs")
+        T = self._morphs[int(morph)][2]
+        w = weights
+        if isinstance(w, torch.Tensor):
+            memory = abi.VKRT_MEMORY_DEVICE
+            if not w.is_cuda or w.device.index != self.device:
+                raise VkrtError(f"morph: weights is on {w.device}, the scene is on cuda:{self.device}")
+            if w.dtype != torch.float32:
+                raise VkrtError(f"morph: weights is {w.dtype}, expected torch.float32")
+            if not w.is_contiguous():
+                raise VkrtError("morph: weights must be contiguous")
+            ptr = w.data_ptr()
+            if ptr % 4:
+                raise VkrtError("morph: weights must be 4-byte aligned")
+        elif isinstance(w, np.ndarray):
+            memory = abi.VKRT_MEMORY_HOST
+            if w.dtype != np.float32:
+                raise VkrtError(f"morph: weights is {w.dtype}, expected float32")
+            if not w.flags["C_CONTIGUOUS"]:
+                raise VkrtError("morph: weights must be contiguous")
+            ptr = w.ctypes.data
+        else:
+            raise VkrtError(f"morph: weights must be a numpy array or a torch tensor, got {type(w).__name__}")
+        if w.ndim != 1 or tuple(w.shape) != (T,):
+            raise VkrtError(f"morph: weights has shape {tuple(w.shape)}, expected ({T},)")
+        if memory == abi.VKRT_MEMORY_HOST and not np.all(np.isfinite(w)):
+            raise VkrtError("morph: weights holds a non-finite value")
+        st = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        _check(self.lib.vkrt_scene_morph_vertices(self._h, int(morph), ptr, memory, st), "vkrt_scene_morph_vertices")
 
     def read_vertices(self, first, count):
         """The live attributes of vertices [first, first + count) (vkrt_debug_read_vertices, synchronises): a dict of float32 arrays,
