@@ -12,10 +12,14 @@
 // ballot... (see publish step: one LDS 64-bit atomic minimum on (t, triangle id), then the winner stores its payload).  The result is the same as in traverse_wide.h:
 // closest = smallest t in (tmin, tmax), ties -> smallest triangle id; any = exists (order-independent definitions).
 #pragma once
+#include "trav_lds.h"
 #include "traverse_wide.h"
 
 // per-wave LDS block: 64 x (u64 key, slot, u, v, donor lane by rank)
 #define VKRT_SHARE_LDS_WORDS 384
+// ... and without the donor plane (traverse_wide8_share<..., DONOR_LDS = false>): VKRT_SHARE_LDS_WORDS_SIX = 320 words, 1280 B, one LDS
+// allocation granule of gfx950, so that the frame kernels' waves of a tree of wide depth <= 9 are charged 6400 B and 24 of them fit a
+// CU (trav_lds.h, which the host shares)
 struct ShareRes
 {
   unsigned long long* key;  // closest: float bits of the best t << 32 | triangle id of the best hit (tie rule); initial tmax << 32 | ~0
@@ -62,9 +66,22 @@ VKRT_DEV ShareRes shareRes(int* lds320)
   return r;
 }
 
+// The match of a sharing or lending step without a plane of its own (DONOR_LDS = false): every lane names a slot -- the r-th giver
+// slot r, the lanes that give nothing the slots behind the givers' in lane order, so no two name the same -- and ds_permute_b32 leaves
+// its lane number in that slot's lane; lane r then holds what donor[r] held, and the r-th taker fetches it with ds_bpermute_b32.  Both
+// go through the LDS crossbar without touching LDS memory.  All 64 lanes must be here (the slot's lane has to receive).
+VKRT_DEV int laneOfRank(bool gives, unsigned giveRank, unsigned long long giveMask, unsigned takeRank, int lane)
+{
+  const unsigned slot = gives ? giveRank : (unsigned)__popcll(giveMask) + (unsigned)lane - giveRank;
+  const int byRank = __builtin_amdgcn_ds_permute((int)(slot << 2), lane);
+  return __builtin_amdgcn_ds_bpermute((int)(takeRank << 2), byRank);
+}
+
 // Must be called by all 64 lanes of a one-wave workgroup (lanes without a ray pass valid = false and only help).
-// stk: this lane's stack column (stride 64 entries), res: the wave's ShareRes block.
-template <bool COUNT, bool ANYHIT, int TM = 0>
+// stk: this lane's stack column (stride 64 entries), res: the wave's ShareRes block: VKRT_SHARE_LDS_WORDS of them with DONOR_LDS,
+// VKRT_SHARE_LDS_WORDS_SIX without (res.donor is not used then: closest-hit walks match in registers, laneOfRank; any-hit walks,
+// which never write u / v and whose lending step is not entered by every lane, keep the match in the u plane).
+template <bool COUNT, bool ANYHIT, int TM = 0, bool DONOR_LDS = true>
 VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, float tmin, float tmax, uint2* stk, ShareRes res, RayHit& hit,
                                    TravCount& tc, uint32_t raySeed = 0u)
 {
@@ -75,6 +92,10 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
   const float4* __restrict__ tris = sc.tris;
   const int stride = 64;
   const int lane = (int)lane_id();
+  // (used only where DONOR_LDS || ANYHIT.  Without the donor plane an any-hit walk keeps its matches in the u plane, as ints: that
+  //  holds only while NO any-hit path stores u or v -- publish and the lending step below store the slot alone -- and every access
+  //  is fenced by shareSync.  An any-hit stage that wants u / v published needs a plane of its own again.)
+  int* const donor = DONOR_LDS ? res.donor : (int*)res.u;
   const ShareStk stkBase = (ShareStk)stk, stkCap = stkBase + (int)(sc.stackCap >> 1) * stride;  // the lane's column: [stkBase, stkCap)
   const unsigned shareMin = sc.shareMinIdle;
   bool farFirst = ANYHIT && anyhit_far_first(sc, o, d, tmax);  // child order of this lane's ray (traverse.h)
@@ -164,10 +185,20 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
             e = make_uint2(T.x | 0x80000000u, upper);
             T.y &= ~upper;
           }
-          res.donor[giveRank] = lane;  // r-th donor feeds the r-th idle lane
+          if(DONOR_LDS || ANYHIT)
+            donor[giveRank] = lane;  // r-th donor feeds the r-th idle lane
         }
-        shareSync();
-        const int src = takes ? res.donor[takeRank] : lane;
+        int src = lane;
+        if(DONOR_LDS || ANYHIT)
+        {
+          shareSync();
+          if(takes) src = donor[takeRank];
+        }
+        else
+        {
+          const int giver = laneOfRank(wants, giveRank, donorMask, takeRank, lane);
+          if(takes) src = giver;
+        }
         const unsigned ex = (unsigned)__shfl((int)e.x, src), ey = (unsigned)__shfl((int)e.y, src);
         const float ox = __shfl(o.x, src), oy = __shfl(o.y, src), oz = __shfl(o.z, src);
         const float dx = __shfl(d.x, src), dy = __shfl(d.y, src), dz = __shfl(d.z, src);
@@ -221,6 +252,9 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
         bt = __uint_as_float((unsigned)(k >> 32));
         bg = (int)(unsigned)k;
       }
+      // (laneOfRank below needs all 64 lanes at its call: the sharing step above stands outside this block; the lending step inside it
+      //  is reached by every lane of a closest-hit walk because `finished` is still false here for !ANYHIT and lendOn, which gates
+      //  the lending, lets the lanes without work in.  An any-hit walk does leave lanes behind here, and matches through LDS.)
       if(!finished)
       {
         // A candidate hit lives only between the tests of one site and its publication right behind them (kept across the whole
@@ -397,15 +431,25 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
               const unsigned hi = 31u - (unsigned)__clz((int)T.y);
               T.y &= ~(1u << hi);
               ls = T.x + hi;
-              res.donor[lendRank] = lane;  // r-th lender feeds the r-th free lane
+              if(DONOR_LDS || ANYHIT)
+                donor[lendRank] = lane;  // r-th lender feeds the r-th free lane
             }
             if(tests)
             {
               s = T.x + (unsigned)__ffs((int)T.y) - 1u;
               T.y &= T.y - 1u;
             }
-            shareSync();
-            const int src = borrows ? res.donor[freeRank] : lane;
+            int src = lane;
+            if(DONOR_LDS || ANYHIT)
+            {
+              shareSync();
+              if(borrows) src = donor[freeRank];
+            }
+            else
+            {
+              const int lender = laneOfRank(multi, lendRank, lendMask, freeRank, lane);  // (a closest-hit walk: all 64 lanes are here)
+              if(borrows) src = lender;
+            }
             const unsigned bs = (unsigned)__shfl((int)ls, src);
             const f3 ro = mk3(__shfl(o.x, src), __shfl(o.y, src), __shfl(o.z, src));
             const f3 rd = mk3(__shfl(d.x, src), __shfl(d.y, src), __shfl(d.z, src));
@@ -492,7 +536,13 @@ VKRT_DEV void traverse_wide8_share(const DevScene& sc, bool valid, f3 o, f3 d, f
   if(__builtin_expect(busy, 0))  // [isa: prologue_epilogue]
     VKRT_TRAV_FAULT(sc);
   shareSync();
-  hit.t = __uint_as_float((unsigned)(res.key[lane] >> 32)); hit.u = res.u[lane]; hit.v = res.v[lane]; hit.slot = res.slot[lane];
+  // (the lane's result addresses are formed again here, from a lane number the compiler cannot tie to the prologue's: held across the
+  //  loop for these four loads they cost three registers of every iteration)
+  int home = lane;
+  asm volatile("" : "+v"(home));
+  hit.t = __uint_as_float((unsigned)(res.key[home] >> 32)); hit.u = res.u[home]; hit.v = res.v[home]; hit.slot = res.slot[home];
   if(ANYHIT)
     hit.t = tmax;
+  if(ANYHIT && !DONOR_LDS)
+    hit.u = 0.0f;  // (what an any-hit walk leaves there in the other layout; here the plane held the matches)
 }

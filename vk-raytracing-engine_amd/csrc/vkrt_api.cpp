@@ -24,6 +24,7 @@
 #include "kernels.h"
 #include "scene_options.h"
 #include "scene_pack.h"
+#include "trav_lds.h"
 #include "wide_node.h"
 
 #include "lbvh.h"
@@ -670,8 +671,8 @@ void installTree(vkrt_scene* s, vkrt::BuiltTree& t)
   s->dev.triShade = s->accel.triShade.get<const uint4>();
   s->dev.layout = t.layout;
   s->dev.rootRef = t.rootRef;
-  // wide8: at most one pending group per level (uint2 entries = 2 words)
-  s->dev.stackCap = t.layout == 1 ? 2 * (t.maxDepth + 1) : t.maxDepth + 2;
+  // (trav_lds.h; traversalSettings adds the room for parked triangle groups)
+  s->dev.stackCap = travStackCap(t.layout, t.maxDepth, false, 0u);
   s->info.node_count = t.nodeCount;
   s->info.max_depth = t.maxDepth;
   s->info.sah_cost = t.sahCost;
@@ -731,8 +732,9 @@ int traversalSettings(vkrt_scene* s)
   {
     // triangle postponing (traverse_wide.h): lanes with pending triangles before a wave tests them; 0 = immediate
     s->dev.triThreshold = (uint32_t)s->opt[VKRT_OPT_TRI_THRESHOLD];
-    if(s->dev.triThreshold != 0u)
-      s->dev.stackCap += 2 * VKRT_W8_POSTPONE_ROOM;  // room for parked triangle groups (uint2 entries)
+    // room for parked triangle groups (uint2 entries).  The stack is what decides how many traversal waves a CU holds: six per SIMD
+    // up to wide depth 9, five beyond (travLdsPlan, trav_lds.h)
+    s->dev.stackCap = travStackCap(1u, s->info.max_depth, s->dev.triThreshold != 0u, VKRT_W8_POSTPONE_ROOM);
     // work sharing inside a traversal wave (traverse_share.h): minimum number of idle lanes before they take over subtrees
     s->dev.shareMinIdle = (uint32_t)s->opt[VKRT_OPT_WF_SHARE];
     s->dev.sharePeriodMask = (uint32_t)s->opt[VKRT_OPT_WF_SHARE_PERIOD];

@@ -48,11 +48,12 @@ VKRT_DEV void storeHit(const TraceParams& P, const WfBuffers& B, int par, int ki
 }
 
 // ---- traversal: one thread per queued ray, workgroups homogeneous in ray kind -----------------------------------
-// (waves per SIMD: five for the non-default triangle modes of the wide 64-thread kernel, like TM = 0 gets on its own; the instrumented
-// kernels with the alpha-test stage would spill VGPRs at five -- their dissolve / watertight siblings already do -- and ask for four)
+// (waves per SIMD of the wide 64-thread kernel: six for the product instantiation, TM = 0 without counters -- 80 registers, and 6400 B
+// of LDS per wave up to wide depth 9: trav_lds.h, profiles/r12_experiments.md; five for the non-default triangle modes; the instrumented
+// kernels with the alpha-test stage asked for four when five would spill, and the instrumented TM = 0 kernel asks for nothing)
 template <bool COUNT, bool WIDE, int TB, int TM = 0>
 __global__ __launch_bounds__(TB)
-__attribute__((amdgpu_waves_per_eu(TM != 0 && WIDE && TB == 64 ? (COUNT && (TM & VKRT_TM_ALPHA) != 0 ? 4 : 5) : 1)))
+__attribute__((amdgpu_waves_per_eu(WIDE && TB == 64 ? (TM == 0 ? (COUNT ? 1 : 6) : COUNT && (TM & VKRT_TM_ALPHA) != 0 ? 4 : 5) : 1)))
 void k_wf_traverse(const TraceParams P, const WfBuffers B, const int round)
 {
   extern __shared__ int lds_stack[];
@@ -82,34 +83,50 @@ void k_wf_traverse(const TraceParams P, const WfBuffers B, const int round)
   const bool valid = qi < count;
   // the ray of this lane: origin from R0; the shadow ray of a pair record and every C / S ray take R1 and R0.w, the closest-hit
   // ray of a pair record takes R2 and the closest-hit tmax
+  // The kernel with the sharing walks loads it on the branch that walks it: loaded up here, the ray's eight registers stay live across
+  // the OTHER walk of the closest-hit / any-hit pair (the allocator sees both behind one load), which alone put the kernel over the 80
+  // registers of six waves per SIMD (profiles/r12_experiments.md #168).  The other instantiations keep the load where it was.
+  constexpr bool SHARING = WIDE && TB == 64;
   float4 r0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), r1 = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
-  if(valid)
-  {
-    r0 = wfLoad(rec(B, par, type, WF_R0, qi));
-    r1 = wfLoad(rec(B, par, type, kind == WF_K_CLOSEST_P ? WF_R2 : WF_R1, qi));
-    if(kind == WF_K_CLOSEST_P)
-      r0.w = 10000.0f;
-  }
+  auto loadRay = [&]() {
+    if(valid)
+    {
+      r0 = wfLoad(rec(B, par, type, WF_R0, qi));
+      r1 = wfLoad(rec(B, par, type, kind == WF_K_CLOSEST_P ? WF_R2 : WF_R1, qi));
+      if(kind == WF_K_CLOSEST_P)
+        r0.w = 10000.0f;
+    }
+  };
+  if(!SHARING)
+    loadRay();
   // any-hit stage: the payload's seed when the ray is traced (S0.w: after the shading that produced the ray, raytrace.rgen:64-97)
   uint32_t raySeed = 0u;
   if((TM & VKRT_TM_DISSOLVE) && valid)
     raySeed = __float_as_uint(wfLoad(rec(B, par, type, WF_S0, qi)).w);
   TravCount tc;
-  __shared__ int shareLds[VKRT_SHARE_LDS_WORDS];
+  __shared__ int shareLds[VKRT_SHARE_LDS_WORDS_SIX];
   RayHit hit;
   if(WIDE && TB == 64 && P.sc.shareMinIdle != 0u && P.sc.triThreshold != 0u)  // launch-uniform
   {
     // the whole wave walks together: lanes past the end of the stream have no ray of their own but help
     uint2* stk = ((uint2*)lds_stack) + threadIdx.x;
     if(anyHit)
-      traverse_wide8_share<COUNT, true, TM>(P.sc, valid, mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z), 0.001f, r0.w, stk, shareRes(shareLds), hit, tc, raySeed);
+    {
+      loadRay();
+      traverse_wide8_share<COUNT, true, TM, false>(P.sc, valid, mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z), 0.001f, r0.w, stk, shareRes(shareLds), hit, tc, raySeed);
+    }
     else
-      traverse_wide8_share<COUNT, false, TM>(P.sc, valid, mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z), 0.001f, r0.w, stk, shareRes(shareLds), hit, tc, raySeed);
+    {
+      loadRay();
+      traverse_wide8_share<COUNT, false, TM, false>(P.sc, valid, mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z), 0.001f, r0.w, stk, shareRes(shareLds), hit, tc, raySeed);
+    }
     if(valid)
       storeHit(P, B, par, kind, qi, hit);
   }
   else if(valid)
   {
+    if(SHARING)
+      loadRay();
     traverse_any<COUNT, WIDE, TM>(P.sc, mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z), 0.001f, r0.w, anyHit, lds_stack, (int)threadIdx.x, TB, hit, tc, raySeed);
     storeHit(P, B, par, kind, qi, hit);
   }
@@ -129,7 +146,7 @@ void k_wf_traverse(const TraceParams P, const WfBuffers B, const int round)
 // makes the same state again.  A lane outside the shard or the image has no ray and only helps, like the tail lanes of a stream.
 template <bool COUNT, int TM>
 __global__ __launch_bounds__(64)
-__attribute__((amdgpu_waves_per_eu(TM != 0 ? 5 : 1)))
+__attribute__((amdgpu_waves_per_eu(TM != 0 ? 5 : COUNT ? 1 : 6)))
 void k_wf_traverse_camera(const TraceParams P, const WfBuffers B, const int round, const int smpl)
 {
   extern __shared__ int lds_stack[];
@@ -160,10 +177,10 @@ void k_wf_traverse_camera(const TraceParams P, const WfBuffers B, const int roun
     if(smpl == 0) atomicAdd(&P.counters->v[blockIdx.x % VKRT_COUNTER_SLOTS][5], (unsigned long long)nValid);
   }
   TravCount tc;
-  __shared__ int shareLds[VKRT_SHARE_LDS_WORDS];
+  __shared__ int shareLds[VKRT_SHARE_LDS_WORDS_SIX];
   RayHit hit;
   uint2* stk = ((uint2*)lds_stack) + threadIdx.x;
-  traverse_wide8_share<COUNT, false, TM>(P.sc, valid, o, d, 0.001f, 10000.0f, stk, shareRes(shareLds), hit, tc, raySeed);
+  traverse_wide8_share<COUNT, false, TM, false>(P.sc, valid, o, d, 0.001f, 10000.0f, stk, shareRes(shareLds), hit, tc, raySeed);
   if(valid)
     storeHit(P, B, par, WF_K_CLOSEST_C, w, hit);
   if(COUNT)
