@@ -110,27 +110,11 @@ def test_skin_vertices_and_read_vertices_refusals_without_a_device():
     assert b"vkrt_debug_read_vertices: scene is NULL" in lib.vkrt_last_error()
 
 
-class _NoLibrary:
-    def __getattr__(self, name):
-        raise AssertionError(f"the library was reached ({name}): the refusal must come before the call")
-
-
-def _renderer_without_scene(vertices=10, skins=()):
-    from vkrt_amd.renderer import Renderer
-
-    r = Renderer.__new__(Renderer)  # no scene: the checks run before any use of the handle
-    r.device = 0
-    r._vertex_count = vertices
-    r._skins = list(skins)
-    r._h = None
-    r.lib = _NoLibrary()
-    return r
-
-
 def test_python_refuses_bad_skins_before_the_call():
+    from renderer_stand_ins import renderer_without_scene
     from vkrt_amd.renderer import VkrtError
 
-    r = _renderer_without_scene(10, skins=[(6, 2, 3)])
+    r = renderer_without_scene(10, skins=[(6, 2, 3)])
     j, w = (lambda n: np.zeros((n, 4), np.uint16)), (lambda n: np.full((n, 4), 0.25, np.float32))
     nan = w(2)
     nan[1, 2] = np.nan
@@ -196,39 +180,10 @@ def test_python_refuses_tensor_faults_through_a_stand_in():
     """Device matrices without a device: a stand-in that answers like a tensor on cuda:0 reaches the dtype, contiguity, alignment, device
     and shape checks."""
     import torch
+    from renderer_stand_ins import Fake, renderer_without_scene
     from vkrt_amd.renderer import VkrtError
 
-    class _Dev:
-        def __init__(self, index):
-            self.index = index
-
-        def __str__(self):
-            return f"cuda:{self.index}"
-
-    class Fake(torch.Tensor):
-        """answers like a float32 CUDA tensor of the given shape; holds no data"""
-
-        @staticmethod
-        def __new__(cls, shape, dtype=torch.float32, index=0, contiguous=True, ptr=0x1000):
-            t = torch.Tensor._make_subclass(cls, torch.zeros(shape, dtype=dtype))
-            t._index, t._contiguous, t._ptr = index, contiguous, ptr
-            return t
-
-        @property
-        def is_cuda(self):
-            return True
-
-        @property
-        def device(self):
-            return _Dev(self._index)
-
-        def is_contiguous(self, *a, **k):
-            return self._contiguous
-
-        def data_ptr(self):
-            return self._ptr
-
-    r = _renderer_without_scene(10, skins=[(0, 4, 3)])
+    r = renderer_without_scene(10, skins=[(0, 4, 3)])
     bad = [
         (Fake((3, 16), index=1), "cuda:1"),
         (Fake((3, 16), dtype=torch.float64), "float64"),
@@ -245,13 +200,13 @@ def test_python_refuses_tensor_faults_through_a_stand_in():
 
 
 def test_skin_kernels_use_no_scratch_and_spill_nothing():
-    """the compiler's resource report (tools/skin_resources.py) for gfx950, and the committed copy of it"""
+    """the compiler's resource report (tools/kernel_resources.py) for gfx950, and the committed copy of it"""
     import json
 
     sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import skin_resources
+    import kernel_resources
 
-    kernels, problems = skin_resources.measure()
+    kernels, problems = kernel_resources.measure("skin.hip", ("k_skin", "k_skin_capture"))
     assert not problems, problems
     assert set(kernels) == {"k_skin", "k_skin_capture"}
     for k, v in kernels.items():

@@ -1,0 +1,326 @@
+"""The host-only argument rules of vkrt_scene_update_vertices, vkrt_scene_add_skin / _skin_vertices, vkrt_scene_add_morph /
+_morph_vertices and vkrt_debug_read_vertices (csrc/vertex_anim.cpp) on the CPU, for a scene of 20 vertices with the skin [10, 16) and
+the morph [4, 6): every refusal that needs a scene with its return code and its exact message, the accepted neighbours of each, where
+a non-finite value is reported, and each refusal winning over every later one in the order include/vkrt.h states.  vertex_anim.cpp
+is compiled with g++ into a ctypes shim that chains the checks as vkrt_api.cpp does, and once more with the address and
+undefined-behaviour sanitizers into a stand-alone program that replays the same calls."""
+import ctypes as C
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from vkrt_amd import abi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "vk-raytracing-engine_amd", "csrc")
+SOURCES = [os.path.join(CSRC, "vertex_anim.cpp")]
+OK, BAD = abi.VKRT_OK, abi.VKRT_ERR_INVALID_ARGUMENT
+HOST, DEVICE = abi.VKRT_MEMORY_HOST, abi.VKRT_MEMORY_DEVICE
+U, S, M = C.sizeof(abi.VertexUpdate), C.sizeof(abi.SkinDesc), C.sizeof(abi.MorphDesc)
+
+# The entry points as vkrt_api.cpp chains them: the descriptor checks, the NULL out_* and NULL scene refusals (the API's own, restated
+# here), the rules that need the scene.  The scene's records are wider than a VertexRange, as the library's are (RangeSet::stride).
+SHIM = r"""
+#include <cstdio>
+#include "vertex_anim.h"
+using namespace vkrt;
+namespace {
+struct Record : VertexRange { void* mem; uint32_t n; };
+const Record kSkins[] = {{{10, 6}, nullptr, 3}}, kMorphs[] = {{{4, 2}, nullptr, 3}};  // n: the skin's joint count, the morph's target count
+const size_t kVertices = 20;
+const RangeSet skins{kSkins, 1, sizeof(Record)}, morphs{kMorphs, 1, sizeof(Record)};
+char g_msg[600];
+int done(int rc, const std::string& err) { snprintf(g_msg, sizeof g_msg, "%s", err.c_str()); return rc; }
+int isNull(const char* who, const char* what) { snprintf(g_msg, sizeof g_msg, "%s: %s is NULL", who, what); return VKRT_ERR_INVALID_ARGUMENT; }
+}
+extern "C" {
+const char* shim_message() { return g_msg; }
+int shim_update(int size, uint32_t first, uint32_t count, uint32_t memory, const float* positions, int scene)
+{
+  const vkrt_vertex_update u = {(uint32_t)size, first, count, memory, positions, nullptr, nullptr, nullptr};
+  std::string err;
+  if(int rc = check_update_desc(size < 0 ? nullptr : &u, err)) return done(rc, err);
+  if(!scene) return isNull("vkrt_scene_update_vertices", "scene");
+  return done(check_update_range(u, kVertices, err), err);
+}
+int shim_add_skin(int size, uint32_t first, uint32_t count, uint32_t jointCount, const uint16_t* joints, const float* weights, int out, int scene)
+{
+  const vkrt_skin_desc k = {(uint32_t)size, first, count, jointCount, joints, weights};
+  std::string err;
+  if(int rc = check_skin_desc(size < 0 ? nullptr : &k, err)) return done(rc, err);
+  if(!out) return isNull("vkrt_scene_add_skin", "out_skin");
+  if(!scene) return isNull("vkrt_scene_add_skin", "scene");
+  return done(check_skin_range(k, kVertices, skins, morphs, err), err);
+}
+int shim_skin_vertices(uint32_t skin, const float* matrices, uint32_t memory, int scene)
+{
+  std::string err;
+  if(int rc = check_memory("vkrt_scene_skin_vertices", memory, err)) return done(rc, err);
+  if(!scene) return isNull("vkrt_scene_skin_vertices", "scene");
+  if(int rc = check_skin_index(skin, skins.size, err)) return done(rc, err);
+  return done(check_joint_matrices(matrices, memory, kSkins[skin].n, err), err);
+}
+int shim_add_morph(int size, uint32_t first, uint32_t count, uint32_t targets, const float* dp, const float* dn, const float* dt, int out, int scene)
+{
+  const vkrt_morph_desc m = {(uint32_t)size, first, count, targets, dp, dn, dt};
+  std::string err;
+  if(int rc = check_morph_desc(size < 0 ? nullptr : &m, err)) return done(rc, err);
+  if(!out) return isNull("vkrt_scene_add_morph", "out_morph");
+  if(!scene) return isNull("vkrt_scene_add_morph", "scene");
+  int inSkin = -2;
+  if(int rc = check_morph_range(m, kVertices, skins, morphs, inSkin, err)) return done(rc, err);
+  return done(VKRT_OK, "inSkin " + std::to_string(inSkin));  // (an accepted call leaves err alone: it is empty here)
+}
+int shim_morph_vertices(uint32_t morph, const float* weights, uint32_t memory, int scene)
+{
+  std::string err;
+  if(int rc = check_memory("vkrt_scene_morph_vertices", memory, err)) return done(rc, err);
+  if(!scene) return isNull("vkrt_scene_morph_vertices", "scene");
+  if(int rc = check_morph_index(morph, morphs.size, err)) return done(rc, err);
+  return done(check_morph_weights(weights, memory, kMorphs[morph].n, err), err);
+}
+int shim_read_vertices(uint32_t first, uint32_t count)
+{
+  std::string err;
+  return done(check_vertex_range("vkrt_debug_read_vertices", first, count, kVertices, err), err);
+}
+}
+"""
+
+
+class F:
+    """n floats of 0.25 with the values `bad` ({index: "nan" | "inf" | "-inf"}) among them"""
+    def __init__(self, n, bad=None):
+        self.n, self.bad = n, dict(bad or {})
+
+    def numpy(self):
+        a = np.full(self.n, 0.25, np.float32)
+        for i, v in self.bad.items():
+            a[i] = float(v)
+        return a
+
+    def cpp(self):
+        return "floats(%d, {%s})" % (self.n, ", ".join('{%d, %s}' % (i, {"nan": "NAN", "inf": "INFINITY", "-inf": "-INFINITY"}[v]) for i, v in self.bad.items()))
+
+
+class J:
+    """n joint indices, all 0 but `bad` ({index: value})"""
+    def __init__(self, n, bad=None):
+        self.n, self.bad = n, dict(bad or {})
+
+    def numpy(self):
+        a = np.zeros(self.n, np.uint16)
+        for i, v in self.bad.items():
+            a[i] = v
+        return a
+
+    def cpp(self):
+        return "joints(%d, {%s})" % (self.n, ", ".join("{%d, %d}" % iv for iv in self.bad.items()))
+
+
+class P:
+    """a device address that is never read"""
+    def __init__(self, address):
+        self.address = address
+
+    def cpp(self):
+        return "(const float*)%dull" % self.address
+
+
+def skin(first, count, jc=3, joints=True, weights=True, size=S, out=1, scene=1):
+    """a shim_add_skin call; joints / weights: True = good arrays of the range's length"""
+    return ("shim_add_skin", size, first, count, jc, J(4 * count) if joints is True else joints, F(4 * count) if weights is True else weights, out, scene)
+
+
+def morph(first, count, targets=2, dp=True, dn=None, dt=None, size=M, out=1, scene=1):
+    return ("shim_add_morph", size, first, count, targets, F(3 * targets * count) if dp is True else dp, dn, dt, out, scene)
+
+
+def update(first, count, memory=HOST, positions=True, size=U, scene=1):
+    return ("shim_update", size, first, count, memory, F(3 * count) if positions is True else positions, scene)
+
+
+SKIN, MORPH, UPDATE = "vkrt_scene_add_skin: ", "vkrt_scene_add_morph: ", "vkrt_scene_update_vertices: "
+POSE_S, POSE_M = "vkrt_scene_skin_vertices: ", "vkrt_scene_morph_vertices: "
+STRADDLE = " straddle the boundary of skin 0's [10, 16): a morph lies inside one skin or outside all"
+NAN3 = F(18, {15: "nan"})  # T = 2, n = 3: element 15 is target 1, vertex 2 of the range
+
+# (call, return code, message)
+CASES = [
+    # ---- a range outside the scene, in each call that takes one; an index outside the scene's skins and morphs
+    (update(19, 2), BAD, UPDATE + "vertices [19, 21) outside the scene's 20 vertices"),
+    (update(21, 0, positions=None), BAD, UPDATE + "vertices [21, 21) outside the scene's 20 vertices"),
+    (skin(19, 2), BAD, SKIN + "vertices [19, 21) outside the scene's 20 vertices"),
+    (morph(19, 2), BAD, MORPH + "vertices [19, 21) outside the scene's 20 vertices"),
+    (("shim_read_vertices", 19, 2), BAD, "vkrt_debug_read_vertices: vertices [19, 21) outside the scene's 20 vertices"),
+    (("shim_skin_vertices", 1, F(48), HOST, 1), BAD, POSE_S + "skin 1 outside the scene's 1 skins"),
+    (("shim_morph_vertices", 1, F(3), HOST, 1), BAD, POSE_M + "morph 1 outside the scene's 1 morphs"),
+    # ---- first + count in 64 bits: refused as outside, not wrapped to [4294967295, 1)
+    (update(0xFFFFFFFF, 2), BAD, UPDATE + "vertices [4294967295, 4294967297) outside the scene's 20 vertices"),
+    (skin(0xFFFFFFFF, 2), BAD, SKIN + "vertices [4294967295, 4294967297) outside the scene's 20 vertices"),
+    (morph(0xFFFFFFFF, 2), BAD, MORPH + "vertices [4294967295, 4294967297) outside the scene's 20 vertices"),
+    (("shim_read_vertices", 0xFFFFFFFF, 2), BAD, "vkrt_debug_read_vertices: vertices [4294967295, 4294967297) outside the scene's 20 vertices"),
+    # ---- count == 0
+    (skin(0, 0), BAD, SKIN + "count is 0"),
+    (skin(20, 0, joints=None, weights=None), BAD, SKIN + "count is 0"),
+    (morph(0, 0), BAD, MORPH + "count is 0"),
+    (update(20, 0), OK, ""),                                                                  # (an update of nothing is accepted)
+    (("shim_read_vertices", 20, 0), OK, ""),
+    # ---- overlaps
+    (skin(9, 2), BAD, SKIN + "vertices [9, 11) overlap skin 0's [10, 16)"),
+    (skin(15, 2), BAD, SKIN + "vertices [15, 17) overlap skin 0's [10, 16)"),
+    (skin(12, 1), BAD, SKIN + "vertices [12, 13) overlap skin 0's [10, 16)"),
+    (skin(3, 2), BAD, SKIN + "vertices [3, 5) overlap morph 0's [4, 6): add skins before morphs"),
+    (skin(5, 1), BAD, SKIN + "vertices [5, 6) overlap morph 0's [4, 6): add skins before morphs"),
+    (morph(3, 2), BAD, MORPH + "vertices [3, 5) overlap morph 0's [4, 6)"),
+    (morph(5, 1), BAD, MORPH + "vertices [5, 6) overlap morph 0's [4, 6)"),
+    # ---- a morph across a skin's edge: the lower one, the upper one, both
+    (morph(9, 2), BAD, MORPH + "vertices [9, 11)" + STRADDLE),
+    (morph(15, 2), BAD, MORPH + "vertices [15, 17)" + STRADDLE),
+    (morph(8, 10), BAD, MORPH + "vertices [8, 18)" + STRADDLE),
+    # ---- accepted: ranges that only touch, at the skin's edges, the skin's whole range, the scene's last vertex
+    (morph(2, 2), OK, "inSkin -1"), (morph(6, 4), OK, "inSkin -1"), (morph(16, 4), OK, "inSkin -1"), (morph(19, 1), OK, "inSkin -1"),
+    (morph(10, 1), OK, "inSkin 0"), (morph(15, 1), OK, "inSkin 0"), (morph(11, 3), OK, "inSkin 0"), (morph(10, 6), OK, "inSkin 0"),
+    (morph(0, 1, targets=256, dp=None, dt=F(3 * 256)), OK, "inSkin -1"),
+    (skin(2, 2), OK, ""), (skin(6, 4), OK, ""), (skin(16, 4), OK, ""), (skin(19, 1), OK, ""), (skin(0, 4, jc=65536, joints=J(16, {15: 65535})), OK, ""),
+    (update(19, 1), OK, ""), (update(0, 20), OK, ""), (update(0, 20, memory=DEVICE, positions=P(0x1004)), OK, ""), (update(3, 2, positions=None), OK, ""),
+    (("shim_read_vertices", 19, 1), OK, ""), (("shim_read_vertices", 0, 20), OK, ""),
+    (("shim_skin_vertices", 0, F(48), HOST, 1), OK, ""), (("shim_skin_vertices", 0, P(0x1010), DEVICE, 1), OK, ""),
+    (("shim_morph_vertices", 0, F(3), HOST, 1), OK, ""), (("shim_morph_vertices", 0, P(0x1004), DEVICE, 1), OK, ""),
+    # ---- a non-finite value: at its lowest index, with the vertex / target / joint it belongs to, in array order
+    (update(5, 3, positions=F(9, {7: "inf", 8: "nan"})), BAD, UPDATE + "positions[7] (vertex 7) is not finite"),
+    (update(5, 3, memory=DEVICE, positions=P(0x1000)), OK, ""),                                # (device memory is not looked at)
+    (skin(2, 3, weights=F(12, {9: "nan", 11: "inf"})), BAD, SKIN + "weights[9] (vertex 4) is not finite"),
+    (skin(2, 3, joints=J(12, {6: 3, 7: 9}), weights=F(12, {0: "nan"})), BAD, SKIN + "joints[6] (vertex 3) is 3, joint_count is 3"),
+    (morph(7, 3, dp=NAN3, dn=F(18, {4: "inf"}), dt=F(18, {11: "-inf"})), BAD, MORPH + "position_deltas[15] (target 1, vertex 9) is not finite"),
+    (morph(7, 3, dn=F(18, {4: "inf", 5: "nan"}), dt=F(18, {11: "-inf"})), BAD, MORPH + "normal_deltas[4] (target 0, vertex 8) is not finite"),
+    (morph(7, 3, dp=None, dn=F(18), dt=F(18, {11: "-inf"})), BAD, MORPH + "tangent_deltas[11] (target 1, vertex 7) is not finite"),
+    (("shim_skin_vertices", 0, F(48, {33: "nan", 40: "inf"}), HOST, 1), BAD, POSE_S + "joint_matrices[33] (joint 2) is not finite"),
+    (("shim_morph_vertices", 0, F(3, {1: "inf", 2: "nan"}), HOST, 1), BAD, POSE_M + "weights[1] is not finite"),
+    # ---- each refusal wins over every later one.  vkrt_scene_update_vertices: everything behind the one named is wrong as well
+    (update(30, 3, memory=7, positions=F(9, {0: "nan"}), size=-1, scene=0), BAD, UPDATE + "update is NULL"),
+    (update(30, 3, memory=7, positions=F(9, {0: "nan"}), size=U - 1, scene=0), BAD, UPDATE + f"vkrt_vertex_update.struct_size {U - 1} < {U} (ABI mismatch)"),
+    (update(30, 3, memory=7, positions=F(9, {0: "nan"}), scene=0), BAD, UPDATE + "memory 7 is neither VKRT_MEMORY_HOST nor VKRT_MEMORY_DEVICE"),
+    (update(30, 3, positions=F(9, {0: "nan"}), scene=0), BAD, UPDATE + "scene is NULL"),
+    (update(30, 3, positions=F(9, {0: "nan"})), BAD, UPDATE + "vertices [30, 33) outside the scene's 20 vertices"),
+    # vkrt_scene_add_skin: [5, 11) lies over the morph and over the skin
+    (skin(30, 2, jc=0, joints=None, weights=None, size=-1, out=0, scene=0), BAD, SKIN + "desc is NULL"),
+    (skin(30, 2, jc=0, joints=None, weights=None, size=S - 1, out=0, scene=0), BAD, SKIN + f"vkrt_skin_desc.struct_size {S - 1} < {S} (ABI mismatch)"),
+    (skin(30, 2, jc=0, joints=None, weights=None, out=0, scene=0), BAD, SKIN + "joint_count 0 outside 1..65536"),
+    (skin(30, 2, jc=65537, joints=None, weights=None, out=0, scene=0), BAD, SKIN + "joint_count 65537 outside 1..65536"),
+    (skin(30, 2, joints=None, weights=None, out=0, scene=0), BAD, SKIN + "joints is NULL"),
+    (skin(30, 2, joints=J(8, {5: 4}), weights=None, out=0, scene=0), BAD, SKIN + "weights is NULL"),
+    (skin(30, 2, joints=J(8, {5: 4}), weights=F(8, {2: "nan"}), out=0, scene=0), BAD, SKIN + "joints[5] (vertex 31) is 4, joint_count is 3"),
+    (skin(30, 2, weights=F(8, {2: "nan"}), out=0, scene=0), BAD, SKIN + "weights[2] (vertex 30) is not finite"),
+    (skin(30, 2, out=0, scene=0), BAD, SKIN + "out_skin is NULL"),
+    (skin(30, 2, scene=0), BAD, SKIN + "scene is NULL"),
+    (skin(21, 0, joints=None, weights=None), BAD, SKIN + "vertices [21, 21) outside the scene's 20 vertices"),   # outside, then empty
+    (skin(5, 6), BAD, SKIN + "vertices [5, 11) overlap skin 0's [10, 16)"),                                      # a skin, then a morph
+    # vkrt_scene_add_morph
+    (morph(30, 3, targets=0, dp=None, size=-1, out=0, scene=0), BAD, MORPH + "desc is NULL"),
+    (morph(30, 3, targets=0, dp=None, size=M - 1, out=0, scene=0), BAD, MORPH + f"vkrt_morph_desc.struct_size {M - 1} < {M} (ABI mismatch)"),
+    (morph(30, 3, targets=0, dp=None, out=0, scene=0), BAD, MORPH + "target_count 0 outside 1..256"),
+    (morph(30, 3, targets=257, dp=None, out=0, scene=0), BAD, MORPH + "target_count 257 outside 1..256"),
+    (morph(30, 3, dp=None, out=0, scene=0), BAD, MORPH + "position_deltas, normal_deltas and tangent_deltas are all NULL"),
+    (morph(30, 3, dp=NAN3, out=0, scene=0), BAD, MORPH + "position_deltas[15] (target 1, vertex 32) is not finite"),
+    (morph(30, 3, out=0, scene=0), BAD, MORPH + "out_morph is NULL"),
+    (morph(30, 3, scene=0), BAD, MORPH + "scene is NULL"),
+    (morph(21, 0, dp=NAN3), BAD, MORPH + "vertices [21, 21) outside the scene's 20 vertices"),                  # outside, then empty (no delta is read)
+    (morph(5, 6), BAD, MORPH + "vertices [5, 11) overlap morph 0's [4, 6)"),                                     # a morph, then the straddle
+    # vkrt_scene_skin_vertices, vkrt_scene_morph_vertices
+    (("shim_skin_vertices", 5, None, 7, 0), BAD, POSE_S + "memory 7 is neither VKRT_MEMORY_HOST nor VKRT_MEMORY_DEVICE"),
+    (("shim_skin_vertices", 5, None, DEVICE, 0), BAD, POSE_S + "scene is NULL"),
+    (("shim_skin_vertices", 5, None, DEVICE, 1), BAD, POSE_S + "skin 5 outside the scene's 1 skins"),
+    (("shim_skin_vertices", 0, None, DEVICE, 1), BAD, POSE_S + "joint_matrices is NULL"),
+    (("shim_skin_vertices", 0, None, HOST, 1), BAD, POSE_S + "joint_matrices is NULL"),
+    (("shim_skin_vertices", 0, P(0x1008), DEVICE, 1), BAD, POSE_S + "joint_matrices 0x1008 is not 16-byte aligned"),
+    (("shim_morph_vertices", 5, None, 2, 0), BAD, POSE_M + "memory 2 is neither VKRT_MEMORY_HOST nor VKRT_MEMORY_DEVICE"),
+    (("shim_morph_vertices", 5, None, HOST, 0), BAD, POSE_M + "scene is NULL"),
+    (("shim_morph_vertices", 5, None, HOST, 1), BAD, POSE_M + "morph 5 outside the scene's 1 morphs"),
+    (("shim_morph_vertices", 0, None, HOST, 1), BAD, POSE_M + "weights is NULL"),
+    (("shim_morph_vertices", 0, P(0x1002), DEVICE, 1), BAD, POSE_M + "weights 0x1002 is not 4-byte aligned"),
+]
+
+SIGNATURES = {"shim_update": "iIIIpi", "shim_add_skin": "iIIIppii", "shim_skin_vertices": "IpIi", "shim_add_morph": "iIIIpppii",
+              "shim_morph_vertices": "IpIi", "shim_read_vertices": "II"}
+CTYPE = {"i": C.c_int, "I": C.c_uint32, "p": C.c_void_p}
+
+
+@pytest.fixture(scope="module")
+def shim(tmp_path_factory):
+    d = tmp_path_factory.mktemp("vertex_anim_shim")
+    src, so = d / "shim.cpp", d / "libshim.so"
+    src.write_text(SHIM)
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-fPIC", "-shared", "-I", CSRC, str(src), *SOURCES, "-o", str(so)], check=True)
+    lib = C.CDLL(str(so))
+    for name, sig in SIGNATURES.items():
+        getattr(lib, name).argtypes = [CTYPE[c] for c in sig]
+    lib.shim_message.restype = C.c_char_p
+    return lib
+
+
+def run(lib, call):
+    keep = [a.numpy() if isinstance(a, (F, J)) else a for a in call[1:]]
+    args = [a.ctypes.data if isinstance(a, np.ndarray) else a.address if isinstance(a, P) else a for a in keep]
+    rc = getattr(lib, call[0])(*args)
+    return rc, lib.shim_message().decode()
+
+
+def test_every_case_returns_its_code_and_its_exact_message(shim):
+    for call, rc, message in CASES:
+        assert run(shim, call) == (rc, message), call
+
+
+# ---- under the sanitizers ----------------------------------------------------------------------------------------------------------------
+PROGRAM_HEAD = r"""
+#include <cmath>
+#include <cstring>
+#include <algorithm>
+#include <deque>
+#include <memory>
+#include <utility>
+namespace {
+std::deque<std::unique_ptr<float[]>> g_floats;
+std::deque<std::unique_ptr<uint16_t[]>> g_joints;
+const float* floats(size_t n, std::initializer_list<std::pair<size_t, float>> bad)
+{  // exactly n elements on the heap (not NULL for n = 0): a read past the end is the sanitizer's to report
+  g_floats.emplace_back(new float[n]);
+  std::fill_n(g_floats.back().get(), n, 0.25f);
+  for(const auto& b : bad) g_floats.back()[b.first] = b.second;
+  return g_floats.back().get();
+}
+const uint16_t* joints(size_t n, std::initializer_list<std::pair<size_t, int>> bad)
+{
+  g_joints.emplace_back(new uint16_t[n]());
+  for(const auto& b : bad) g_joints.back()[b.first] = (uint16_t)b.second;
+  return g_joints.back().get();
+}
+int failures = 0;
+void expect(int line, int got, int rc, const char* message)
+{
+  if(got == rc && strcmp(shim_message(), message) == 0) return;
+  failures++;
+  printf("case %d: %d '%s', expected %d '%s'\n", line, got, shim_message(), rc, message);
+}
+}
+int main()
+{
+"""
+
+
+def _cpp(a):
+    return "nullptr" if a is None else a.cpp() if isinstance(a, (F, J, P)) else "%du" % a if a > 0x7FFFFFFF else str(a)
+
+
+def test_the_same_calls_run_cleanly_under_the_sanitizers(tmp_path):
+    lines = ["  expect(%d, %s(%s), %d, %s);" % (i, call[0], ", ".join(_cpp(a) for a in call[1:]), rc, json.dumps(message))
+             for i, (call, rc, message) in enumerate(CASES)]
+    src, exe = tmp_path / "replay.cpp", tmp_path / "replay"
+    src.write_text(SHIM + PROGRAM_HEAD + "\n".join(lines) + '\n  printf("cases %d failures %d\\n", ' + str(len(CASES)) + ", failures);\n  return failures != 0;\n}\n")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC, str(src),
+                    *SOURCES, "-o", str(exe)], check=True)
+    p = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert p.returncode == 0 and p.stdout.strip().endswith(f"cases {len(CASES)} failures 0"), (p.returncode, p.stdout[-2000:], p.stderr[-3000:])

@@ -83,27 +83,12 @@ def test_refusals_that_need_no_device_come_in_the_headers_order():
         assert b"scene is NULL" in lib.vkrt_last_error(), lib.vkrt_last_error()
 
 
-class _NoLibrary:
-    def __getattr__(self, name):
-        raise AssertionError(f"the library was reached ({name}): the refusal must come before the call")
-
-
-def _renderer_without_scene(vertices=10):
-    from vkrt_amd.renderer import Renderer
-
-    r = Renderer.__new__(Renderer)  # no scene: the checks run before any use of the handle
-    r.device = 0
-    r._vertex_count = vertices
-    r._h = None
-    r.lib = _NoLibrary()
-    return r
-
-
 def test_python_refuses_bad_arrays_and_ranges_before_the_call():
     import torch
+    from renderer_stand_ins import renderer_without_scene
     from vkrt_amd.renderer import VkrtError
 
-    r = _renderer_without_scene(10)
+    r = renderer_without_scene(10)
     f32 = lambda n, w: np.zeros((n, w), np.float32)  # noqa: E731
     bad = [
         (dict(first=0, positions=np.zeros((2, 3), np.float64)), "positions"),          # dtype
@@ -133,39 +118,10 @@ def test_python_refuses_tensor_faults_through_a_stand_in():
     """Device tensors without a device: a stand-in that answers like a tensor on cuda:0 reaches the dtype, contiguity, device and
     numpy / torch mix checks."""
     import torch
+    from renderer_stand_ins import Fake, renderer_without_scene
     from vkrt_amd.renderer import VkrtError
 
-    class _Dev:
-        def __init__(self, index):
-            self.index = index
-
-        def __str__(self):
-            return f"cuda:{self.index}"
-
-    class Fake(torch.Tensor):
-        """answers like a float32 CUDA tensor of the given shape; holds no data"""
-
-        @staticmethod
-        def __new__(cls, shape, dtype=torch.float32, index=0, contiguous=True):
-            t = torch.Tensor._make_subclass(cls, torch.zeros(shape, dtype=dtype))
-            t._index, t._contiguous = index, contiguous
-            return t
-
-        @property
-        def is_cuda(self):
-            return True
-
-        @property
-        def device(self):
-            return _Dev(self._index)
-
-        def is_contiguous(self, *a, **k):
-            return self._contiguous
-
-        def data_ptr(self):
-            return 0x1000
-
-    r = _renderer_without_scene(10)
+    r = renderer_without_scene(10)
     bad = [
         (dict(first=0, positions=Fake((2, 3), index=1)), "positions"),                          # another device
         (dict(first=0, positions=Fake((2, 3), dtype=torch.float64)), "positions"),              # dtype

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Register, scratch and LDS use of the skinning kernels (csrc/skin.hip: k_skin, k_skin_capture), from the compiler's own report
-(-Rpass-analysis=kernel-resource-usage): no GPU needed.  Writes profiles/skin_kernel_resources.json and checks the condition of the
-feature: neither kernel reserves scratch or spills a register.
+"""Register, scratch and LDS use of named kernels of one translation unit of csrc/, from the compiler's own report
+(-Rpass-analysis=kernel-resource-usage): no GPU needed.  Writes profiles/<unit>_kernel_resources.json and checks the condition the
+vertex-animation units were merged under: none of the kernels reserves scratch or spills a register.
 
-    python tools/skin_resources.py [--out FILE]"""
+    python tools/kernel_resources.py skin.hip k_skin k_skin_capture [--out FILE]
+    python tools/kernel_resources.py morph.hip k_morph_live k_morph_bind [--out FILE]"""
 import argparse
 import json
 import os
@@ -13,8 +14,6 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from motion_resources import CSRC, FIELDS, FLAGS, HIPCC, ROOT  # noqa: E402
-
-KERNELS = ("k_skin", "k_skin_capture")
 
 
 def resources(unit):
@@ -37,12 +36,12 @@ def resources(unit):
     return kernels
 
 
-def measure():
-    """({kernel: fields}, [problems]) of the working tree's skin.hip"""
-    found = resources("skin.hip")
-    new = {k: found[k] for k in KERNELS if k in found}
+def measure(unit, names):
+    """({kernel: fields}, [problems]) of the kernels `names` of the working tree's csrc/<unit>"""
+    found = resources(unit)
+    new = {k: found[k] for k in names if k in found}
     problems = []
-    if set(new) != set(KERNELS):
+    if set(new) != set(names):
         problems.append(f"kernels found: {sorted(found)}")
     for k, v in new.items():
         if v["scratch_bytes"] or v["vgpr_spills"] or v["sgpr_spills"]:
@@ -52,13 +51,16 @@ def measure():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "skin_kernel_resources.json"))
+    ap.add_argument("unit", help="a translation unit of csrc/, e.g. skin.hip")
+    ap.add_argument("kernels", nargs="+")
+    ap.add_argument("--out")
     a = ap.parse_args()
-    new, problems = measure()
+    out = a.out or os.path.join(ROOT, "profiles", os.path.splitext(a.unit)[0] + "_kernel_resources.json")
+    new, problems = measure(a.unit, a.kernels)
     doc = {"hipcc": subprocess.run([HIPCC, "--version"], capture_output=True, text=True).stdout.splitlines()[0], "flags": " ".join(FLAGS),
            "note": "from -Rpass-analysis=kernel-resource-usage, no GPU run.  waves_per_simd = the compiler's occupancy figure.",
            "kernels": new, "conditions_met": not problems, "problems": problems}
-    with open(a.out, "w") as f:
+    with open(out, "w") as f:
         json.dump(doc, f, indent=1)
         f.write("\n")
     for k, v in new.items():

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
+#include <initializer_list>
 #include <memory>
 #include <string>
 #include <type_traits>
@@ -48,6 +49,49 @@ public:
 private:
   struct Free { void operator()(void* p) const { (void)hipFree(p); } };
   std::unique_ptr<void, Free> p_;
+};
+
+// The staging buffer of a scene's host-sourced vertex data: update arrays, joint matrices, morph weights.  One rule makes one buffer
+// enough for all of them: a call that stages waits for its stream before it returns, so at the next put() nothing reads the buffer
+// any more, and it may be overwritten, or freed to grow.  It only grows.
+class StageBuf
+{
+public:
+  struct Part
+  {
+    const float* src;   // host array, or NULL: no part
+    size_t floats;
+    const float** dev;  // where the part lies on the device (left alone without a part)
+  };
+  // The parts back to back, in the order given, copied on `stream`.  The caller orders them so that each starts aligned for its reader
+  // (16-byte elements first), and synchronises `stream` before it returns.
+  hipError_t put(std::initializer_list<Part> parts, hipStream_t stream)
+  {
+    size_t bytes = 0;
+    for(const Part& p : parts)
+      bytes += p.src ? p.floats * sizeof(float) : 0;
+    if(bytes > bytes_)
+    {
+      bytes_ = 0;
+      if(const hipError_t e = buf_.alloc(bytes); e != hipSuccess)
+        return e;
+      bytes_ = bytes;
+    }
+    float* at = buf_.get<float>();
+    for(const Part& p : parts)
+      if(p.src)
+      {
+        if(const hipError_t e = hipMemcpyAsync(at, p.src, p.floats * sizeof(float), hipMemcpyHostToDevice, stream); e != hipSuccess)
+          return e;
+        *p.dev = at;
+        at += p.floats;
+      }
+    return hipSuccess;
+  }
+
+private:
+  DevBuf buf_;
+  size_t bytes_ = 0;
 };
 
 // One event / one stream, destroyed by the destructor or when another owner is moved over it.

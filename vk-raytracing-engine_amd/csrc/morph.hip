@@ -24,47 +24,18 @@ namespace vkrt {
 
 namespace {
 
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef float f3 __attribute__((ext_vector_type(3)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f3u __attribute__((ext_vector_type(3), aligned(4)));  // the scene's own vec3 positions, and the deltas
-
-static_assert(VKRT_VERTEX_QUADS == 3, "the morph kernels write the three float4 of a vertex record");
-
 constexpr unsigned kBlock = 256;
-
-// skin.hip's rule: a zero or overflowing length leaves the vector as it is
-__device__ __forceinline__ f3 normalizeGuarded(f3 a)
-{
-  const float d = (a.x * a.x + a.y * a.y) + a.z * a.z;
-  if(d > 0.0f && d < __builtin_inff())
-  {
-    const float inv = 1.0f / sqrtf(d);
-    return a * inv;
-  }
-  return a;
-}
-
-struct Morphed
-{
-  f3 p, n, t;
-  float tw;
-};
 
 // vertex i of the morph: the captured base, then target after target in index order.
 // The weights are read 64 at a time, one per lane, and the targets in use come out of a ballot: the loop runs once per non-zero
 // weight, its count and every branch in it are wave-uniform, and a weight reaches the lanes through a scalar register (readlane).
 // Every lane of the wave must be here (the callers clamp i instead of returning early): the ballot and the readlane need them.
 // The three loads of a target are issued before the first of its sums; an attribute without deltas sums zeros that are dropped.
-__device__ __forceinline__ Morphed morphVertex(uint32_t i, uint32_t count, uint32_t targetCount, const float4* __restrict__ basePN,
-                                               const float2* __restrict__ baseNyz, const float4* __restrict__ baseTan, const float* __restrict__ dPos,
-                                               const float* __restrict__ dNrm, const float* __restrict__ dTan, const float* __restrict__ weights)
+__device__ __forceinline__ PoseVertex morphVertex(uint32_t i, uint32_t count, uint32_t targetCount, const Pose& base, const float* __restrict__ dPos,
+                                                  const float* __restrict__ dNrm, const float* __restrict__ dTan, const float* __restrict__ weights)
 {
-  const float4 b0 = basePN[i];
-  const float2 b1 = baseNyz[i];
-  const float4 b2 = baseTan[i];
-  const f3 p0 = {b0.x, b0.y, b0.z}, n0 = {b0.w, b1.x, b1.y}, t0 = {b2.x, b2.y, b2.z};
-  f3 P = p0, N = n0, T = t0;
+  const PoseVertex b = pose_load(base, i);
+  f3 P = b.p, N = b.n, T = b.t;
   const uint32_t lane = threadIdx.x & 63u;
   bool any = false;
   for(uint32_t k0 = 0; k0 < targetCount; k0 += 64)
@@ -90,49 +61,35 @@ __device__ __forceinline__ Morphed morphVertex(uint32_t i, uint32_t count, uint3
       T = T + w * dt;
     }
   }
-  Morphed out;
-  out.p = dPos ? P : p0;
-  out.n = dNrm ? (any ? normalizeGuarded(N) : N) : n0;
-  out.t = dTan ? (any ? normalizeGuarded(T) : T) : t0;
-  out.tw = b2.w;
-  return out;
+  return PoseVertex{dPos ? P : b.p, dNrm ? (any ? normalizeGuarded(N) : N) : b.n, dTan ? (any ? normalizeGuarded(T) : T) : b.t, b.tw};
 }
 
-__global__ __launch_bounds__(kBlock) void k_morph_live(uint32_t first, uint32_t count, uint32_t targetCount, const float4* __restrict__ basePN,
-                                                       const float2* __restrict__ baseNyz, const float4* __restrict__ baseTan,
-                                                       const float* __restrict__ dPos, const float* __restrict__ dNrm, const float* __restrict__ dTan,
+__global__ __launch_bounds__(kBlock) void k_morph_live(uint32_t first, uint32_t count, uint32_t targetCount, Pose base, const float* __restrict__ dPos,
+                                                       const float* __restrict__ dNrm, const float* __restrict__ dTan,
                                                        const float* __restrict__ weights, float* __restrict__ positions, float4* __restrict__ vertexPN)
 {
   const uint32_t at = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t i = at < count ? at : count - 1;  // (the lanes past the end redo the last vertex and store nothing)
-  const Morphed m = morphVertex(i, count, targetCount, basePN, baseNyz, baseTan, dPos, dNrm, dTan, weights);
+  const PoseVertex m = morphVertex(i, count, targetCount, base, dPos, dNrm, dTan, weights);
   if(at >= count)
     return;
-  const size_t v = (size_t)first + i;
-  float* rec = (float*)(vertexPN + VKRT_VERTEX_QUADS * v);  // 48 B, 16-byte aligned
-  *(f3u*)(positions + 3 * v) = m.p;
-  *(f4*)rec = f4{m.p.x, m.p.y, m.p.z, m.n.x};        // quad 0 = position.xyz, normal.x
-  *(f2*)(rec + 4) = f2{m.n.y, m.n.z};                // quad 1 = normal.yz, uv (kept)
-  *(f4*)(rec + 8) = f4{m.t.x, m.t.y, m.t.z, m.tw};   // quad 2 = tangent, its handedness as captured
+  live_store(positions, vertexPN, (size_t)first + i, m);
 }
 
-__global__ __launch_bounds__(kBlock) void k_morph_bind(uint32_t count, uint32_t targetCount, const float4* __restrict__ basePN,
-                                                       const float2* __restrict__ baseNyz, const float4* __restrict__ baseTan,
-                                                       const float* __restrict__ dPos, const float* __restrict__ dNrm, const float* __restrict__ dTan,
-                                                       const float* __restrict__ weights, float4* __restrict__ bindPN, float2* __restrict__ bindNyz,
-                                                       float4* __restrict__ bindTan)
+__global__ __launch_bounds__(kBlock) void k_morph_bind(uint32_t count, uint32_t targetCount, float4* __restrict__ basePN, float2* __restrict__ baseNyz,
+                                                       float4* __restrict__ baseTan, const float* __restrict__ dPos, const float* __restrict__ dNrm,
+                                                       const float* __restrict__ dTan, const float* __restrict__ weights, float4* __restrict__ bindPN,
+                                                       float2* __restrict__ bindNyz, float4* __restrict__ bindTan)
 {
+  // (two poses as six pointer arguments: with two Pose arguments the compiler fetches the kernel arguments in other pieces)
+  const Pose base = {basePN, baseTan, baseNyz}, bind = {bindPN, bindTan, bindNyz};
   const uint32_t at = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t i = at < count ? at : count - 1;  // (as in k_morph_live)
-  const Morphed m = morphVertex(i, count, targetCount, basePN, baseNyz, baseTan, dPos, dNrm, dTan, weights);
+  const PoseVertex m = morphVertex(i, count, targetCount, base, dPos, dNrm, dTan, weights);
   if(at >= count)
     return;
-  bindPN[i] = make_float4(m.p.x, m.p.y, m.p.z, m.n.x);
-  bindNyz[i] = make_float2(m.n.y, m.n.z);
-  bindTan[i] = make_float4(m.t.x, m.t.y, m.t.z, m.tw);
+  pose_store(bind, i, m);
 }
-
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 size_t deltaBytes(uint32_t count, uint32_t targetCount) { return align16((size_t)targetCount * count * 3 * sizeof(float)); }
 
@@ -140,18 +97,15 @@ size_t deltaBytes(uint32_t count, uint32_t targetCount) { return align16((size_t
 
 size_t morph_bytes(uint32_t count, uint32_t targetCount, bool hasPos, bool hasNrm, bool hasTan)
 {
-  return 2 * (size_t)count * 16 + align16((size_t)count * 8) + ((size_t)hasPos + (size_t)hasNrm + (size_t)hasTan) * deltaBytes(count, targetCount);
+  return pose_bytes(count) + ((size_t)hasPos + (size_t)hasNrm + (size_t)hasTan) * deltaBytes(count, targetCount);
 }
 
 void morph_carve(void* mem, uint32_t first, uint32_t count, uint32_t targetCount, bool hasPos, bool hasNrm, bool hasTan, MorphArrays& out)
 {
-  char* at = (char*)mem;
   out.first = first;
   out.count = count;
   out.targetCount = targetCount;
-  out.basePN = (float4*)at;   at += (size_t)count * 16;
-  out.baseTan = (float4*)at;  at += (size_t)count * 16;
-  out.baseNyz = (float2*)at;  at += align16((size_t)count * 8);
+  char* at = pose_carve((char*)mem, count, out.base);
   out.dPos = out.dNrm = out.dTan = nullptr;
   if(hasPos)
     out.dPos = (float*)at, at += deltaBytes(count, targetCount);
@@ -165,17 +119,17 @@ hipError_t launch_morph_live(float* positions, float4* vertexPN, const MorphArra
 {
   if(m.count == 0)
     return hipSuccess;
-  hipLaunchKernelGGL(k_morph_live, dim3((m.count + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, m.first, m.count, m.targetCount, m.basePN, m.baseNyz,
-                     m.baseTan, m.dPos, m.dNrm, m.dTan, weights, positions, vertexPN);
+  hipLaunchKernelGGL(k_morph_live, dim3((m.count + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, m.first, m.count, m.targetCount, m.base, m.dPos, m.dNrm,
+                     m.dTan, weights, positions, vertexPN);
   return hipGetLastError();
 }
 
-hipError_t launch_morph_bind(float4* bindPN, float2* bindNyz, float4* bindTan, const MorphArrays& m, const float* weights, hipStream_t stream)
+hipError_t launch_morph_bind(Pose bind, const MorphArrays& m, const float* weights, hipStream_t stream)
 {
   if(m.count == 0)
     return hipSuccess;
-  hipLaunchKernelGGL(k_morph_bind, dim3((m.count + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, m.count, m.targetCount, m.basePN, m.baseNyz, m.baseTan,
-                     m.dPos, m.dNrm, m.dTan, weights, bindPN, bindNyz, bindTan);
+  hipLaunchKernelGGL(k_morph_bind, dim3((m.count + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, m.count, m.targetCount, m.base.pn, m.base.nyz, m.base.tan,
+                     m.dPos, m.dNrm, m.dTan, weights, bind.pn, bind.nyz, bind.tan);
   return hipGetLastError();
 }
 

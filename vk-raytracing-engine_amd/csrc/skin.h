@@ -5,18 +5,18 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "vertex_anim.h"
+#include "vertex_record.h"
+
 namespace vkrt {
 
 // One skin's device arrays, carved out of one allocation (skin_carve): per vertex of [first, first + count) the bind pose captured by
-// vkrt_scene_add_skin (40 B: position + normal.x | normal.yz | tangent, the words of a vertexPN record without its uv) and the
-// influences (8 B of joint indices, 16 B of weights).  Every array starts 16-byte aligned.
-struct SkinArrays
+// vkrt_scene_add_skin (vertex_record.h Pose, 40 B) and the influences (16 B of weights, 8 B of joint indices).  Every array starts
+// 16-byte aligned.
+struct SkinArrays : VertexRange
 {
-  uint32_t first = 0, count = 0;
-  float4* bindPN = nullptr;   // position.xyz, normal.x
-  float4* bindTan = nullptr;  // tangent.xyzw
+  Pose bind;
   float4* weights = nullptr;  // WEIGHTS_0
-  float2* bindNyz = nullptr;  // normal.yz
   uint2* joints = nullptr;    // JOINTS_0: four u16, (j0 | j1 << 16, j2 | j3 << 16)
 };
 
@@ -24,9 +24,9 @@ struct SkinArrays
 size_t skin_bytes(uint32_t count);
 void skin_carve(void* mem, uint32_t first, uint32_t count, SkinArrays& out);
 
-// The bind pose of the skin's range as the scene's arrays hold it at this point of `stream`: a device copy out of `positions`
-// (DevScene::positions) and `vertexPN` (DevScene::vertexPN).
-hipError_t launch_skin_capture(const float* positions, const float4* vertexPN, const SkinArrays& k, hipStream_t stream);
+// Vertices [first, first + count) as the scene's arrays hold them at this point of `stream`, into `pose` (a skin's bind pose, a morph's
+// base shape): a device copy out of `positions` (DevScene::positions) and `vertexPN` (DevScene::vertexPN).
+hipError_t launch_pose_capture(const float* positions, const float4* vertexPN, uint32_t first, uint32_t count, Pose pose, hipStream_t stream);
 
 // One launch of k_skin on `stream`, no allocation, no host synchronisation: the bind pose blended through `jointMatrices` (device,
 // 16-byte aligned, [joint_count][16] column-major, rows 0..2 read) into positions[3 v ..] and the position, normal and tangent words of

@@ -13,22 +13,16 @@
 // multi-dword global accesses at dword alignment, so one code path serves every pointer the caller may pass.
 #include <hip/hip_runtime.h>
 
-#include "device_scene.h"
+#include "vertex_record.h"
 #include "vertex_update.h"
 
 namespace vkrt {
 
 namespace {
 
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef float f3 __attribute__((ext_vector_type(3)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-// the same vectors at the alignment of a float: the caller's arrays, and the scene's own vec3 positions
+// vertex_record.h's vectors at the alignment of a float, like its f3u: the caller's arrays
 typedef float f2u __attribute__((ext_vector_type(2), aligned(4)));
-typedef float f3u __attribute__((ext_vector_type(3), aligned(4)));
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
-
-static_assert(VKRT_VERTEX_QUADS == 3, "k_vertex_update writes the three float4 of a vertex record");
 
 __global__ __launch_bounds__(256) void k_vertex_update(uint32_t first, uint32_t count, const float* __restrict__ pos, const float* __restrict__ nrm,
                                                        const float* __restrict__ tan, const float* __restrict__ uv, float* __restrict__ positions, float4* __restrict__ vertexPN)

@@ -31,6 +31,7 @@
 #include "morph.h"
 #include "refit.h"
 #include "skin.h"
+#include "vertex_anim.h"
 #include "vertex_update.h"
 
 namespace {
@@ -102,8 +103,7 @@ struct vkrt_scene
   vkrt::RefitScratch refit;  // level lists + exact node boxes of the current build (allocated at its first refit)
   // deforming meshes (vkrt_scene_update_vertices)
   bool positionsOnDevice = false;  // a device-sourced update moved vertices the host copy has not seen: the next build downloads them first
-  vkrt::DevBuf vertexStage;        // staging of host-sourced updates (grown by an update larger than every earlier one)
-  size_t vertexStageBytes = 0;
+  vkrt::StageBuf vertexStage;      // staging of host-sourced updates, joint matrices and morph weights
   // skinned meshes (vkrt_scene_add_skin): per skin one allocation holding the captured bind pose and the influences of its vertex range;
   // the ranges are disjoint, the index in the list is the skin's number
   struct Skin
@@ -154,8 +154,34 @@ int upload(vkrt_scene* s, const T* src, size_t count, const T** dst)
   return VKRT_OK;
 }
 
-// a refusal of scene_pack.h's checks, whose reason is in err
+// a refusal of scene_pack.h's or vertex_anim.h's checks, whose reason is in err
 int failWith(int code, const std::string& err) { return fail(code, "%s", err.c_str()); }
+
+// return such a refusal from the enclosing function: CHECK_TRY(check_x(..., err)), a function of namespace vkrt given the macro's own err
+#define CHECK_TRY(call)                                    \
+  do                                                       \
+  {                                                        \
+    std::string err;                                       \
+    if(const int rc_ = vkrt::call; rc_ != VKRT_OK)         \
+      return failWith(rc_, err);                           \
+  } while(0)
+
+// the vertex ranges of the scene's skins or morphs, where they are kept
+template <typename T>
+vkrt::RangeSet rangesOf(const std::vector<T>& v)
+{
+  return vkrt::RangeSet{v.empty() ? nullptr : &v[0].arrays, v.size(), sizeof(T)};
+}
+
+// Live positions moved on the device: the tree is stale until the next refit or build, and -- unless the host copy got the same values --
+// the next build downloads them first.
+void positionsMoved(vkrt_scene* s, bool hostCopyFollowed = false)
+{
+  if(!hostCopyFollowed)
+    s->positionsOnDevice = true;
+  if(s->built)
+    s->stale = true;
+}
 
 // execution mode: wavefront pipeline (default) or the single persistent megakernel
 bool useWavefront(const vkrt_scene* s) { return s->opt[VKRT_OPT_MODE] == 1; }
@@ -1004,26 +1030,12 @@ int vkrt_accel_refit(vkrt_scene* s, void* hip_stream)
 
 int vkrt_scene_update_vertices(vkrt_scene* s, const vkrt_vertex_update* u, void* hip_stream)
 {
-  const char* who = "vkrt_scene_update_vertices";
-  if(!u)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: update is NULL", who);
-  if(u->struct_size < sizeof(vkrt_vertex_update))
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vkrt_vertex_update.struct_size %u < %zu (ABI mismatch)", who, u->struct_size, sizeof(vkrt_vertex_update));
-  if(u->memory != VKRT_MEMORY_HOST && u->memory != VKRT_MEMORY_DEVICE)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: memory %u is neither VKRT_MEMORY_HOST nor VKRT_MEMORY_DEVICE", who, u->memory);
+  CHECK_TRY(check_update_desc(u, err));
   if(!s)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
-  const size_t vertexCount = s->positions.size() / 3;
-  if((uint64_t)u->first + u->count > vertexCount)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vertices [%u, %llu) outside the scene's %zu vertices", who, u->first,
-                (unsigned long long)u->first + u->count, vertexCount);
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "vkrt_scene_update_vertices: scene is NULL");
+  CHECK_TRY(check_update_range(*u, s->positions.size() / 3, err));
   const bool host = u->memory == VKRT_MEMORY_HOST;
   const size_t n = u->count;
-  // the rule of vkrt_scene_create, checked for the whole range before anything changes
-  if(host && u->positions)
-    for(size_t i = 0; i < 3 * n; i++)
-      if(!std::isfinite(u->positions[i]))
-        return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: positions[%zu] (vertex %zu) is not finite", who, i, (size_t)u->first + i / 3);
   if(n == 0 || (!u->positions && !u->normals && !u->tangents && !u->texcoords0))
     return VKRT_OK;
   int rc = setDevice(s);
@@ -1034,30 +1046,9 @@ int vkrt_scene_update_vertices(vkrt_scene* s, const vkrt_vertex_update* u, void*
   d.first = u->first;
   d.count = u->count;
   d.positions = u->positions; d.normals = u->normals; d.tangents = u->tangents; d.texcoords0 = u->texcoords0;
-  if(host)
-  {  // the given arrays, back to back in the scene's staging buffer (16-byte elements first, so every part starts aligned for its loads)
-    const float* src[4] = {u->tangents, u->texcoords0, u->positions, u->normals};
-    const float** dst[4] = {&d.tangents, &d.texcoords0, &d.positions, &d.normals};
-    const size_t width[4] = {4, 2, 3, 3};
-    size_t bytes = 0;
-    for(int k = 0; k < 4; k++)
-      if(src[k]) bytes += n * width[k] * sizeof(float);
-    if(bytes > s->vertexStageBytes)
-    {  // (every earlier host update has waited for its stream: nothing reads the old buffer)
-      s->vertexStageBytes = 0;
-      HIP_TRY(s->vertexStage.alloc(bytes));
-      s->vertexStageBytes = bytes;
-    }
-    size_t at = 0;
-    for(int k = 0; k < 4; k++)
-      if(src[k])
-      {
-        float* part = (float*)(s->vertexStage.get<char>() + at);
-        HIP_TRY(hipMemcpyAsync(part, src[k], n * width[k] * sizeof(float), hipMemcpyHostToDevice, stream));
-        *dst[k] = part;
-        at += n * width[k] * sizeof(float);
-      }
-  }
+  if(host)  // the given arrays through the staging buffer, 16-byte elements first, so every part starts aligned for its loads
+    HIP_TRY(s->vertexStage.put({{u->tangents, 4 * n, &d.tangents}, {u->texcoords0, 2 * n, &d.texcoords0}, {u->positions, 3 * n, &d.positions},
+                                {u->normals, 3 * n, &d.normals}}, stream));
   // Stream-ordered like vkrt_scene_update_nodes: one launch on hip_stream, after whatever still reads the old vertices and before the
   // refit and the next trace (whose internal lane streams fork from and join to the caller's stream).
   HIP_TRY(vkrt::launch_vertex_update(const_cast<float*>(s->dev.positions), const_cast<float4*>(s->dev.vertexPN), d, stream));
@@ -1067,62 +1058,24 @@ int vkrt_scene_update_vertices(vkrt_scene* s, const vkrt_vertex_update* u, void*
     if(u->positions)
       std::copy(u->positions, u->positions + 3 * n, s->positions.begin() + 3 * (size_t)u->first);
   }
-  else if(u->positions)
-    s->positionsOnDevice = true;
-  if(u->positions && s->built)
-    s->stale = true;
+  if(u->positions)
+    positionsMoved(s, host);
   return VKRT_OK;
 }
 
 int vkrt_scene_add_skin(vkrt_scene* s, const vkrt_skin_desc* k, void* hip_stream, uint32_t* out_skin)
 {
   const char* who = "vkrt_scene_add_skin";
-  if(!k)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: desc is NULL", who);
-  if(k->struct_size < sizeof(vkrt_skin_desc))
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vkrt_skin_desc.struct_size %u < %zu (ABI mismatch)", who, k->struct_size, sizeof(vkrt_skin_desc));
-  if(k->joint_count == 0 || k->joint_count > 65536u)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: joint_count %u outside 1..65536", who, k->joint_count);
-  const size_t n = k->count;
-  if(n && !k->joints)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: joints is NULL", who);
-  if(n && !k->weights)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: weights is NULL", who);
-  // the gather of k_skin is bounded here: no later call looks at an index again
-  for(size_t i = 0; i < 4 * n; i++)
-    if(k->joints[i] >= k->joint_count)
-      return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: joints[%zu] (vertex %zu) is %u, joint_count is %u", who, i, (size_t)k->first + i / 4,
-                  (unsigned)k->joints[i], k->joint_count);
-  for(size_t i = 0; i < 4 * n; i++)
-    if(!std::isfinite(k->weights[i]))
-      return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: weights[%zu] (vertex %zu) is not finite", who, i, (size_t)k->first + i / 4);
+  CHECK_TRY(check_skin_desc(k, err));
   if(!out_skin)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: out_skin is NULL", who);
   if(!s)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
-  const size_t vertexCount = s->positions.size() / 3;
-  if((uint64_t)k->first + k->count > vertexCount)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vertices [%u, %llu) outside the scene's %zu vertices", who, k->first,
-                (unsigned long long)k->first + k->count, vertexCount);
-  if(n == 0)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: count is 0", who);
-  for(size_t j = 0; j < s->skins.size(); j++)
-  {
-    const vkrt::SkinArrays& a = s->skins[j].arrays;
-    if(k->first < a.first + a.count && a.first < k->first + k->count)
-      return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vertices [%u, %u) overlap skin %zu's [%u, %u)", who, k->first, k->first + k->count, j, a.first,
-                  a.first + a.count);
-  }
-  for(size_t j = 0; j < s->morphs.size(); j++)
-  {  // (skins come first: a morph inside a skin's range captured its base from that skin's bind pose)
-    const vkrt::MorphArrays& a = s->morphs[j].arrays;
-    if(k->first < a.first + a.count && a.first < k->first + k->count)
-      return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vertices [%u, %u) overlap morph %zu's [%u, %u): add skins before morphs", who, k->first,
-                  k->first + k->count, j, a.first, a.first + a.count);
-  }
+  CHECK_TRY(check_skin_range(*k, s->positions.size() / 3, rangesOf(s->skins), rangesOf(s->morphs), err));
   int rc = setDevice(s);
   if(rc != VKRT_OK)
     return rc;
+  const size_t n = k->count;
   vkrt_scene::Skin skin;
   skin.jointCount = k->joint_count;
   HIP_TRY(skin.mem.alloc(vkrt::skin_bytes(k->count)));
@@ -1130,7 +1083,7 @@ int vkrt_scene_add_skin(vkrt_scene* s, const vkrt_skin_desc* k, void* hip_stream
   HIP_TRY(hipMemcpy(skin.arrays.joints, k->joints, n * 4 * sizeof(uint16_t), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(skin.arrays.weights, k->weights, n * 4 * sizeof(float), hipMemcpyHostToDevice));
   // stream-ordered like the update calls: the bind pose is what the updates enqueued before this call on hip_stream left
-  HIP_TRY(vkrt::launch_skin_capture(s->dev.positions, s->dev.vertexPN, skin.arrays, (hipStream_t)hip_stream));
+  HIP_TRY(vkrt::launch_pose_capture(s->dev.positions, s->dev.vertexPN, k->first, k->count, skin.arrays.bind, (hipStream_t)hip_stream));
   *out_skin = (uint32_t)s->skins.size();
   s->skins.push_back(std::move(skin));
   return VKRT_OK;
@@ -1139,99 +1092,42 @@ int vkrt_scene_add_skin(vkrt_scene* s, const vkrt_skin_desc* k, void* hip_stream
 int vkrt_scene_skin_vertices(vkrt_scene* s, uint32_t skin, const float* joint_matrices, uint32_t memory, void* hip_stream)
 {
   const char* who = "vkrt_scene_skin_vertices";
-  if(memory != VKRT_MEMORY_HOST && memory != VKRT_MEMORY_DEVICE)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: memory %u is neither VKRT_MEMORY_HOST nor VKRT_MEMORY_DEVICE", who, memory);
+  CHECK_TRY(check_memory(who, memory, err));
   if(!s)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
-  if(skin >= s->skins.size())
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: skin %u outside the scene's %zu skins", who, skin, s->skins.size());
-  const bool host = memory == VKRT_MEMORY_HOST;
-  if(!joint_matrices)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: joint_matrices is NULL", who);
-  if(!host && ((uintptr_t)joint_matrices & 15u) != 0)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: joint_matrices %p is not 16-byte aligned", who, (const void*)joint_matrices);
+  CHECK_TRY(check_skin_index(skin, s->skins.size(), err));
   const vkrt_scene::Skin& k = s->skins[skin];
-  const size_t floats = (size_t)k.jointCount * 16, bytes = floats * sizeof(float);
-  if(host)
-    for(size_t i = 0; i < floats; i++)
-      if(!std::isfinite(joint_matrices[i]))
-        return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: joint_matrices[%zu] (joint %zu) is not finite", who, i, i / 16);
+  CHECK_TRY(check_joint_matrices(joint_matrices, memory, k.jointCount, err));
+  const bool host = memory == VKRT_MEMORY_HOST;
   int rc = setDevice(s);
   if(rc != VKRT_OK)
     return rc;
   hipStream_t stream = (hipStream_t)hip_stream;
-  const float4* palette = (const float4*)joint_matrices;
+  const float* palette = joint_matrices;
   if(host)
-  {  // through the staging buffer of host vertex updates (every earlier host call has waited for its stream: nothing reads it)
-    if(bytes > s->vertexStageBytes)
-    {
-      s->vertexStageBytes = 0;
-      HIP_TRY(s->vertexStage.alloc(bytes));
-      s->vertexStageBytes = bytes;
-    }
-    HIP_TRY(hipMemcpyAsync(s->vertexStage.get(), joint_matrices, bytes, hipMemcpyHostToDevice, stream));
-    palette = s->vertexStage.get<const float4>();
-  }
-  HIP_TRY(vkrt::launch_skin(const_cast<float*>(s->dev.positions), const_cast<float4*>(s->dev.vertexPN), k.arrays, palette, stream));
+    HIP_TRY(s->vertexStage.put({{joint_matrices, (size_t)k.jointCount * 16, &palette}}, stream));
+  HIP_TRY(vkrt::launch_skin(const_cast<float*>(s->dev.positions), const_cast<float4*>(s->dev.vertexPN), k.arrays, (const float4*)palette, stream));
   if(host)
     HIP_TRY(hipStreamSynchronize(stream));  // the caller's matrices and the staging buffer are free again
-  s->positionsOnDevice = true;  // (host matrices too: the posed positions exist on the device only)
-  if(s->built)
-    s->stale = true;
+  positionsMoved(s);  // (host matrices too: the posed positions exist on the device only)
   return VKRT_OK;
 }
 
 int vkrt_scene_add_morph(vkrt_scene* s, const vkrt_morph_desc* m, void* hip_stream, uint32_t* out_morph)
 {
   const char* who = "vkrt_scene_add_morph";
-  if(!m)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: desc is NULL", who);
-  if(m->struct_size < sizeof(vkrt_morph_desc))
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vkrt_morph_desc.struct_size %u < %zu (ABI mismatch)", who, m->struct_size, sizeof(vkrt_morph_desc));
-  if(m->target_count == 0 || m->target_count > VKRT_MORPH_TARGETS_MAX)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: target_count %u outside 1..%u", who, m->target_count, (unsigned)VKRT_MORPH_TARGETS_MAX);
-  if(!m->position_deltas && !m->normal_deltas && !m->tangent_deltas)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: position_deltas, normal_deltas and tangent_deltas are all NULL", who);
-  const size_t n = m->count, floats = (size_t)m->target_count * n * 3;
-  const float* const deltas[3] = {m->position_deltas, m->normal_deltas, m->tangent_deltas};
-  const char* const names[3] = {"position_deltas", "normal_deltas", "tangent_deltas"};
-  for(int a = 0; a < 3; a++)
-    if(deltas[a])
-      for(size_t i = 0; i < floats; i++)
-        if(!std::isfinite(deltas[a][i]))
-          return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: %s[%zu] (target %zu, vertex %zu) is not finite", who, names[a], i, i / (3 * n),
-                      (size_t)m->first + i / 3 % n);
+  CHECK_TRY(check_morph_desc(m, err));
   if(!out_morph)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: out_morph is NULL", who);
   if(!s)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
-  const size_t vertexCount = s->positions.size() / 3;
-  if((uint64_t)m->first + m->count > vertexCount)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vertices [%u, %llu) outside the scene's %zu vertices", who, m->first,
-                (unsigned long long)m->first + m->count, vertexCount);
-  if(n == 0)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: count is 0", who);
-  const uint32_t end = m->first + m->count;
-  for(size_t j = 0; j < s->morphs.size(); j++)
-  {
-    const vkrt::MorphArrays& a = s->morphs[j].arrays;
-    if(m->first < a.first + a.count && a.first < end)
-      return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vertices [%u, %u) overlap morph %zu's [%u, %u)", who, m->first, end, j, a.first, a.first + a.count);
-  }
   int inSkin = -1;
-  for(size_t j = 0; j < s->skins.size(); j++)
-  {  // inside one skin or clear of all of them (the skins are disjoint: a range inside one touches no other)
-    const vkrt::SkinArrays& a = s->skins[j].arrays;
-    if(!(m->first < a.first + a.count && a.first < end))
-      continue;
-    if(m->first < a.first || end > a.first + a.count)
-      return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vertices [%u, %u) straddle the boundary of skin %zu's [%u, %u): a morph lies inside one skin or outside all",
-                  who, m->first, end, j, a.first, a.first + a.count);
-    inSkin = (int)j;
-  }
+  CHECK_TRY(check_morph_range(*m, s->positions.size() / 3, rangesOf(s->skins), rangesOf(s->morphs), inSkin, err));
   int rc = setDevice(s);
   if(rc != VKRT_OK)
     return rc;
+  const size_t n = m->count, floats = (size_t)m->target_count * n * 3;
+  const float* const deltas[3] = {m->position_deltas, m->normal_deltas, m->tangent_deltas};
   vkrt_scene::Morph morph;
   morph.skin = inSkin;
   const bool has[3] = {deltas[0] != nullptr, deltas[1] != nullptr, deltas[2] != nullptr};
@@ -1249,18 +1145,14 @@ int vkrt_scene_add_morph(vkrt_scene* s, const vkrt_morph_desc* m, void* hip_stre
   // stream-ordered like the update calls: the base is what the calls enqueued before this one on hip_stream left
   hipStream_t stream = (hipStream_t)hip_stream;
   if(inSkin < 0)
-  {  // (skin.hip's capture: a morph's base arrays are laid out like a skin's bind pose)
-    vkrt::SkinArrays cap;
-    cap.first = a.first, cap.count = a.count, cap.bindPN = a.basePN, cap.bindNyz = a.baseNyz, cap.bindTan = a.baseTan;
-    HIP_TRY(vkrt::launch_skin_capture(s->dev.positions, s->dev.vertexPN, cap, stream));
-  }
+    HIP_TRY(vkrt::launch_pose_capture(s->dev.positions, s->dev.vertexPN, a.first, a.count, a.base, stream));
   else
   {
     const vkrt::SkinArrays& k = s->skins[inSkin].arrays;
-    const size_t off = m->first - k.first;
-    HIP_TRY(hipMemcpyAsync(a.basePN, k.bindPN + off, n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(a.baseNyz, k.bindNyz + off, n * sizeof(float2), hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(a.baseTan, k.bindTan + off, n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+    const vkrt::Pose bind = k.bind.at(m->first - k.first);
+    HIP_TRY(hipMemcpyAsync(a.base.pn, bind.pn, n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(a.base.nyz, bind.nyz, n * sizeof(float2), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(a.base.tan, bind.tan, n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
   }
   *out_morph = (uint32_t)s->morphs.size();
   s->morphs.push_back(std::move(morph));
@@ -1270,55 +1162,31 @@ int vkrt_scene_add_morph(vkrt_scene* s, const vkrt_morph_desc* m, void* hip_stre
 int vkrt_scene_morph_vertices(vkrt_scene* s, uint32_t morph, const float* weights, uint32_t memory, void* hip_stream)
 {
   const char* who = "vkrt_scene_morph_vertices";
-  if(memory != VKRT_MEMORY_HOST && memory != VKRT_MEMORY_DEVICE)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: memory %u is neither VKRT_MEMORY_HOST nor VKRT_MEMORY_DEVICE", who, memory);
+  CHECK_TRY(check_memory(who, memory, err));
   if(!s)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
-  if(morph >= s->morphs.size())
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: morph %u outside the scene's %zu morphs", who, morph, s->morphs.size());
-  const bool host = memory == VKRT_MEMORY_HOST;
-  if(!weights)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: weights is NULL", who);
-  if(!host && ((uintptr_t)weights & 3u) != 0)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: weights %p is not 4-byte aligned", who, (const void*)weights);
+  CHECK_TRY(check_morph_index(morph, s->morphs.size(), err));
   const vkrt_scene::Morph& m = s->morphs[morph];
-  const size_t bytes = (size_t)m.arrays.targetCount * sizeof(float);
-  if(host)
-    for(uint32_t i = 0; i < m.arrays.targetCount; i++)
-      if(!std::isfinite(weights[i]))
-        return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: weights[%u] is not finite", who, i);
+  CHECK_TRY(check_morph_weights(weights, memory, m.arrays.targetCount, err));
+  const bool host = memory == VKRT_MEMORY_HOST;
   int rc = setDevice(s);
   if(rc != VKRT_OK)
     return rc;
   hipStream_t stream = (hipStream_t)hip_stream;
   const float* w = weights;
   if(host)
-  {  // through the staging buffer of host vertex updates (every earlier host call has waited for its stream: nothing reads it)
-    if(bytes > s->vertexStageBytes)
-    {
-      s->vertexStageBytes = 0;
-      HIP_TRY(s->vertexStage.alloc(bytes));
-      s->vertexStageBytes = bytes;
-    }
-    HIP_TRY(hipMemcpyAsync(s->vertexStage.get(), weights, bytes, hipMemcpyHostToDevice, stream));
-    w = s->vertexStage.get<const float>();
-  }
+    HIP_TRY(s->vertexStage.put({{weights, m.arrays.targetCount, &w}}, stream));
   if(m.skin >= 0)
   {  // morph, then skin: the skin's next pose reads the morphed bind pose; the live arrays and the tree are as they were
     const vkrt::SkinArrays& k = s->skins[m.skin].arrays;
-    const size_t off = m.arrays.first - k.first;
-    HIP_TRY(vkrt::launch_morph_bind(k.bindPN + off, k.bindNyz + off, k.bindTan + off, m.arrays, w, stream));
+    HIP_TRY(vkrt::launch_morph_bind(k.bind.at(m.arrays.first - k.first), m.arrays, w, stream));
   }
   else
     HIP_TRY(vkrt::launch_morph_live(const_cast<float*>(s->dev.positions), const_cast<float4*>(s->dev.vertexPN), m.arrays, w, stream));
   if(host)
     HIP_TRY(hipStreamSynchronize(stream));  // the caller's weights and the staging buffer are free again
   if(m.skin < 0)
-  {
-    s->positionsOnDevice = true;  // (host weights too: the morphed positions exist on the device only)
-    if(s->built)
-      s->stale = true;
-  }
+    positionsMoved(s);  // (host weights too: the morphed positions exist on the device only; inside a skin no live vertex moved)
   return VKRT_OK;
 }
 
@@ -1327,10 +1195,7 @@ int vkrt_debug_read_vertices(vkrt_scene* s, uint32_t first, uint32_t count, floa
   const char* who = "vkrt_debug_read_vertices";
   if(!s)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: scene is NULL", who);
-  const size_t vertexCount = s->positions.size() / 3;
-  if((uint64_t)first + count > vertexCount)
-    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: vertices [%u, %llu) outside the scene's %zu vertices", who, first, (unsigned long long)first + count,
-                vertexCount);
+  CHECK_TRY(check_vertex_range(who, first, count, s->positions.size() / 3, err));
   if(!positions && !normals && !tangents && !texcoords0)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: positions, normals, tangents and texcoords0 are all NULL", who);
   const int rc = setDevice(s);

@@ -29,6 +29,37 @@ def load_library():
     return _lib
 
 
+_HOST, _DEVICE = abi.VKRT_MEMORY_HOST, abi.VKRT_MEMORY_DEVICE
+_torch = None  # the module, once a tensor has been vetted (imported late: load_library says why)
+
+
+def _import_torch():
+    global _torch
+    import torch
+
+    _torch = torch
+    return torch
+
+
+class _AnyLength:
+    """a dimension of an expected shape that may have any length: equal to every int, written as its letter"""
+    __hash__ = None
+
+    def __init__(self, letter):
+        self.letter = letter
+
+    def __eq__(self, other):
+        return True
+
+    def __ne__(self, other):
+        return False
+
+    def __repr__(self):
+        return self.letter
+
+
+_N, _T = _AnyLength("n"), _AnyLength("T")
+_VERTEX_ARRAYS = (("positions", (_N, 3)), ("normals", (_N, 3)), ("tangents", (_N, 4)), ("texcoords0", (_N, 2)))  # update_vertices, in vkrt_vertex_update's order
 ALPHA_OPAQUE, ALPHA_MASK = abi.VKRT_ALPHA_OPAQUE, abi.VKRT_ALPHA_MASK  # vkrt_alpha_mode, for Renderer.set_material_alpha
 
 
@@ -186,6 +217,49 @@ class Renderer:
         st = C.c_void_p(stream.cuda_stream) if stream is not None else None
         _check(self.lib.vkrt_scene_update_nodes(self._h, first, n, arr, st), "vkrt_scene_update_nodes")
 
+    def _float_source(self, who, name, a, shape, numpy_only=False, align=1, finite=False):
+        """One float32 source of the vertex calls, vetted before the library sees it: a C-contiguous numpy array (host memory) or, unless
+        numpy_only, a contiguous torch tensor on the scene's device whose address is a multiple of `align`.  shape: the one it must
+        have as a tuple, _N or _T where any length will do, e.g. (_N, 3); finite: a host array holds no non-finite value.  Returns (pointer,
+        memory kind, the array's shape).  The device path of update_vertices runs this per array at 8 us per call: it is written to be
+        cheap (profiles/r13_experiments.md)."""
+        if isinstance(a, np.ndarray):
+            memory, f32, contiguous, ptr = _HOST, np.float32, a.flags.c_contiguous, a.ctypes.data
+        else:
+            torch = _torch or _import_torch()
+            if numpy_only or not isinstance(a, torch.Tensor):
+                raise VkrtError(f"{who}: {name} must be a numpy array{'' if numpy_only else ' or a torch tensor'}, got {type(a).__name__}")
+            if not a.is_cuda or a.device.index != self.device:
+                raise VkrtError(f"{who}: {name} is on {a.device}, the scene is on cuda:{self.device}")
+            memory, f32, contiguous, ptr = _DEVICE, torch.float32, a.is_contiguous(), a.data_ptr()
+        if a.dtype != f32:
+            raise VkrtError(f"{who}: {name} is {a.dtype}, expected float32")
+        if not contiguous:
+            raise VkrtError(f"{who}: {name} must be contiguous")
+        if ptr % align and memory == _DEVICE:
+            raise VkrtError(f"{who}: {name} must be {align}-byte aligned")
+        have = a.shape
+        if have != shape:  # (one tuple comparison: an _AnyLength in `shape` equals every length)
+            raise VkrtError(f"{who}: {name} has shape {tuple(have)}, expected {shape}")
+        if finite and memory == _HOST and not np.all(np.isfinite(a)):
+            raise VkrtError(f"{who}: {name} holds a non-finite value")
+        return ptr, memory, have
+
+    def _vertex_range(self, who, first, n, empty_ok=True):
+        """`first` as an int, with vertices [first, first + n) inside the scene"""
+        if isinstance(first, bool) or not isinstance(first, (int, np.integer)) or first < 0 or int(first) + n > self._vertex_count or not (n or empty_ok):
+            raise VkrtError(f"{who}: first: vertices [{first}, {first} + {n}) {'' if empty_ok else 'empty or '}outside the scene's "
+                            f"{self._vertex_count} vertices")
+        return int(first)
+
+    @staticmethod
+    def _overlapping(ranges, first, n):
+        """the number of the skin or morph in `ranges` ((first, count, ...) each) that overlaps vertices [first, first + n), or None"""
+        for k, (f0, c0, _) in enumerate(ranges):
+            if first < f0 + c0 and f0 < first + n:
+                return k
+        return None
+
     def update_vertices(self, first, positions=None, normals=None, tangents=None, texcoords0=None, stream=None):
         """vkrt_scene_update_vertices: new attributes for vertices [first, first + n) of the scene's shared vertex arrays (absolute
         indices, a mesh's vertexOffset included).  positions, normals: (n, 3); tangents: (n, 4); texcoords0: (n, 2); float32; None
@@ -194,44 +268,20 @@ class Renderer:
         call.  Enqueued on `stream` (a torch stream; None = the default stream).  With positions the tree is stale until refit() or
         build().  Refused here, before the call: a wrong dtype or shape, a non-contiguous tensor, a tensor on another device, numpy and
         torch mixed in one call, lengths that differ, a range outside the scene."""
-        import torch
-
-        given = [(k, a, w) for k, a, w in (("positions", positions, 3), ("normals", normals, 3), ("tangents", tangents, 4),
-                                           ("texcoords0", texcoords0, 2)) if a is not None]
-        kinds = set()
-        n = None
-        ptr = {}
-        for k, a, w in given:
-            if isinstance(a, torch.Tensor):
-                kinds.add("torch")
-                if not a.is_cuda or a.device.index != self.device:
-                    raise VkrtError(f"update_vertices: {k} is on {a.device}, the scene is on cuda:{self.device}")
-                if a.dtype != torch.float32:
-                    raise VkrtError(f"update_vertices: {k} is {a.dtype}, expected torch.float32")
-                if not a.is_contiguous():
-                    raise VkrtError(f"update_vertices: {k} must be contiguous")
-                ptr[k] = a.data_ptr()
-            elif isinstance(a, np.ndarray):
-                kinds.add("numpy")
-                if a.dtype != np.float32:
-                    raise VkrtError(f"update_vertices: {k} is {a.dtype}, expected float32")
-                if not a.flags["C_CONTIGUOUS"]:
-                    raise VkrtError(f"update_vertices: {k} must be contiguous")
-                ptr[k] = a.ctypes.data
-            else:
-                raise VkrtError(f"update_vertices: {k} must be a numpy array or a torch tensor, got {type(a).__name__}")
-            if len(kinds) > 1:
+        n, memory, ptr = None, _HOST, [None, None, None, None]
+        for i, a in enumerate((positions, normals, tangents, texcoords0)):
+            if a is None:
+                continue
+            k, shape = _VERTEX_ARRAYS[i]
+            ptr[i], kind, have = self._float_source("update_vertices", k, a, shape)
+            if n is not None and kind != memory:
                 raise VkrtError(f"update_vertices: {k}: numpy arrays and torch tensors mixed in one call")
-            if a.ndim != 2 or a.shape[1] != w:
-                raise VkrtError(f"update_vertices: {k} has shape {tuple(a.shape)}, expected (n, {w})")
-            if n is not None and a.shape[0] != n:
-                raise VkrtError(f"update_vertices: {k} has {a.shape[0]} vertices, the arrays before it {n}")
-            n = int(a.shape[0])
+            if n is not None and have[0] != n:
+                raise VkrtError(f"update_vertices: {k} has {have[0]} vertices, the arrays before it {n}")
+            n, memory = int(have[0]), kind
         n = n or 0
-        if isinstance(first, bool) or not isinstance(first, (int, np.integer)) or first < 0 or int(first) + n > self._vertex_count:
-            raise VkrtError(f"update_vertices: first: vertices [{first}, {first} + {n}) outside the scene's {self._vertex_count} vertices")
-        u = abi.VertexUpdate(C.sizeof(abi.VertexUpdate), int(first), n, abi.VKRT_MEMORY_DEVICE if "torch" in kinds else abi.VKRT_MEMORY_HOST,
-                             ptr.get("positions"), ptr.get("normals"), ptr.get("tangents"), ptr.get("texcoords0"))
+        first = self._vertex_range("update_vertices", first, n)
+        u = abi.VertexUpdate(C.sizeof(abi.VertexUpdate), first, n, memory, *ptr)
         st = C.c_void_p(stream.cuda_stream) if stream is not None else None
         _check(self.lib.vkrt_scene_update_vertices(self._h, C.byref(u), st), "vkrt_scene_update_vertices")
 
@@ -242,37 +292,34 @@ class Renderer:
         takes (default joints.max() + 1).  Returns the skin's number.  Refused here, before the call: a wrong dtype or shape, a
         non-contiguous array, lengths that differ, an empty range or one outside the scene or overlapping an earlier skin's, a joint
         index outside [0, joint_count), a non-finite weight."""
-        for k, a, kinds, want in (("joints", joints, "iu", "an integer"), ("weights", weights, "f", "float32")):
-            if not isinstance(a, np.ndarray):
-                raise VkrtError(f"add_skin: {k} must be a numpy array, got {type(a).__name__}")
-            if a.dtype.kind not in kinds or (k == "weights" and a.dtype != np.float32):
-                raise VkrtError(f"add_skin: {k} is {a.dtype}, expected {want} dtype")
-            if a.ndim != 2 or a.shape[1] != 4:
-                raise VkrtError(f"add_skin: {k} has shape {tuple(a.shape)}, expected (n, 4)")
-            if not a.flags["C_CONTIGUOUS"]:
-                raise VkrtError(f"add_skin: {k} must be contiguous")
+        if not isinstance(joints, np.ndarray):
+            raise VkrtError(f"add_skin: joints must be a numpy array, got {type(joints).__name__}")
+        if joints.dtype.kind not in "iu":
+            raise VkrtError(f"add_skin: joints is {joints.dtype}, expected an integer dtype")
+        if joints.ndim != 2 or joints.shape[1] != 4:
+            raise VkrtError(f"add_skin: joints has shape {tuple(joints.shape)}, expected (n, 4)")
+        if not joints.flags["C_CONTIGUOUS"]:
+            raise VkrtError("add_skin: joints must be contiguous")
         n = int(joints.shape[0])
+        weights_ptr, _, _ = self._float_source("add_skin", "weights", weights, (_N, 4), numpy_only=True, finite=True)
         if weights.shape[0] != n:
             raise VkrtError(f"add_skin: weights has {weights.shape[0]} vertices, joints {n}")
-        if isinstance(first, bool) or not isinstance(first, (int, np.integer)) or first < 0 or n == 0 or int(first) + n > self._vertex_count:
-            raise VkrtError(f"add_skin: first: vertices [{first}, {first} + {n}) empty or outside the scene's {self._vertex_count} vertices")
-        first = int(first)
-        for k, (f0, c0, _) in enumerate(self._skins):
-            if first < f0 + c0 and f0 < first + n:
-                raise VkrtError(f"add_skin: first: vertices [{first}, {first + n}) overlap skin {k}'s [{f0}, {f0 + c0})")
-        for k, (f0, c0, _) in enumerate(getattr(self, "_morphs", ())):  # skins come first: a morph inside one captured its bind pose
-            if first < f0 + c0 and f0 < first + n:
-                raise VkrtError(f"add_skin: first: vertices [{first}, {first + n}) overlap morph {k}'s [{f0}, {f0 + c0}): add skins before morphs")
+        first = self._vertex_range("add_skin", first, n, empty_ok=False)
+        k = self._overlapping(self._skins, first, n)
+        if k is not None:
+            raise VkrtError(f"add_skin: first: vertices [{first}, {first + n}) overlap skin {k}'s [{self._skins[k][0]}, {sum(self._skins[k][:2])})")
+        k = self._overlapping(self._morphs, first, n)  # skins come first: a morph inside one captured its bind pose
+        if k is not None:
+            raise VkrtError(f"add_skin: first: vertices [{first}, {first + n}) overlap morph {k}'s [{self._morphs[k][0]}, {sum(self._morphs[k][:2])}): "
+                            "add skins before morphs")
         if joint_count is None:
             joint_count = int(joints.max()) + 1
         if isinstance(joint_count, bool) or not isinstance(joint_count, (int, np.integer)) or not 1 <= joint_count <= 65536:
             raise VkrtError(f"add_skin: joint_count {joint_count!r} outside 1..65536")
         if int(joints.min()) < 0 or int(joints.max()) >= joint_count:
             raise VkrtError(f"add_skin: joints holds indices in [{int(joints.min())}, {int(joints.max())}], joint_count is {joint_count}")
-        if not np.all(np.isfinite(weights)):
-            raise VkrtError("add_skin: weights holds a non-finite value")
         j16 = np.ascontiguousarray(joints, np.uint16)
-        d = abi.SkinDesc(C.sizeof(abi.SkinDesc), first, n, int(joint_count), j16.ctypes.data, weights.ctypes.data)
+        d = abi.SkinDesc(C.sizeof(abi.SkinDesc), first, n, int(joint_count), j16.ctypes.data, weights_ptr)
         out = abi.c_u()
         st = C.c_void_p(stream.cuda_stream) if stream is not None else None
         _check(self.lib.vkrt_scene_add_skin(self._h, C.byref(d), st, C.byref(out)), "vkrt_scene_add_skin")
@@ -287,36 +334,9 @@ class Renderer:
         tangents of the skin's vertices from the captured bind pose; the tree is stale until refit() or build().  Refused here, before
         the call: a skin index out of range, a wrong dtype or shape, a non-contiguous or misaligned tensor, a tensor on another
         device, a non-finite host matrix."""
-        import torch
-
         if isinstance(skin, bool) or not isinstance(skin, (int, np.integer)) or not 0 <= skin < len(self._skins):
             raise VkrtError(f"skin: skin {skin!r} outside the scene's {len(self._skins)} skins")
-        jc = self._skins[int(skin)][2]
-        m = joint_matrices
-        if isinstance(m, torch.Tensor):
-            memory = abi.VKRT_MEMORY_DEVICE
-            if not m.is_cuda or m.device.index != self.device:
-                raise VkrtError(f"skin: joint_matrices is on {m.device}, the scene is on cuda:{self.device}")
-            if m.dtype != torch.float32:
-                raise VkrtError(f"skin: joint_matrices is {m.dtype}, expected torch.float32")
-            if not m.is_contiguous():
-                raise VkrtError("skin: joint_matrices must be contiguous")
-            ptr = m.data_ptr()
-            if ptr % 16:
-                raise VkrtError("skin: joint_matrices must be 16-byte aligned")
-        elif isinstance(m, np.ndarray):
-            memory = abi.VKRT_MEMORY_HOST
-            if m.dtype != np.float32:
-                raise VkrtError(f"skin: joint_matrices is {m.dtype}, expected float32")
-            if not m.flags["C_CONTIGUOUS"]:
-                raise VkrtError("skin: joint_matrices must be contiguous")
-            ptr = m.ctypes.data
-        else:
-            raise VkrtError(f"skin: joint_matrices must be a numpy array or a torch tensor, got {type(m).__name__}")
-        if m.ndim != 2 or tuple(m.shape) != (jc, 16):
-            raise VkrtError(f"skin: joint_matrices has shape {tuple(m.shape)}, expected ({jc}, 16)")
-        if memory == abi.VKRT_MEMORY_HOST and not np.all(np.isfinite(m)):
-            raise VkrtError("skin: joint_matrices holds a non-finite value")
+        ptr, memory, _ = self._float_source("skin", "joint_matrices", joint_matrices, (self._skins[int(skin)][2], 16), align=16, finite=True)
         st = C.c_void_p(stream.cuda_stream) if stream is not None else None
         _check(self.lib.vkrt_scene_skin_vertices(self._h, int(skin), ptr, memory, st), "vkrt_scene_skin_vertices")
 
@@ -332,34 +352,23 @@ class Renderer:
                  if a is not None]
         if not given:
             raise VkrtError("add_morph: position_deltas, normal_deltas and tangent_deltas are all None")
+        ptr = {}
         for k, a in given:
-            if not isinstance(a, np.ndarray):
-                raise VkrtError(f"add_morph: {k} must be a numpy array, got {type(a).__name__}")
-            if a.dtype != np.float32:
-                raise VkrtError(f"add_morph: {k} is {a.dtype}, expected float32 dtype")
-            if a.ndim != 3 or a.shape[2] != 3:
-                raise VkrtError(f"add_morph: {k} has shape {tuple(a.shape)}, expected (T, n, 3)")
-            if not a.flags["C_CONTIGUOUS"]:
-                raise VkrtError(f"add_morph: {k} must be contiguous")
+            ptr[k], _, _ = self._float_source("add_morph", k, a, (_T, _N, 3), numpy_only=True, finite=True)
             if a.shape != given[0][1].shape:
                 raise VkrtError(f"add_morph: {k} has shape {tuple(a.shape)}, {given[0][0]} {tuple(given[0][1].shape)}")
         T, n = int(given[0][1].shape[0]), int(given[0][1].shape[1])
         if not 1 <= T <= abi.VKRT_MORPH_TARGETS_MAX:
             raise VkrtError(f"add_morph: {given[0][0]} has {T} targets, outside 1..{abi.VKRT_MORPH_TARGETS_MAX}")
-        if isinstance(first, bool) or not isinstance(first, (int, np.integer)) or first < 0 or n == 0 or int(first) + n > self._vertex_count:
-            raise VkrtError(f"add_morph: first: vertices [{first}, {first} + {n}) empty or outside the scene's {self._vertex_count} vertices")
-        first = int(first)
-        for k, (f0, c0, _) in enumerate(self._morphs):
-            if first < f0 + c0 and f0 < first + n:
-                raise VkrtError(f"add_morph: first: vertices [{first}, {first + n}) overlap morph {k}'s [{f0}, {f0 + c0})")
-        for k, (f0, c0, _) in enumerate(self._skins):
-            if first < f0 + c0 and f0 < first + n and (first < f0 or first + n > f0 + c0):
-                raise VkrtError(f"add_morph: first: vertices [{first}, {first + n}) straddle the boundary of skin {k}'s [{f0}, {f0 + c0})")
-        for k, a in given:
-            if not np.all(np.isfinite(a)):
-                raise VkrtError(f"add_morph: {k} holds a non-finite value")
-        ptr = [None if a is None else a.ctypes.data for a in (position_deltas, normal_deltas, tangent_deltas)]
-        d = abi.MorphDesc(C.sizeof(abi.MorphDesc), first, n, T, *ptr)
+        first = self._vertex_range("add_morph", first, n, empty_ok=False)
+        k = self._overlapping(self._morphs, first, n)
+        if k is not None:
+            raise VkrtError(f"add_morph: first: vertices [{first}, {first + n}) overlap morph {k}'s [{self._morphs[k][0]}, {sum(self._morphs[k][:2])})")
+        k = self._overlapping(self._skins, first, n)  # (the skins are disjoint: a range inside one touches no other)
+        if k is not None and (first < self._skins[k][0] or first + n > sum(self._skins[k][:2])):
+            raise VkrtError(f"add_morph: first: vertices [{first}, {first + n}) straddle the boundary of skin {k}'s [{self._skins[k][0]}, "
+                            f"{sum(self._skins[k][:2])})")
+        d = abi.MorphDesc(C.sizeof(abi.MorphDesc), first, n, T, ptr.get("position_deltas"), ptr.get("normal_deltas"), ptr.get("tangent_deltas"))
         out = abi.c_u()
         st = C.c_void_p(stream.cuda_stream) if stream is not None else None
         _check(self.lib.vkrt_scene_add_morph(self._h, C.byref(d), st, C.byref(out)), "vkrt_scene_add_morph")
@@ -375,36 +384,9 @@ class Renderer:
         a skin writes that skin's bind pose, which the skin's next skin() carries into the scene.  Refused here, before the call: a
         morph index out of range, a wrong dtype or shape, a non-contiguous or misaligned tensor, a tensor on another device, a
         non-finite host weight."""
-        import torch
-
         if isinstance(morph, bool) or not isinstance(morph, (int, np.integer)) or not 0 <= morph < len(self._morphs):
             raise VkrtError(f"morph: morph {morph!r} outside the scene's {len(self._morphs)} morphs")
-        T = self._morphs[int(morph)][2]
-        w = weights
-        if isinstance(w, torch.Tensor):
-            memory = abi.VKRT_MEMORY_DEVICE
-            if not w.is_cuda or w.device.index != self.device:
-                raise VkrtError(f"morph: weights is on {w.device}, the scene is on cuda:{self.device}")
-            if w.dtype != torch.float32:
-                raise VkrtError(f"morph: weights is {w.dtype}, expected torch.float32")
-            if not w.is_contiguous():
-                raise VkrtError("morph: weights must be contiguous")
-            ptr = w.data_ptr()
-            if ptr % 4:
-                raise VkrtError("morph: weights must be 4-byte aligned")
-        elif isinstance(w, np.ndarray):
-            memory = abi.VKRT_MEMORY_HOST
-            if w.dtype != np.float32:
-                raise VkrtError(f"morph: weights is {w.dtype}, expected float32")
-            if not w.flags["C_CONTIGUOUS"]:
-                raise VkrtError("morph: weights must be contiguous")
-            ptr = w.ctypes.data
-        else:
-            raise VkrtError(f"morph: weights must be a numpy array or a torch tensor, got {type(w).__name__}")
-        if w.ndim != 1 or tuple(w.shape) != (T,):
-            raise VkrtError(f"morph: weights has shape {tuple(w.shape)}, expected ({T},)")
-        if memory == abi.VKRT_MEMORY_HOST and not np.all(np.isfinite(w)):
-            raise VkrtError("morph: weights holds a non-finite value")
+        ptr, memory, _ = self._float_source("morph", "weights", weights, (self._morphs[int(morph)][2],), align=4, finite=True)
         st = C.c_void_p(stream.cuda_stream) if stream is not None else None
         _check(self.lib.vkrt_scene_morph_vertices(self._h, int(morph), ptr, memory, st), "vkrt_scene_morph_vertices")
 
