@@ -373,6 +373,52 @@ typedef struct vkrt_vertex_update {
 } vkrt_vertex_update;
 int vkrt_scene_update_vertices(vkrt_scene* scene, const vkrt_vertex_update* update, void* hip_stream);
 
+/* ---- moving instances from device memory (the instance buffer of a TLAS update that a compute pass has just written: a rigid-body
+ *      simulation, a particle or crowd system, a learned policy driving thousands of instances).  With it a frame of a moving scene --
+ *      vkrt_scene_motion_mark, update, vkrt_accel_refit, trace -- has no host round trip left.  These entry points came after ABI
+ *      version 4 without changing it or any existing struct: detect them by symbol. ---------------------------------------------------
+ * New transforms for count nodes: the dense form (node_indices == NULL) moves nodes [first, first+count), entry k being node first + k;
+ * the sparse form moves node node_indices[k] with entry k, and first must be 0.  world_matrices holds 16 floats per entry, column-major
+ * object->world like vkrt_node.worldMatrix; only rows 0..2 are read (elements 3, 7, 11 and 15 of an entry are ignored).
+ * Scope: the call changes transforms only.  Every node keeps its primMesh, its visibility (vkrt_scene_set_instance_visibility), its
+ *   dissolve flag and its slot.  Stream ordering and the stale tree are those of vkrt_scene_update_nodes: enqueued on hip_stream
+ *   (NULL = default stream) after what was enqueued there before and before what comes after; with a built tree, trace, G-buffer,
+ *   hybrid, ray-query and vkrt_debug_* tree hooks return VKRT_ERR_NOT_BUILT until vkrt_accel_refit or vkrt_accel_build.  One
+ *   vkrt_accel_refit serves any number of node, vertex, skin and morph updates before it.  vkrt_hit_surface and vkrt_hit_motion read
+ *   the live records and see the new transforms without a refit; the motion snapshot (vkrt_scene_motion_mark) is untouched.
+ * The record (96 B per node, what vkrt_debug_read_instances returns) is the one vkrt_scene_create and vkrt_scene_update_nodes write:
+ *   o2w[4 r + c] = M[4 c + r]; w2o = the cofactor inverse of o2w's 3x3 in binary64, in a fixed operation order with inv = 1.0 / det,
+ *   each entry rounded to binary32; the mirrored bit of the visibility word = (binary64 determinant < 0).  One set of functions makes it
+ *   on the host and on the device: a device update is bit for bit a host update of the same matrices, a singular one (a zero scale:
+ *   infinities and NaNs in w2o) included.  One corner is open: an inverse entry so small that its binary32 value is subnormal (matrix
+ *   entries near 1e38) may differ between the two.
+ * VKRT_MEMORY_DEVICE: the arrays are device memory on the scene's device, world_matrices 16-byte and node_indices 4-byte aligned, valid
+ *   until the stream has passed the call.  The call is one kernel launch on hip_stream: nothing is allocated, nothing synchronises,
+ *   and the values are not inspected.  A non-finite or singular matrix is the caller's matter, exactly as a non-finite position of a
+ *   device vertex update: it cannot make any kernel read or write out of bounds, and a later correct update + refit repairs the scene
+ *   completely; what rays return in between is unspecified.  An index >= node_count skips its entry.  With duplicate indices, which
+ *   entry wins is unspecified.  The library's host copy of the matrices falls behind the device: vkrt_accel_build (every builder and
+ *   the scene bounds read that copy) and vkrt_debug_split_references download the records first -- they synchronise anyway -- and
+ *   refuse a scene that holds a non-finite matrix with VKRT_ERR_INVALID_ARGUMENT, building nothing.  A host vkrt_scene_update_nodes
+ *   in between is fine: it still checks primMesh, which no device update changes.
+ * VKRT_MEMORY_HOST: the contract of vkrt_scene_update_nodes, for the sparse form too.  Every matrix element is checked finite and
+ *   every index < node_count before anything changes; the arrays are copied before return; the records travel as kernel arguments,
+ *   so nothing is staged and the call does not wait for the stream (unlike a host vertex update); the host copy follows.  Duplicate
+ *   indices are applied in order: the last entry wins.
+ * Refused with VKRT_ERR_INVALID_ARGUMENT, changing nothing, in this order: a NULL update; struct_size < sizeof(vkrt_node_update); a
+ * memory value that is neither of the two; first != 0 together with node_indices; a NULL scene; a dense range outside the scene's
+ * nodes; (count > 0) NULL world_matrices; (device memory) a misaligned array; (host memory) an index out of range; (host memory) a
+ * non-finite element.  Then count == 0: VKRT_OK, nothing is enqueued, the tree does not become stale.  Then, without a device:
+ * VKRT_ERR_NO_DEVICE. */
+typedef struct vkrt_node_update {
+  uint32_t struct_size;           /* sizeof(vkrt_node_update) */
+  uint32_t first, count;          /* node_indices == NULL: nodes [first, first+count); else count entries and first must be 0 */
+  uint32_t memory;                /* vkrt_memory: where the two arrays live */
+  const float*    world_matrices; /* [count][16], column-major object->world like vkrt_node.worldMatrix; only rows 0..2 are read */
+  const uint32_t* node_indices;   /* NULL, or [count]: entry k moves node node_indices[k] (sparse update) */
+} vkrt_node_update;
+int vkrt_scene_update_node_transforms(vkrt_scene* scene, const vkrt_node_update* update, void* hip_stream);
+
 /* ---- skinned meshes (glTF skins: JOINTS_0 / WEIGHTS_0 per vertex, a palette of joint matrices per frame): linear-blend skinning inside
  *      the library, straight into the scene's live vertex arrays.  These entry points came after ABI version 4 without changing it or
  *      any existing struct: detect them by symbol. ------------------------------------------------------------------------------------
@@ -548,7 +594,8 @@ typedef struct vkrt_instance_visibility { /* 4 B; every node starts as {0xFF, VK
  * values.  It does not make the tree stale and works on a stale one.  Refused with VKRT_ERR_INVALID_ARGUMENT, changing nothing, in this
  * order: a NULL array with count > 0; an entry with mask 0, unknown flag bits or reserved != 0; a NULL scene; a range outside the
  * scene's nodes.  Then, without a device: VKRT_ERR_NO_DEVICE.  The visibility of a node survives vkrt_scene_update_nodes,
- * vkrt_accel_refit and vkrt_accel_build. */
+ * vkrt_scene_update_node_transforms, vkrt_accel_refit and vkrt_accel_build.  The call writes the visibility word of each record and
+ * nothing else of it: a transform that came from device memory stays in place. */
 int vkrt_scene_set_instance_visibility(vkrt_scene* scene, uint32_t first, uint32_t count, const vkrt_instance_visibility* vis, void* hip_stream);
 /* Reads the host copy (no synchronisation).  VKRT_ERR_INVALID_ARGUMENT: a NULL array with count > 0, a NULL scene, a range outside. */
 int vkrt_scene_get_instance_visibility(const vkrt_scene* scene, uint32_t first, uint32_t count, vkrt_instance_visibility* out);
@@ -995,6 +1042,12 @@ int vkrt_debug_split_references(vkrt_scene* scene, uint32_t split_percent /* 1..
  * A NULL array is skipped.  Needs no tree.  A NULL scene, a range outside the scene's vertices or all four arrays NULL:
  * VKRT_ERR_INVALID_ARGUMENT. */
 int vkrt_debug_read_vertices(vkrt_scene* scene, uint32_t first, uint32_t count, float* positions, float* normals, float* tangents, float* texcoords0);
+/* The instance records of nodes [first, first+count) exactly as the kernels read them (synchronises the device; a test hook like the
+ * other vkrt_debug_* calls, no kernel of its own), 96 B per node: float o2w[12], the object->world rows, row-major 3x4; float w2o[9],
+ * the row-major inverse of their 3x3; int32 primMesh; uint32 visibility word (bits 0-7 mask, bits 8-15 vkrt_instance_flags, bit 16 set
+ * when the 3x3 has a negative determinant); int32 pad = 0.  Needs no tree.  A NULL scene or out, a range outside the scene's nodes or
+ * bytes != 96 * count: VKRT_ERR_INVALID_ARGUMENT. */
+int vkrt_debug_read_instances(vkrt_scene* scene, uint32_t first, uint32_t count, void* out, uint64_t bytes);
 /* The work of vkrt_closest_point on n queries of a HOST array (synchronises the device; a test hook like the other vkrt_debug_* calls):
  * out[0] = nodes visited, out[1] = triangle records tested, summed over the queries, by an instrumented instantiation of the same
  * walk.  opts and the order of errors as vkrt_closest_point; a NULL out: VKRT_ERR_INVALID_ARGUMENT. */

@@ -213,6 +213,11 @@ class VertexUpdate(C.Structure):
                 ("tangents", C.c_void_p), ("texcoords0", C.c_void_p)]
 
 
+# moving instances from host or device memory (vkrt_scene_update_node_transforms): the two arrays are host or device pointers, by `memory`
+class NodeUpdate(C.Structure):
+    _fields_ = [("struct_size", c_u), ("first", c_u), ("count", c_u), ("memory", c_u), ("world_matrices", C.c_void_p), ("node_indices", C.c_void_p)]
+
+
 # skinned meshes (vkrt_scene_add_skin): joints (u16 x 4 per vertex) and weights (f32 x 4 per vertex) are host pointers
 class SkinDesc(C.Structure):
     _fields_ = [("struct_size", c_u), ("first", c_u), ("count", c_u), ("joint_count", c_u), ("joints", C.c_void_p), ("weights", C.c_void_p)]
@@ -228,6 +233,7 @@ class MorphDesc(C.Structure):
 
 
 assert C.sizeof(VertexUpdate) == 48
+assert C.sizeof(NodeUpdate) == 32
 assert C.sizeof(SkinDesc) == 32
 assert C.sizeof(MorphDesc) == 40
 assert C.sizeof(Ray) == 32
@@ -291,6 +297,7 @@ VKRT_SYMBOLS = [
     "vkrt_scene_update_nodes",
     "vkrt_accel_refit",
     "vkrt_scene_update_vertices",
+    "vkrt_scene_update_node_transforms",
     "vkrt_scene_add_skin",
     "vkrt_scene_skin_vertices",
     "vkrt_scene_add_morph",
@@ -332,6 +339,7 @@ VKRT_SYMBOLS = [
     "vkrt_debug_read_triangle_ids",
     "vkrt_debug_split_references",
     "vkrt_debug_read_vertices",
+    "vkrt_debug_read_instances",
     "vkrt_debug_closest_point_work",
     "vkrt_debug_trace_rays",
     "vkrt_debug_eval_math",
@@ -367,6 +375,11 @@ def declare_vkrt(lib):
     lib.vkrt_accel_refit.restype = C.c_int
     lib.vkrt_scene_update_vertices.argtypes = [C.c_void_p, P(VertexUpdate), C.c_void_p]
     lib.vkrt_scene_update_vertices.restype = C.c_int
+    lib.vkrt_scene_update_node_transforms.argtypes = [C.c_void_p, P(NodeUpdate), C.c_void_p]
+    lib.vkrt_scene_update_node_transforms.restype = C.c_int
+    # (scene, first, count, out: host pointer to 96-B records, bytes)
+    lib.vkrt_debug_read_instances.argtypes = [C.c_void_p, c_u, c_u, C.c_void_p, C.c_uint64]
+    lib.vkrt_debug_read_instances.restype = C.c_int
     # (scene, desc, stream, out_skin) / (scene, skin, joint matrices: host or device pointer by `memory`, memory, stream)
     lib.vkrt_scene_add_skin.argtypes = [C.c_void_p, P(SkinDesc), C.c_void_p, P(c_u)]
     lib.vkrt_scene_add_skin.restype = C.c_int

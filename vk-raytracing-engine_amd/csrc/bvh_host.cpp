@@ -6,6 +6,7 @@
 // BVH covers the whole scene.  Output is the 64-byte node / 48-byte triangle layout of
 // device_scene.h, nodes in depth-first order (a node's first child is usually the next line).
 #include "bvh_host.h"
+#include "instance_record.h"
 #include "tri_prep.h"
 #include "wide_node.h"
 
@@ -191,24 +192,8 @@ struct Ctx
 
 void invert3x3_rows(const float o2w[12], float w2o[9])
 {
-  // cofactor inverse of the upper-left 3x3 in double, fixed operation order
-  const double a = o2w[0], b = o2w[1], c = o2w[2];
-  const double d = o2w[4], e = o2w[5], f = o2w[6];
-  const double g = o2w[8], h = o2w[9], i = o2w[10];
-  const double A = e * i - f * h;
-  const double B = -(d * i - f * g);
-  const double C = d * h - e * g;
-  const double det = a * A + b * B + c * C;
-  const double inv = 1.0 / det;
-  w2o[0] = (float)(A * inv);
-  w2o[1] = (float)(-(b * i - c * h) * inv);
-  w2o[2] = (float)((b * f - c * e) * inv);
-  w2o[3] = (float)(B * inv);
-  w2o[4] = (float)((a * i - c * g) * inv);
-  w2o[5] = (float)(-(a * f - c * d) * inv);
-  w2o[6] = (float)(C * inv);
-  w2o[7] = (float)(-(a * h - b * g) * inv);
-  w2o[8] = (float)((a * e - b * d) * inv);
+  // cofactor inverse of the upper-left 3x3 in double, fixed operation order: instance_record.h, shared with the device
+  vkrt_invert3x3_rows(o2w, w2o);
 }
 
 

@@ -2,6 +2,7 @@
 // the texel pool with its mip chains, the footprint pool and the material records.  Plain C++, nothing of the device.
 #include "scene_pack.h"
 #include "bvh_host.h"
+#include "instance_record.h"
 
 #include <algorithm>
 #include <cmath>
@@ -120,17 +121,12 @@ int validate_scene(const vkrt_scene_desc* d, std::string& err)
 
 void make_instance(const vkrt_node& node, const vkrt_instance_visibility& vis, DevInstance& in)
 {
+  // (the arithmetic is instance_record.h's, which k_nu_transforms runs on the device for vkrt_scene_update_node_transforms)
   memset(&in, 0, sizeof in);
-  for(int r = 0; r < 3; r++)
-    for(int c = 0; c < 4; c++)
-      in.o2w[r * 4 + c] = node.worldMatrix[c * 4 + r];
-  invert3x3_rows(in.o2w, in.w2o);
+  vkrt_instance_rows(node.worldMatrix, in.o2w);
+  vkrt_invert3x3_rows(in.o2w, in.w2o);
   in.primMesh = node.primMesh;
-  // facing: a mirroring transform turns the world-space winding around (traverse.h query_rejects); decided in double on the matrix
-  const float* m = in.o2w;
-  const double det = (double)m[0] * ((double)m[5] * m[10] - (double)m[6] * m[9]) - (double)m[1] * ((double)m[4] * m[10] - (double)m[6] * m[8]) +
-                     (double)m[2] * ((double)m[4] * m[9] - (double)m[5] * m[8]);
-  in.vis = (uint32_t)vis.mask | ((uint32_t)vis.flags << 8) | (det < 0.0 ? VKRT_VIS_MIRRORED : 0u);
+  in.vis = (uint32_t)vis.mask | ((uint32_t)vis.flags << 8) | vkrt_mirrored_bit(in.o2w);
 }
 
 int pack_scene(const vkrt_scene_desc* d, bool texQuadsAllowed, PackedScene& out, std::string& err)

@@ -29,6 +29,7 @@
 
 #include "lbvh.h"
 #include "morph.h"
+#include "node_update.h"
 #include "refit.h"
 #include "skin.h"
 #include "vertex_anim.h"
@@ -67,7 +68,7 @@ struct vkrt_scene
   std::vector<float> positions;  // (after a device-sourced vkrt_scene_update_vertices: behind the device's until the next build, positionsOnDevice)
   std::vector<uint32_t> indices;
   std::vector<vkrt_prim_mesh> primMeshes;
-  std::vector<vkrt_node> nodes;
+  std::vector<vkrt_node> nodes;  // (after a device-sourced vkrt_scene_update_node_transforms: matrices behind the device's, nodesOnDevice)
   uint32_t lightCount = 0, materialCount = 0;
   std::vector<float> materialAlpha;  // pbrBaseColorFactor.a per material (the any-hit stage's dissolve), host copy for the host builder
   // device allocations
@@ -101,6 +102,8 @@ struct vkrt_scene
   bool stale = false;      // node transforms or vertex positions changed since the tree was built or refitted: no trace until the next refit or build
   bool refitted = false;   // the tree has been refitted since its build: vkrt_accel_get_info reads the refit's SAH cost from the device
   vkrt::RefitScratch refit;  // level lists + exact node boxes of the current build (allocated at its first refit)
+  bool nodesOnDevice = false;  // a device-sourced vkrt_scene_update_node_transforms moved nodes whose matrices `nodes` has not seen: whoever
+                               // reads matrices from `nodes` (the builders, scene_bounds, the split hook) downloads the records first
   // deforming meshes (vkrt_scene_update_vertices)
   bool positionsOnDevice = false;  // a device-sourced update moved vertices the host copy has not seen: the next build downloads them first
   vkrt::StageBuf vertexStage;      // staging of host-sourced updates, joint matrices and morph weights
@@ -225,6 +228,37 @@ int computeNodeMasks(vkrt_scene* s, hipStream_t stream)
 int setDevice(const vkrt_scene* s)
 {
   HIP_TRY(hipSetDevice(s->device));
+  return VKRT_OK;
+}
+
+// Nodes moved by a device-sourced vkrt_scene_update_node_transforms: bring the matrices of the host copy up to date from the instance
+// records (o2w = rows 0-2; the bottom row, which nothing reads, becomes 0 0 0 1).  Synchronises the device.  A matrix that is not finite
+// -- the device path does not inspect its values -- is refused like one given to vkrt_scene_create, and the host copy stays as it was.
+int downloadNodeTransforms(vkrt_scene* s, const char* who)
+{
+  if(!s->nodesOnDevice)
+    return VKRT_OK;
+  const int rc = setDevice(s);
+  if(rc != VKRT_OK)
+    return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<DevInstance> inst(s->nodes.size());
+  if(!inst.empty())
+    HIP_TRY(hipMemcpy(inst.data(), s->dev.instances, inst.size() * sizeof(DevInstance), hipMemcpyDeviceToHost));
+  std::vector<vkrt_node> fresh = s->nodes;
+  for(size_t i = 0; i < fresh.size(); i++)
+  {
+    float* M = fresh[i].worldMatrix;
+    for(int r = 0; r < 3; r++)
+      for(int c = 0; c < 4; c++)
+        M[c * 4 + r] = inst[i].o2w[r * 4 + c];
+    M[3] = M[7] = M[11] = 0.0f;
+    M[15] = 1.0f;
+    if(std::string err; vkrt::check_transform(fresh[i], (uint32_t)i, err) != VKRT_OK)
+      return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: after a device-sourced vkrt_scene_update_node_transforms: %s", who, err.c_str());
+  }
+  s->nodes.swap(fresh);
+  s->nodesOnDevice = false;
   return VKRT_OK;
 }
 
@@ -921,6 +955,9 @@ int vkrt_accel_build(vkrt_scene* s, uint32_t flags, void* hip_stream)
       HIP_TRY(hipMemcpy(s->positions.data(), s->dev.positions, s->positions.size() * sizeof(float), hipMemcpyDeviceToHost));
     s->positionsOnDevice = false;
   }
+  // nodes moved by a device-sourced vkrt_scene_update_node_transforms: every builder and scene_bounds read the matrices of the host copy
+  if(const int rc = downloadNodeTransforms(s, "vkrt_accel_build"); rc != VKRT_OK)
+    return rc;
   const bool deviceBuild = flags == 0 || (flags & (VKRT_BUILD_LBVH_GPU | VKRT_BUILD_PLOC_GPU)) != 0;
   if(s->opt[VKRT_OPT_SPLIT_BUDGET] >= 0 || !deviceBuild)
   {
@@ -1025,6 +1062,101 @@ int vkrt_accel_refit(vkrt_scene* s, void* hip_stream)
     return fail(rc, "vkrt_accel_refit: %s", err.c_str());
   s->refitted = true;
   s->stale = false;
+  return VKRT_OK;
+}
+
+int vkrt_scene_update_node_transforms(vkrt_scene* s, const vkrt_node_update* u, void* hip_stream)
+{
+  const char* who = "vkrt_scene_update_node_transforms";
+  const int bad = VKRT_ERR_INVALID_ARGUMENT;
+  if(!u)
+    return fail(bad, "%s: update is NULL", who);
+  if(u->struct_size < sizeof(vkrt_node_update))
+    return fail(bad, "%s: vkrt_node_update.struct_size %u < %zu (ABI mismatch)", who, u->struct_size, sizeof(vkrt_node_update));
+  if(u->memory != VKRT_MEMORY_HOST && u->memory != VKRT_MEMORY_DEVICE)
+    return fail(bad, "%s: memory %u is neither VKRT_MEMORY_HOST nor VKRT_MEMORY_DEVICE", who, u->memory);
+  if(u->node_indices && u->first != 0)
+    return fail(bad, "%s: first is %u with node_indices given (a sparse update takes first = 0)", who, u->first);
+  if(!s)
+    return fail(bad, "%s: scene is NULL", who);
+  const size_t nodeCount = s->nodes.size(), n = u->count;
+  if(!u->node_indices && (uint64_t)u->first + u->count > nodeCount)
+    return fail(bad, "%s: nodes [%u, %llu) outside the scene's %zu nodes", who, u->first, (unsigned long long)u->first + u->count, nodeCount);
+  if(n && !u->world_matrices)
+    return fail(bad, "%s: world_matrices is NULL", who);
+  const bool host = u->memory == VKRT_MEMORY_HOST;
+  if(!host)
+  {
+    if(((uintptr_t)u->world_matrices & 15u) != 0)
+      return fail(bad, "%s: world_matrices %p is not 16-byte aligned", who, (const void*)u->world_matrices);
+    if(((uintptr_t)u->node_indices & 3u) != 0)
+      return fail(bad, "%s: node_indices %p is not 4-byte aligned", who, (const void*)u->node_indices);
+  }
+  else
+  {  // the rules of vkrt_scene_update_nodes, checked for every entry before anything changes
+    if(u->node_indices)
+      for(size_t k = 0; k < n; k++)
+        if(u->node_indices[k] >= nodeCount)
+          return fail(bad, "%s: node_indices[%zu] is %u, outside the scene's %zu nodes", who, k, u->node_indices[k], nodeCount);
+    for(size_t k = 0; k < 16 * n; k++)
+      if(!std::isfinite(u->world_matrices[k]))
+        return fail(bad, "%s: world_matrices[%zu] (entry %zu, node %u) is not finite", who, k, k / 16,
+                    u->node_indices ? u->node_indices[k / 16] : u->first + (uint32_t)(k / 16));
+  }
+  if(n == 0)
+    return VKRT_OK;
+  if(!host)
+  {
+    const int rc = setDevice(s);
+    if(rc != VKRT_OK)
+      return rc;
+    // One launch on hip_stream, stream-ordered like vkrt_scene_update_nodes; no allocation, no copy, no wait.  The host copy of the
+    // matrices falls behind: its readers download the records first (downloadNodeTransforms).
+    HIP_TRY(vkrt::launch_node_transforms(const_cast<DevInstance*>(s->dev.instances), (uint32_t)nodeCount, u->first, u->count, u->world_matrices,
+                                         u->node_indices, (hipStream_t)hip_stream));
+    s->nodesOnDevice = true;
+    if(s->built)
+      s->stale = true;
+    return VKRT_OK;
+  }
+  // host memory: vkrt_scene_update_nodes itself -- the dense form in one call, the sparse form run by run of consecutive indices, in the
+  // order given (so the last of several entries for one node wins)
+  std::vector<vkrt_node> nodes(n);
+  for(size_t k = 0; k < n; k++)
+  {
+    std::copy(u->world_matrices + 16 * k, u->world_matrices + 16 * k + 16, nodes[k].worldMatrix);
+    nodes[k].primMesh = s->nodes[u->node_indices ? u->node_indices[k] : (size_t)u->first + k].primMesh;
+  }
+  if(!u->node_indices)
+    return vkrt_scene_update_nodes(s, u->first, u->count, nodes.data(), hip_stream);
+  for(size_t k = 0; k < n;)
+  {
+    size_t end = k + 1;
+    while(end < n && u->node_indices[end] == u->node_indices[end - 1] + 1u)
+      end++;
+    if(const int rc = vkrt_scene_update_nodes(s, u->node_indices[k], (uint32_t)(end - k), &nodes[k], hip_stream); rc != VKRT_OK)
+      return rc;
+    k = end;
+  }
+  return VKRT_OK;
+}
+
+int vkrt_debug_read_instances(vkrt_scene* s, uint32_t first, uint32_t count, void* out, uint64_t bytes)
+{
+  const char* who = "vkrt_debug_read_instances";
+  if(!s || !out)
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: NULL argument", who);
+  if((uint64_t)first + count > s->nodes.size())
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: nodes [%u, %llu) outside the scene's %zu nodes", who, first, (unsigned long long)first + count,
+                s->nodes.size());
+  if(bytes != (uint64_t)count * sizeof(DevInstance))
+    return fail(VKRT_ERR_INVALID_ARGUMENT, "%s: bytes %llu != %zu x %u records", who, (unsigned long long)bytes, sizeof(DevInstance), count);
+  const int rc = setDevice(s);
+  if(rc != VKRT_OK)
+    return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  if(count)
+    HIP_TRY(hipMemcpy(out, s->dev.instances + first, (size_t)count * sizeof(DevInstance), hipMemcpyDeviceToHost));
   return VKRT_OK;
 }
 
@@ -1353,13 +1485,15 @@ int vkrt_scene_set_instance_visibility(vkrt_scene* s, uint32_t first, uint32_t c
     return rc;
   if((rc = setDevice(s)) != VKRT_OK)
     return rc;
-  // the whole records again, made from the host copies (bit for bit what the device holds, with the new visibility word) and sent as
-  // kernel arguments on hip_stream like vkrt_scene_update_nodes does: stream-ordered, nothing staged, no synchronisation
-  std::vector<DevInstance> inst(count);
+  // the visibility words alone, sent as kernel arguments on hip_stream like vkrt_scene_update_nodes sends its records: stream-ordered,
+  // nothing staged, no synchronisation.  The kernel keeps each record's mirrored bit and does not touch its transform, so a transform
+  // that came from device memory (vkrt_scene_update_node_transforms) stays; with the host copy current the records are bit for bit
+  // what make_instance gives for the node and the new visibility
+  std::vector<uint32_t> words(count);
   for(uint32_t i = 0; i < count; i++)
-    vkrt::make_instance(s->nodes[(size_t)first + i], vis[i], inst[i]);
+    words[i] = (uint32_t)vis[i].mask | ((uint32_t)vis[i].flags << 8);
   hipStream_t stream = (hipStream_t)hip_stream;
-  HIP_TRY(vkrt::upload_instances(const_cast<DevInstance*>(s->dev.instances), first, count, inst.data(), stream));
+  HIP_TRY(vkrt::launch_instance_visibility(const_cast<DevInstance*>(s->dev.instances), first, count, words.data(), stream));
   std::copy(vis, vis + count, s->vis.begin() + first);
   noteMasks(s);
   // the table follows the masks on the same stream (a stale tree too: records and topology are those of its build or last refit)
@@ -1897,6 +2031,8 @@ int vkrt_debug_split_references(vkrt_scene* s, uint32_t split_percent, float* pr
   if(rc != VKRT_OK)
     return rc;
   HIP_TRY(hipDeviceSynchronize());
+  if((rc = downloadNodeTransforms(s, "vkrt_debug_split_references")) != VKRT_OK)
+    return rc;
   // the builders' view of the scene with the option as it stands now; the installed tree keeps the setting it was built with
   DevScene sc = s->dev;
   sc.watertight = s->opt[VKRT_OPT_WATERTIGHT] != 0 ? 1u : 0u;

@@ -61,6 +61,9 @@ class _AnyLength:
 _N, _T = _AnyLength("n"), _AnyLength("T")
 _VERTEX_ARRAYS = (("positions", (_N, 3)), ("normals", (_N, 3)), ("tangents", (_N, 4)), ("texcoords0", (_N, 2)))  # update_vertices, in vkrt_vertex_update's order
 ALPHA_OPAQUE, ALPHA_MASK = abi.VKRT_ALPHA_OPAQUE, abi.VKRT_ALPHA_MASK  # vkrt_alpha_mode, for Renderer.set_material_alpha
+# one 96-B instance record (Renderer.read_instances; include/vkrt.h vkrt_debug_read_instances)
+INSTANCE_DTYPE = np.dtype([("o2w", "<f4", 12), ("w2o", "<f4", 9), ("primMesh", "<i4"), ("vis", "<u4"), ("pad", "<i4")])
+assert INSTANCE_DTYPE.itemsize == 96
 
 
 class VkrtError(RuntimeError):
@@ -202,10 +205,55 @@ class Renderer:
         _check(self.lib.vkrt_accel_build(self._h, flags, None), "vkrt_accel_build")
         self.build_kind = kind
 
-    def update_nodes(self, first, world_matrices, stream=None):
-        """vkrt_scene_update_nodes: new transforms for nodes [first, first + n).  world_matrices: (n, 16) float32, column-major like
-        vkrt_node.worldMatrix and FlatScene.nodes["worldMatrix"]; every node keeps its primMesh.  Enqueued on `stream` (a torch stream;
-        None = the default stream); the tree is stale until refit() or build()."""
+    def update_nodes(self, first, world_matrices, stream=None, indices=None):
+        """New transforms for nodes [first, first + n), or with `indices` for the n nodes it names (then first must be 0).
+        world_matrices: (n, 16) float32, column-major like vkrt_node.worldMatrix and FlatScene.nodes["worldMatrix"]; every node keeps
+        its primMesh and its visibility.  Enqueued on `stream` (a torch stream; None = the default stream); the tree is stale until
+        refit() or build().
+        numpy arrays take the host path (vkrt_scene_update_nodes; with indices the host form of vkrt_scene_update_node_transforms):
+        checked finite, copied before return, no wait.  A contiguous float32 torch tensor on the scene's device takes the device path
+        (vkrt_scene_update_node_transforms with VKRT_MEMORY_DEVICE): one launch, no copy, no synchronisation, values not inspected, an
+        index >= the node count skips its entry; indices is then an int32 or uint32 tensor of n entries on that device, and both
+        tensors must live until `stream` has passed the call.  Refused here, before the call: a wrong dtype, shape or device, a
+        non-contiguous tensor, numpy and torch mixed in one call, a range outside the scene, first != 0 with indices."""
+        who = "update_nodes"
+        torch = _torch or _import_torch()
+        st = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        tensors = [isinstance(a, torch.Tensor) for a in (world_matrices, indices) if a is not None]
+        if any(tensors) and not all(tensors):
+            raise VkrtError(f"{who}: numpy arrays and torch tensors mixed in one call")
+        count = self._prim_mesh.shape[0]
+        if any(tensors) or indices is not None:
+            if isinstance(first, bool) or not isinstance(first, (int, np.integer)) or first < 0 or (indices is not None and first != 0):
+                raise VkrtError(f"{who}: first is {first!r}: an integer >= 0, and 0 with indices")
+            if any(tensors):
+                mptr, memory, have = self._float_source(who, "world_matrices", world_matrices, (_N, 16), align=16)
+                n, iptr = int(have[0]), None
+                if indices is not None:
+                    if not indices.is_cuda or indices.device.index != self.device:
+                        raise VkrtError(f"{who}: indices is on {indices.device}, the scene is on cuda:{self.device}")
+                    if indices.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+                        raise VkrtError(f"{who}: indices is {indices.dtype}, expected int32 or uint32")
+                    if not indices.is_contiguous():
+                        raise VkrtError(f"{who}: indices must be contiguous")
+                    if tuple(indices.shape) != (n,):
+                        raise VkrtError(f"{who}: indices has shape {tuple(indices.shape)}, expected ({n},)")
+                    iptr = indices.data_ptr()
+                    if iptr % 4:
+                        raise VkrtError(f"{who}: indices must be 4-byte aligned")
+            else:  # the sparse host form
+                m = np.ascontiguousarray(world_matrices, np.float32).reshape(-1, 16)
+                ix = np.asarray(indices)
+                n = m.shape[0]
+                if ix.dtype.kind not in "iu" or ix.shape != (n,) or np.any(ix < 0) or np.any(ix >= count):
+                    raise VkrtError(f"{who}: indices must be {n} integers in [0, {count})")
+                ix = np.ascontiguousarray(ix, np.uint32)
+                mptr, iptr, memory = m.ctypes.data, ix.ctypes.data, _HOST
+            if indices is None and int(first) + n > count:
+                raise VkrtError(f"{who}: nodes [{first}, {first + n}) outside the scene's {count} nodes")
+            u = abi.NodeUpdate(C.sizeof(abi.NodeUpdate), int(first), n, memory, mptr, iptr)
+            _check(self.lib.vkrt_scene_update_node_transforms(self._h, C.byref(u), st), "vkrt_scene_update_node_transforms")
+            return
         m = np.ascontiguousarray(world_matrices, np.float32).reshape(-1, 16)
         first, n = int(first), m.shape[0]
         if first < 0 or first + n > self._prim_mesh.shape[0]:
@@ -400,6 +448,17 @@ class Renderer:
         _check(self.lib.vkrt_debug_read_vertices(self._h, int(first), int(count), *(out[k].ctypes.data for k in ("positions", "normals", "tangents",
                                                                                                          "texcoords0"))), "vkrt_debug_read_vertices")
         return out
+
+    def read_instances(self, first, count):
+        """The instance records of nodes [first, first + count) as the kernels read them (vkrt_debug_read_instances, synchronises): a
+        numpy array of INSTANCE_DTYPE, 96 B per node -- o2w (12 floats, row-major 3x4), w2o (9 floats), primMesh, vis, pad."""
+        ok = all(not isinstance(x, bool) and isinstance(x, (int, np.integer)) for x in (first, count))
+        nodes = self._prim_mesh.shape[0]
+        if not ok or first < 0 or count < 0 or int(first) + int(count) > nodes:
+            raise VkrtError(f"read_instances: nodes [{first}, {first} + {count}) outside the scene's {nodes} nodes")
+        out = np.zeros(max(int(count), 1), INSTANCE_DTYPE)
+        _check(self.lib.vkrt_debug_read_instances(self._h, int(first), int(count), out.ctypes.data, 96 * int(count)), "vkrt_debug_read_instances")
+        return out[:int(count)]
 
     def set_instance_visibility(self, first, masks, flags=None, stream=None):
         """vkrt_scene_set_instance_visibility for nodes [first, first + n): masks = n ints in 1..255 (the instance masks of the
