@@ -228,7 +228,7 @@ def test_what_bench_times_rows_match_oracle():
 @pytest.mark.parametrize("same_seed", [False, True])
 def test_long_calls_run_as_batches_and_equal_single_calls(cornell_flat, same_seed):
     """A call of more than VKRT_FRAMES_PER_BATCH (32) frames is rendered as batches with their own first frame index and seed offset
-    (csrc/vkrt_api.cpp): 33 and 70 frames in one call == that many single calls, with and without
+    (csrc/api_frames.cpp): 33 and 70 frames in one call == that many single calls, with and without
     VKRT_TRACE_SAME_SEED_EVERY_FRAME; and the per-kernel timing record of a long timed call covers every batch."""
     from vkrt_amd import abi
     from vkrt_amd.flat_scene import make_push_constants

@@ -14,7 +14,7 @@ The watertight test and the dissolve stage are arithmetics of their own, each wi
 their variants are compared among themselves.  Every variant runs a plain launch (the product kernels) and an instrumented one
 (their counting twins: `hits` is only tallied there), and the two must agree as well.
 
-The library has no way to force stackCap below what a tree needs (it is derived from the tree's depth, csrc/vkrt_api.cpp), so the
+The library has no way to force stackCap below what a tree needs (it is derived from the tree's depth, csrc/api_accel.cpp), so the
 case "parked groups tested out for lack of room" is not forced here; the strips of the artist-like atrium reach the flush path
 through VKRT_W8_MAX_POSTPONED instead.
 

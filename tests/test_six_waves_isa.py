@@ -41,7 +41,7 @@ int main()
 
 
 def postpone_room():
-    """VKRT_W8_POSTPONE_ROOM of csrc/device_scene.h: the entries vkrt_api.cpp adds to a wide8 stack for parked triangle groups"""
+    """VKRT_W8_POSTPONE_ROOM of csrc/device_scene.h: the entries api_accel.cpp adds to a wide8 stack for parked triangle groups"""
     m = re.search(r"^#define VKRT_W8_POSTPONE_ROOM (\d+)\b", open(os.path.join(CSRC, "device_scene.h")).read(), flags=re.M)
     return int(m.group(1))
 

@@ -2,7 +2,7 @@
 _morph_vertices and vkrt_debug_read_vertices (csrc/vertex_anim.cpp) on the CPU, for a scene of 20 vertices with the skin [10, 16) and
 the morph [4, 6): every refusal that needs a scene with its return code and its exact message, the accepted neighbours of each, where
 a non-finite value is reported, and each refusal winning over every later one in the order include/vkrt.h states.  vertex_anim.cpp
-is compiled with g++ into a ctypes shim that chains the checks as vkrt_api.cpp does, and once more with the address and
+is compiled with g++ into a ctypes shim that chains the checks as api_vertices.cpp does, and once more with the address and
 undefined-behaviour sanitizers into a stand-alone program that replays the same calls."""
 import ctypes as C
 import json
@@ -21,7 +21,7 @@ OK, BAD = abi.VKRT_OK, abi.VKRT_ERR_INVALID_ARGUMENT
 HOST, DEVICE = abi.VKRT_MEMORY_HOST, abi.VKRT_MEMORY_DEVICE
 U, S, M = C.sizeof(abi.VertexUpdate), C.sizeof(abi.SkinDesc), C.sizeof(abi.MorphDesc)
 
-# The entry points as vkrt_api.cpp chains them: the descriptor checks, the NULL out_* and NULL scene refusals (the API's own, restated
+# The entry points as api_vertices.cpp chains them: the descriptor checks, the NULL out_* and NULL scene refusals (the API's own, restated
 # here), the rules that need the scene.  The scene's records are wider than a VertexRange, as the library's are (RangeSet::stride).
 SHIM = r"""
 #include <cstdio>

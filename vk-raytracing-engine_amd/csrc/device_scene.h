@@ -88,7 +88,7 @@ struct DevSurfaceScene : DevScene
 #define VKRT_W8_MAX_POSTPONED 8  // parked triangle groups per lane (traverse_wide.h, traverse_share.h), held in the free top end of its stack column
 #endif
 #ifndef VKRT_W8_POSTPONE_ROOM
-#define VKRT_W8_POSTPONE_ROOM 0  // entries of the column reserved for them on top of the node stack's own depth (vkrt_api.cpp); groups parked beyond
+#define VKRT_W8_POSTPONE_ROOM 0  // entries of the column reserved for them on top of the node stack's own depth (api_accel.cpp); groups parked beyond
                                  // these are tested out when a node push needs the slot (profiles/r04_experiments.md #117)
 #endif
 

@@ -230,7 +230,7 @@ __global__ __launch_bounds__(VKRT_BLOCK) void k_eval_shade(unsigned n, const flo
   o[18] = 0.0f; o[19] = 0.0f;
 }
 
-// ---- launch wrappers (called from vkrt_api.cpp) ------------------------------------------------------
+// ---- launch wrappers (called from the api_*.cpp units) ------------------------------------------------------
 // MINW = minimum waves per SIMD the register allocator must allow: 3 measured +34 % over the unconstrained build and
 // level with 4 (profiles/r01_experiments.md #2, #3), so the product build carries that one variant.
 hipError_t vkrt_launch_pathtrace(const TraceParams& P, unsigned gridBlocks, bool count, hipStream_t stream)

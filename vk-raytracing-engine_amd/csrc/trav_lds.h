@@ -1,5 +1,5 @@
 // trav_lds.h -- what a traversal wave of the frame kernels (wf_traverse.hip) is charged in LDS, and how many of them a CU then holds.
-// vkrt_api.cpp takes the stack size from travStackCap when a tree is installed and decides nothing else: every depth runs the same kernels
+// api_accel.cpp takes the stack size from travStackCap when a tree is installed and decides nothing else: every depth runs the same kernels
 // on the same block, and the depth alone makes the charge.  travLdsPlan states that charge for the checks: tests/test_six_waves_isa.py
 // compiles this header alone, for the CPU (no HIP type), and holds the kernels' static block and the measured granule to it.
 //

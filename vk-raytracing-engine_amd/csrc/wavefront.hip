@@ -557,7 +557,7 @@ hipError_t vkrt_launch_wavefront(const TraceParams& P, const WfBuffers& B, const
   const int L = lanes.F * lanes.S;
   const bool staged = lanes.F > 1;
   if(staged && wfPoolEvents(lanes.frames) > async->poolSize)
-    return hipErrorInvalidValue;  // (vkrt_api.cpp sizes the pool with the same function)
+    return hipErrorInvalidValue;  // (api_frames.cpp sizes the pool with the same function)
   // a single lane is the caller's stream and B itself; several have internal streams and their slices of B
   hipStream_t laneStream[VKRT_WF_MAX_LANES];
   WfBuffers Bq[VKRT_WF_MAX_LANES];

@@ -1,6 +1,6 @@
 // wf_schedule.h -- the host-side schedule of a wavefront frame call: which launches it turns into, in what host order, on which lane and
 // behind which event, and how much the caller keeps for it (frame groups, pool events, timing events).  wavefront.hip issues what this
-// header enumerates and vkrt_api.cpp allocates what it says.  No HIP type: tests/test_wf_schedule.py compiles it alone, for the CPU.
+// header enumerates and api_frames.cpp allocates what it says.  No HIP type: tests/test_wf_schedule.py compiles it alone, for the CPU.
 #pragma once
 #include <algorithm>
 #include <cstddef>
