@@ -814,6 +814,73 @@ int vkrt_scene_set_material_alpha(vkrt_scene* scene, uint32_t first, uint32_t co
 /* Reads the host copy (no synchronisation).  VKRT_ERR_INVALID_ARGUMENT: a NULL array with count > 0, a NULL scene, a range outside. */
 int vkrt_scene_get_material_alpha(const vkrt_scene* scene, uint32_t first, uint32_t count, vkrt_material_alpha* out);
 
+/* ---- editing a live scene's lights, materials and textures (a moved light, a changed colour or texture binding, a video texture or
+ *      the result of a render-to-texture pass: what a Vulkan application does with vkCmdUpdateBuffer and vkCmdCopyBufferToImage +
+ *      vkCmdBlitImage between frames).  These entry points came after ABI version 4 without changing it or any existing struct: detect
+ *      them by symbol. -------------------------------------------------------------------------------------------------------------
+ * Ordering: each of the three calls is enqueued on hip_stream (NULL = the default stream), ordered after what was enqueued there before
+ * (a frame that still reads the old values) and before what comes after (the next query or frame, which sees the new values).
+ * Not stale: none of them makes the tree stale; all of them work on a stale tree and before vkrt_accel_build; like
+ * vkrt_scene_set_material_alpha the next query or frame on that stream sees the new values without a refit.  The one exception is the
+ * dissolve rule of vkrt_scene_update_materials below.  A refused call changes nothing; the first failing check of a call's list wins.
+ * Tables, sizes and counts are those of vkrt_scene_create: the number of lights, materials and textures, every texture's size, is_srgb
+ * and place in the pools are fixed.  While none of these entry points is called the library launches what it launched before.
+ *
+ * vkrt_scene_update_lights: new records for lights [first, first+count), taken as given exactly as at vkrt_scene_create, which does not
+ * inspect them; lightsCount of the frame calls stays the caller's, within [0, light_count].
+ *   VKRT_MEMORY_HOST    the array is copied before return: the 32-B records travel as kernel arguments; nothing is staged and the call
+ *                       does not wait for the stream.
+ *   VKRT_MEMORY_DEVICE  the array is device memory on the scene's device, 16-byte aligned, valid until the stream has passed the call;
+ *                       the call is one stream-ordered device copy, with no allocation and no host synchronisation.
+ * Refused with VKRT_ERR_INVALID_ARGUMENT, in this order: a NULL update; struct_size < sizeof(vkrt_light_update); a memory value that is
+ * neither VKRT_MEMORY_HOST nor VKRT_MEMORY_DEVICE; a NULL scene; a range outside the scene's lights; (count > 0) NULL lights; (device
+ * memory) lights that is not 16-byte aligned.  Then count == 0: VKRT_OK with nothing enqueued.  Then, without a device:
+ * VKRT_ERR_NO_DEVICE. */
+typedef struct vkrt_light_update {
+  uint32_t struct_size;     /* sizeof(vkrt_light_update) */
+  uint32_t first, count;
+  uint32_t memory;          /* vkrt_memory */
+  const GltfLight* lights;  /* [count], entry k = light first + k */
+} vkrt_light_update;
+int vkrt_scene_update_lights(vkrt_scene* scene, const vkrt_light_update* update, void* hip_stream);
+/* vkrt_scene_update_materials: new materials [first, first+count) from a host array, which may be reused on return: both device records
+ * of each material are re-made by the code that makes them at vkrt_scene_create and travel as kernel arguments (192 B per material,
+ * chunked); nothing is staged and the call does not wait for the stream.  The records are bit for bit what vkrt_scene_create packs for a
+ * scene created with these materials.  The alpha mode and cutoff of a material are kept: they belong to
+ * vkrt_scene_set_material_alpha.  Texture indices may change freely among the scene's textures.
+ * Refused, in this order: VKRT_ERR_INVALID_ARGUMENT for a NULL array with count > 0; for a texture index >= texture_count in a scene
+ * that has textures (the rule of vkrt_scene_create); for a NULL scene; for a range outside the scene's materials; VKRT_ERR_UNSUPPORTED
+ * for a reference to a texture with a side above 32768.  Then count == 0: VKRT_OK.  Then, without a device: VKRT_ERR_NO_DEVICE.
+ * Dissolve: the any-hit dissolve stage (VKRT_OPT_ANYHIT_DISSOLVE) reads pbrBaseColorFactor[3] from the live record, so changing it among
+ * values < 1 needs nothing; but the builders flag the triangles of a material with alpha < 1 at build time.  When the scene's last
+ * vkrt_accel_build ran with VKRT_OPT_ANYHIT_DISSOLVE = 1 and after the update some material has alpha < 1 that did not have alpha < 1 at
+ * that build, the tree needs a rebuild, not only a refit: until the next vkrt_accel_build every call that needs a built tree, and
+ * vkrt_accel_refit, return VKRT_ERR_NOT_BUILT with a message naming vkrt_scene_update_materials.  The opposite direction (< 1 becoming
+ * >= 1) needs nothing: a flagged triangle with alpha >= 1 is never ignored. */
+int vkrt_scene_update_materials(vkrt_scene* scene, uint32_t first, uint32_t count, const GltfPBRMaterial* materials, void* hip_stream);
+/* vkrt_scene_update_texture: replaces the whole image of one texture; width and height must equal the texture's (sub-rectangles,
+ * resizing and adding textures are out of scope).  After the call, in stream order, level 0 in the RGBA8 pool, the texture's footprint
+ * records (when the scene has that pool) and every mip level behind level 0 hold bit for bit what vkrt_scene_create packs from the new
+ * texels: the scene renders, samples (vkrt_hit_surface, the alpha test, the G-buffer's implicit-LOD taps) and reads back exactly like a
+ * scene created with that image.  The mip levels are vkCmdBlitImage's with VK_FILTER_LINEAR, level by level, as at vkrt_scene_create; the
+ * 8-bit sRGB codes come from a table of thresholds the host derived from its own encode function at vkrt_scene_create, so that the device
+ * never evaluates a curve whose last bit could differ.
+ *   VKRT_MEMORY_DEVICE  rgba8 is device memory on the scene's device, 16-byte aligned, valid until the stream has passed the call; no
+ *                       allocation, no host synchronisation, at most 1 + VKRT_MAX_MIPS (16) kernel launches.
+ *   VKRT_MEMORY_HOST    the texels are staged through the scene's staging buffer, the same kernels run, and the call waits for the
+ *                       stream before it returns, like a host-sourced vkrt_scene_update_vertices.
+ * Refused with VKRT_ERR_INVALID_ARGUMENT, in this order: a NULL update; struct_size < sizeof(vkrt_texture_update); a memory value that
+ * is neither of the two; a NULL scene; a texture index out of range (always, in a scene without textures); a width or height that is
+ * not the texture's; NULL rgba8; (device memory) rgba8 that is not 16-byte aligned.  Then, without a device: VKRT_ERR_NO_DEVICE. */
+typedef struct vkrt_texture_update {
+  uint32_t struct_size;  /* sizeof(vkrt_texture_update) */
+  uint32_t texture;
+  uint32_t width, height;
+  uint32_t memory;       /* vkrt_memory */
+  const uint8_t* rgba8;  /* width*height RGBA8 texels, row-major, top row first */
+} vkrt_texture_update;
+int vkrt_scene_update_texture(vkrt_scene* scene, const vkrt_texture_update* update, void* hip_stream);
+
 /* ---- path trace (replaces HelloVulkan::pathtrace :1423-1448 = one
  *      vkCmdTraceRaysKHR over raytrace.rgen/.rchit/.rmiss/raytraceShadow.rmiss) ---- */
 uint32_t vkrt_shard_rows(const vkrt_shard* shard); /* rows of the shard's buffer */
@@ -1048,6 +1115,17 @@ int vkrt_debug_read_vertices(vkrt_scene* scene, uint32_t first, uint32_t count, 
  * when the 3x3 has a negative determinant); int32 pad = 0.  Needs no tree.  A NULL scene or out, a range outside the scene's nodes or
  * bytes != 96 * count: VKRT_ERR_INVALID_ARGUMENT. */
 int vkrt_debug_read_instances(vkrt_scene* scene, uint32_t first, uint32_t count, void* out, uint64_t bytes);
+/* The light records [first, first+count) (32 B each, GltfLight), the material records [first, first+count) (192 B each: the 128-B record
+ * of the queries and the G-buffer -- GltfPBRMaterial, pad, alpha mode, alpha cutoff, four 16-B texture references --, then the 64-B record
+ * of the hit shader) and one level of one texture, exactly as the kernels read them (each synchronises the device; test hooks like the
+ * other vkrt_debug_* calls, no kernel of their own).  vkrt_debug_read_texture: texels = the level's RGBA8 texels, max(1, width >> level)
+ * x max(1, height >> level) of them; for level 0, when quads != NULL, also the texture's footprint records, 16 B per texel (the texels
+ * (x, y) (x+1, y) (x, y+1) (x+1, y+1), wrapped): VKRT_ERR_UNSUPPORTED when the scene has no footprint pool.  None needs a tree.  A NULL
+ * scene or out / texels, a range, texture or level outside the scene's, quads with a level above 0, or a byte count that is not the
+ * records': VKRT_ERR_INVALID_ARGUMENT. */
+int vkrt_debug_read_lights(vkrt_scene* scene, uint32_t first, uint32_t count, void* out, uint64_t bytes);
+int vkrt_debug_read_materials(vkrt_scene* scene, uint32_t first, uint32_t count, void* out, uint64_t bytes);
+int vkrt_debug_read_texture(vkrt_scene* scene, uint32_t texture, uint32_t level, void* texels, uint64_t texel_bytes, void* quads, uint64_t quad_bytes);
 /* The work of vkrt_closest_point on n queries of a HOST array (synchronises the device; a test hook like the other vkrt_debug_* calls):
  * out[0] = nodes visited, out[1] = triangle records tested, summed over the queries, by an instrumented instantiation of the same
  * walk.  opts and the order of errors as vkrt_closest_point; a NULL out: VKRT_ERR_INVALID_ARGUMENT. */

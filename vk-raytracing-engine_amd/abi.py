@@ -232,6 +232,17 @@ class MorphDesc(C.Structure):
                 ("normal_deltas", C.c_void_p), ("tangent_deltas", C.c_void_p)]
 
 
+# editing a live scene (vkrt_scene_update_lights / vkrt_scene_update_texture): `lights` / `rgba8` are host or device pointers, by `memory`
+class LightUpdate(C.Structure):
+    _fields_ = [("struct_size", c_u), ("first", c_u), ("count", c_u), ("memory", c_u), ("lights", C.c_void_p)]
+
+
+class TextureUpdate(C.Structure):
+    _fields_ = [("struct_size", c_u), ("texture", c_u), ("width", c_u), ("height", c_u), ("memory", c_u), ("rgba8", C.c_void_p)]
+
+
+assert C.sizeof(LightUpdate) == 24
+assert C.sizeof(TextureUpdate) == 32
 assert C.sizeof(VertexUpdate) == 48
 assert C.sizeof(NodeUpdate) == 32
 assert C.sizeof(SkinDesc) == 32
@@ -315,6 +326,9 @@ VKRT_SYMBOLS = [
     "vkrt_hit_motion",
     "vkrt_scene_set_material_alpha",
     "vkrt_scene_get_material_alpha",
+    "vkrt_scene_update_lights",
+    "vkrt_scene_update_materials",
+    "vkrt_scene_update_texture",
     "vkrt_shard_rows",
     "vkrt_pathtrace",
     "vkrt_pathtrace_frames",
@@ -340,6 +354,9 @@ VKRT_SYMBOLS = [
     "vkrt_debug_split_references",
     "vkrt_debug_read_vertices",
     "vkrt_debug_read_instances",
+    "vkrt_debug_read_lights",
+    "vkrt_debug_read_materials",
+    "vkrt_debug_read_texture",
     "vkrt_debug_closest_point_work",
     "vkrt_debug_trace_rays",
     "vkrt_debug_eval_math",
@@ -380,6 +397,20 @@ def declare_vkrt(lib):
     # (scene, first, count, out: host pointer to 96-B records, bytes)
     lib.vkrt_debug_read_instances.argtypes = [C.c_void_p, c_u, c_u, C.c_void_p, C.c_uint64]
     lib.vkrt_debug_read_instances.restype = C.c_int
+    # editing a live scene: (scene, update, stream) / (scene, first, count, host materials, stream) / (scene, update, stream)
+    lib.vkrt_scene_update_lights.argtypes = [C.c_void_p, P(LightUpdate), C.c_void_p]
+    lib.vkrt_scene_update_lights.restype = C.c_int
+    lib.vkrt_scene_update_materials.argtypes = [C.c_void_p, c_u, c_u, C.c_void_p, C.c_void_p]
+    lib.vkrt_scene_update_materials.restype = C.c_int
+    lib.vkrt_scene_update_texture.argtypes = [C.c_void_p, P(TextureUpdate), C.c_void_p]
+    lib.vkrt_scene_update_texture.restype = C.c_int
+    # (scene, first, count, out: host pointer to 32-B / 192-B records, bytes); (scene, texture, level, texels, bytes, quads or NULL, bytes)
+    lib.vkrt_debug_read_lights.argtypes = [C.c_void_p, c_u, c_u, C.c_void_p, C.c_uint64]
+    lib.vkrt_debug_read_lights.restype = C.c_int
+    lib.vkrt_debug_read_materials.argtypes = [C.c_void_p, c_u, c_u, C.c_void_p, C.c_uint64]
+    lib.vkrt_debug_read_materials.restype = C.c_int
+    lib.vkrt_debug_read_texture.argtypes = [C.c_void_p, c_u, c_u, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
+    lib.vkrt_debug_read_texture.restype = C.c_int
     # (scene, desc, stream, out_skin) / (scene, skin, joint matrices: host or device pointer by `memory`, memory, stream)
     lib.vkrt_scene_add_skin.argtypes = [C.c_void_p, P(SkinDesc), C.c_void_p, P(c_u)]
     lib.vkrt_scene_add_skin.restype = C.c_int

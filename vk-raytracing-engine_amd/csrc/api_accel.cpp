@@ -252,6 +252,9 @@ int accelBuildOnce(vkrt_scene* s, uint32_t flags, int splitBudget, hipStream_t s
   }
   s->info.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   s->built = true;
+  if(s->opt[VKRT_OPT_ANYHIT_DISSOLVE] != 0)  // what the triangle flags of this tree cover (vkrt_scene_update_materials' dissolve rule)
+    for(const float a : s->materialAlpha)
+      s->builtNonOpaque.push_back(a < 1.0f ? 1 : 0);
   return VKRT_OK;
 }
 
@@ -346,6 +349,9 @@ int vkrt_accel_refit(vkrt_scene* s, void* hip_stream)
     return fail(VKRT_ERR_INVALID_ARGUMENT, "scene is NULL");
   if(!s->built)
     return fail(VKRT_ERR_NOT_BUILT, "vkrt_accel_refit before vkrt_accel_build");
+  if(s->dissolveRebuild)
+    return fail(VKRT_ERR_NOT_BUILT, "vkrt_accel_refit after vkrt_scene_update_materials gave a material alpha < 1 that was opaque when the tree was built "
+                "with VKRT_OPT_ANYHIT_DISSOLVE: a refit keeps the triangle flags, vkrt_accel_build first");
   RC_TRY(enter(s));
   hipStream_t stream = (hipStream_t)hip_stream;
   std::string err;

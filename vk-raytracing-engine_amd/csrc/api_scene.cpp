@@ -111,6 +111,10 @@ int vkrt_scene_create(const vkrt_scene_desc* d, int device, vkrt_scene** out)
   if(!packed.texQuads.empty())
     RC_TRY(upload(s, packed.texQuads.data(), packed.texQuads.size(), &quads));
   RC_TRY(upload(s, packed.srgbLut, 512, &lut));
+  RC_TRY(upload(s, packed.srgbEncode, (size_t)VKRT_SRGB_THRESHOLDS, &s->srgbEncode));
+  s->textures = packed.textures;
+  s->texMips = packed.texMips;
+  s->texQuadFirst = packed.texQuadFirst;
   D.vertexPN = (const float4*)pn;
   s->surfacePrimMeshes = (const uint4*)pm;
   D.texQuads = (const uint4*)quads;

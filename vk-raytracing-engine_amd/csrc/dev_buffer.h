@@ -51,8 +51,8 @@ private:
   std::unique_ptr<void, Free> p_;
 };
 
-// The staging buffer of a scene's host-sourced vertex data: update arrays, joint matrices, morph weights.  One rule makes one buffer
-// enough for all of them: a call that stages waits for its stream before it returns, so at the next put() nothing reads the buffer
+// The staging buffer of a scene's host-sourced data: vertex update arrays, joint matrices, morph weights, the texels of a texture
+// update.  One rule makes one buffer enough for all of them: a call that stages waits for its stream before it returns, so at the next put() nothing reads the buffer
 // any more, and it may be overwritten, or freed to grow.  It only grows.
 class StageBuf
 {
@@ -70,13 +70,8 @@ public:
     size_t bytes = 0;
     for(const Part& p : parts)
       bytes += p.src ? p.floats * sizeof(float) : 0;
-    if(bytes > bytes_)
-    {
-      bytes_ = 0;
-      if(const hipError_t e = buf_.alloc(bytes); e != hipSuccess)
-        return e;
-      bytes_ = bytes;
-    }
+    if(const hipError_t e = reserve(bytes); e != hipSuccess)
+      return e;
     float* at = buf_.get<float>();
     for(const Part& p : parts)
       if(p.src)
@@ -88,8 +83,26 @@ public:
       }
     return hipSuccess;
   }
+  // One part of any type: `bytes` from src to the start of the buffer (256-byte aligned), copied on `stream`; the same rule for the caller.
+  hipError_t putBytes(const void* src, size_t bytes, const void** dev, hipStream_t stream)
+  {
+    if(const hipError_t e = reserve(bytes); e != hipSuccess)
+      return e;
+    *dev = buf_.get();
+    return hipMemcpyAsync(buf_.get(), src, bytes, hipMemcpyHostToDevice, stream);
+  }
 
 private:
+  hipError_t reserve(size_t bytes)
+  {
+    if(bytes <= bytes_)
+      return hipSuccess;
+    bytes_ = 0;
+    if(const hipError_t e = buf_.alloc(bytes); e != hipSuccess)
+      return e;
+    bytes_ = bytes;
+    return hipSuccess;
+  }
   DevBuf buf_;
   size_t bytes_ = 0;
 };

@@ -1,4 +1,4 @@
-// entry_checks.cpp -- the argument rules of the node-update, visibility, material-alpha, query and frame entry points (entry_checks.h):
+// entry_checks.cpp -- the argument rules of the node-update, visibility, material-alpha, scene-edit, query and frame entry points (entry_checks.h):
 // host-only, no HIP type.
 #include "entry_checks.h"
 
@@ -118,6 +118,74 @@ int check_material_range(const char* who, uint32_t first, uint32_t count, uint32
   if((uint64_t)first + count <= materialCount)
     return VKRT_OK;
   return refuse(kBad, err, "%s: materials [%u, %llu) outside the scene's %u materials", who, first, (unsigned long long)first + count, materialCount);
+}
+
+int check_light_update_desc(const vkrt_light_update* u, std::string& err)
+{
+  const char* who = "vkrt_scene_update_lights";
+  if(!u)
+    return refuse(kBad, err, "%s: update is NULL", who);
+  if(u->struct_size < sizeof(vkrt_light_update))
+    return refuse(kBad, err, "%s: vkrt_light_update.struct_size %u < %zu (ABI mismatch)", who, u->struct_size, sizeof(vkrt_light_update));
+  if(u->memory != VKRT_MEMORY_HOST && u->memory != VKRT_MEMORY_DEVICE)
+    return refuse(kBad, err, "%s: memory %u is neither VKRT_MEMORY_HOST nor VKRT_MEMORY_DEVICE", who, u->memory);
+  return VKRT_OK;
+}
+
+int check_light_update_range(const vkrt_light_update& u, uint32_t lightCount, std::string& err)
+{
+  const char* who = "vkrt_scene_update_lights";
+  if((uint64_t)u.first + u.count > lightCount)
+    return refuse(kBad, err, "%s: lights [%u, %llu) outside the scene's %u lights", who, u.first, (unsigned long long)u.first + u.count, lightCount);
+  if(u.count && !u.lights)
+    return refuse(kBad, err, "%s: lights is NULL", who);
+  if(u.memory != VKRT_MEMORY_HOST && ((uintptr_t)u.lights & 15u) != 0)
+    return refuse(kBad, err, "%s: lights %p is not 16-byte aligned", who, (const void*)u.lights);
+  return VKRT_OK;
+}
+
+int check_material_update_values(const char* who, uint32_t count, const GltfPBRMaterial* materials, uint32_t textureCount, std::string& err)
+{
+  if(count && !materials)
+    return refuse(kBad, err, "%s: materials is NULL", who);
+  if(textureCount > 0)
+    for(uint32_t i = 0; i < count; i++)
+    {
+      const int32_t t[4] = {materials[i].pbrBaseColorTexture, materials[i].metallicRoughnessTexture, materials[i].normalTexture, materials[i].emissiveTexture};
+      for(int k = 0; k < 4; k++)
+        if(t[k] >= (int32_t)textureCount)
+          return refuse(kBad, err, "%s: materials[%u]: texture index %d out of range (the scene has %u textures)", who, i, t[k], textureCount);
+    }
+  return VKRT_OK;
+}
+
+int check_texture_update_desc(const vkrt_texture_update* u, std::string& err)
+{
+  const char* who = "vkrt_scene_update_texture";
+  if(!u)
+    return refuse(kBad, err, "%s: update is NULL", who);
+  if(u->struct_size < sizeof(vkrt_texture_update))
+    return refuse(kBad, err, "%s: vkrt_texture_update.struct_size %u < %zu (ABI mismatch)", who, u->struct_size, sizeof(vkrt_texture_update));
+  if(u->memory != VKRT_MEMORY_HOST && u->memory != VKRT_MEMORY_DEVICE)
+    return refuse(kBad, err, "%s: memory %u is neither VKRT_MEMORY_HOST nor VKRT_MEMORY_DEVICE", who, u->memory);
+  return VKRT_OK;
+}
+
+int check_texture_index(const char* who, uint32_t texture, uint32_t textureCount, std::string& err)
+{
+  return texture >= textureCount ? refuse(kBad, err, "%s: texture %u outside the scene's %u textures", who, texture, textureCount) : VKRT_OK;
+}
+
+int check_texture_update_image(const vkrt_texture_update& u, uint32_t width, uint32_t height, std::string& err)
+{
+  const char* who = "vkrt_scene_update_texture";
+  if(u.width != width || u.height != height)
+    return refuse(kBad, err, "%s: width x height %ux%u: texture %u is %ux%u (an update replaces the whole image)", who, u.width, u.height, u.texture, width, height);
+  if(!u.rgba8)
+    return refuse(kBad, err, "%s: rgba8 is NULL", who);
+  if(u.memory != VKRT_MEMORY_HOST && ((uintptr_t)u.rgba8 & 15u) != 0)
+    return refuse(kBad, err, "%s: rgba8 %p is not 16-byte aligned", who, (const void*)u.rgba8);
+  return VKRT_OK;
 }
 
 int check_query_opts(const vkrt_query_opts* q, const char* who, std::string& err)

@@ -1,4 +1,4 @@
-// entry_checks.h -- what the node-update, visibility, material-alpha, query and frame entry points refuse of their arguments before they
+// entry_checks.h -- what the node-update, visibility, material-alpha, scene-edit, query and frame entry points refuse of their arguments before they
 // touch the device, each rule once (entry_checks.cpp).  No HIP type: tests/test_entry_checks.py compiles it with g++.  Like
 // vertex_anim.h: VKRT_OK, or a vkrt code with the whole message of vkrt_last_error in err; the functions take plain facts -- counts,
 // pointers, the structs of include/vkrt.h -- and never a scene.  A call that is accepted leaves err alone and allocates nothing.  The
@@ -28,6 +28,19 @@ int check_node_update_range(const vkrt_node_update& u, size_t nodeCount, std::st
 int check_visibility_values(const char* who, uint32_t count, const vkrt_instance_visibility* vis, std::string& err);
 int check_alpha_values(const char* who, uint32_t count, const vkrt_material_alpha* alpha, std::string& err);
 int check_material_range(const char* who, uint32_t first, uint32_t count, uint32_t materialCount, std::string& err);
+
+// ---- editing a live scene (vkrt_scene_update_lights / _materials / _texture), each in the order include/vkrt.h lists
+// of the descriptor alone: NULL, struct_size, memory
+int check_light_update_desc(const vkrt_light_update* u, std::string& err);
+// behind the NULL-scene refusal: the range, NULL lights with count > 0, a misaligned device array
+int check_light_update_range(const vkrt_light_update& u, uint32_t lightCount, std::string& err);
+// the array (NULL with count > 0); then, when the scene is known and has textures (textureCount > 0), the rule of validate_scene: no
+// texture index >= textureCount.  The range behind the NULL-scene refusal is check_material_range's
+int check_material_update_values(const char* who, uint32_t count, const GltfPBRMaterial* materials, uint32_t textureCount, std::string& err);
+int check_texture_update_desc(const vkrt_texture_update* u, std::string& err);
+// behind the NULL-scene refusal: the index; then, with the size of that texture, the size, NULL rgba8, a misaligned device array
+int check_texture_index(const char* who, uint32_t texture, uint32_t textureCount, std::string& err);
+int check_texture_update_image(const vkrt_texture_update& u, uint32_t width, uint32_t height, std::string& err);
 
 // ---- queries
 // the options of vkrt_intersect_ex / vkrt_occluded_ex / vkrt_intersect_multi (include/vkrt.h)

@@ -3,6 +3,7 @@
 #include "scene_pack.h"
 #include "bvh_host.h"
 #include "instance_record.h"
+#include "texture_pack.h"
 
 #include <algorithm>
 #include <cmath>
@@ -31,21 +32,16 @@ int fail(std::string& err, int code, const char* fmt, ...)
 float srgbEncode(float c) { return c <= 0.0031308f ? 12.92f * c : 1.055f * powf(c, 1.0f / 2.4f) - 0.055f; }
 void downsampleLevel(const uint32_t* src, uint32_t sw, uint32_t sh, uint32_t* dst, uint32_t dw, uint32_t dh, bool srgb, const float* lut512)
 {
+  // (the filter is texture_pack.h's, which k_se_mip runs on the device for vkrt_scene_update_texture; the encode is the curve itself)
   for(uint32_t y = 0; y < dh; y++)
     for(uint32_t x = 0; x < dw; x++)
     {
-      const float fu = ((float)x + 0.5f) * ((float)sw / (float)dw) - 0.5f, fv = ((float)y + 0.5f) * ((float)sh / (float)dh) - 0.5f;
-      const float flx = floorf(fu), fly = floorf(fv), ax = fu - flx, ay = fv - fly;
-      auto cl = [](int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); };
-      const int x0 = cl((int)flx, (int)sw), x1 = cl((int)flx + 1, (int)sw), y0 = cl((int)fly, (int)sh), y1 = cl((int)fly + 1, (int)sh);
-      const uint32_t p[4] = {src[(size_t)y0 * sw + x0], src[(size_t)y0 * sw + x1], src[(size_t)y1 * sw + x0], src[(size_t)y1 * sw + x1]};
+      float f[4];
+      vkrt_mip_filter(src, sw, sh, dw, dh, x, y, srgb, lut512, f);
       uint32_t out = 0;
       for(int c = 0; c < 4; c++)
       {
-        const uint32_t base = (srgb && c < 3) ? 0u : 256u;
-        const float t00 = lut512[base + ((p[0] >> (8 * c)) & 255u)], t10 = lut512[base + ((p[1] >> (8 * c)) & 255u)];
-        const float t01 = lut512[base + ((p[2] >> (8 * c)) & 255u)], t11 = lut512[base + ((p[3] >> (8 * c)) & 255u)];
-        float v = (t00 * (1.0f - ax) + t10 * ax) * (1.0f - ay) + (t01 * (1.0f - ax) + t11 * ax) * ay;
+        float v = f[c];
         if(srgb && c < 3) v = srgbEncode(v);
         v = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);
         out |= (uint32_t)(v * 255.0f + 0.5f) << (8 * c);
@@ -129,6 +125,69 @@ void make_instance(const vkrt_node& node, const vkrt_instance_visibility& vis, D
   in.vis = (uint32_t)vis.mask | ((uint32_t)vis.flags << 8) | vkrt_mirrored_bit(in.o2w);
 }
 
+uint32_t srgb_encode_code(float v)
+{
+  v = srgbEncode(v);
+  v = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);
+  return (uint32_t)(v * 255.0f + 0.5f);
+}
+
+void make_srgb_encode_table(float T[VKRT_SRGB_THRESHOLDS])
+{
+  // non-negative binary32 values order like their bit patterns: bisect on those.  The code of 0 is 0 and the code of 1 is 255, so every
+  // q in 1..255 has a threshold in (0, 1]
+  T[0] = 0.0f;
+  for(uint32_t q = 1; q < VKRT_SRGB_THRESHOLDS; q++)
+  {
+    uint32_t lo = 0u, hi = 0x3f800000u;  // code(lo) < q <= code(hi)
+    while(hi - lo > 1u)
+    {
+      const uint32_t mid = lo + (hi - lo) / 2u;
+      float v;
+      memcpy(&v, &mid, 4);
+      (srgb_encode_code(v) >= q ? hi : lo) = mid;
+    }
+    memcpy(&T[q], &hi, 4);
+  }
+}
+
+int make_material(const GltfPBRMaterial& m, const DevTexture* table, uint32_t textureCount, const uint32_t* quadFirst, bool wantQuads, DevMaterial& mat,
+                  DevShadeMaterial& sm, std::string& err)
+{
+  memset(&mat, 0, sizeof mat);
+  mat.m = m;
+  mat.alphaMode = kDefaultAlpha.mode;
+  mat.alphaCutoff = kDefaultAlpha.cutoff;
+  memset(&sm, 0, sizeof sm);
+  for(int k = 0; k < 3; k++)
+  {
+    sm.f[k] = mat.m.pbrBaseColorFactor[k];
+    sm.f[5 + k] = mat.m.emissiveFactor[k];
+  }
+  sm.f[3] = mat.m.metallicFactor;
+  sm.f[4] = mat.m.roughnessFactor;
+  const int idx[4] = {mat.m.pbrBaseColorTexture, mat.m.metallicRoughnessTexture, mat.m.normalTexture, mat.m.emissiveTexture};
+  for(int k = 0; k < 4; k++)
+  {
+    DevTexRef& r = mat.tex[k];
+    r = DevTexRef{0u, 1u | (1u << 16), 0u, 0u};
+    if(idx[k] >= 0 && (uint32_t)idx[k] < textureCount)
+    {
+      const DevTexture& t = table[(size_t)idx[k]];
+      if(t.width == 0u || t.height == 0u || t.width > 32768u || t.height > 32768u)
+        return fail(err, VKRT_ERR_UNSUPPORTED, "texture %d is %ux%u (supported: 1..32768 per side)", idx[k], t.width, t.height);
+      r = DevTexRef{t.offset, t.width | (t.height << 16), 1u | ((t.srgb & 1u) ? 2u : 0u), wantQuads ? quadFirst[(size_t)idx[k]] : 0u};
+    }
+    // (the reference order of DevShadeMaterial is VKRT_TEXREF_*: BASE, MR, NORMAL, EMISSIVE = the order of idx[])
+    const uint32_t base = wantQuads ? r.quads : r.offset;
+    if(base >> 31)
+      return fail(err, VKRT_ERR_UNSUPPORTED, "texture pool of 2^31 records and more is not supported");
+    sm.ref[2 * k] = ((r.wh & 0xffffu) - 1u) | (idx[k] > -1 ? 1u << 15 : 0u) | (((r.wh >> 16) - 1u) << 16) | ((r.flags & 1u) << 31);
+    sm.ref[2 * k + 1] = base | ((r.flags & 2u) << 30);
+  }
+  return VKRT_OK;
+}
+
 int pack_scene(const vkrt_scene_desc* d, bool texQuadsAllowed, PackedScene& out, std::string& err)
 {
   // (normals / uv travel inside vertexPN; the ePrimLookup indirection of hello_vulkan.cpp:363-368 is resolved per triangle
@@ -167,7 +226,7 @@ int pack_scene(const vkrt_scene_desc* d, bool texQuadsAllowed, PackedScene& out,
   pool.clear();
   // footprint pool (DevScene::texQuads): 16 bytes per level-0 texel; built when it stays below 2 GiB and the caller allows it (without
   // it the path tracer gathers the four texels of a tap one by one, as it did up to round 3; same values either way)
-  std::vector<uint32_t> quadFirst(d->texture_count, 0u);
+  std::vector<uint32_t> quadFirst(d->texture_count, 0u);  // (kept in out.texQuadFirst)
   uint64_t quadTotal = 1;  // record 0 = white dummy (hits without a texture read it and discard it)
   for(uint32_t t = 0; t < d->texture_count; t++)
   {
@@ -177,26 +236,7 @@ int pack_scene(const vkrt_scene_desc* d, bool texQuadsAllowed, PackedScene& out,
   const bool wantQuads = quadTotal * 16ull < (2ull << 30) && texQuadsAllowed;
   quads.clear();
   if(wantQuads)
-  {
     quads.assign((size_t)quadTotal * 4, 0xffffffffu);
-    for(uint32_t t = 0; t < d->texture_count; t++)
-    {
-      const vkrt_texture& tx = d->textures[t];
-      const uint32_t* src = (const uint32_t*)tx.rgba8;
-      uint32_t* dst = &quads[(size_t)quadFirst[t] * 4];
-      for(uint32_t y = 0; y < tx.height; y++)
-      {
-        const uint32_t y1 = y + 1 == tx.height ? 0 : y + 1;
-        for(uint32_t x = 0; x < tx.width; x++)
-        {
-          const uint32_t x1 = x + 1 == tx.width ? 0 : x + 1;
-          uint32_t* q = dst + ((size_t)y * tx.width + x) * 4;
-          memcpy(&q[0], &src[(size_t)y * tx.width + x], 4); memcpy(&q[1], &src[(size_t)y * tx.width + x1], 4);
-          memcpy(&q[2], &src[(size_t)y1 * tx.width + x], 4); memcpy(&q[3], &src[(size_t)y1 * tx.width + x1], 4);
-        }
-      }
-    }
-  }
   for(uint32_t t = 0; t < d->texture_count; t++)
   {
     const vkrt_texture& tx = d->textures[t];
@@ -204,6 +244,11 @@ int pack_scene(const vkrt_scene_desc* d, bool texQuadsAllowed, PackedScene& out,
     size_t at = pool.size();
     pool.resize(at + n);
     memcpy(&pool[at], tx.rgba8, n * 4);
+    // (the footprints are texture_pack.h's, which k_se_level0 writes on the device, read from the pool's aligned copy of level 0)
+    if(wantQuads)
+      for(uint32_t y = 0; y < tx.height; y++)
+        for(uint32_t x = 0; x < tx.width; x++)
+          vkrt_footprint(&pool[at], tx.width, tx.height, x, y, &quads[((size_t)quadFirst[t] + (size_t)y * tx.width + x) * 4]);
     // the mip chain behind level 0 (sampled by the hybrid G-buffer's implicit-LOD texture(); the path tracer reads level 0)
     uint32_t levels = 1, w = tx.width, h = tx.height;
     mipTable[(size_t)t * VKRT_MAX_MIPS] = (uint32_t)at;
@@ -225,41 +270,11 @@ int pack_scene(const vkrt_scene_desc* d, bool texQuadsAllowed, PackedScene& out,
   out.materials.resize(d->material_count);
   out.shadeMaterials.resize(d->material_count);
   for(uint32_t i = 0; i < d->material_count; i++)
-  {
-    DevMaterial& mat = out.materials[i];
-    memset(&mat, 0, sizeof mat);
-    mat.m = d->materials[i];
-    mat.alphaMode = kDefaultAlpha.mode;
-    mat.alphaCutoff = kDefaultAlpha.cutoff;
-    DevShadeMaterial& sm = out.shadeMaterials[i];
-    memset(&sm, 0, sizeof sm);
-    for(int k = 0; k < 3; k++)
-    {
-      sm.f[k] = mat.m.pbrBaseColorFactor[k];
-      sm.f[5 + k] = mat.m.emissiveFactor[k];
-    }
-    sm.f[3] = mat.m.metallicFactor;
-    sm.f[4] = mat.m.roughnessFactor;
-    const int idx[4] = {mat.m.pbrBaseColorTexture, mat.m.metallicRoughnessTexture, mat.m.normalTexture, mat.m.emissiveTexture};
-    for(int k = 0; k < 4; k++)
-    {
-      DevTexRef& r = mat.tex[k];
-      r = DevTexRef{0u, 1u | (1u << 16), 0u, 0u};
-      if(idx[k] >= 0 && (uint32_t)idx[k] < d->texture_count)
-      {
-        const DevTexture& t = table[(size_t)idx[k]];
-        if(t.width == 0u || t.height == 0u || t.width > 32768u || t.height > 32768u)
-          return fail(err, VKRT_ERR_UNSUPPORTED, "texture %d is %ux%u (supported: 1..32768 per side)", idx[k], t.width, t.height);
-        r = DevTexRef{t.offset, t.width | (t.height << 16), 1u | ((t.srgb & 1u) ? 2u : 0u), wantQuads ? quadFirst[(size_t)idx[k]] : 0u};
-      }
-      // (the reference order of DevShadeMaterial is VKRT_TEXREF_*: BASE, MR, NORMAL, EMISSIVE = the order of idx[])
-      const uint32_t base = wantQuads ? r.quads : r.offset;
-      if(base >> 31)
-        return fail(err, VKRT_ERR_UNSUPPORTED, "texture pool of 2^31 records and more is not supported");
-      sm.ref[2 * k] = ((r.wh & 0xffffu) - 1u) | (idx[k] > -1 ? 1u << 15 : 0u) | (((r.wh >> 16) - 1u) << 16) | ((r.flags & 1u) << 31);
-      sm.ref[2 * k + 1] = base | ((r.flags & 2u) << 30);
-    }
-  }
+    if(const int rc = make_material(d->materials[i], table.data(), d->texture_count, quadFirst.data(), wantQuads, out.materials[i], out.shadeMaterials[i], err);
+       rc != VKRT_OK)
+      return rc;
+  out.texQuadFirst = quadFirst;
+  make_srgb_encode_table(out.srgbEncode);
   // the hit shader addresses its tables with 32-bit byte offsets (shade.h BufView): refuse what does not fit
   if((uint64_t)pool.size() * 4 >= (4ull << 30) || (uint64_t)d->vertex_count * VKRT_VERTEX_BYTES >= (4ull << 30) || (uint64_t)d->material_count * 128 >= (4ull << 30) ||
      (uint64_t)d->node_count * 96 >= (4ull << 30))

@@ -6,6 +6,7 @@
 #include <vector>
 #include "../../include/vkrt.h"
 #include "scene_records.h"
+#include "texture_pack.h"
 
 namespace vkrt {
 
@@ -25,6 +26,10 @@ struct PackedScene
   std::vector<uint32_t> texels;            // RGBA8 pool, every level (one white texel when the scene has no texture)
   std::vector<uint32_t> texQuads;          // footprint pool, 4 words per record; empty = the scene has none
   float srgbLut[512];
+  // what an edit of the live scene needs besides (vkrt_scene_update_materials, vkrt_scene_update_texture): each texture's first record in
+  // the footprint pool, and the thresholds of the sRGB encode (make_srgb_encode_table)
+  std::vector<uint32_t> texQuadFirst;
+  float srgbEncode[VKRT_SRGB_THRESHOLDS];
 };
 
 // node transforms: vkrt_scene_create and vkrt_scene_update_nodes refuse the same ones
@@ -34,6 +39,18 @@ int validate_scene(const vkrt_scene_desc* d, std::string& err);
 // The tables of a validated scene.  texQuadsAllowed = false: no footprint pool (the VKRT_TEX_QUADS=0 test hook).  VKRT_ERR_UNSUPPORTED
 // with the reason in err for a referenced texture side above 32768, a pool of 2^31 records and tables of 4 GiB.
 int pack_scene(const vkrt_scene_desc* d, bool texQuadsAllowed, PackedScene& out, std::string& err);
+// The DevMaterial and DevShadeMaterial of one material, with kDefaultAlpha: the same code at vkrt_scene_create (pack_scene calls it per
+// material) and at vkrt_scene_update_materials, so that an updated record is bit for bit the one a scene created with the material gets.
+// table: the scene's DevTexture records; quadFirst: each texture's first footprint record (read when wantQuads, the scene has that pool).
+// An index outside [0, textureCount) makes the 1x1 invalid reference.  VKRT_ERR_UNSUPPORTED with the reason in err for a referenced
+// texture side above 32768 and a base of 2^31 and more.
+int make_material(const GltfPBRMaterial& m, const DevTexture* table, uint32_t textureCount, const uint32_t* quadFirst, bool wantQuads, DevMaterial& mat,
+                  DevShadeMaterial& sm, std::string& err);
+// The 8-bit code pack_scene gives a filtered linear colour value of an sRGB texture: powf, clamp, * 255 + 0.5, truncation
+uint32_t srgb_encode_code(float v);
+// T[0] = 0; T[q], q = 1..255: the smallest binary32 v >= 0 with srgb_encode_code(v) >= q, found by bisection over bit patterns.  The device
+// quantises with these (texture_pack.h vkrt_srgb_quantise) instead of evaluating the curve
+void make_srgb_encode_table(float T[VKRT_SRGB_THRESHOLDS]);
 // gl_ObjectToWorldEXT / gl_WorldToObjectEXT of one node (rchit:72-76) and its ray-query visibility: the same code at vkrt_scene_create,
 // vkrt_scene_update_nodes and vkrt_scene_set_instance_visibility, so that a moved scene's records are bit for bit those of a scene
 // created with the moved nodes

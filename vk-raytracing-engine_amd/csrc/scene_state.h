@@ -105,6 +105,16 @@ struct vkrt_scene
   const DevInstance* prevInstances() const { return motion.get() ? motion.get<const DevInstance>() : dev.instances; }
   const float* prevPositions() const { return motion.get() ? (const float*)(motion.get<const char>() + motionPositionsAt()) : dev.positions; }
   size_t motionPositionsAt() const { return std::max<size_t>(nodes.size() * sizeof(DevInstance), 16); }
+  // editing the live scene (api_edit.cpp).  The texture tables as vkrt_scene_create packed them, which are fixed: the DevTexture records,
+  // the level offsets ([texture][VKRT_MAX_MIPS]) and each texture's first footprint record (read when dev.texQuads exists); the
+  // thresholds of the sRGB encode on the device (released with `tables`)
+  std::vector<DevTexture> textures;
+  std::vector<uint32_t> texMips, texQuadFirst;
+  const float* srgbEncode = nullptr;
+  // the dissolve rule of vkrt_scene_update_materials: per material, had it alpha < 1 at the last vkrt_accel_build (empty: that build ran
+  // with VKRT_OPT_ANYHIT_DISSOLVE = 0, or there is no tree); and whether an update since has made the tree's triangle flags insufficient
+  std::vector<uint8_t> builtNonOpaque;
+  bool dissolveRebuild = false;
 };
 
 namespace vkrt {
@@ -127,6 +137,9 @@ inline int checkBuilt(const vkrt_scene* s, const char* who)
 {
   if(!s->built)
     return fail(VKRT_ERR_NOT_BUILT, "%s before vkrt_accel_build", who);
+  if(s->dissolveRebuild)
+    return fail(VKRT_ERR_NOT_BUILT, "%s after vkrt_scene_update_materials gave a material alpha < 1 that was opaque when the tree was built with "
+                "VKRT_OPT_ANYHIT_DISSOLVE: vkrt_accel_build first", who);
   if(s->stale)
     return fail(VKRT_ERR_NOT_BUILT, "%s after vkrt_scene_update_nodes / vkrt_scene_update_vertices: vkrt_accel_refit or vkrt_accel_build first", who);
   return VKRT_OK;
@@ -181,6 +194,8 @@ inline void freeAccel(vkrt_scene* s)
   s->refit = RefitScratch{};
   s->refitted = false;
   s->stale = false;
+  s->builtNonOpaque.clear();
+  s->dissolveRebuild = false;
 }
 
 inline void noteMasks(vkrt_scene* s)

@@ -8,6 +8,7 @@ import os
 import numpy as np
 
 from . import LIB_PATH, abi
+from .flat_scene import LIGHT_DTYPE, MAT_DTYPE
 
 _lib = None
 
@@ -64,6 +65,10 @@ ALPHA_OPAQUE, ALPHA_MASK = abi.VKRT_ALPHA_OPAQUE, abi.VKRT_ALPHA_MASK  # vkrt_al
 # one 96-B instance record (Renderer.read_instances; include/vkrt.h vkrt_debug_read_instances)
 INSTANCE_DTYPE = np.dtype([("o2w", "<f4", 12), ("w2o", "<f4", 9), ("primMesh", "<i4"), ("vis", "<u4"), ("pad", "<i4")])
 assert INSTANCE_DTYPE.itemsize == 96
+# the records of vkrt_debug_read_materials: the 128-B record of the queries and the G-buffer, then the 64-B record of the hit shader
+MATERIAL_RECORD_DTYPE = np.dtype([("m", MAT_DTYPE), ("pad", "<i4"), ("alphaMode", "<u4"), ("alphaCutoff", "<f4"), ("tex", "<u4", (4, 4)),
+                                  ("f", "<f4", 8), ("ref", "<u4", 8)])
+assert MATERIAL_RECORD_DTYPE.itemsize == 192
 
 
 class VkrtError(RuntimeError):
@@ -173,6 +178,7 @@ class Renderer:
         self._prim_mesh = np.array(flat.nodes["primMesh"], np.int32)  # update_nodes keeps every node's primMesh
         self._vertex_count = int(flat.positions.shape[0])
         self._material_count = int(flat.materials.shape[0])
+        self._texture_sizes = [(int(t["rgba8"].shape[1]), int(t["rgba8"].shape[0])) for t in flat.textures]  # (width, height), fixed
         self._triangle_count = int((np.asarray(flat.prim_meshes["indexCount"], np.int64)[self._prim_mesh] // 3).sum())  # instanced
         self._skins = []  # (first, count, joint_count) of every add_skin, in the library's numbering
         self._morphs = []  # (first, count, target_count) of every add_morph, in the library's numbering
@@ -527,6 +533,130 @@ class Renderer:
         arr = (abi.MaterialAlpha * max(n, 1))()
         _check(self.lib.vkrt_scene_get_material_alpha(self._h, 0, n, arr), "vkrt_scene_get_material_alpha")
         return (np.array([arr[i].mode for i in range(n)], np.uint32), np.array([arr[i].cutoff for i in range(n)], np.float32))
+
+    @staticmethod
+    def _int_range(who, what, first, n, total):
+        """`first` as an int, with [first, first + n) inside the scene's `total` records"""
+        ok = not isinstance(first, bool) and isinstance(first, (int, np.integer)) and not isinstance(n, bool) and isinstance(n, (int, np.integer))
+        if not ok or first < 0 or n < 0 or int(first) + int(n) > total:
+            raise VkrtError(f"{who}: {what} [{first}, {first} + {n}) outside the scene's {total} {what}")
+        return int(first)
+
+    def _device_tensor(self, who, name, a, dtype, shape):
+        """the address of a contiguous, 16-byte aligned torch tensor of `dtype` and `shape` on the scene's device"""
+        if not a.is_cuda or a.device.index != self.device:
+            raise VkrtError(f"{who}: {name} is on {a.device}, the scene is on cuda:{self.device}")
+        if a.dtype != dtype:
+            raise VkrtError(f"{who}: {name} is {a.dtype}, expected {dtype}")
+        if not a.is_contiguous():
+            raise VkrtError(f"{who}: {name} must be contiguous")
+        if a.shape != shape:
+            raise VkrtError(f"{who}: {name} has shape {tuple(a.shape)}, expected {shape}")
+        if a.data_ptr() % 16:
+            raise VkrtError(f"{who}: {name} must be 16-byte aligned")
+        return a.data_ptr()
+
+    def update_lights(self, first, lights, stream=None):
+        """vkrt_scene_update_lights: new records for lights [first, first + n), taken as given.  lights: a numpy array of LIGHT_DTYPE
+        (n,) takes the host path (copied before return, no wait); a contiguous float32 (n, 8) torch tensor on the scene's device --
+        position, color, intensity, and the bits of the int32 type -- takes the device path: one stream-ordered copy, no
+        synchronisation, the tensor must live until `stream` has passed the call.  Enqueued on `stream` (a torch stream; None = the
+        default stream); the next frame on it sees the new lights, without a refit.  Refused here, before the call: a wrong dtype,
+        shape or device, a non-contiguous or misaligned tensor, a range outside the scene's lights."""
+        who = "update_lights"
+        if isinstance(lights, np.ndarray):
+            if lights.dtype != LIGHT_DTYPE or lights.ndim != 1:
+                raise VkrtError(f"{who}: lights is {lights.dtype} of shape {lights.shape}, expected LIGHT_DTYPE (n,)")
+            keep = np.ascontiguousarray(lights)
+            n, ptr, memory = int(keep.shape[0]), keep.ctypes.data, _HOST
+        else:
+            torch = _torch or _import_torch()
+            if not isinstance(lights, torch.Tensor):
+                raise VkrtError(f"{who}: lights must be a numpy array or a torch tensor, got {type(lights).__name__}")
+            ptr, memory = self._device_tensor(who, "lights", lights, torch.float32, (_N, 8)), _DEVICE
+            n = int(lights.shape[0])
+        first = self._int_range(who, "lights", first, n, self.lights_count)
+        u = abi.LightUpdate(C.sizeof(abi.LightUpdate), first, n, memory, ptr)
+        st = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        _check(self.lib.vkrt_scene_update_lights(self._h, C.byref(u), st), "vkrt_scene_update_lights")
+
+    def update_materials(self, first, materials, stream=None):
+        """vkrt_scene_update_materials: new materials [first, first + n) from a numpy array of MAT_DTYPE (n,), copied before return;
+        both device records of each are re-made as at scene creation and enqueued on `stream` (a torch stream; None = the default
+        stream) with no wait.  Alpha modes and cutoffs stay (set_material_alpha); texture indices may change among the scene's
+        textures.  Under VKRT_OPT_ANYHIT_DISSOLVE a material that becomes non-opaque (alpha < 1) asks for build() before the next
+        trace (include/vkrt.h).  Refused here, before the call: a wrong dtype or shape, a range outside the scene's materials, a
+        texture index beyond the scene's textures."""
+        who = "update_materials"
+        if not isinstance(materials, np.ndarray) or materials.dtype != MAT_DTYPE or materials.ndim != 1:
+            raise VkrtError(f"{who}: materials must be a numpy array of MAT_DTYPE (n,), got {getattr(materials, 'dtype', type(materials).__name__)}")
+        keep = np.ascontiguousarray(materials)
+        n = int(keep.shape[0])
+        first = self._int_range(who, "materials", first, n, self._material_count)
+        textures = len(self._texture_sizes)
+        for k in ("pbrBaseColorTexture", "metallicRoughnessTexture", "normalTexture", "emissiveTexture"):
+            if textures and n and int(keep[k].max()) >= textures:
+                raise VkrtError(f"{who}: {k} {int(keep[k].max())} beyond the scene's {textures} textures")
+        st = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        _check(self.lib.vkrt_scene_update_materials(self._h, first, n, keep.ctypes.data, st), "vkrt_scene_update_materials")
+
+    def update_texture(self, texture, rgba8, stream=None):
+        """vkrt_scene_update_texture: a new image for texture `texture`, uint8 (height, width, 4) of the texture's own size.  A numpy
+        array takes the host path (staged, the call waits for `stream`); a contiguous torch tensor on the scene's device takes the
+        device path: no copy, no synchronisation, the tensor must live until `stream` has passed the call.  Level 0, the footprint
+        records and every mip level are rebuilt on the device, bit for bit what scene creation packs from the image.  Enqueued on
+        `stream` (a torch stream; None = the default stream); no refit is needed.  Refused here, before the call: a texture index out
+        of range, a wrong dtype, size or device, a non-contiguous or misaligned tensor."""
+        who = "update_texture"
+        if isinstance(texture, bool) or not isinstance(texture, (int, np.integer)) or not 0 <= texture < len(self._texture_sizes):
+            raise VkrtError(f"{who}: texture {texture!r} outside the scene's {len(self._texture_sizes)} textures")
+        w, h = self._texture_sizes[int(texture)]
+        if isinstance(rgba8, np.ndarray):
+            if rgba8.dtype != np.uint8 or rgba8.shape != (h, w, 4):
+                raise VkrtError(f"{who}: rgba8 is {rgba8.dtype} of shape {rgba8.shape}, expected uint8 ({h}, {w}, 4)")
+            keep = np.ascontiguousarray(rgba8)
+            ptr, memory = keep.ctypes.data, _HOST
+        else:
+            torch = _torch or _import_torch()
+            if not isinstance(rgba8, torch.Tensor):
+                raise VkrtError(f"{who}: rgba8 must be a numpy array or a torch tensor, got {type(rgba8).__name__}")
+            ptr, memory = self._device_tensor(who, "rgba8", rgba8, torch.uint8, (h, w, 4)), _DEVICE
+        u = abi.TextureUpdate(C.sizeof(abi.TextureUpdate), int(texture), w, h, memory, ptr)
+        st = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        _check(self.lib.vkrt_scene_update_texture(self._h, C.byref(u), st), "vkrt_scene_update_texture")
+
+    def read_lights(self, first, count):
+        """The light records [first, first + count) as the kernels read them (vkrt_debug_read_lights, synchronises): LIGHT_DTYPE."""
+        first = self._int_range("read_lights", "lights", first, count, self.lights_count)
+        out = np.zeros(max(int(count), 1), LIGHT_DTYPE)
+        _check(self.lib.vkrt_debug_read_lights(self._h, first, int(count), out.ctypes.data, 32 * int(count)), "vkrt_debug_read_lights")
+        return out[:int(count)]
+
+    def read_materials(self, first, count):
+        """Both device records of materials [first, first + count) (vkrt_debug_read_materials, synchronises): MATERIAL_RECORD_DTYPE,
+        192 B per material."""
+        first = self._int_range("read_materials", "materials", first, count, self._material_count)
+        out = np.zeros(max(int(count), 1), MATERIAL_RECORD_DTYPE)
+        _check(self.lib.vkrt_debug_read_materials(self._h, first, int(count), out.ctypes.data, 192 * int(count)), "vkrt_debug_read_materials")
+        return out[:int(count)]
+
+    def read_texture(self, texture, level=0, quads=False):
+        """One level of one texture as the kernels read it (vkrt_debug_read_texture, synchronises): uint8 (h, w, 4) of the level's
+        size; with quads (level 0 only) a pair of it and the texture's footprint records, uint32 (h, w, 4).  A scene without a
+        footprint pool refuses quads with VKRT_ERR_UNSUPPORTED."""
+        who = "read_texture"
+        if isinstance(texture, bool) or not isinstance(texture, (int, np.integer)) or not 0 <= texture < len(self._texture_sizes):
+            raise VkrtError(f"{who}: texture {texture!r} outside the scene's {len(self._texture_sizes)} textures")
+        w, h = self._texture_sizes[int(texture)]
+        levels = int(np.floor(np.log2(max(w, h)))) + 1
+        if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or not 0 <= level < min(levels, 16) or (quads and level != 0):
+            raise VkrtError(f"{who}: level {level!r} outside texture {texture}'s {min(levels, 16)} levels (quads: level 0 only)")
+        lw, lh = max(1, w >> int(level)), max(1, h >> int(level))
+        texels = np.zeros((lh, lw, 4), np.uint8)
+        q = np.zeros((lh, lw, 4), np.uint32) if quads else None
+        _check(self.lib.vkrt_debug_read_texture(self._h, int(texture), int(level), texels.ctypes.data, texels.nbytes, q.ctypes.data if quads else None,
+                                                q.nbytes if quads else 0), "vkrt_debug_read_texture")
+        return (texels, q) if quads else texels
 
     def read_node_masks(self):
         """The wide8 tree's node-mask table (vkrt_debug_read_node_masks): uint8 [nodes, 8], byte s = the OR of the instance masks
